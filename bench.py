@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Benchmark of the SimCLR pretraining step on MI355X (BASELINE.json metric: images/sec).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  --dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/<name>.npy (dump_outputs below).
   N>1 without WORLD_SIZE in the environment: bench.py re-launches itself as
       python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
   (one rank per GPU over RCCL); launched that way by a driver it just runs as one rank.
@@ -181,6 +182,30 @@ def percentiles(ms):
         return None
     pick = lambda q: s[min(len(s) - 1, int(q * (len(s) - 1) + 0.5))]
     return dict(p10=round(pick(0.1), 3), median=round(pick(0.5), 3), p90=round(pick(0.9), 3), n=len(s))
+
+
+DUMP_SAMPLE = 1 << 22       # elements kept of a larger output: 16 MB of float32 per array, under 64 MB for the whole dump
+
+
+def dump_outputs(out_dir, out, model):
+    """What one training step handed its caller, as float32 `out_dir/<name>.npy`: the loss and metric scalars and the l2-normalised
+    embeddings it returned, and the variables and gradients it left in the model.  An array of more than DUMP_SAMPLE elements is
+    replaced by a fixed seeded sample of its flattened elements (the same indices in every run), so that two builds can be compared
+    output for output."""
+    import numpy as np
+    arrays = dict(contrast_loss=out['con_loss'].value, contrast_acc=out['logits_con'].contrast_acc,
+                  contrast_entropy=out['logits_con'].contrast_entropy, supervised_loss=out['sup_loss'].value,
+                  supervised_acc=out['sup_loss'].acc, weight_decay=out['weight_decay'], total_loss=out['total_loss'],
+                  embeddings=out['con_loss'].normalized,
+                  variables=torch.cat([v.value.detach().reshape(-1).float() for v in model.variables]),
+                  gradients=torch.cat([v.grad.detach().reshape(-1).float() for v in model.trainable_variables]))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
 
 
 def build_step(args, dtype, strategy, world, rank, dev, f32_matmul=None):
@@ -405,7 +430,11 @@ def main():
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo: the ranks talk over gloo and share cuda:0 when the box has fewer GPUs than ranks (exercises '
                          'the N > 1 launch path on a single-GPU box; RCCL refuses two ranks on one device)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.backend == 'gloo':
         os.environ['SIMCLR_DIST_BACKEND'] = 'gloo'
         if torch.cuda.device_count() < args.gpus:
@@ -440,7 +469,7 @@ def main():
     marks[0].record()
     for i in range(args.steps):
         f, l = next(data)
-        step_fn(f, l)
+        last = step_fn(f, l)
         marks[i + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
@@ -456,6 +485,11 @@ def main():
     if strategy is not None:
         coll_counts = dict(stat_collectives_per_step=(strategy.stat_collectives - coll0[0]) / args.steps,
                            hidden_collectives_per_step=(strategy.hidden_collectives - coll0[1]) / args.steps)
+    # before any further step: the instrumented steps below move the model's variables and gradients on.  `last` is then
+    # dropped so that it keeps none of the step's tensors alive when the side runs below free the step's memory.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)
+    del last
 
     # ---- instrumented steps (per-launch HIP events), outside the headline region
     prof = None

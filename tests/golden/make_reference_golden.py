@@ -11,8 +11,8 @@ and weight-decay arithmetic, the metrics, the blur filter, FixedPadding, and the
 restated.  What they do not pin: TensorFlow's own kernels.
 
 `reference_cases(ref_dir)` runs the reference; `oracle_cases()` computes the same keys with oracle/*.py.  The test
-(tests/test_reference_pin.py) compares oracle_cases() with the committed fixtures everywhere, and re-runs
-reference_cases() against them wherever /root/reference exists.
+(tests/test_reference_pin.py) compares oracle_cases() with the committed fixtures; `--check` re-runs reference_cases()
+against them (it needs the reference checkout, so it is not part of the test suite).
 """
 import importlib
 import importlib.machinery

@@ -104,6 +104,45 @@ def test_parity_mode_and_ntxent_accounting_fields():
     assert 'warm=3' in csrc and 'min_steps=10' in csrc
 
 
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 .npy files; an output of more than DUMP_SAMPLE elements
+    becomes the same sorted sample of its elements in every run, and the whole dump stays under 64 MB."""
+    import inspect
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    src = inspect.getsource(b.main)
+    for needle in ("'--dump-outputs'", 'last = step_fn(f, l)', 'dump_outputs(args.dump_outputs, last, model)'):
+        assert needle in src, needle
+    # the dump is taken before the instrumented steps, which would move the variables and gradients past the last timed step
+    assert src.index('dump_outputs(args.dump_outputs') < src.index('prof = ops.KernelProfiler()')
+    n = b.DUMP_SAMPLE // 2 + 1000                   # two trainable tensors of n elements + one statistic: both big arrays get sampled
+    ns = types.SimpleNamespace
+    w = [ns(value=torch.arange(i * n, (i + 1) * n, dtype=torch.float32), grad=torch.arange(i * n, (i + 1) * n, dtype=torch.float32))
+         for i in range(2)]
+    stat = ns(value=torch.arange(2 * n, 2 * n + 64, dtype=torch.float32))
+    model = ns(variables=w + [stat], trainable_variables=w)
+    one = lambda x: torch.tensor([x])
+    emb = torch.randn(16, 4)
+    out = dict(con_loss=ns(value=one(2.5), normalized=emb), logits_con=ns(contrast_acc=one(0.25), contrast_entropy=one(1.5)),
+               sup_loss=ns(value=one(6.9), acc=one(0.0)), weight_decay=one(1e-3), total_loss=one(9.401))
+    b.dump_outputs(str(tmp_path / 'a'), out, model)
+    b.dump_outputs(str(tmp_path / 'b'), out, model)
+    names = {'contrast_loss', 'contrast_acc', 'contrast_entropy', 'supervised_loss', 'supervised_acc', 'weight_decay', 'total_loss',
+             'embeddings', 'variables', 'gradients'}
+    assert {p.name for p in (tmp_path / 'a').iterdir()} == {x + '.npy' for x in names}
+    got = {x: np.load(tmp_path / 'a' / (x + '.npy')) for x in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(tmp_path / 'a' / (x + '.npy')) for x in names) <= 64 << 20
+    assert got['total_loss'].tolist() == [np.float32(9.401)] and np.array_equal(got['embeddings'], emb.numpy())
+    for x, total in (('variables', 2 * n + 64), ('gradients', 2 * n)):
+        s = got[x]
+        # element values equal their positions here: a sorted sample of distinct elements of the concatenation
+        assert s.shape == (b.DUMP_SAMPLE,) and np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < total
+        assert np.array_equal(s, np.load(tmp_path / 'b' / (x + '.npy')))
+
+
 def test_headline_is_the_tolerance_meeting_mode():
     """with no flags the top-level value / dtype / roofline of the line belong to the fastest mode that meets
     north_star's tolerances (fp32 storage, three fp16-piece terms forward, three bf16-piece terms backward); the bf16 speed mode is a

@@ -2,12 +2,10 @@
 
 The fixtures were produced in the build container by importing /root/reference/tf2/{objective,lars_optimizer,metrics,resnet,
 data_util,model}.py unmodified on top of oracle/tfshim.py (a float64 numpy stand-in for the TensorFlow / Keras calls they make) --
-tests/golden/make_reference_golden.py.  Here: (1) every fixture is recomputed with oracle/*.py and must agree; (2) wherever
-the reference checkout exists, the fixtures are regenerated from it in a subprocess and must be reproduced exactly."""
+tests/golden/make_reference_golden.py.  Here every fixture is recomputed with oracle/*.py and must agree.  The suite uses the committed
+fixtures only; regenerating them from a reference checkout is `python tests/golden/make_reference_golden.py --check`."""
 import importlib.util
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -48,15 +46,6 @@ def test_variable_names_follow_the_lars_name_filters():
     assert bn and all('batch_normalization' in n for n in bn)
     assert [n for n in names if 'head_supervised' in n] == ['head_supervised/linear_layer/dense_3/bias:0', 'head_supervised/linear_layer/dense_3/kernel:0']
     assert sum(n.endswith('kernel:0') for n in names) == 53 + 3 + 1          # 53 convolutions, 3 projection-head layers, the linear-eval head
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(os.environ.get('SIMCLR_REFERENCE', '/root/reference'), 'tf2')),
-                    reason='reference checkout not present (GPU box): the committed fixtures are used as they are')
-def test_fixtures_are_reproduced_by_the_reference_source():
-    # a subprocess: the stand-in registers itself as `tensorflow`, which must not leak into this interpreter
-    r = subprocess.run([sys.executable, SCRIPT, '--check'], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert 'tensorflow' not in sys.modules or not getattr(sys.modules['tensorflow'], '_SIMCLR_SHIM', False)
 
 
 # ---- the PRODUCT's Python mirrors (simclr_amd/*.py, no HIP call involved) against the same fixtures --------------------------------

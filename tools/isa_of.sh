@@ -2,7 +2,7 @@
 # tools/isa_of.sh <mangled-substring>: compiles csrc/conv.hip with -save-temps and prints the instruction skeleton (loads, stores, waits,
 # MFMAs) and the register numbers of the first kernel whose mangled name contains the substring.  A development aid, not part of the build.
 set -e
-C=/root/repo/simclr_amd/csrc
+C=$(cd "$(dirname "$0")/../simclr_amd/csrc" && pwd)
 cd $C
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -c conv.hip -o build/conv.o -save-temps=obj
 S=$C/build/conv-hip-amdgcn-amd-amdhsa-gfx950.s

@@ -1,8 +1,8 @@
 """Overlap of the collective-library kernels with compute, from a rocprofv3 kernel trace of a one-rank step with every collective
 issued:
 
-    cd /tmp && SIMCLR_FORCE_COLLECTIVES=1 rocprofv3 --kernel-trace --output-format csv -d OUT -o fc -- \
-        python /root/repo/bench.py --steps 3 --warmup 2 --no_cpu_baseline --no_pmc --no_parity --no_f32 --no_kernel_events
+    R=$PWD; cd /tmp && SIMCLR_FORCE_COLLECTIVES=1 rocprofv3 --kernel-trace --output-format csv -d OUT -o fc -- \
+        python $R/bench.py --steps 3 --warmup 2 --no_cpu_baseline --no_pmc --no_parity --no_f32 --no_kernel_events
     python tools/overlap_trace.py OUT --steps 5 --out profiles/r06_overlap_forced_collectives.json
 
 With SIMCLR_FORCE_COLLECTIVES=1 a single rank builds the three communicators (hidden / statistics / gradients) and issues collective A
