@@ -354,7 +354,7 @@ int simclr_l2_loss_f32(const float* x, long long n, float* out, simclr_stream_t 
  *   dW = (h^T dm)*a + ((h^T h) W)*b + colsum(h) (x) d ;   d(h) = dm (a*W)^T + h (W diag(b) W^T) + W d.
  * simclr_bn_fold_pre -> a, b, d, W*b (fp32), the first N columns of the extended dgrad weights and the bias W d
  * (simclr_bn_fold_coeffs: a, b, d alone);  [GEMMs h^T dm, h^T h via simclr_conv2d_wgrad; (h^T h) W and (W*b) W^T via simclr_conv2d_fwd];
- * simclr_bn_fold_post -> dW and the last K columns of the extended weights;  simclr_conv2d_dgrad_bn_ext -> d(h) with the fused
+ * simclr_bn_fold_post -> dW and the last K columns of the extended weights (dW alone with wext = q = NULL);  simclr_conv2d_dgrad_bn_ext -> d(h) with the fused
  * BN-backward reduce of the producer BN, reading dm and h (K-extended reduction) instead of a materialised dh. ---- */
 int simclr_bn_fold_coeffs(const float* scale, const float* mean, const float* rstd, const float* c1, const float* c2,
                           float* a, float* b, float* d, int C, simclr_stream_t stream);

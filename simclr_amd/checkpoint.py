@@ -18,6 +18,7 @@ on the others keeps their bookkeeping in step without touching the directory).  
 returned status, not fatal, unless `assert_consumed()` is asked for; a shape mismatch is always an error.
 """
 import json
+import logging
 import os
 
 import torch
@@ -188,7 +189,14 @@ def try_restore_from_checkpoint(model, optimizer, model_dir, checkpoint=None, ke
     if latest:
         status = manager.checkpoint.restore(latest).expect_partial()
     elif checkpoint:
-        status = Checkpoint(model=model).restore(checkpoint, model_only=True).expect_partial()
+        status = Checkpoint(model=model).restore(checkpoint, model_only=True)
+        # a supervised head of another class count (fine-tuning on a new label set) keeps its fresh initialisation; any other
+        # shape difference is an error
+        head = [m for m in status.shape_mismatch if 'head_supervised' in m[0]]
+        if head:
+            logging.warning('checkpoint %s: supervised head of a different shape not restored (fresh head kept): %s', checkpoint, head)
+            status.shape_mismatch = [m for m in status.shape_mismatch if 'head_supervised' not in m[0]]
+        status.expect_partial()
         if zero_init_logits_layer and getattr(model, 'supervised_head', None) is not None:
             for v in model.supervised_head.trainable_variables:
                 v.value.zero_()

@@ -458,7 +458,8 @@ __global__ __launch_bounds__(256) void bn_fold_pre(const T* __restrict__ w, cons
   if (threadIdx.x == 0) e[i] = (float)sh[0];
 }
 
-// dw[i][j] = a[j]*t1[i][j] + b[j]*gw[i][j] + d[j]*cs[i]  (+= if accumulate);  wext[i][N + k] = T(q[k][i])
+// dw[i][j] = a[j]*t1[i][j] + b[j]*gw[i][j] + d[j]*cs[i]  (+= if accumulate);  wext[i][N + k] = T(q[k][i]) unless wext == nullptr
+// (no data gradient follows: the conv's input is a frozen layer's output, fine_tune_after_block)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_fold_post(const float* __restrict__ t1, const float* __restrict__ gw,
                                                     const double* __restrict__ cs, const float* __restrict__ cs32,
@@ -467,7 +468,8 @@ __global__ __launch_bounds__(256) void bn_fold_post(const float* __restrict__ t1
                                                     const float* __restrict__ q, float* __restrict__ dw, T* __restrict__ wext,
                                                     int K, int N, int accumulate) {
   const long long total = (long long)K * N;
-  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total + (long long)K * K; t += gridDim.x * 256ll) {
+  const long long end = total + (wext != nullptr ? (long long)K * K : 0ll);
+  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < end; t += gridDim.x * 256ll) {
     if (t < total) {
       const int i = (int)(t / N), j = (int)(t % N);
       const float v = fmaf(a[j], t1[t], fmaf(b[j], gw[t], d[j] * (cs ? (float)cs[i] : cs32[i])));
@@ -685,7 +687,8 @@ int simclr_bn_fold_post(const float* t1, const float* gw, const double* cs, cons
                         hipStream_t stream) {
   SIMCLR_CHECK_ARG((cs != nullptr) != (cs32 != nullptr), "bn_fold_post: give the column sums as fp64 OR fp32");
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "bn_fold_post: bad dtype %d", dtype);
-  const long long total = (long long)K * N + (long long)K * K;
+  SIMCLR_CHECK_ARG((wext == nullptr) == (q == nullptr), "bn_fold_post: wext and q are given together or not at all");
+  const long long total = (long long)K * N + (wext != nullptr ? (long long)K * K : 0ll);
   const int grid = (int)min((total + 255) / 256, 1ll << 20);
   if (dtype == SIMCLR_DT_BF16)
     hipLaunchKernelGGL((bn_fold_post<uint16_t>), dim3(grid), dim3(256), 0, stream, t1, gw, cs, cs32, a, b, d, q, dw, (uint16_t*)wext, K, N, accumulate);

@@ -44,7 +44,8 @@ __global__ void pack_views(const float* __restrict__ img, T* __restrict__ xp, in
 }
 
 // y[v,oy,ox,c] = max over the k x k window of relu(x*scale+shift); arg = first max tap.
-template <typename T>
+// WANT_ARG = false: a forward that no backward pass follows (a frozen stem in finetune mode) -- no tap ids are tracked or stored.
+template <typename T, bool WANT_ARG>
 __global__ void bnrelu_maxpool_fwd(const T* __restrict__ x, const float* __restrict__ scale,
                                    const float* __restrict__ shift, T* __restrict__ y,
                                    uint8_t* __restrict__ arg, int V, int H, int W, int C, int OH, int OW,
@@ -77,11 +78,12 @@ __global__ void bnrelu_maxpool_fwd(const T* __restrict__ x, const float* __restr
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
           const float a = fmaxf(fmaf(xv[e], sc[e], sh[e]), 0.f);
-          if (a > best[e]) { best[e] = a; bi[e] = ky * ksz + kx; }
+          if (a > best[e]) { best[e] = a; if (WANT_ARG) bi[e] = ky * ksz + kx; }
         }
       }
     }
     *(u32x4*)(y + (long long)pix * C + c0) = f32_to_chunk<T>(best);
+    if (!WANT_ARG) continue;
     // tap ids of the EPC channels as ONE 4- or 8-byte store
     uint32_t w[EPC / 4];
 #pragma unroll
@@ -933,13 +935,24 @@ int simclr_bnrelu_maxpool_fwd(const void* x, const float* scale, const float* sh
   SIMCLR_CHECK_ARG(ksz * ksz <= 255, "bnrelu_maxpool_fwd: window too large");
   SIMCLR_CHECK_ARG((long long)V * H * W < (1ll << 31) && (long long)V * OH * OW < (1ll << 31), "bnrelu_maxpool_fwd: pixel count overflows int32");
   const long long total = (long long)V * OH * OW * (C / epc);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((bnrelu_maxpool_fwd<uint16_t>), dim3(grid_for(total)), dim3(256), 0, stream,
-                                (const uint16_t*)x, scale, shift, (uint16_t*)y, arg, V, H, W, C, OH, OW, ksz,
-                                stride, pad_t, pad_l),
-             hipLaunchKernelGGL((bnrelu_maxpool_fwd<float>), dim3(grid_for(total)), dim3(256), 0, stream,
-                                (const float*)x, scale, shift, (float*)y, arg, V, H, W, C, OH, OW, ksz, stride,
-                                pad_t, pad_l));
+  // arg == nullptr: the pooled output only (no backward pass will read the tap ids)
+  if (arg != nullptr) {
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((bnrelu_maxpool_fwd<uint16_t, true>), dim3(grid_for(total)), dim3(256), 0, stream,
+                                  (const uint16_t*)x, scale, shift, (uint16_t*)y, arg, V, H, W, C, OH, OW, ksz,
+                                  stride, pad_t, pad_l),
+               hipLaunchKernelGGL((bnrelu_maxpool_fwd<float, true>), dim3(grid_for(total)), dim3(256), 0, stream,
+                                  (const float*)x, scale, shift, (float*)y, arg, V, H, W, C, OH, OW, ksz, stride,
+                                  pad_t, pad_l));
+  } else {
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((bnrelu_maxpool_fwd<uint16_t, false>), dim3(grid_for(total)), dim3(256), 0, stream,
+                                  (const uint16_t*)x, scale, shift, (uint16_t*)y, nullptr, V, H, W, C, OH, OW, ksz,
+                                  stride, pad_t, pad_l),
+               hipLaunchKernelGGL((bnrelu_maxpool_fwd<float, false>), dim3(grid_for(total)), dim3(256), 0, stream,
+                                  (const float*)x, scale, shift, (float*)y, nullptr, V, H, W, C, OH, OW, ksz, stride,
+                                  pad_t, pad_l));
+  }
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

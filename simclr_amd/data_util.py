@@ -175,7 +175,8 @@ def preprocess_for_train_batch(images, height, width, color_jitter_strength=0., 
                                sizes=None, views=1, params=None):
     """Batched preprocess_for_train (tf2/data_util.py:443-475).  images: device tensor [b, Hs, Ws, 3], uint8 or float32
     in [0,1] -- a canvas; `sizes` [b, 2] gives each image's valid (height, width) inside it (default: the whole canvas).
-    Returns float32 [b, height, width, 3*views]."""
+    Returns float32 [b, height, width, 3*views].  views=1 with color_jitter_strength=0 is train_mode=finetune's
+    preprocessing (tf2/data.py:52-58: one view, crop + flip, no colour distortion)."""
     if impl != 'simclrv2':
         raise ValueError('Unknown impl {} for random brightness.'.format(impl))      # the build ships simclrv2 only
     b = images.shape[0]

@@ -93,6 +93,9 @@ class WarmUpAndCosineDecay:
 class LinearLayer(Layer):  # tf2/model.py:119-154
     def __init__(self, num_classes, use_bias=True, use_bn=False, name='linear_layer', **kwargs):
         # Note: use_bias is ignored for the dense layer when use_bn=True (it is used for BN's center).
+        # pad_multiple: the compute copies pad the class dimension to this multiple (64: the data gradient's reduction
+        # dimension, conv2d_dgrad needs Cout % 64 == 0 in bf16 / % 32 in fp32)
+        self.pad_multiple = kwargs.get('pad_multiple', 16)
         self.num_classes = num_classes
         self.use_bias = use_bias
         self.use_bn = use_bn
@@ -110,7 +113,8 @@ class LinearLayer(Layer):  # tf2/model.py:119-154
     def build(self, cin):
         n = self.num_classes(cin) if callable(self.num_classes) else self.num_classes
         self.nout = n
-        self.npad = (n + 15) // 16 * 16
+        pm = self.pad_multiple
+        self.npad = (n + pm - 1) // pm * pm
         RT.seed += 1
         g = torch.Generator().manual_seed(RT.seed)
         w = torch.randn(cin, n, generator=g) * 0.01                   # RandomNormal(stddev=.01), :145
@@ -126,9 +130,10 @@ class LinearLayer(Layer):  # tf2/model.py:119-154
         w4 = self.kernel.value.view(1, 1, self.cin, self.nout)
         if self.npad == self.nout:
             self.w_t = ops.prep_weights(w4, 0, dtype)
-        else:   # class dimension padded to a multiple of 16 with zero rows
+        else:   # class dimension padded to a multiple of pad_multiple with zero rows
             self.w_t = torch.zeros(self.npad, self.cin, device=RT.device, dtype=dtype)
             ops.prep_weights(w4, 0, dtype, out=self.w_t[:self.nout])
+        # class dimension padded: the data-gradient copy is made on first use (LinearLayer.backward(need_dx=True), finetune)
         self.w_d = ops.prep_weights(w4, 1, dtype) if self.npad == self.nout else None
         self._version = RT.weights_version
         self._dtype = dtype
@@ -166,6 +171,9 @@ class LinearLayer(Layer):  # tf2/model.py:119-154
             ops.colsum(dy, self.nout, self.bias.ensure_grad())
         if not need_dx:
             return None
+        if self.w_d is None:
+            # [cin, npad] with zero columns for the padded classes (the padded columns of dy are zero as well)
+            self.w_d = ops.prep_weights(self.kernel.value.view(1, 1, self.cin, self.nout), 1, dy.dtype, cout_p=self.npad)
         return ops.conv2d_dgrad(dy4, self.w_d, 1, 1, 1, 0, 1, 1).view(V, self.cin)
 
 
@@ -209,8 +217,11 @@ class ProjectionHead(Layer):  # tf2/model.py:157-213
         # The first element is the output of the projection head, the second the finetune-head input.
         return hiddens_list[-1], hiddens_list[FLAGS.ft_proj_selector]
 
-    def backward(self, d):
-        for layer in reversed(self.linear_layers):
+    def backward(self, d, upto=None):
+        """d: gradient wrt hiddens_list[upto] (default: the projection output).  Only layers 0 .. upto-1 run their
+        backward -- finetune mode's gradient enters at ft_proj_selector (tf2/model.py:268-270)."""
+        layers = self.linear_layers if upto is None else self.linear_layers[:upto]
+        for layer in reversed(layers):
             d = layer.backward(d)
         if self.linear_layers and d.dtype != self._in_dtype:
             d = ops.cast(d, self._in_dtype)
@@ -231,7 +242,8 @@ class SupLogits:
 class SupervisedHead(Layer):  # tf2/model.py:216-225
     def __init__(self, num_classes, name='head_supervised', **kwargs):
         with scope(name):
-            self.linear_layer = LinearLayer(num_classes)
+            # finetune: the gradient flows through this layer into the projection head / encoder (no stop_gradient)
+            self.linear_layer = LinearLayer(num_classes, pad_multiple=64 if FLAGS.train_mode == 'finetune' else 16)
 
     def __call__(self, inputs, training):
         z = self.linear_layer(inputs, training)
@@ -266,8 +278,6 @@ class Model(Layer):
         if inputs.dim() != 4 or inputs.shape[3] % 3 != 0:
             raise ValueError('The input channels dimension must be statically known '
                              f'(got input shape {tuple(inputs.shape)})')
-        if FLAGS.train_mode == 'finetune':
-            raise NotImplementedError('train_mode=finetune is outside the pretraining hot path')
         # (evaluation passes do not go through ops.begin_step.)  Inference mode normalises with the MOVING statistics, so nothing bounds the
         # activations to fp16's range (a freshly initialised network's moving averages do not normalise at all): the split-fp16 forward is
         # for training-mode BatchNorm only, an inference forward runs its fp32 products as six bf16 terms instead (same accuracy class).
@@ -279,10 +289,16 @@ class Model(Layer):
         k, s = self.resnet_model.stem_kernel_stride
         # (training: the 7x7 stem's weight gradient reads the image as bf16 pieces in the three-term modes -- written by the packing pass)
         rm = self.resnet_model
-        ps_cout = rm.stem_conv.filters if (training and not rm.stem_pre and not rm.cifar_stem) else 0
+        ps_cout = rm.stem_conv.filters if (training and rm.stem_trainable and not rm.stem_pre and not rm.cifar_stem) else 0
         packed = PackedInput(inputs.contiguous(), num_transforms, k, s, RT.dtype, presplit_for_cout=ps_cout)   # split + concat, :250-259
         hiddens = self.resnet_model(packed, training=training)                     # :262
         proj, sup_in = self._projection_head(hiddens, training)                    # :265-266
+        if FLAGS.train_mode == 'finetune':
+            # one view, no stop_gradient: the supervised head reads hiddens_list[ft_proj_selector] (:268-270).  Every projection
+            # layer ran (its BatchNorm moving statistics moved); the ones at and above the selector get no gradient.
+            for l in self._projection_head.linear_layers[FLAGS.ft_proj_selector:]:
+                l.release()
+            return None, self.supervised_head(sup_in, training)
         self._proj_is_encoder = proj is hiddens
         self._proj_dtype = proj.dtype
         proj32 = ops.cast(proj, torch.float32) if proj.dtype != torch.float32 else proj
@@ -300,11 +316,73 @@ class Model(Layer):
                 ops.axpy_f32(FLAGS.weight_decay * self._wd_grad_scale, k.value, k.grad)
 
     def backward(self, d_proj, d_sup=None, on_stage=None):
-        """d_proj: float32 [k*b, proj_out_dim]; d_sup: gradient wrt the supervised logits."""
+        """d_proj: float32 [k*b, proj_out_dim]; d_sup: gradient wrt the supervised logits.
+        train_mode=finetune: d_proj is None and d_sup carries the whole gradient (backward_finetune)."""
+        if FLAGS.train_mode == 'finetune':
+            return self.backward_finetune(d_sup, on_stage)
         self.backward_supervised(d_sup)
         d = ops.cast(d_proj, self._proj_dtype) if self._proj_dtype != torch.float32 else d_proj
         d = self._projection_head.backward(d)
         self.resnet_model.backward(d, on_stage=on_stage)
+
+    def backward_finetune(self, d_sup, on_stage=None):
+        """tape.gradient of the finetune loss (tf2/run.py:577-622): the supervised head (weights and, where anything below it
+        trains, its input), the projection head from ft_proj_selector downwards, then the encoder up to its first frozen layer."""
+        rm = self.resnet_model
+        sel = FLAGS.ft_proj_selector
+        encoder_trains = rm.first_trainable_group < len(rm.block_groups)
+        need_dx = encoder_trains or any(l.trainable_variables for l in self._projection_head.linear_layers[:sel])
+        lin = self.supervised_head.linear_layer
+        d = lin.backward(d_sup, need_dx=need_dx)
+        if 'lars' in FLAGS.optimizer and FLAGS.weight_decay:       # d/dw of add_weight_decay, :49-60
+            ops.axpy_f32(FLAGS.weight_decay * self._wd_grad_scale, lin.kernel.value, lin.kernel.grad)
+        if not need_dx:
+            return
+        d = self._projection_head.backward(d, upto=sel)
+        if encoder_trains:
+            rm.backward(d, on_stage=on_stage)
+
+    def variables_without_gradient(self):
+        """finetune: the projection-head variables at and above ft_proj_selector, which no path connects to the loss (tape.gradient
+        returns None for them; the L2 term of add_weight_decay may still give the kernels a gradient, see run.make_single_step)."""
+        if FLAGS.train_mode != 'finetune':
+            return []
+        return [v for l in self._projection_head.linear_layers[FLAGS.ft_proj_selector:] for v in l.trainable_variables]
+
+    def build_variables(self):
+        """Create every variable from the layer configuration alone -- no device work, in the order (and with the initial values) of
+        the lazy build of the first forward pass.  Plain ResNet encoders (no selective kernels)."""
+        rm = self.resnet_model
+        if rm.stem_pre or FLAGS.sk_ratio > 0:
+            raise NotImplementedError('build_variables: selective-kernel / ResNet-D encoders build at their first forward pass')
+        c = rm.stem_conv
+        c.build(3)
+        rm.stem_bn.build(c.filters, c.cout_p)
+        cin = c.filters
+        for g in rm.block_groups:
+            for b in g.layers:
+                # the forward's build order: shortcut conv and conv1 read the block input, then conv2 (and conv3) in sequence
+                chain = [b.conv1, b.conv2] + ([b.conv3] if isinstance(b, resnet.BottleneckBlock) else [])
+                pairs = list(zip(chain, [b.bn1, b.bn2] + ([b.bn3] if len(chain) == 3 else [])))
+                if b.shortcut is not None:
+                    pairs.insert(0, (b.shortcut.conv, b.shortcut.bn))
+                    b.shortcut.conv.build(cin)
+                x = cin
+                for cv in chain:
+                    cv.build(x)
+                    x = cv.filters
+                for cv, bn in pairs:
+                    bn.build(cv.filters, cv.cout_p)
+                cin = x
+        feats = [cin]
+        for l in self._projection_head.linear_layers:
+            l.build(feats[-1])
+            if l.use_bn:
+                l.bn_relu.build(l.npad)
+            feats.append(l.npad)
+        if self.supervised_head is not None:
+            sel = FLAGS.ft_proj_selector if FLAGS.proj_head_mode != 'none' else 0
+            self.supervised_head.linear_layer.build(feats[sel])
 
     _wd_grad_scale = 1.0   # set to 1/num_replicas by the step (loss / R, tf2/run.py:617)
 

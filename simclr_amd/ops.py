@@ -732,12 +732,13 @@ def same_pad(size, k, s):
     return out, total // 2
 
 
-def bnrelu_maxpool_fwd(x, scale, shift, ksz=3, stride=2):
+def bnrelu_maxpool_fwd(x, scale, shift, ksz=3, stride=2, want_arg=True):
+    """want_arg=False: no backward pass follows (a frozen stem) -- the tap ids are neither tracked nor stored; arg is None."""
     V, H, W, C = x.shape
     OH, pt = same_pad(H, ksz, stride)
     OW, pl = same_pad(W, ksz, stride)
     y = torch.empty(V, OH, OW, C, device=x.device, dtype=x.dtype)
-    arg = torch.empty(V, OH, OW, C, device=x.device, dtype=torch.uint8)
+    arg = torch.empty(V, OH, OW, C, device=x.device, dtype=torch.uint8) if want_arg else None
     lib().bnrelu_maxpool_fwd(_p(x), _p(scale), _p(shift), _p(y), _p(arg), V, H, W, C, OH, OW, ksz, stride,
                              pt, pl, dt(x), _s())
     return y, arg
@@ -918,12 +919,14 @@ def bn_fold_pre(w_d, scale, mean, rstd, c1, c2):
 
 
 def bn_fold_post(t1, gw, cs, a, b, d, q, dw, wext, accumulate=False):
-    """cs: column sums of h, fp64 [>=K] (bn_reduce_slots output) or fp32 [K] (conv2d_gram)."""
+    """cs: column sums of h, fp64 [>=K] (bn_reduce_slots output) or fp32 [K] (conv2d_gram).  q = wext = None: the weight gradient
+    only (no data gradient follows)."""
     K, N = t1.shape
-    assert tuple(q.shape) == (K, K) and tuple(dw.shape) == (K, N) and cs.is_contiguous()
+    assert (q is None) == (wext is None)
+    assert (q is None or tuple(q.shape) == (K, K)) and tuple(dw.shape) == (K, N) and cs.is_contiguous()
     c64, c32 = (_p(cs), None) if cs.dtype == torch.float64 else (None, _p(cs))
     lib().bn_fold_post(_p(t1), _p(gw), c64, c32, _p(a), _p(b), _p(d), _p(q), _p(dw), _p(wext), K, N, int(accumulate),
-                       dt(wext), _s())
+                       dt(wext) if wext is not None else dt(t1), _s())
     return dw
 
 

@@ -32,6 +32,13 @@ from .lars_optimizer import Variable
 
 BATCH_NORM_EPSILON = 1e-5  # tf2/resnet.py:28
 
+# BatchNorm inside layers frozen by fine_tune_after_block (train_mode=finetune) keeps running in TRAINING mode: batch statistics, moving
+# averages updated.  The reference builds its BatchNormalization objects inside BatchNormRelu / BlockGroup after
+# `super().__init__(trainable=False)`; Keras stores `_trainable` in the constructor without propagating it to sublayers created later, so
+# each BN's own `trainable` stays True, and Keras forces inference mode only for a BN whose own `trainable` is False.  (The comment at
+# tf2/resnet.py:616-618 says otherwise; the code is what runs.)  False: frozen BatchNorm normalises with its moving statistics instead.
+FROZEN_BN_USES_BATCH_STATISTICS = True
+
 
 # --------------------------------------------------------------------------- runtime context
 class _Runtime:
@@ -52,6 +59,24 @@ class _Runtime:
         self.convs = []              # every built Conv2dFixedPadding with a (w_t, w_d) pair: refreshed in one launch
         self._conv_batch = None
 
+    @property
+    def weights_version(self):
+        return self._weights_version
+
+    @weights_version.setter
+    def weights_version(self, v):
+        # a change of unknown scope (checkpoint restore, a caller writing weights): frozen layers' compute copies are stale too
+        self._weights_version = v
+        self.frozen_version = v
+
+    def optimizer_stepped(self):
+        """The optimizer updated the TRAINABLE weights: frozen layers (fine_tune_after_block) keep their compute copies."""
+        self._weights_version += 1
+
+    def frozen_key(self):
+        """What a frozen layer's compute copies depend on besides its (unchanging) master weight."""
+        return (self.frozen_version, self.dtype) + tuple(ops._TERMS)
+
     def const(self, C, value):
         """Cached constant fp32 vector on the device (means 0 / rstd 1 for plain column sums)."""
         key = (C, float(value), str(self.device))
@@ -67,6 +92,9 @@ class _Runtime:
         self.convs = [r for r in self.convs if r() is not None]      # weak references: models may have been dropped
         convs = [r() for r in self.convs]
         convs = [c for c in convs if c is not None and c.kernel is not None]
+        fk = self.frozen_key()
+        # frozen layers' copies are made once per (restore, storage mode, arithmetic mode), not after every optimizer step
+        convs = [c for c in convs if c.trainable or getattr(c, '_frozen_key', None) != fk]
         entries = [(c.kernel.value, c.cin_p, c.cout_p) for c in convs]
         if self._conv_batch is None or not self._conv_batch.matches(entries, self.dtype):
             self._conv_batch = ops.WeightPairBatch(entries, self.dtype)
@@ -74,6 +102,7 @@ class _Runtime:
             c.w_t, c.w_d = w_t, w_d
             c._version = self.weights_version
             c._dtype = self.dtype
+            c._frozen_key = None if c.trainable else fk
 
     def wgrad_stream(self):
         """Side stream for the weight-gradient kernels (SIMCLR_WGRAD_STREAM=1), else None."""
@@ -147,7 +176,19 @@ class PackedInput:
 
 
 class Layer:
-    trainable = True
+    """trainable: a layer-level switch as in Keras -- setting it to False freezes the layer and every sublayer it holds at that time; the
+    variables of a frozen layer drop out of `trainable_variables` and stay in `variables` (and in checkpoints)."""
+    _trainable = True
+
+    @property
+    def trainable(self):
+        return self._trainable
+
+    @trainable.setter
+    def trainable(self, value):
+        self._trainable = bool(value)
+        for l in self.sublayers():
+            l.trainable = value
 
     def sublayers(self):
         out = []
@@ -167,7 +208,20 @@ class Layer:
 
     @property
     def trainable_variables(self):
-        return [v for v in self.variables if v.trainable]
+        if not self.trainable:
+            return []
+        vs = [v for v in self.__dict__.values() if isinstance(v, Variable) and v.trainable]
+        for l in self.sublayers():
+            vs.extend(l.trainable_variables)
+        return vs
+
+    def release(self):
+        """Drop what a forward pass kept for a backward pass that will not come (frozen layers)."""
+        for a in ('saved', 'out', 'relu_bits', '_prep'):
+            if a in self.__dict__:
+                setattr(self, a, None)
+        for l in self.sublayers():
+            l.release()
 
 
 def _variance_scaling(shape, fan_in, gen):
@@ -240,7 +294,7 @@ class BatchNormRelu(Layer):  # tf2/resnet.py:31-78
             self.build(inputs.c, C)
         g, b = self._pg, self._pb
         rows = math.prod(inputs.shape[:-1])
-        if training:
+        if training and (self.trainable or FROZEN_BN_USES_BATCH_STATISTICS):
             if inputs.stats is None and sums is None:
                 raise NotImplementedError('BatchNormRelu input must come from a conv/dense epilogue')
             if sums is not None:
@@ -457,9 +511,12 @@ class Conv2dFixedPadding(Layer):  # tf2/resnet.py:183-208
     def _refresh(self, stem_geo=None):
         if self._version == RT.weights_version and getattr(self, '_dtype', None) == RT.dtype:
             return
+        if not self.trainable and self._version >= 0 and getattr(self, '_frozen_key', None) == RT.frozen_key():
+            return                  # frozen (fine_tune_after_block): the optimizer step did not change this weight
         w = self.kernel.value
         if stem_geo is not None:
             self.w_s = ops.prep_weights(w, 2, RT.dtype, stem_geo['KHP'], stem_geo['KWP'], cout_p=self.cout_p)
+            self._frozen_key = None if self.trainable else RT.frozen_key()
         else:
             # first refresh of a layer (lazy build during the first forward) or a layer outside the registry (built under
             # an earlier RT.reset()): its own launch; afterwards every version bump refreshes ALL layers with one launch
@@ -561,7 +618,7 @@ class Conv2dFixedPadding(Layer):  # tf2/resnet.py:183-208
         return ops.conv2d_fwd_bn_apply(x, self.w_t, k, k, s, pad, OH, OW, scale, shift, res=res, relu=relu,
                                        want_bits=want_bits, rscale=rs, rshift=rb)
 
-    def backward_folded(self, dm, bn_out, partial, fuse_bn, s2_from_gemm=False, dx_out=None, accumulate=False):
+    def backward_folded(self, dm, bn_out, partial, fuse_bn, s2_from_gemm=False, dx_out=None, accumulate=False, need_dx=True):
         """1x1 stride-1 conv whose output c = h W goes through `bn_out` (BatchNorm, no ReLU before the add): the BN backward
         dh = a*dm + b*c + d is folded into this layer's gradients by linearity (csrc/bn.hip bn_fold_*), so neither the
         streaming BN-backward pass nor dh exists.  dm: masked gradient wrt bn_out's output; coeffs = (c1, c2) of bn_out.
@@ -583,7 +640,10 @@ class Conv2dFixedPadding(Layer):  # tf2/resnet.py:183-208
             coeffs = bn_out._bwd_finalize(partial, st['count'])
         a, b, d, wb, wext, e = ops.bn_fold_pre(self.w_d, st['scale'], st['mean'], st['rstd'], coeffs[0], coeffs[1])
         w_d32, w_t32 = self._f32_copies()
-        q = ops.small_gemm_nt(wb, w_d32)                                                        # (W*b) W^T   [K, K]
+        # (W*b) W^T [K, K] and wext's last K columns feed the data gradient only: skipped when none follows (freezing boundary)
+        q = ops.small_gemm_nt(wb, w_d32) if need_dx else None
+        if not need_dx:
+            wext = None
         if self.kernel.trainable:
             with _wgrad_side_stream(h, dm):
                 if sv.get('gram') is not None and sv.get('gram_version') == self._version:
@@ -600,6 +660,8 @@ class Conv2dFixedPadding(Layer):  # tf2/resnet.py:183-208
             z = torch.zeros(K, N, device=h.device)
             ops.bn_fold_post(z, z, torch.zeros(K, device=h.device), a, b, d, q, torch.empty(K, N, device=h.device), wext)
         join_wgrad_stream()                       # wext's last K columns come from bn_fold_post
+        if not need_dx:                           # the input is a frozen layer's output (fine_tune_after_block boundary)
+            return None, None
         if fuse_bn is None:                       # conv input is not a BatchNorm output (projection shortcut at a block entry)
             return ops.conv2d_dgrad_ext(dm, h, wext, e, out=dx_out, accumulate=accumulate), None
         return ops.conv2d_dgrad_bn_ext(dm, h, wext, e, fuse_bn)
@@ -804,16 +866,20 @@ class _Shortcut(Layer):
                 not self.resnet_d and c.strides == 1 and c.kernel is not None and not c.padded and
                 ops.gram_supported(c.cin_p, RT.dtype) and _bn_fold_enabled() and _bn_s2_enabled())
 
-    def backward_folded(self, d_sum, partial):
+    def backward_folded(self, d_sum, partial, need_dx=True):
         """partial: slots whose sum(dm) part is valid for d_sum (the tail BN's, same upstream gradient)."""
-        d, _ = self.conv.backward_folded(d_sum, self.bn, partial, None, s2_from_gemm=True)
+        d, _ = self.conv.backward_folded(d_sum, self.bn, partial, None, s2_from_gemm=True, need_dx=need_dx)
         self.bn.saved = None
         return d
 
-    def backward(self, d_sum, coeffs=None, sparse=False):
+    def backward(self, d_sum, coeffs=None, sparse=False, need_dx=True):
         """sparse: the caller completes the result with an accumulating data gradient (the block's conv1) -- a strided 1x1 projection
-        then stores only the quarter of dx that receives a tap (ops.conv2d_dgrad sparse: no zero fill, nothing read back from it)."""
+        then stores only the quarter of dx that receives a tap (ops.conv2d_dgrad sparse: no zero fill, nothing read back from it).
+        need_dx=False: the block input is a frozen layer's output -- weight gradients only."""
         d_raw, _ = self.bn.backward(d_sum, mask_mode=0, coeffs=coeffs, ps_for=self.conv)
+        if not need_dx:
+            self.conv.backward(d_raw, need_dx=False)
+            return None
         sp = (sparse and not self.resnet_d and self.conv.strides == 2 and not self.conv.padded and ops.sparse_dgrad_enabled(RT.dtype))
         d = self.conv.backward(d_raw, sparse=sp)
         if self.resnet_d:
@@ -833,7 +899,7 @@ def _block_entry(block, inputs, training):
     return raw_sc.t, sc_bn, block.bn1(raw1, training)
 
 
-def _block_tail_backward(block, bn_tail, dout, dout_partial, conv_tail=None, sparse_shortcut=False):
+def _block_tail_backward(block, bn_tail, dout, dout_partial, conv_tail=None, sparse_shortcut=False, need_dx=True):
     """Backward of relu(bn_tail(h) + shortcut): returns (dh, dx_shortcut_path).  When the tail's reduce arrived fused
     (dout_partial) and the block has a projection shortcut, the two BatchNorm backward reductions -- same upstream
     gradient -- share one statistics exchange."""
@@ -843,12 +909,13 @@ def _block_tail_backward(block, bn_tail, dout, dout_partial, conv_tail=None, spa
             sc_part = block.shortcut.bn.bwd_reduce(dsum, mask_mode=0)
             co_t, co_s = bwd_finalize_many([(bn_tail, dout_partial), (block.shortcut.bn, sc_part)])
             dh = bn_tail.backward_fused(dout, dout_partial, coeffs=co_t, ps_for=conv_tail)
-            return dh, block.shortcut.backward(dsum, coeffs=co_s, sparse=sparse_shortcut)
+            return dh, block.shortcut.backward(dsum, coeffs=co_s, sparse=sparse_shortcut, need_dx=need_dx)
         dh = bn_tail.backward_fused(dout, dout_partial, ps_for=conv_tail)
     else:
         dh, dsum = bn_tail.backward(dout, mask_src=block.out, mask_mode=1, want_masked=True, ps_for=conv_tail)
-    dx = block.shortcut.backward(dsum, sparse=sparse_shortcut) if block.shortcut is not None else dsum
-    return dh, dx
+    if block.shortcut is not None:
+        return dh, block.shortcut.backward(dsum, sparse=sparse_shortcut, need_dx=need_dx)
+    return dh, (dsum if need_dx else None)
 
 
 class ResidualBlock(Layer):  # tf2/resnet.py:314-382
@@ -867,21 +934,25 @@ class ResidualBlock(Layer):  # tf2/resnet.py:314-382
     def __call__(self, inputs, training):
         sc, sc_bn, h = _block_entry(self, inputs, training)
         h = self.conv2(h, training)
-        out = self.bn2(h, training, relu=True, add=sc, add_bn=sc_bn, want_bits=training)     # relu(inputs + shortcut), :382
+        out = self.bn2(h, training, relu=True, add=sc, add_bn=sc_bn, want_bits=training and self.trainable)   # relu(inputs + shortcut), :382
         self.out = out.t
         return out
 
     def tail_info(self):
         return self.bn2.fusion_info(mask_src=self.out)
 
-    def backward(self, dout, dout_partial=None, prev_tail=None):
+    def backward(self, dout, dout_partial=None, prev_tail=None, need_dx=True):
         """dout_partial given: dout is already ReLU-masked and the tail BN's reduce is done (fused into
         the next block's dgrad).  prev_tail: tail_info() of the block feeding this one -- its reduce is
-        fused into this block's last dgrad.  Returns (dx, partial-or-None)."""
-        dh, dx = _block_tail_backward(self, self.bn2, dout, dout_partial, self.conv2)
+        fused into this block's last dgrad.  need_dx=False: the block input is a frozen layer's output
+        (fine_tune_after_block) -- weight gradients only.  Returns (dx, partial-or-None)."""
+        dh, dx = _block_tail_backward(self, self.bn2, dout, dout_partial, self.conv2, need_dx=need_dx)
         self.out = None
         dm1, part1 = self.conv2.backward(dh, fuse_bn=self.bn1.fusion_info())
         dh1 = self.bn1.backward_fused(dm1, part1, ps_for=self.conv1)
+        if not need_dx:
+            self.conv1.backward(dh1, need_dx=False)
+            return None, None
         if prev_tail is not None and self.conv1.strides == 1:
             return self.conv1.backward(dh1, dx_out=dx, accumulate=True, fuse_bn=prev_tail)
         self.conv1.backward(dh1, dx_out=dx, accumulate=True)
@@ -923,14 +994,15 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
             # either (folded BatchNorm backward, sum(dm*x^) from the weight-gradient GEMM).
             st = self.conv3.forward_gram_stats(h) if _conv3_stats_from_gram() else self.conv3.forward_stats_only(h)
             scale, shift = self.bn3.prepare(st, training)
-            y, bits = self.conv3.forward_bn_apply(h, scale, shift, res=sc, relu=True, want_bits=True, res_bn=sc_bn)
+            r = self.conv3.forward_bn_apply(h, scale, shift, res=sc, relu=True, want_bits=self.trainable, res_bn=sc_bn)
+            y, bits = r if self.trainable else (r, None)        # a frozen block keeps no ReLU mask: no backward pass reads it
             self.bn3.relu_bits = bits
             self.bn3.saved['y'] = y
             self.bn3.saved['masked'] = True
             out = Act(y, c=st.c)
         else:
             h = self.conv3(h, training)
-            out = self.bn3(h, training, relu=True, add=sc, add_bn=sc_bn, want_bits=training)     # relu(inputs + shortcut), :487
+            out = self.bn3(h, training, relu=True, add=sc, add_bn=sc_bn, want_bits=training and self.trainable)   # relu(inputs + shortcut), :487
         self.out = out.t
         return out
 
@@ -957,7 +1029,7 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
         # foldable tail: the consumer's dgrad epilogue only masks and sums dm (no read of this block's conv3 output)
         return self.bn3.fusion_info(mask_src=self.out, sums_only=self._foldable() and _bn_s2_enabled())
 
-    def backward(self, dout, dout_partial=None, prev_tail=None):
+    def backward(self, dout, dout_partial=None, prev_tail=None, need_dx=True):
         """See ResidualBlock.backward.  Returns (dx, partial-or-None)."""
         fold = dout_partial is not None and self._foldable()
         if getattr(self, 'fused_tail', False) and not fold:
@@ -969,9 +1041,9 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
             if self.shortcut is None:
                 dx = dout
             elif self.shortcut.foldable():
-                dx = self.shortcut.backward_folded(dout, dout_partial)
+                dx = self.shortcut.backward_folded(dout, dout_partial, need_dx=need_dx)
             else:
-                dx = self.shortcut.backward(dout, sparse=True)        # completed by conv1's accumulating data gradient below
+                dx = self.shortcut.backward(dout, sparse=True, need_dx=need_dx)   # completed by conv1's accumulating data gradient below
             self.out = None
             dm2, part2 = self.conv3.backward_folded(dout, self.bn3, dout_partial, fuse_bn=self.bn2.fusion_info(),
                                                     s2_from_gemm=_bn_s2_enabled())
@@ -982,11 +1054,14 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
                 dh1 = self.bn1.backward_fused(dm1, part1, ps_for=self.conv1)
             else:
                 dh1, _ = self.bn1.backward(self.conv2.backward(dh2), ps_for=self.conv1)
+            if not need_dx:
+                self.conv1.backward(dh1, need_dx=False)
+                return None, None
             if prev_tail is not None:
                 return self.conv1.backward(dh1, dx_out=dx, accumulate=True, fuse_bn=prev_tail)
             self.conv1.backward(dh1, dx_out=dx, accumulate=True)
             return dx, None
-        dh3, dx = _block_tail_backward(self, self.bn3, dout, dout_partial, self.conv3, sparse_shortcut=True)
+        dh3, dx = _block_tail_backward(self, self.bn3, dout, dout_partial, self.conv3, sparse_shortcut=True, need_dx=need_dx)
         self.out = None
         if self.sk is not None:
             dsk = self.conv3.backward(dh3)
@@ -1003,6 +1078,9 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
                 dh1 = self.bn1.backward_fused(dm1, part1, ps_for=self.conv1)
             else:
                 dh1, _ = self.bn1.backward(self.conv2.backward(dh2), ps_for=self.conv1)
+        if not need_dx:
+            self.conv1.backward(dh1, need_dx=False)
+            return None, None
         if prev_tail is not None:
             return self.conv1.backward(dh1, dx_out=dx, accumulate=True, fuse_bn=prev_tail)
         self.conv1.backward(dh1, dx_out=dx, accumulate=True)
@@ -1024,13 +1102,16 @@ class BlockGroup(Layer):  # tf2/resnet.py:490-526
     def __call__(self, inputs, training):
         for layer in self.layers:
             inputs = layer(inputs, training)
+            if not self.trainable:
+                layer.release()          # frozen (fine_tune_after_block): nothing is kept for a backward pass
         return inputs
 
-    def backward(self, d, partial=None, prev_tail=None):
-        """prev_tail: tail_info() of the last block of the previous group (None for group 1)."""
+    def backward(self, d, partial=None, prev_tail=None, need_dx=True):
+        """prev_tail: tail_info() of the last block of the previous group (None for group 1).  need_dx=False: this group's
+        input is a frozen layer's output -- the first block launches its weight gradients but no data gradient of its input."""
         for i in range(len(self.layers) - 1, -1, -1):
             pt = self.layers[i - 1].tail_info() if i > 0 else prev_tail
-            d, partial = self.layers[i].backward(d, partial, pt)
+            d, partial = self.layers[i].backward(d, partial, pt, need_dx=need_dx or i > 0)
         return d, partial
 
 
@@ -1042,8 +1123,6 @@ class Resnet(Layer):  # tf2/resnet.py:529-699
             dropblock_keep_probs = [None] * 4
         if not isinstance(dropblock_keep_probs, list) or len(dropblock_keep_probs) != 4:
             raise ValueError('dropblock_keep_probs is not valid:', dropblock_keep_probs)   # :546-547
-        if FLAGS.train_mode == 'finetune' and FLAGS.fine_tune_after_block != -1:
-            raise NotImplementedError('layer freezing (fine_tune_after_block) is outside the pretraining hot path')
         self.cifar_stem = cifar_stem
         self.resnet_d = (not cifar_stem) and FLAGS.sk_ratio > 0
         self.endpoints = {}
@@ -1074,6 +1153,25 @@ class Resnet(Layer):  # tf2/resnet.py:529-699
                                                     dropblock_keep_prob=dropblock_keep_probs[i],
                                                     dropblock_size=dropblock_size))
             self.block_groups[-1].layers[-1].is_final = True     # its output feeds the pooling: no consumer conv folds its tail
+        self._apply_freezing()
+
+    def _apply_freezing(self):
+        """Layer freezing of tf2/resnet.py:548-691 (train_mode=finetune).  fine_tune_after_block = -1: nothing frozen; k in 0..3: the
+        stem and block_group1 .. block_group{k} (stop_gradient on the input of block_group{k+1}); 4 -- and, by the reference's
+        construction, any other value -- the whole encoder.  `first_trainable_group`: index of the first block group whose variables
+        train (4: none); `stem_trainable`: the stem's."""
+        k = FLAGS.fine_tune_after_block
+        if FLAGS.train_mode != 'finetune' or k == -1:
+            self.stem_trainable, self.first_trainable_group = True, 0
+            return
+        self.stem_trainable = False
+        self.first_trainable_group = k if 0 <= k <= 3 else 4
+        for l in self.stem_pre + [self.stem_conv, self.stem_bn]:
+            l.trainable = False
+        for g in self.block_groups[:self.first_trainable_group]:
+            g.trainable = False
+        if self.first_trainable_group == 4:
+            self.trainable = False
 
     @property
     def stem_kernel_stride(self):
@@ -1097,9 +1195,13 @@ class Resnet(Layer):  # tf2/resnet.py:529-699
             self._pool = None
         else:                                                                    # BN+ReLU+maxpool, :602-611
             scale, shift = self.stem_bn.prepare(raw, training)
-            y, arg = ops.bnrelu_maxpool_fwd(raw.t, scale, shift, 3, 2)
-            self._pool = dict(arg=arg, H=raw.t.shape[1], W=raw.t.shape[2])
+            keep = self.stem_trainable                # a frozen stem's backward never runs: no tap ids
+            y, arg = ops.bnrelu_maxpool_fwd(raw.t, scale, shift, 3, 2, want_arg=keep)
+            self._pool = dict(arg=arg, H=raw.t.shape[1], W=raw.t.shape[2]) if keep else None
             x = Act(y)
+        if not self.stem_trainable:
+            for l in self.stem_pre + [self.stem_conv, self.stem_bn]:
+                l.release()
         self.endpoints['initial_max_pool'] = x.t
         for i, g in enumerate(self.block_groups):
             x = g(x, training)
@@ -1112,18 +1214,27 @@ class Resnet(Layer):  # tf2/resnet.py:529-699
 
     def backward(self, dh, on_stage=None):
         """dh: [V, C] gradient wrt the pooled features.  on_stage(i) is called when block group
-        i (4..1) has finished its backward, and on_stage(0) after the stem (gradient bucketing)."""
+        i (4..1) has finished its backward, and on_stage(0) after the stem (gradient bucketing).
+        With frozen layers (fine_tune_after_block) the pass stops at the first trainable group: its first block computes
+        weight gradients only, no fusion reaches across the boundary, and neither the frozen groups nor the stem run."""
+        g0 = self.first_trainable_group
+        if g0 >= len(self.block_groups):
+            raise RuntimeError('Resnet.backward with the whole encoder frozen (fine_tune_after_block=%d)' % FLAGS.fine_tune_after_block)
         _, H, W, _ = self._final.shape
         if dh.dtype != self._final.dtype:
             dh = ops.cast(dh, self._final.dtype)
         d = ops.global_avgpool_bwd(dh, H, W)
         self._final = None
         partial = None
-        for i, g in reversed(list(enumerate(self.block_groups))):
-            prev_tail = self.block_groups[i - 1].layers[-1].tail_info() if i > 0 else None
-            d, partial = g.backward(d, partial, prev_tail)
+        for i in range(len(self.block_groups) - 1, g0 - 1, -1):
+            boundary = i == g0 and not self.stem_trainable
+            prev_tail = self.block_groups[i - 1].layers[-1].tail_info() if (i > 0 and not boundary) else None
+            d, partial = self.block_groups[i].backward(d, partial, prev_tail, need_dx=not boundary)
             if on_stage is not None:
                 on_stage(i + 1)
+        if not self.stem_trainable:
+            self.endpoints = {}
+            return None
         if self._pool is not None:
             sb = self.stem_bn.saved
             C = sb['x'].shape[-1]

@@ -1,4 +1,4 @@
-"""The pretraining step and driver -- mirror of /root/reference/tf2/run.py for the hot path.
+"""The training step and driver -- mirror of /root/reference/tf2/run.py for the hot path.
 
 `make_single_step` restates `single_step` (tf2/run.py:557-622) line for line on the HIP
 kernels: model forward, contrastive + supervised losses, metrics, weight decay, loss / R,
@@ -42,22 +42,30 @@ class GradSync:
 
     Gradients live in ONE flat fp32 buffer ordered last-layer-first, cut into buckets at block
     group boundaries; each bucket's all-reduce is issued asynchronously as soon as the backward
-    pass has produced it, so xGMI traffic overlaps the remaining dgrad/wgrad kernels."""
+    pass has produced it, so xGMI traffic overlaps the remaining dgrad/wgrad kernels.  Frozen
+    block groups (finetune, fine_tune_after_block) have no gradients and no bucket; buckets the
+    backward pass never announced (the whole encoder frozen) are issued by `wait`."""
 
     def __init__(self, model, strategy):
         self.strategy = strategy
         self.flat = model._flat_grads
         order, offs = model._flat_order, model._flat_offsets
-        marks = ['block_group4', 'block_group3', 'block_group2', 'block_group1']
         cuts = [0]
-        for mk in marks:                      # bucket k ends where block group (4-k) ends
-            last = max(i for i, v in enumerate(order) if mk in v.name)
+        self.stage_to_bucket = {}
+        for g in (4, 3, 2, 1):                # a bucket ends where a (trainable) block group ends
+            mk = 'block_group%d' % g
+            idx = [i for i, v in enumerate(order) if mk in v.name]
+            if not idx:
+                continue
+            last = idx[-1]
             end = offs[last + 1] if last + 1 < len(order) else self.flat.numel()
+            self.stage_to_bucket[g] = len(cuts) - 1
             cuts.append(end)
+        self._groups = len(cuts) - 1
         cuts.append(self.flat.numel())
         self.ranges = [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
-        self.stage_to_bucket = {4: 0, 3: 1, 2: 2, 1: 3}
         self.works = []
+        self.issued = set()
 
     def on_stage(self, stage):
         """Called by the backward pass after block group `stage` (4..1) is done; 0 = stem done."""
@@ -65,16 +73,25 @@ class GradSync:
             return
         join_wgrad_stream()          # this bucket's weight gradients may still be running on the side stream
         if stage == 0:
-            idx = len(self.ranges) - 1 if len(self.ranges) > 4 else None
+            idx = len(self.ranges) - 1 if len(self.ranges) > self._groups else None
         else:
             idx = self.stage_to_bucket.get(stage)
         if idx is None or idx >= len(self.ranges):
             return
+        self._issue(idx)
+
+    def _issue(self, idx):
         a, b = self.ranges[idx]
+        self.issued.add(idx)
         self.works.append(dist.all_reduce(self.flat[a:b], op=dist.ReduceOp.SUM,
                                           group=getattr(self.strategy, 'grad_group', self.strategy.group), async_op=True))
 
     def wait(self):
+        if collectives_on(self.strategy):
+            for idx in range(len(self.ranges)):
+                if idx not in self.issued:
+                    self._issue(idx)
+        self.issued = set()
         for w in self.works:
             w.wait()
         self.works = []
@@ -96,7 +113,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
         def supervised_part():
             if supervised_head_outputs is not None:
                 l = labels['labels'] if isinstance(labels, dict) else labels
-                # labels are reused for both views (tf2/run.py:599-600: l = concat([l, l], 0))
+                # pretraining: labels are reused for both views (tf2/run.py:599-600: l = concat([l, l], 0)); finetune: one view
                 sup_box['loss'] = obj_lib.add_supervised_loss(labels=l, logits=supervised_head_outputs)   # :601
         if projection_head_outputs is not None:
             outputs = projection_head_outputs
@@ -113,6 +130,13 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
         if model._flat_grads is None:
             model.allocate_flat_grads()
             state['sync'] = GradSync(model, strategy)
+            # finetune: variables no path connects to the loss get no gradient -- tape.gradient returns None and apply_gradients
+            # drops the pair, so they stay bitwise unchanged; with momentum / Adam the L2 term of add_weight_decay (tf2/model.py:62-69)
+            # still gives their non-BatchNorm kernels the gradient wd * w, which the update kernel adds
+            lars = isinstance(optimizer, model_lib.lars_optimizer.LARSOptimizer)
+            skip = {id(v) for v in model.variables_without_gradient()
+                    if lars or not getattr(optimizer, '_takes_l2', lambda n: False)(v.name)}
+            state['apply'] = [v for v in model._flat_order if id(v) not in skip]
         sync = state['sync']
         model._wd_grad_scale = 1.0 / R
         # NT-Xent backward launches the reduce-scatter of the key-side gradient (transpose of collective A); the
@@ -120,13 +144,17 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
         if con_loss is not None:
             con_loss.backward_start(1.0 / R)
         d_sup = sup_loss.backward() if sup_loss is not None else None
-        model.backward_supervised(d_sup)
-        d_proj = con_loss.backward_finish() if con_loss is not None else None
-        model.backward(d_proj, None, on_stage=sync.on_stage)
+        if FLAGS.train_mode == 'finetune':
+            # no stop_gradient: supervised head -> projection head below ft_proj_selector -> trainable encoder layers
+            model.backward(None, d_sup, on_stage=sync.on_stage)
+        else:
+            model.backward_supervised(d_sup)
+            d_proj = con_loss.backward_finish() if con_loss is not None else None
+            model.backward(d_proj, None, on_stage=sync.on_stage)
         join_wgrad_stream()
         sync.wait()
-        optimizer.apply_gradients([(v.grad, v) for v in model._flat_order])                # :622
-        RT.weights_version += 1
+        optimizer.apply_gradients([(v.grad, v) for v in state['apply']])                   # :622
+        RT.optimizer_stepped()
         ops.end_step()
         if strategy is not None:
             strategy.check_health()          # a timed-out statistics exchange of an earlier step raises here (no device sync)
@@ -182,10 +210,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
     return single_step
 
 
-def synthetic_batches(batch, image_size, num_classes, device, seed=0, pool=2):
-    """i.i.d. U[0,1) two-view batches [b, H, W, 6] + one-hot labels."""
+def synthetic_batches(batch, image_size, num_classes, device, seed=0, pool=2, views=2):
+    """i.i.d. U[0,1) two-view batches [b, H, W, 6] + one-hot labels; views=1: the single-view
+    [b, H, W, 3] batches of train_mode=finetune (tf2/data.py:52-58)."""
     g = torch.Generator(device='cpu').manual_seed(seed)
-    feats = [torch.rand(batch, image_size, image_size, 6, generator=g).to(device) for _ in range(pool)]
+    feats = [torch.rand(batch, image_size, image_size, 3 * views, generator=g).to(device) for _ in range(pool)]
     labs = [torch.nn.functional.one_hot(torch.randint(0, num_classes, (batch,), generator=g), num_classes)
             .float().to(device) for _ in range(pool)]
     i = 0
@@ -350,7 +379,8 @@ def main(argv):
     optimizer = model_lib.build_optimizer(learning_rate)
     step_fn = make_single_step(model, optimizer, strategy)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
-    data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep)
+    data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep,
+                             views=1 if FLAGS.train_mode == 'finetune' else 2)
     manager = None
     summary_writer = metrics.JsonlSummaryWriter(FLAGS.model_dir) if (FLAGS.model_dir and rank0) else None   # :526
     log_every = FLAGS.checkpoint_steps or 10
