@@ -82,6 +82,22 @@ int simclr_ntxent_bwd(const float* z_local, const float* z_all, int n, int N, in
 /* dense logits_ab [n,N] (objective.py:80,89) for API parity only; not on the hot path. */
 int simclr_ntxent_logits_ab(const float* z_local, const float* z_all, int n, int N, int D,
                             float temperature, float* logits_ab, simclr_stream_t stream);
+/* Wide NT-Xent: the same three computations for ANY width D (proj_out_dim > 256; proj_head_mode=none feeds the encoder's
+ * 512 ... 8192-wide output), as LDS-tiled GEMMs with a k-loop over D.  D is a plain width (no option bits); `terms` is the matrix
+ * arithmetic, and only 0 = exact fp32-input MFMA is implemented (anything else returns an error).  The backward writes dS once
+ * into the workspace ([2n, 2N] fp32, padded to the tile) and runs dz_local = dS z_all and dz_all = dS^T z_local as two GEMMs:
+ * no atomics, bitwise run-to-run deterministic.  A workspace holds one fwd/bwd pair, as for simclr_ntxent_fwd. */
+size_t simclr_ntxent_wide_workspace_bytes(int n, int N, int D);
+/* objective.py:55-87 + metrics.py:28-31, arguments and outputs as simclr_ntxent_fwd. */
+int simclr_ntxent_wide_fwd(const float* z_local, const float* z_all, int n, int N, int D, int terms, int rank,
+                           float temperature, float* out, float* row_stats, void* workspace, simclr_stream_t stream);
+/* tape.gradient of objective.py:76-87 + metrics.py:33-35, arguments and outputs as simclr_ntxent_bwd. */
+int simclr_ntxent_wide_bwd(const float* z_local, const float* z_all, int n, int N, int D, int terms, int rank,
+                           float temperature, const float* row_stats, float grad_scale, float* dz_local,
+                           float* dz_all, float* out, void* workspace, simclr_stream_t stream);
+/* dense logits_ab [n,N] (objective.py:80,89) on the matrix cores. */
+int simclr_ntxent_wide_logits_ab(const float* z_local, const float* z_all, int n, int N, int D, int terms,
+                                 float temperature, float* logits_ab, simclr_stream_t stream);
 
 /* ---- LARS: tf2/lars_optimizer.py:83-137 (_resource_apply_dense), all tensors in 2 launches ---- */
 /* table: device int64[5*T] = {w ptrs | g ptrs | v ptrs | numel | flags(bit0 use_weight_decay :139-148,

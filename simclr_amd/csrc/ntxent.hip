@@ -610,6 +610,301 @@ size_t ws_floats(int n, int N, int D) {
   return off_rowterm(p, D) + (size_t)2 * p.rows_pad_q;
 }
 
+// ==============================================================================
+// Wide NT-Xent: any D (proj_out_dim > 256, proj_head_mode=none: the encoder's 512 ... 8192-wide pooled output).
+// The sweeps above keep a whole D-wide row per lane in registers and a 64 x D tile in LDS, which stops at D = 256.  Here every
+// product is an LDS-tiled GEMM with a k-loop in chunks of kWKc, on the same fp32-input MFMA (exact f32) and the same formulation:
+//   forward   S = Q K^T (keys = MFMA rows, queries = lane columns) -> per (query, 16*W-key strip) partial row statistics in the
+//             forward-sweep record format -> ntxent_finalize_rows / ntxent_reduce_out (fixed-order merges, shared with the sweeps);
+//   backward  S recomputed -> dS = (softmax - onehot) * grad_scale / (n T) written ONCE as a [rows_pad_q, rows_pad_k] fp32 array
+//             (plus the entropy partials) -> dz_local = dS K and dz_all = dS^T Q as two GEMMs, each output element one MFMA chain
+//             over the whole k range (no split-k, no atomics: bitwise run-to-run deterministic).
+// A workgroup (4 waves, 2 x 2) owns an E x E output tile, E = 32 W (W = 2: 64, W = 4: 128); a wave owns W x W 16x16 blocks.
+// Operands are staged global -> registers -> LDS one chunk ahead (the loads of chunk c+1 run under the MFMAs of chunk c), each in
+// its global orientation: RK = X[r * ld + k] (row r holds k contiguous), KR = X[k * ld + r].  Loads past the logical extents read
+// zeros, so D, n and N need no padding.
+// ==============================================================================
+constexpr int kWKc = 32;   // k per LDS stage
+
+template <int E> constexpr int wop_floats() { return E * (kWKc + 4); }   // LDS floats per staged operand (RK pitch kWKc+4, KR pitch E+4)
+
+// the float4s of one E x kWKc operand chunk this thread moves: RK -> (row r, k..k+3), KR -> (k, rows r..r+3); zeros out of range
+template <int E, bool KR>
+__device__ __forceinline__ void w_fetch(float4* pf, const float* __restrict__ X, int ld, int rlim, int klim, int r0, int k0, bool vec,
+                                        int tid) {
+#pragma unroll
+  for (int j = 0; j < E * kWKc / 1024; ++j) {
+    const int idx = tid + j * 256;
+    const int r = KR ? (idx % (E / 4)) * 4 : idx / (kWKc / 4);
+    const int k = KR ? idx / (E / 4) : (idx % (kWKc / 4)) * 4;
+    const int gr = r0 + r, gk = k0 + k;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (KR) {
+      if (gk < klim) {
+        const float* p = X + (size_t)gk * ld + gr;
+        if (vec && gr + 3 < rlim) v = *(const float4*)p;
+        else {
+          if (gr < rlim) v.x = p[0];
+          if (gr + 1 < rlim) v.y = p[1];
+          if (gr + 2 < rlim) v.z = p[2];
+          if (gr + 3 < rlim) v.w = p[3];
+        }
+      }
+    } else {
+      if (gr < rlim) {
+        const float* p = X + (size_t)gr * ld + gk;
+        if (vec && gk + 3 < klim) v = *(const float4*)p;
+        else {
+          if (gk < klim) v.x = p[0];
+          if (gk + 1 < klim) v.y = p[1];
+          if (gk + 2 < klim) v.z = p[2];
+          if (gk + 3 < klim) v.w = p[3];
+        }
+      }
+    }
+    pf[j] = v;
+  }
+}
+template <int E, bool KR>
+__device__ __forceinline__ void w_store(float* s, const float4* pf, int tid) {
+#pragma unroll
+  for (int j = 0; j < E * kWKc / 1024; ++j) {
+    const int idx = tid + j * 256;
+    if (KR) *(float4*)(s + (idx / (E / 4)) * (E + 4) + (idx % (E / 4)) * 4) = pf[j];
+    else *(float4*)(s + (idx / (kWKc / 4)) * (kWKc + 4) + (idx % (kWKc / 4)) * 4) = pf[j];
+  }
+}
+// MFMA operand of tile row rr for the 16-k group kq: component j = X(rr, 16 kq + 4 g + j) -- k-slot g of MFMA step j (both
+// operands use this k order).  The pitches (kWKc+4, E+4 = 4 mod 64 dwords) keep both reads free of bank conflicts.
+template <int E, bool KR>
+__device__ __forceinline__ float4 w_frag(const float* s, int rr, int kq, int g) {
+  if (KR) {
+    const float* p = s + (16 * kq + 4 * g) * (E + 4) + rr;
+    return make_float4(p[0], p[E + 4], p[2 * (E + 4)], p[3 * (E + 4)]);
+  }
+  return *(const float4*)(s + rr * (kWKc + 4) + 16 * kq + 4 * g);
+}
+
+// acc[i][w][r] = sum_k A(m, k) B(n, k) for m = m0 + 16 W wm + 16 i + 4 g + r, n = n0 + 16 W wn + 16 w + fl  (wm = wave & 1,
+// wn = wave >> 1): rows on the MFMA's A side, columns on the lane.  k runs 0 .. K-1 in a fixed order.
+template <int W, bool A_KR, bool B_KR>
+__device__ __forceinline__ void wide_tile(float* lds, const float* __restrict__ A, int lda, int mlim, bool avec,
+                                          const float* __restrict__ B, int ldb, int nlim, bool bvec, int K, int m0, int n0,
+                                          f32x4 (&acc)[W][W]) {
+  constexpr int E = 32 * W;
+  float* sa = lds;
+  float* sb = lds + wop_floats<E>();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
+#pragma unroll
+  for (int i = 0; i < W; ++i)
+#pragma unroll
+    for (int w = 0; w < W; ++w) acc[i][w] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float4 pa[E * kWKc / 1024], pb[E * kWKc / 1024];
+  const int nst = (K + kWKc - 1) / kWKc;
+  if (nst > 0) {
+    w_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, 0, avec, tid);
+    w_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, 0, bvec, tid);
+  }
+  for (int st = 0; st < nst; ++st) {
+    __syncthreads();
+    w_store<E, A_KR>(sa, pa, tid);
+    w_store<E, B_KR>(sb, pb, tid);
+    __syncthreads();
+    if (st + 1 < nst) {
+      w_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, (st + 1) * kWKc, avec, tid);
+      w_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, (st + 1) * kWKc, bvec, tid);
+    }
+#pragma unroll
+    for (int kq = 0; kq < kWKc / 16; ++kq) {
+      float4 a[W], b[W];
+#pragma unroll
+      for (int i = 0; i < W; ++i) a[i] = w_frag<E, A_KR>(sa, 16 * W * wm + 16 * i + fl, kq, g);
+#pragma unroll
+      for (int w = 0; w < W; ++w) b[w] = w_frag<E, B_KR>(sb, 16 * W * wn + 16 * w + fl, kq, g);
+#pragma unroll
+      for (int i = 0; i < W; ++i)
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b[w].x, acc[i][w], 0, 0, 0);
+          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b[w].y, acc[i][w], 0, 0, 0);
+          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b[w].z, acc[i][w], 0, 0, 0);
+          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b[w].w, acc[i][w], 0, 0, 0);
+        }
+    }
+  }
+}
+
+// Forward: S tile (blockIdx.x = key tile, blockIdx.y = query tile) -> part[split][q][8] as ntxent_fwd_partial writes it, one split
+// per (key tile, wave row): split = 2 * blockIdx.x + wm covers the 16 W keys of that wave row.
+template <int W>
+__global__ __launch_bounds__(256) void ntxent_wide_fwd_partial(const float* __restrict__ zq, const float* __restrict__ zk, int n,
+                                                               int N, int D, int rank, float scale2, int vec,
+                                                               float* __restrict__ part, int rows_pad) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  constexpr int E = 32 * W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
+  const int two_n = 2 * n, two_N = 2 * N;
+  const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
+  f32x4 acc[W][W];
+  wide_tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, D, m0, n0, acc);
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const int q = n0 + 16 * W * wn + 16 * w + fl;
+    int mask_col, pos_col;
+    row_cols(q, n, N, rank, mask_col, pos_col);
+    float m0s = -INFINITY, l0 = 0.f, m1 = -INFINITY, l1 = 0.f, pos = -INFINITY, av = -INFINITY;
+    int ai = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = m0 + 16 * W * wm + 16 * i + 4 * g + r;
+        const float t = acc[i][w][r] * scale2;
+        if (col == pos_col) pos = t;
+        if (col < two_N && col != mask_col) {
+          if (col < N) {
+            const float mn = fmaxf(m0s, t);
+            l0 = l0 * exp2f(m0s - mn) + exp2f(t - mn);
+            m0s = mn;
+          } else {
+            const float mn = fmaxf(m1, t);
+            l1 = l1 * exp2f(m1 - mn) + exp2f(t - mn);
+            m1 = mn;
+            if (t > av || (t == av && col < ai)) { av = t; ai = col; }
+          }
+        }
+      }
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+      const float om0 = __shfl_xor(m0s, o, 64), ol0 = __shfl_xor(l0, o, 64);
+      const float om1 = __shfl_xor(m1, o, 64), ol1 = __shfl_xor(l1, o, 64);
+      const float op = __shfl_xor(pos, o, 64), oav = __shfl_xor(av, o, 64);
+      const int oai = __shfl_xor(ai, o, 64);
+      ml_merge(m0s, l0, om0, ol0);
+      ml_merge(m1, l1, om1, ol1);
+      pos = fmaxf(pos, op);
+      arg_merge(av, ai, oav, oai);
+    }
+    if (g == 0 && q < two_n) {
+      float* p = part + ((size_t)(2 * blockIdx.x + wm) * rows_pad + q) * kPartStride;
+      p[0] = m0s; p[1] = l0; p[2] = m1; p[3] = l1; p[4] = pos; p[5] = av;
+      p[6] = __int_as_float(ai); p[7] = 0.f;
+    }
+  }
+}
+
+// Backward, phase 1: S tile recomputed -> ds[q][key] = (softmax - onehot(pos)) * gscale (masked column and padding -> 0) over the
+// whole [rows_pad_q, rows_pad_k] grid, and the contrast-entropy partials of tf2/metrics.py:33-35 (a rows, ab block) per split.
+template <int W>
+__global__ __launch_bounds__(256) void ntxent_wide_ds(const float* __restrict__ zq, const float* __restrict__ zk, int n, int N, int D,
+                                                      int rank, float scale2, int vec, const float* __restrict__ row_stats,
+                                                      float gscale, float* __restrict__ ds, int ldds, float* __restrict__ epart,
+                                                      int rows_pad) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  constexpr int E = 32 * W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
+  const int two_n = 2 * n, two_N = 2 * N;
+  const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
+  f32x4 acc[W][W];
+  wide_tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, D, m0, n0, acc);
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const int q = n0 + 16 * W * wn + 16 * w + fl;
+    int mask_col, pos_col;
+    row_cols(q, n, N, rank, mask_col, pos_col);
+    const float lse = q < two_n ? row_stats[2 * q] : 0.f, lse_ab = q < two_n ? row_stats[2 * q + 1] : 0.f;
+    float ent = 0.f;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+      const int c0 = m0 + 16 * W * wm + 16 * i + 4 * g;
+      float d4[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = c0 + r;
+        const float t = acc[i][w][r] * scale2;
+        float d = 0.f;
+        if (q < two_n && col < two_N && col != mask_col) {
+          d = exp2f(t - lse);
+          if (col == pos_col) d -= 1.f;
+          if (q < n && col >= N) {
+            const float pab = exp2f(t - lse_ab);
+            ent -= pab * __logf(pab + 1e-8f);
+          }
+        }
+        d4[r] = d * gscale;
+      }
+      *(float4*)(ds + (size_t)q * ldds + c0) = make_float4(d4[0], d4[1], d4[2], d4[3]);
+    }
+    ent += __shfl_xor(ent, 16, 64);
+    ent += __shfl_xor(ent, 32, 64);
+    if (g == 0 && q < two_n) epart[(size_t)(2 * blockIdx.x + wm) * rows_pad + q] = ent;
+  }
+}
+
+// C[m][n] = alpha * sum_k A(m, k) B(n, k) for m < M, n < Nc (blockIdx.x = column tile, blockIdx.y = row tile): the two backward
+// products and the dense logits_ab.
+template <int W, bool A_KR, bool B_KR>
+__global__ __launch_bounds__(256) void ntxent_wide_gemm(const float* __restrict__ A, int lda, int avec, const float* __restrict__ B,
+                                                        int ldb, int bvec, int M, int Nc, int K, float alpha, float* __restrict__ C,
+                                                        int ldc) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  constexpr int E = 32 * W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
+  const int m0 = blockIdx.y * E, n0 = blockIdx.x * E;
+  f32x4 acc[W][W];
+  wide_tile<W, A_KR, B_KR>(lds, A, lda, M, avec, B, ldb, Nc, bvec, K, m0, n0, acc);
+#pragma unroll
+  for (int i = 0; i < W; ++i)
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const int c = n0 + 16 * W * wn + 16 * w + fl;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + 16 * W * wm + 16 * i + 4 * g + r;
+        if (m < M && c < Nc) C[(size_t)m * ldc + c] = acc[i][w][r] * alpha;
+      }
+    }
+}
+
+// Tile edge of an M x Nc output: 128 where that still gives the chip >= 256 workgroups, else 64.
+int wide_edge(int M, int Nc) { return (long long)ceil_div(M, 128) * ceil_div(Nc, 128) >= 256 ? 128 : 64; }
+struct WidePlan { int E, rows_pad_q, rows_pad_k, nsplit; };
+WidePlan make_wide_plan(int n, int N) {
+  WidePlan p;
+  p.E = wide_edge(2 * N, 2 * n);
+  p.rows_pad_q = ceil_div(2 * n, p.E) * p.E;
+  p.rows_pad_k = ceil_div(2 * N, p.E) * p.E;
+  p.nsplit = 2 * (p.rows_pad_k / p.E);
+  return p;
+}
+// workspace layout: [forward partials | row terms | entropy partials | dS]
+size_t wide_off_rowterm(const WidePlan& p) { return (size_t)p.nsplit * p.rows_pad_q * kPartStride; }
+size_t wide_off_ep(const WidePlan& p) { return wide_off_rowterm(p) + (size_t)2 * p.rows_pad_q; }
+size_t wide_off_ds(const WidePlan& p) { return wide_off_ep(p) + (size_t)p.nsplit * p.rows_pad_q; }
+size_t wide_ws_floats(int n, int N) {
+  WidePlan p = make_wide_plan(n, N);
+  return wide_off_ds(p) + (size_t)p.rows_pad_q * p.rows_pad_k;
+}
+// float4 loads allowed: 16-byte aligned base and a row pitch that keeps every row so
+int vec_ok(const void* p, int ld) { return ((uintptr_t)p % 16 == 0 && ld % 4 == 0) ? 1 : 0; }
+
+template <bool A_KR, bool B_KR>
+void launch_wide_gemm(const float* A, int lda, const float* B, int ldb, int M, int Nc, int K, float alpha, float* C, int ldc,
+                      hipStream_t stream) {
+  const int E = wide_edge(M, Nc);
+  dim3 grid(ceil_div(Nc, E), ceil_div(M, E));
+  if (E == 128)
+    hipLaunchKernelGGL((ntxent_wide_gemm<4, A_KR, B_KR>), grid, dim3(256), 0, stream, A, lda, vec_ok(A, lda), B, ldb, vec_ok(B, ldb),
+                       M, Nc, K, alpha, C, ldc);
+  else
+    hipLaunchKernelGGL((ntxent_wide_gemm<2, A_KR, B_KR>), grid, dim3(256), 0, stream, A, lda, vec_ok(A, lda), B, ldb, vec_ok(B, ldb),
+                       M, Nc, K, alpha, C, ldc);
+}
+
 }  // namespace
 
 extern "C" {
@@ -714,6 +1009,87 @@ int simclr_ntxent_logits_ab(const float* z_local, const float* z_all, int n, int
   SIMCLR_CHECK_ARG(n > 0 && N > 0 && D > 0, "ntxent_logits_ab: bad shape");
   hipLaunchKernelGGL(ntxent_logits_ab_kernel, dim3(ceil_div(N, 256), n), dim3(256), 0, stream,
                      z_local, z_all, n, N, D, 1.0f / temperature, logits_ab);
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- wide NT-Xent (any D; tf2/objective.py:53-87): same contracts as simclr_ntxent_fwd / _bwd / _logits_ab above ------------------
+size_t simclr_ntxent_wide_workspace_bytes(int n, int N, int D) {
+  if (n <= 0 || N < n || D <= 0) return 0;
+  return wide_ws_floats(n, N) * sizeof(float);
+}
+
+int simclr_ntxent_wide_fwd(const float* z_local, const float* z_all, int n, int N, int D, int terms, int rank, float temperature,
+                           float* out, float* row_stats, void* workspace, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(terms == 0, "ntxent_wide_fwd: matrix arithmetic must be exact (0) (got %d)", terms);
+  SIMCLR_CHECK_ARG(n > 0 && N >= n && N % n == 0, "ntxent_wide_fwd: need N = R*n (n=%d N=%d)", n, N);
+  SIMCLR_CHECK_ARG(rank >= 0 && rank < N / n, "ntxent_wide_fwd: rank %d out of range", rank);
+  SIMCLR_CHECK_ARG(D > 0, "ntxent_wide_fwd: bad D %d", D);
+  SIMCLR_CHECK_ARG(temperature > 0.f, "ntxent_wide_fwd: temperature must be > 0");
+  SIMCLR_CHECK_ARG(z_local && z_all && out && row_stats && workspace, "ntxent_wide_fwd: null argument");
+  const WidePlan p = make_wide_plan(n, N);
+  float* part = (float*)workspace;
+  float* rowterm = part + wide_off_rowterm(p);
+  const float scale2 = kLog2e / temperature;
+  const int vec = vec_ok(z_local, D) & vec_ok(z_all, D);
+  dim3 grid(p.rows_pad_k / p.E, p.rows_pad_q / p.E);
+  if (p.E == 128)
+    hipLaunchKernelGGL(ntxent_wide_fwd_partial<4>, grid, dim3(256), 0, stream, z_local, z_all, n, N, D, rank, scale2, vec, part,
+                       p.rows_pad_q);
+  else
+    hipLaunchKernelGGL(ntxent_wide_fwd_partial<2>, grid, dim3(256), 0, stream, z_local, z_all, n, N, D, rank, scale2, vec, part,
+                       p.rows_pad_q);
+  SIMCLR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ntxent_finalize_rows, dim3(ceil_div(2 * n, 16)), dim3(256), 0, stream, part, p.nsplit, p.rows_pad_q, n, N, rank,
+                     row_stats, rowterm);
+  hipLaunchKernelGGL(ntxent_reduce_out, dim3(1), dim3(256), 0, stream, rowterm, n, out);
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+int simclr_ntxent_wide_bwd(const float* z_local, const float* z_all, int n, int N, int D, int terms, int rank, float temperature,
+                           const float* row_stats, float grad_scale, float* dz_local, float* dz_all, float* out, void* workspace,
+                           hipStream_t stream) {
+  SIMCLR_CHECK_ARG(terms == 0, "ntxent_wide_bwd: matrix arithmetic must be exact (0) (got %d)", terms);
+  SIMCLR_CHECK_ARG(n > 0 && N >= n && N % n == 0, "ntxent_wide_bwd: need N = R*n (n=%d N=%d)", n, N);
+  SIMCLR_CHECK_ARG(rank >= 0 && rank < N / n, "ntxent_wide_bwd: rank %d out of range", rank);
+  SIMCLR_CHECK_ARG(D > 0, "ntxent_wide_bwd: bad D %d", D);
+  SIMCLR_CHECK_ARG(temperature > 0.f, "ntxent_wide_bwd: temperature must be > 0");
+  SIMCLR_CHECK_ARG(z_local && z_all && row_stats && dz_local && dz_all && out && workspace, "ntxent_wide_bwd: null argument");
+  const WidePlan p = make_wide_plan(n, N);
+  float* ep = (float*)workspace + wide_off_ep(p);
+  float* ds = (float*)workspace + wide_off_ds(p);
+  const float scale2 = kLog2e / temperature;
+  const float gscale = grad_scale / (temperature * (float)n);
+  const int vec = vec_ok(z_local, D) & vec_ok(z_all, D);
+  dim3 grid(p.rows_pad_k / p.E, p.rows_pad_q / p.E);
+  if (p.E == 128)
+    hipLaunchKernelGGL(ntxent_wide_ds<4>, grid, dim3(256), 0, stream, z_local, z_all, n, N, D, rank, scale2, vec, row_stats, gscale,
+                       ds, p.rows_pad_k, ep, p.rows_pad_q);
+  else
+    hipLaunchKernelGGL(ntxent_wide_ds<2>, grid, dim3(256), 0, stream, z_local, z_all, n, N, D, rank, scale2, vec, row_stats, gscale,
+                       ds, p.rows_pad_k, ep, p.rows_pad_q);
+  SIMCLR_CHECK_LAUNCH();
+  // out[2] = contrast entropy: the entropy tail of ntxent_combine_all (no gradient blocks), fixed split order
+  hipLaunchKernelGGL(ntxent_combine_all, dim3(1), dim3(256), 0, stream, (const float*)nullptr, p.nsplit, p.rows_pad_q, 0,
+                     (const float*)nullptr, 0, 0, 0, D, 0.f, (float*)nullptr, (float*)nullptr, ep, n, out, 0, 0);
+  SIMCLR_CHECK_LAUNCH();
+  // dz_local[q][:] = sum_key dS[q][key] z_all[key][:];  dz_all[key][:] = sum_q dS[q][key] z_local[q][:]
+  launch_wide_gemm<false, true>(ds, p.rows_pad_k, z_all, D, 2 * n, D, 2 * N, 1.f, dz_local, D, stream);
+  SIMCLR_CHECK_LAUNCH();
+  launch_wide_gemm<true, true>(ds, p.rows_pad_k, z_local, D, 2 * N, D, 2 * n, 1.f, dz_all, D, stream);
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+int simclr_ntxent_wide_logits_ab(const float* z_local, const float* z_all, int n, int N, int D, int terms, float temperature,
+                                 float* logits_ab, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(terms == 0, "ntxent_wide_logits_ab: matrix arithmetic must be exact (0) (got %d)", terms);
+  SIMCLR_CHECK_ARG(n > 0 && N > 0 && D > 0, "ntxent_wide_logits_ab: bad shape");
+  SIMCLR_CHECK_ARG(temperature > 0.f, "ntxent_wide_logits_ab: temperature must be > 0");
+  SIMCLR_CHECK_ARG(z_local && z_all && logits_ab, "ntxent_wide_logits_ab: null argument");
+  // logits_ab[i][j] = <z_local[i], z_all[N + j]> / T
+  launch_wide_gemm<false, false>(z_local, D, z_all + (size_t)N * D, D, n, N, D, 1.0f / temperature, logits_ab, N, stream);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -50,7 +50,9 @@ _DEFS = [
     ('temperature', 0.1, float, 'Temperature parameter for contrastive loss.'),          # :183
     ('hidden_norm', True, bool, 'Temperature parameter for contrastive loss.'),          # :187
     ('proj_head_mode', 'nonlinear', str, "'none', 'linear', 'nonlinear'."),              # :191
-    ('proj_out_dim', 128, int, 'Number of head projection dimension.'),                  # :195
+    ('proj_out_dim', 128, int, 'Number of head projection dimension.  MI355X build: any width; up to 256 the contrastive loss runs '
+                               'the register-resident NT-Xent sweeps, wider embeddings (and proj_head_mode=none, which feeds the '
+                               "encoder's 512 ... 8192-wide output) the tiled wide NT-Xent kernels."),     # :195
     ('num_proj_layers', 3, int, 'Number of non-linear head layers.'),                    # :199
     ('ft_proj_selector', 0, int, 'Which layer of the projection head to use during fine-tuning.'),  # :203
     ('global_bn', True, bool, 'Whether to aggregate BN statistics across distributed cores.'),  # :208
@@ -74,7 +76,8 @@ _DEFS = [
                                   "compute_dtype='bf16': fp32 heads on a bf16 encoder always run the exact fp32-input MFMA."),
     ('ntxent_matmul', 'exact', str, "MI355X build: matrix arithmetic of the fused NT-Xent sweeps: 'exact' = fp32-input MFMA (default); 'f16x3' = "
                                      "three fp16-piece MFMA terms per product (l2-normalised hiddens lie in fp16's range; ~2^-22 / temperature on "
-                                     "the logits) -- 2-3x faster at the 8-GPU shape, opt-in."),
+                                     "the logits) -- 2-3x faster at the 8-GPU shape, opt-in.  Embeddings wider than 256 (the wide NT-Xent kernels) always run "
+                                     "'exact': 'f16x3' falls back to it there."),
     ('head_dtype', 'same', str, "MI355X build: dtype of the projection / supervised heads: 'same' (= compute_dtype) or 'f32' "
                                 "(the heads are 0.2 % of the FLOPs; fp32 there keeps the loss gradient exact)."),
 ]

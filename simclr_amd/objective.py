@@ -123,8 +123,10 @@ def add_contrastive_loss(hidden, hidden_norm=True, temperature=1.0, strategy=Non
     if overlap is not None:
         overlap()
     z_all = pending()
-    # FLAGS.ntxent_matmul='f16x3' (opt-in): the sweeps' fp32 products as three fp16-piece MFMA terms -- l2-normalised rows only
-    split = bool(hidden_norm) and getattr(FLAGS, 'ntxent_matmul', 'exact') == 'f16x3'
+    # FLAGS.ntxent_matmul='f16x3' (opt-in): the sweeps' fp32 products as three fp16-piece MFMA terms -- l2-normalised rows only;
+    # embeddings wider than 256 (the wide NT-Xent kernels) run exact whatever the flag says
+    split = (bool(hidden_norm) and getattr(FLAGS, 'ntxent_matmul', 'exact') == 'f16x3'
+             and not ops.ntxent_is_wide(hidden.shape[1]))
     out, row_stats, ws = ops.ntxent_fwd(z, z_all, rank, temperature, split=split)
     state = {'done': False, 'dz_local': None, 'slot': None}
 

@@ -142,7 +142,14 @@ def _ntxent_pad(z):
     return z if Dk == D else torch.nn.functional.pad(z, (0, Dk - D))
 
 
+def ntxent_is_wide(D):
+    """Embeddings wider than the register-resident sweeps (proj_out_dim > 256, proj_head_mode='none') run the wide NT-Xent path."""
+    return D > _NTXENT_DIMS[-1]
+
+
 def ntxent_workspace(n, N, D, device):
+    if ntxent_is_wide(D):
+        return ntxent_wide_workspace(n, N, D, device)
     D = _ntxent_dim(D)
     nbytes = lib().ntxent_workspace_bytes(n, N, D)
     return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
@@ -150,10 +157,13 @@ def ntxent_workspace(n, N, D, device):
 
 def ntxent_fwd(z_local, z_all, rank, temperature, ws=None, split=False):
     """split: three fp16-piece MFMA terms per fp32 product in the sweeps (SIMCLR_FMT_TERMS(13) in the D argument) -- for
-    l2-normalised rows; default = exact fp32-input MFMA."""
+    l2-normalised rows; default = exact fp32-input MFMA.  D > 256 runs the wide path, which has exact arithmetic only: there
+    split is ignored (FLAGS.ntxent_matmul's help says so)."""
     n, D = z_local.shape[0] // 2, z_local.shape[1]
     N = z_all.shape[0] // 2
     assert z_local.dtype == torch.float32 and z_all.dtype == torch.float32
+    if ntxent_is_wide(D):
+        return ntxent_wide_fwd(z_local, z_all, rank, temperature, ws)
     z_local, z_all = _ntxent_pad(z_local), _ntxent_pad(z_all)
     D = z_local.shape[1]
     if ws is None:
@@ -169,6 +179,8 @@ def ntxent_fwd(z_local, z_all, rank, temperature, ws=None, split=False):
 def ntxent_bwd(z_local, z_all, rank, temperature, row_stats, grad_scale, out, ws, split=False):
     n, D0 = z_local.shape[0] // 2, z_local.shape[1]
     N = z_all.shape[0] // 2
+    if ntxent_is_wide(D0):
+        return ntxent_wide_bwd(z_local, z_all, rank, temperature, row_stats, grad_scale, out, ws)
     z_local, z_all = _ntxent_pad(z_local), _ntxent_pad(z_all)
     D = z_local.shape[1]
     dz_local = torch.empty_like(z_local)
@@ -183,11 +195,56 @@ def ntxent_bwd(z_local, z_all, rank, temperature, row_stats, grad_scale, out, ws
 
 
 def ntxent_logits_ab(z_local, z_all, temperature):
+    if ntxent_is_wide(z_local.shape[1]):
+        return ntxent_wide_logits_ab(z_local, z_all, temperature)
     z_local, z_all = _ntxent_pad(z_local), _ntxent_pad(z_all)
     n, D = z_local.shape[0] // 2, z_local.shape[1]
     N = z_all.shape[0] // 2
     out = torch.empty(n, N, device=z_local.device, dtype=torch.float32)
     lib().ntxent_logits_ab(_p(z_local), _p(z_all), n, N, D, float(temperature), _p(out), _s())
+    return out
+
+
+# Wide NT-Xent (csrc/ntxent.hip, simclr_ntxent_wide_*): any width D as LDS-tiled GEMMs with a k-loop over D, exact fp32-input MFMA.
+# ntxent_fwd / _bwd / _logits_ab / _workspace route D > 256 here; the functions are public so that the two paths can be compared at
+# D <= 256.  Same return contracts as their register-resident counterparts.
+def ntxent_wide_workspace(n, N, D, device):
+    nbytes = lib().ntxent_wide_workspace_bytes(n, N, D)
+    assert nbytes > 0, 'ntxent_wide_workspace: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+
+
+def ntxent_wide_fwd(z_local, z_all, rank, temperature, ws=None):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    assert z_local.dtype == torch.float32 and z_all.dtype == torch.float32 and z_all.shape[1] == D
+    if ws is None:
+        ws = ntxent_wide_workspace(n, N, D, z_local.device)
+    out = step_scalars(4, z_local.device)
+    row_stats = torch.empty(2 * n, 2, device=z_local.device, dtype=torch.float32)
+    _launch('ntxent_wide_fwd', 8.0 * n * N * D, 4.0 * (2 * n + 2 * N) * D,
+            lambda: lib().ntxent_wide_fwd(_p(z_local), _p(z_all), n, N, D, 0, rank, float(temperature), _p(out), _p(row_stats),
+                                          _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def ntxent_wide_bwd(z_local, z_all, rank, temperature, row_stats, grad_scale, out, ws):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    dz_local = torch.empty_like(z_local)
+    dz_all = torch.empty_like(z_all)
+    # flops: S recomputed + dS K + dS^T Q; bytes: read h_local + h_all, write dH_local + dH_all (as ntxent_bwd)
+    _launch('ntxent_wide_bwd', 24.0 * n * N * D, 2.0 * (2 * n + 2 * N) * D * 4,
+            lambda: lib().ntxent_wide_bwd(_p(z_local), _p(z_all), n, N, D, 0, rank, float(temperature), _p(row_stats),
+                                          float(grad_scale), _p(dz_local), _p(dz_all), _p(out), _p(ws), _s()))
+    return dz_local, dz_all
+
+
+def ntxent_wide_logits_ab(z_local, z_all, temperature):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    out = torch.empty(n, N, device=z_local.device, dtype=torch.float32)
+    lib().ntxent_wide_logits_ab(_p(z_local), _p(z_all), n, N, D, 0, float(temperature), _p(out), _s())
     return out
 
 

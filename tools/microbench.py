@@ -252,6 +252,21 @@ def main():
                 print('ntxent n=%d N=%d %s: fwd %.0f us bwd %.0f us | fused fwd+bwd %.1f TF/s (24nND), algorithmic %.1f GB/s' % (
                     n, N, 'f16x3' if split else 'exact', t_f, t_b, fl / (t_f + t_b) / 1e6, by / (t_f + t_b) / 1e3), flush=True)
                 res.append(dict(layer='ntxent n%d N%d%s' % (n, N, ' f16x3' if split else ''), fwd_us=t_f, bwd_us=t_b, flops=fl, bytes=by))
+        # the wide path (D > 256: proj_out_dim > 256, proj_head_mode=none), exact fp32-input MFMA; matrix FLOPs: forward S = 8nND,
+        # backward S again + dS K + dS^T Q = 24nND
+        for (n, N, D) in [(512, 512, 2048), (512, 4096, 2048), (512, 4096, 512), (128, 1024, 8192)]:
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            t_f = timeit(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws), args.iters)
+            t_b = timeit(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws), args.iters)
+            ff, fb = 8.0 * n * N * D, 24.0 * n * N * D
+            print('ntxent wide n=%d N=%d D=%d: fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s)' % (
+                n, N, D, t_f, ff / t_f / 1e6, t_b, fb / t_b / 1e6), flush=True)
+            res.append(dict(layer='ntxent wide n%d N%d D%d' % (n, N, D), fwd_us=t_f, bwd_us=t_b, fwd_flops=ff, bwd_flops=fb))
+            del zl, za, ws, out, rs
     if 'lars' in what:
         from simclr_amd.lars_optimizer import LARSOptimizer, Variable
         sizes = []
