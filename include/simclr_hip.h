@@ -131,8 +131,7 @@ int simclr_adam_multi_tensor(const long long* table, int num_tensors, const long
  * range -- BatchNorm outputs, images, weights do; an out-of-range operand gives inf / NaN, never a silently wrong value; the
  * stem keeps six bf16 terms).  This call sets the process-wide DEFAULT only: a convolution / dense entry point whose `dtype`
  * carries SIMCLR_FMT_TERMS(t) runs with t whatever the default is (the re-entrant form; simclr_amd/ops.py always sends it).
- * The setting is a LOWER bound on accuracy: the non-persistent fallback kernel (debug switch SIMCLR_NO_PERSISTENT, or more than
- * 64 N-tiles) always runs the exact fp32 MFMA whatever is selected here.
+ * The setting is a LOWER bound on accuracy: the non-persistent fallback kernel (more than 64 N-tiles) always runs the exact fp32 MFMA whatever is selected here.
  * simclr_get_f32_matmul(0 | 1) returns the forward | backward setting. */
 int simclr_set_f32_matmul(int fwd_terms, int bwd_terms);
 int simclr_get_f32_matmul(int which);

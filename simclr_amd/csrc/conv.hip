@@ -20,6 +20,8 @@
 // BatchNorm statistics (tf2/resnet.py:50-60) reduce with 4 xor-shuffles in the epilogue.
 #include "common.h"
 #include <stdlib.h>
+#include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -3291,22 +3293,57 @@ static bool take_ps_w(int* dtype) {
 }
 
 // ---- which instantiation ran: ONE place that records every forward / dgrad launch decision ----------
-// SIMCLR_LAUNCH replaces hipLaunchKernelGGL inside launch_igemm_one: it writes the kernel's template-argument list (as spelled
-// at the launch site, with the element size and the GEMM role appended) plus grid / block / LDS into g_last_inst and launches --
-// unless SIMCLR_DRY_RUN=1, in which case NOTHING touches the device: tools/instantiation_table.py walks the layer classes of
-// the benchmark models on a machine without a GPU, dumps (layer class -> instantiation) to profiles/, and a CPU test asserts
-// that the table has not changed behind anybody's back.  simclr_conv2d_last_instantiation() returns the record.
-static char g_last_inst[512] = "";
+// Every forward / dgrad kernel is launched through run_igemm / run_persistent / run_wide: they write the template-argument
+// list of the instantiation they launch (concrete element type and role, trailing arguments that equal their defaults left
+// out), the element size, the GEMM role and grid / block / LDS into g_last_inst and launch -- unless SIMCLR_DRY_RUN=1, in
+// which case NOTHING touches the device: tools/instantiation_table.py walks the layer classes of the benchmark models on a
+// machine without a GPU, dumps (layer class -> instantiation) to profiles/, and a CPU test asserts that the table has not
+// changed behind anybody's back.  simclr_conv2d_last_instantiation() returns the record.
+static thread_local char g_last_inst[512] = "";
 static bool dry_run() { return simclr_dry_run(); }
 template <typename T, int MODE> static void record_inst(const char* kern, unsigned grid, unsigned block, size_t lds, const ConvP& p) {
-  snprintf(g_last_inst, sizeof(g_last_inst), "%s elt=%d role=%s grid=%u block=%u lds=%zu m_tiles=%d n_tiles=%d tail_parts=%d", kern,
+  snprintf(g_last_inst, sizeof(g_last_inst), "(%s) elt=%d role=%s grid=%u block=%u lds=%zu m_tiles=%d n_tiles=%d tail_parts=%d", kern,
            (int)sizeof(T), MODE == MODE_FWD ? "fwd" : "dgrad", grid, block, lds, p.m_tiles, p.n_tiles, p.rem_parts);
 }
-#define SIMCLR_LAUNCH(kern, grid, block, lds, stream, ...)                                   \
-  do {                                                                                       \
-    record_inst<T, MODE>(#kern, (grid).x, (block).x, (size_t)(lds), p);                      \
-    if (!dry_run()) hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);         \
-  } while (0)
+template <typename T> static const char* type_name() { return sizeof(T) == 2 ? "uint16_t" : "float"; }
+static const char* mode_name(int mode) { return mode == MODE_FWD ? "MODE_FWD" : "MODE_DGRAD"; }
+static const char* tf(bool v) { return v ? "true" : "false"; }
+
+template <typename T, int MODE, int BN, bool STATS, bool GLDS>
+static void run_igemm(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const ConvP& p) {
+  char name[128];
+  snprintf(name, sizeof(name), "conv_igemm<%s, %s, %d, %s, %s>", type_name<T>(), mode_name(MODE), BN, tf(STATS), tf(GLDS));
+  record_inst<T, MODE>(name, grid.x, block.x, lds, p);
+  if (!dry_run()) hipLaunchKernelGGL((conv_igemm<T, MODE, BN, STATS, GLDS>), grid, block, lds, stream, p);
+}
+
+template <int MODE, bool STATS, bool BNEPI, bool FLAT>
+static void run_wide(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const ConvP& p) {
+  char name[128];
+  snprintf(name, sizeof(name), "conv_igemm_wide<%s, %s, %s, %s>", mode_name(MODE), tf(STATS), tf(BNEPI), tf(FLAT));
+  record_inst<uint16_t, MODE>(name, grid.x, block.x, lds, p);
+  if (!dry_run()) hipLaunchKernelGGL((conv_igemm_wide<MODE, STATS, BNEPI, FLAT>), grid, block, lds, stream, p);
+}
+
+template <typename T, int MODE, int BM, int BN, int NW, int STAGES, bool STATS, bool BNEPI, bool EXT = false,
+          bool WIN = false, bool FAPPLY = false, int SPL = 0, bool TAIL = false, bool PSB = false, int FAS = 0, int EPS = 0, bool PSX = false>
+static void run_persistent(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const ConvP& p) {
+  // the defaulted arguments (all false / 0) are printed up to the last one that is set
+  const int opt[9] = {EXT, WIN, FAPPLY, SPL, TAIL, PSB, FAS, EPS, PSX};
+  const bool is_bool[9] = {true, true, true, false, true, true, false, false, true};
+  int n = 9;
+  while (n > 0 && opt[n - 1] == 0) --n;
+  char name[256];
+  int len = snprintf(name, sizeof(name), "conv_igemm_persistent<%s, %s, %d, %d, %d, %d, %s, %s", type_name<T>(), mode_name(MODE), BM, BN, NW,
+                     STAGES, tf(STATS), tf(BNEPI));
+  for (int i = 0; i < n; ++i)
+    len += is_bool[i] ? snprintf(name + len, sizeof(name) - len, ", %s", tf(opt[i])) : snprintf(name + len, sizeof(name) - len, ", %d", opt[i]);
+  snprintf(name + len, sizeof(name) - len, ">");
+  record_inst<T, MODE>(name, grid.x, block.x, lds, p);
+  if (!dry_run())
+    hipLaunchKernelGGL((conv_igemm_persistent<T, MODE, BM, BN, NW, STAGES, STATS, BNEPI, EXT, WIN, FAPPLY, SPL, TAIL, PSB, FAS, EPS, PSX>),
+                       grid, block, lds, stream, p);
+}
 
 static const void* zero_page() {
   static void* zp = nullptr;
@@ -3346,25 +3383,21 @@ static bool igemm_use_256(const ConvP& p, bool fwd) {
   if (p.KH != 1 || p.KW != 1 || p.M < 150000) return false;
   if (p.bn_mode && !p.fapply) return false;          // fused BN-backward reduce epilogue
   if (fwd && !p.fapply && p.stats && p.K < 128) return false;
-  // classes (SIMCLR_IGEMM_256_CLASSES, bit mask): 1 = forward with the fused BatchNorm-apply epilogue, 2 = other forward
-  // launches, 4 = plain / K-extended dgrad.  Inside the training step class 1 LOSES 2.5 ms of 67 on ResNet-50 1x although it
-  // wins stand-alone (a 151 KB workgroup needs a whole CU's LDS: it cannot start until the previous kernel has drained
-  // from that CU, nothing can start beside it, and the fused epilogue has no second workgroup to hide behind); classes
-  // 2 and 4 are neutral there (66.96 / 67.01 vs 66.9 ms) and gain 2.5 % on ResNet-50 2x + SK (298.9 vs 305.7 ms,
-  // profiles/r03_notes.md) -> default 6.
-  const char* c = getenv("SIMCLR_IGEMM_256_CLASSES");
-  const int classes = c ? atoi(c) : 6;
-  const int cls = p.fapply ? 1 : (fwd ? 2 : 4);
-  return (classes & cls) != 0;
+  // Not the forward with the fused BatchNorm-apply epilogue: inside the training step it LOSES 2.5 ms of 67 on ResNet-50 1x
+  // although it wins stand-alone (a 151 KB workgroup needs a whole CU's LDS: it cannot start until the previous kernel has
+  // drained from that CU, nothing can start beside it, and the fused epilogue has no second workgroup to hide behind); the
+  // other forward launches and the plain / K-extended dgrad are neutral there (66.96 / 67.01 vs 66.9 ms) and gain 2.5 % on
+  // ResNet-50 2x + SK (298.9 vs 305.7 ms, profiles/r03_notes.md).
+  return !p.fapply;
 }
 
-// Eight-phase 256 x 256 tile (csrc/igemm_wide.h).  SIMCLR_IGEMM_WIDE: 0 = off, 1 = on for the layers the rule below picks,
-// 2 = on wherever the kernel is applicable (tests).  Applicable: bf16, Cout a multiple of 256, whole 64-channel k-tiles, no
+// Eight-phase 256 x 256 tile (csrc/igemm_wide.h).  SIMCLR_IGEMM_WIDE: 0 = off, 2 = on wherever the kernel is applicable (tests),
+// anything else = on for the layers the rule below picks.  Applicable: bf16, Cout a multiple of 256, whole 64-channel k-tiles, no
 // K-extension / fused BatchNorm-apply epilogue (those stay on conv_igemm_persistent).
 static bool igemm_use_wide(const ConvP& p, bool fwd) {
   const char* e = getenv("SIMCLR_IGEMM_WIDE");
   const int mode = e ? atoi(e) : 1;
-  if (mode <= 0) return false;
+  if (mode == 0) return false;
   if (p.N % 256 != 0 || p.N / 256 > 32 || p.ntaps <= 0 || p.IC % 64 != 0 || p.x2 || p.fapply) return false;
   if (p.bn_mode && p.bn_mode != 4 && !p.bn_x) return false;
   // 32-bit byte offsets into the operands, below the out-of-range marker of the kernel (0xF0000000)
@@ -3379,34 +3412,35 @@ static bool igemm_use_wide(const ConvP& p, bool fwd) {
   //   dgrad + BatchNorm-backward reduce: loses everywhere but at 7^2 (+4 ... +29 %: one workgroup per CU cannot hide the
   //   row pass's operand loads) -> stays on conv_igemm_persistent.
   if (p.M < 32768) return false;
-  // modes 3 / 4 (A/B runs): the rule for the forward launches only / for the data-gradient launches only.
   // Forward, round 5: only launches of >= 300 GFLOP.  Stand-alone the wide tile wins on every layer it applies to, but a 150 KB workgroup
   // needs a whole CU's LDS -- it cannot start until the previous kernel has drained from that CU and nothing starts beside it -- and
   // INSIDE the training step that fixed cost outweighs the gain on ResNet-50 1x (105 ... 237 GFLOP per launch: 63.19 -> 62.65 ms per
   // step with the forward rule off, three interleaved runs) while ResNet-50 2x + SK (420 ... 950 GFLOP per launch) loses 2.4 ms of 286
   // without it (profiles/r05_notes.md section 8).
-  // mode 5: the rule of round 4 (no work threshold on the forward launches), kept for A/B runs against the current default
-  if (fwd) return mode != 4 && !(p.KH == 3 && p.KW == 3 && p.stride == 1) && (mode == 3 || mode == 5 || 2.0 * (double)p.M * p.K * p.N >= 3.0e11);
-  return mode != 3 && !p.bn_mode && !p.accumulate && p.KH == 1 && p.KW == 1 && p.IC >= 512;
+  if (fwd) return !(p.KH == 3 && p.KW == 3 && p.stride == 1) && 2.0 * (double)p.M * p.K * p.N >= 3.0e11;
+  return !p.bn_mode && !p.accumulate && p.KH == 1 && p.KW == 1 && p.IC >= 512;
 }
 
-// Short-K layers (1x1 convolutions from <= SIMCLR_IGEMM_BN64_K channels, default 128: one or two k-tiles per output tile)
-// are pure streaming: with the 64-wide tile three workgroups fit a CU instead of two, so the load phase of one tile, the
-// MFMA / staging of another and the store phase of a third overlap (the gathered operand is then re-read from L2 by N/64
-// workgroups instead of N/128 -- irrelevant for an HBM-bound layer).  Measured in the step: 66.49 / 66.33 vs 66.72 / 66.66 ms
-// (-0.3 ms, two interleaved pairs, profiles/r03_notes.md); K <= 64 alone and K <= 256 give 66.60 / 66.50.
+// Short-K layers (1x1 convolutions from <= 64 channels: one k-tile per output tile) are pure streaming: with the 64-wide tile three
+// workgroups fit a CU instead of two, so the load phase of one tile, the MFMA / staging of another and the store phase of a third
+// overlap (the gathered operand is then re-read from L2 by N/64 workgroups instead of N/128 -- irrelevant for an HBM-bound layer).
+// Measured in the step: 66.49 / 66.33 vs 66.72 / 66.66 ms (-0.3 ms, two interleaved pairs, profiles/r03_notes.md).
 static bool igemm_narrow(const ConvP& p, size_t esz, bool dgrad = false) {
   // Round 5 (three interleaved runs each on one box, profiles/r05_notes.md section 8): K <= 64 only -- 63.19 -> 62.56 ms per step; the K = 128
   // layers (28^2 128 -> 512) are better off on the 128-wide tile now that its epilogues carry their options as compile-time constants.
-  static const int kmax = getenv("SIMCLR_IGEMM_BN64_K") ? atoi(getenv("SIMCLR_IGEMM_BN64_K")) : 64;
-  // fp32 storage, three-term DATA GRADIENT launches (their 64-wide tiles run three per CU): K <= 128 (SIMCLR_IGEMM_BN64_K32).  Measured in
-  // the step, three interleaved triples on one box (r06_call23): data-gradient family 44.40 -> 43.63 ms (K <= 64: 43.93); the forward
-  // launches LOSE on the narrow tile (38.69 -> 39.77 ms) and keep 128 columns.
-  static const int kmax32 = getenv("SIMCLR_IGEMM_BN64_K32") ? atoi(getenv("SIMCLR_IGEMM_BN64_K32")) : 128;
+  constexpr int kmax = 64;
+  // fp32 storage, three-term DATA GRADIENT launches (their 64-wide tiles run three per CU): K <= 128.  Measured in the step, three
+  // interleaved triples on one box (r06_call23): data-gradient family 44.40 -> 43.63 ms (K <= 64: 43.93); the forward launches LOSE on
+  // the narrow tile (38.69 -> 39.77 ms) and keep 128 columns.
+  constexpr int kmax32 = 128;
   if (esz == 4)
-    return dgrad && kmax32 > 0 && p.split == 3 && p.N > 64 && p.KH == 1 && p.KW == 1 && p.stride == 1 && !p.x2 && p.K <= kmax32 && p.N / 64 <= 64;
+    return dgrad && p.split == 3 && p.N > 64 && p.KH == 1 && p.KW == 1 && p.stride == 1 && !p.x2 && p.K <= kmax32 && p.N / 64 <= 64;
   return esz == 2 && p.N > 64 && p.KH == 1 && p.KW == 1 && p.stride == 1 && !p.x2 && p.K <= kmax && p.N / 64 <= 64;
 }
+
+// One lock for the library-owned per-stream scratch tables below (g_split_scratch, g_presplit): entry points may be called from
+// several host threads.
+static std::mutex g_scratch_mutex;
 
 // ---- split tail of the persistent forward / dgrad grid (ConvP::rem_*) -------------------------------------------------
 // The persistent grid gives every workgroup ceil(m_tiles / mslots) tiles although the last round is mostly empty: 3.06
@@ -3419,19 +3453,19 @@ struct SplitScratch { hipStream_t stream; float* ws; size_t floats; unsigned* fl
 static SplitScratch g_split_scratch[8];
 static int g_split_scratch_n = 0;
 
-// units: pieces one tile's reduction can be cut in (k-steps; 64-channel chunks of nine k-steps on the halo-window path)
-static int g_last_split_parts = 0;      // simclr_conv2d_last_split_parts (tests)
+static thread_local int g_last_split_parts = 0;      // simclr_conv2d_last_split_parts (tests)
+// The decision: rem_full / rem_tiles / rem_parts of p for a persistent grid of `grid` workgroups (rem_parts = 0: whole tiles only).
+// units: pieces one tile's reduction can be cut in (k-steps; 64-channel chunks of nine k-steps on the halo-window path).
 // `wide`: the caller is the eight-phase 256 x 256 launch.  Default policy (SIMCLR_IGEMM_SPLIT unset): split the tail of the
 // wide launches only -- measured per ResNet-50 layer at 1024 views (profiles/r04_notes.md) the 128-wide tiles gain 4-6 % on the
 // 3x3 layers at 14^2 / 7^2 and LOSE up to 14 % on the 1x1 layers at 7^2 (a 17-30 us tile is not long enough to pay for the
 // exchange), -0.65 ms per training step in sum; the 256-wide tiles gain 1-4 % (their tiles are four times longer).
 // SIMCLR_IGEMM_SPLIT=0: never, =1: every eligible launch, >= 2: every eligible launch with at most that many parts.
-static bool igemm_split_tail(ConvP& p, int grid, int units, int unit_steps, size_t tile_floats, hipStream_t stream, bool wide = false) {
-  g_last_split_parts = 0;
+static void split_tail_plan(ConvP& p, int grid, int units, int unit_steps, bool wide = false) {
   p.rem_parts = 0; p.rem_full = 0; p.rem_tiles = 0; p.part_ws = nullptr; p.part_flags = nullptr; p.part_err = nullptr;
   const char* e = getenv("SIMCLR_IGEMM_SPLIT");
   const int mode = e ? atoi(e) : (wide ? 1 : 0);
-  if (mode == 0 || p.n_tiles <= 0 || grid % p.n_tiles != 0) return true;
+  if (mode == 0 || p.n_tiles <= 0 || grid % p.n_tiles != 0) return;
   const int mslots = grid / p.n_tiles;
   const int full = p.m_tiles / mslots, R = p.m_tiles - full * mslots;
   const int max_parts = mode > 1 ? mode : 8;
@@ -3445,17 +3479,21 @@ static bool igemm_split_tail(ConvP& p, int grid, int units, int unit_steps, size
   if (P > max_parts_u) P = max_parts_u;
   // nothing to gain: no remainder, too few workgroups per remainder tile, short reductions (streaming layers: the
   // partial exchange would cost more than the idle round), or so many rounds that one more is noise
-  if (R == 0 || full == 0 || P < 2 || full > 24) return true;
-  const size_t slots = (size_t)R * p.n_tiles * (P - 1);
-  if (dry_run()) {                                  // decision only: nothing is allocated, nothing will be launched
-    p.rem_full = full; p.rem_tiles = R; p.rem_parts = P; g_last_split_parts = P;
-    return true;
-  }
+  if (R == 0 || full == 0 || P < 2 || full > 24) return;
+  p.rem_full = full; p.rem_tiles = R; p.rem_parts = P;
+}
+
+// The scratch of the split tail p.rem_* asks for (tile_floats per partial tile): false if there is none -- more streams than
+// buffers, no memory, or the buffer would have to grow while the stream is captured -- and the launch runs whole tiles instead.
+static bool split_tail_scratch(ConvP& p, size_t tile_floats, hipStream_t stream) {
+  if (dry_run()) return true;                       // decision only: nothing is allocated, nothing will be launched
+  const size_t slots = (size_t)p.rem_tiles * p.n_tiles * (p.rem_parts - 1);
+  std::lock_guard<std::mutex> lock(g_scratch_mutex);
   SplitScratch* sc = nullptr;
   for (int i = 0; i < g_split_scratch_n; ++i)
     if (g_split_scratch[i].stream == stream) sc = &g_split_scratch[i];
   if (!sc) {
-    if (g_split_scratch_n == 8) return true;        // more streams than scratch buffers: run without the split
+    if (g_split_scratch_n == 8) return false;
     sc = &g_split_scratch[g_split_scratch_n++];
     *sc = SplitScratch{stream, nullptr, 0, nullptr, 0};
   }
@@ -3465,7 +3503,7 @@ static bool igemm_split_tail(ConvP& p, int grid, int units, int unit_steps, size
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream && (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) {
       (void)hipGetLastError();
-      return true;
+      return false;
     }
     unsigned lost = 0;                                 // the time-out count travels to the new allocation (sticky)
     if (sc->flags) (void)hipMemcpy(&lost, sc->flags + sc->nflags, sizeof(unsigned), hipMemcpyDeviceToHost);
@@ -3483,12 +3521,10 @@ static bool igemm_split_tail(ConvP& p, int grid, int units, int unit_steps, size
       if (sc->ws) (void)hipFree(sc->ws);
       if (sc->flags) (void)hipFree(sc->flags);
       sc->ws = nullptr; sc->flags = nullptr;
-      return true;                                   // no scratch: the un-split schedule is still correct
+      return false;
     }
     sc->floats = want_f; sc->nflags = want_n;
   }
-  p.rem_full = full; p.rem_tiles = R; p.rem_parts = P;
-  g_last_split_parts = P;
   p.part_ws = sc->ws; p.part_flags = sc->flags; p.part_err = sc->flags + sc->nflags;
   return true;
 }
@@ -3497,6 +3533,7 @@ static bool igemm_split_tail(ConvP& p, int grid, int units, int unit_steps, size
 // healthy device.  Synchronous (copies the sticky counters back): call it where the host synchronises anyway.
 static int split_tail_timeouts(unsigned* host_total) {
   SIMCLR_CHECK_ARG(host_total != nullptr, "conv2d_split_tail_timeouts: null argument");
+  std::lock_guard<std::mutex> lock(g_scratch_mutex);
   unsigned total = 0;
   for (int i = 0; i < g_split_scratch_n; ++i) {
     if (!g_split_scratch[i].flags) continue;
@@ -3525,12 +3562,15 @@ static int split_tail_timeouts(unsigned* host_total) {
 struct PresplitScratch { hipStream_t stream; void* buf; size_t bytes; };
 static PresplitScratch g_presplit[8];
 static int g_presplit_n = 0;
-static int g_last_presplit = 0;          // simclr_conv2d_last_presplit (tests): 1 if the most recent dgrad launch ran PSB
-static int g_igemm_fail = 0;             // set by launch_igemm_one when a launch cannot honour its operand format (pre-split input without PSB)
-static const void* presplit_weights(const void* w, long long rows, int K, hipStream_t stream, bool f16 = false) {
+static thread_local int g_last_presplit = 0;          // simclr_conv2d_last_presplit (tests): 1 if the most recent dgrad launch ran PSB
+static bool presplit_enabled(long long rows, int K) {
   const char* e = getenv("SIMCLR_F32_PRESPLIT");
-  if ((e && atoi(e) == 0) || K % 32 != 0 || rows <= 0) return nullptr;
+  return !(e && atoi(e) == 0) && K % 32 == 0 && rows > 0;
+}
+// The pre-split copy of w (nullptr: no buffer, the caller re-plans without it).
+static const void* presplit_weights(const void* w, long long rows, int K, hipStream_t stream, bool f16) {
   if (dry_run()) return w;                           // decision only
+  std::lock_guard<std::mutex> lock(g_scratch_mutex);
   PresplitScratch* sc = nullptr;
   for (int i = 0; i < g_presplit_n; ++i)
     if (g_presplit[i].stream == stream) sc = &g_presplit[i];
@@ -3555,265 +3595,264 @@ static const void* presplit_weights(const void* w, long long rows, int K, hipStr
   return sc->buf;
 }
 
+// ---- forward / dgrad launches: plan, resources, launch -------------------------------------------------------------------
+// plan_igemm decides everything about one launch from its ConvP, element type and role alone: the kernel family, every
+// template argument, grid / block / LDS and the kernel arguments -- and which library resources it needs (split-tail scratch,
+// pre-split weights).  launch_igemm_one acquires them; when one is not available it plans again without it (can_split /
+// can_presplit = false), which is how the fallbacks are spelled: whole tiles instead of a split tail, six bf16 terms instead
+// of three fp16 pieces, the in-register split instead of PSB -- or "unsupported" for a pre-split operand nothing else reads.
+// launch_plan then maps the finished plan onto the one instantiation that has exactly these template arguments.
+struct IgemmPlan {
+  enum Family {
+    EMPTY,          // no rows (an empty pixel class): nothing to launch
+    UNSUPPORTED,    // a pre-split operand on a launch with no kernel that reads it
+    WIDE,           // eight-phase 256 x 256 tile (conv_igemm_wide)
+    TILE256,        // 256 x 256 persistent tile, 8 waves
+    TILE128,        // 128 x BN persistent tile, 4 waves: gather, halo window (win) or fused BatchNorm apply (fapply)
+    FALLBACK,       // non-persistent conv_igemm (no taps, or more than 64 N-tiles)
+  } family = EMPTY;
+  ConvP p;
+  int bn = 0, spl = 0, fas = 0, eps = 0;                           // conv_igemm(_persistent) template arguments
+  bool stats = false, bnepi = false, ext = false, win = false, fapply = false, tail = false, psb = false, psx = false;
+  bool flat = false;                                               // conv_igemm_wide
+  unsigned grid = 0, block = 0;
+  size_t lds = 0;
+  size_t tile_floats = 0;          // split tail (p.rem_parts >= 2): fp32 partial-tile size of the scratch
+  bool presplit = false;           // psb with weights the launch pre-splits itself (fp16 pieces when spl == 13)
+};
+
 template <typename T, int MODE>
-void launch_igemm_one(ConvP p, hipStream_t stream) {
-  const bool narrow = igemm_narrow(p, sizeof(T), MODE == MODE_DGRAD);
+static IgemmPlan plan_igemm(const ConvP& p0, bool can_split, bool can_presplit) {
+  constexpr bool bf16 = sizeof(T) == 2, fwd = MODE == MODE_FWD;
+  IgemmPlan k;
+  ConvP& p = k.p;
+  p = p0;
+  const bool narrow = igemm_narrow(p, sizeof(T), !fwd);
   const int BN = (p.N <= 64 || narrow) ? 64 : 128;
   p.m_tiles = ceil_div(p.M, 128);
   p.n_tiles = ceil_div(p.N, BN);
-  if (p.M <= 0) return;
-  // p.split: set by the entry point (terms_of: the call's own terms or the process-wide default)
+  if (p.M <= 0) return k;
 #ifdef SIMCLR_DIAG
   { const char* e = getenv("SIMCLR_DIAG"); p.diag = e ? atoi(e) : 0; }
 #endif
-  const int grid = ceil_div(p.m_tiles, 8) * 8 * p.n_tiles;
-  size_t lds = 2 * (128 + BN) * 128;
-  const size_t epi = 128 * (BN * 2 + 8) + 128 * sizeof(long long);
-  if (sizeof(T) == 2 && epi > lds) lds = epi;
   const bool st = p.stats != nullptr;
-  static const bool no_glds = getenv("SIMCLR_NO_GLDS") != nullptr;   // A/B switches for benchmarking
-  static const bool no_persist = getenv("SIMCLR_NO_PERSISTENT") != nullptr;
-  if ((p.bn_mode || p.fapply || !p.y || (!no_glds && !no_persist)) && p.ntaps > 0 && p.n_tiles <= 64) {
-    // Tile choice: 128x128 / 128x64, 4 waves, 2-stage LDS ring, 2-3 workgroups per CU.  Measured
-    // alternatives that were slower on every ResNet-50 layer (profiles/r01_notes.md): 256x128 with 8
-    // waves (one workgroup per CU), and 3-stage rings with counted vmcnt for either tile.
-    // persistent grid: 2-3 workgroups per CU, rounded to a multiple of 8*n_tiles, at most one per tile
-    int bn_, nt_, pg;
-    igemm_persistent_grid(p.M, p.N, &bn_, &nt_, &pg, narrow);
-    const size_t plds = 2 * (128 + BN) * 128 + 5 * BN * sizeof(float) + 128 * sizeof(long long);
-    // 256 x 256 tile, 8 waves of 128 x 64 (one workgroup per CU): half the L2->LDS bytes per FLOP of the 128 x 128 tile
-    // (which needs 64 B/clk/CU from L2 at the MFMA peak -- more than an XCD's L2 delivers) and 0.375 instead of 0.5 KB
-    // of LDS fragment reads per MFMA.  SIMCLR_IGEMM_TILE: 128 / 256 force a tile, unset = igemm_use_256 (measured per
-    // layer class, profiles/r03_notes.md).  The statistics slots of the 128-wide geometry (simclr_conv2d_stats_slots)
-    // are never fewer than this grid's M-slots.
-    if constexpr (sizeof(T) == 2) {
-      if (igemm_use_wide(p, MODE == MODE_FWD)) {
-        // eight-phase 256 x 256 tile (csrc/igemm_wide.h): one 8-wave workgroup per CU, 150 KB of LDS
-        p.x_bytes = (unsigned)((long long)p.V * p.IH * p.IW * p.pixpitch * 2);
-        { const int dist[3] = {8, 128, 136}, chw = p.cls_h * p.cls_w;
-          for (int i = 0; i < 3; ++i) {
-            p.rs_dq[i] = dist[i] / chw;
-            const int r = dist[i] - p.rs_dq[i] * chw;
-            p.rs_drow[i] = r / p.cls_w; p.rs_dcol[i] = r - p.rs_drow[i] * p.cls_w;
-          } }
-        p.m_tiles = ceil_div(p.M, 256);
-        p.n_tiles = p.N / 256;
-        const int unit = 8 * p.n_tiles;
-        int pgw = max(unit, (256 / unit) * unit);
-        pgw = min(pgw, ceil_div(p.m_tiles, 8) * unit);
-        // ring 128 KB + BN parameters 4 KB + row offsets 2 KB + per-wave statistics 16 KB + border coordinates 8 KB
-        const size_t ldsw = 131072 + 4 * 256 * sizeof(float) + 256 * sizeof(long long) + 8 * 256 * 2 * sizeof(float) + 4 * 512 * sizeof(int);
-        igemm_split_tail(p, pgw, p.ntaps * (p.IC / 64), 1, (size_t)256 * 256, stream, true);
-        const bool flatw = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.cs == 1 && p.IH == p.OH && p.IW == p.OW;
-#define LWD(STv, BEv)                                                                                                          \
-        do {                                                                                                                   \
-          if (flatw) SIMCLR_LAUNCH((conv_igemm_wide<MODE, STv, BEv, true>), dim3(pgw), dim3(512), ldsw, stream, p);       \
-          else SIMCLR_LAUNCH((conv_igemm_wide<MODE, STv, BEv, false>), dim3(pgw), dim3(512), ldsw, stream, p);            \
-        } while (0)
-        if (p.bn_mode) LWD(true, true);
-        else if (st) LWD(true, false);
-        else LWD(false, false);
-#undef LWD
-        return;
-      }
-      if (igemm_use_256(p, MODE == MODE_FWD)) {
-        p.m_tiles = ceil_div(p.M, 256);
-        p.n_tiles = p.N / 256;
-        const int unit = 8 * p.n_tiles;
-        int pg2 = max(unit, (256 / unit) * unit);
-        pg2 = min(pg2, ceil_div(p.m_tiles, 8) * unit);
-        const size_t lds2 = 2 * (256 + 256) * 128 + 5 * 256 * sizeof(float) + 256 * sizeof(long long) + 8 * 256 * 2 * sizeof(float);
-        igemm_split_tail(p, pg2, p.ntaps * (p.IC / 64) + (p.x2 ? p.ic2 / 64 : 0), 1, (size_t)256 * 256, stream);
-        if (p.fapply) { p.rem_parts = 0; g_last_split_parts = 0; }
-#define L2(STv, BEv, EXv, FAv)                                                                                                \
-        do {                                                                                                                   \
-          if (p.rem_parts >= 2) { if constexpr (!(FAv)) SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 256, 256, 8, 2, STv, BEv, EXv, false, FAv, 0, true>), dim3(pg2), dim3(512), lds2, stream, p); } \
-          else SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 256, 256, 8, 2, STv, BEv, EXv, false, FAv>), dim3(pg2), dim3(512), lds2, stream, p); \
-        } while (0)
-        if (p.fapply) { if constexpr (MODE == MODE_FWD) L2(false, false, false, true); }
-        else if (p.x2 && p.bn_mode) L2(true, true, true, false);
-        else if (p.x2) L2(false, false, true, false);
-        else if (p.bn_mode) L2(true, true, false, false);
-        else if (st) L2(true, false, false, false);
-        else L2(false, false, false, false);
-#undef L2
-        return;
-      }
-    }
-    const int bk_elems = 128 / (int)sizeof(T);
-    const bool win3 = [&] {
-      static const bool no_win = []{ const char* e = getenv("SIMCLR_CONV3_WIN"); return e && e[0] == '0'; }();
-      // fp32 storage (round 6): the three-term launches with pre-split weights (checked below); SIMCLR_CONV3_WIN=0 gathers in both storages
-      // (A/B of the fp32 path: 143.94 / 144.15 / 144.00 -> 141.75 / 141.58 / 141.22 ms per step, r06_call35)
-      if (sizeof(T) == 4 && !(p.split == 3 || p.split == 13)) return false;
-      return !no_win && !p.fapply && !p.x2 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.cs == 1 &&
-             p.ntaps == 9 && p.IH == p.OH && p.IW == p.OW && p.IW <= 62 && p.accumulate < 2;
-    }();
-    // reduction units the tail can be split in: k-steps, or 64-channel chunks on the halo-window path
-    // (bf16 128 x 128 tiles only: the 64-wide tiles are the short-K streaming layers, the fp32 kernels keep whole tiles)
-    if (sizeof(T) == 2 && BN == 128 && !p.fapply)
-      igemm_split_tail(p, pg, win3 ? p.IC / bk_elems : p.ntaps * (p.IC / bk_elems) + (p.x2 ? p.ic2 / bk_elems : 0),
-                       win3 ? 9 : 1, (size_t)128 * BN, stream);
-    else { p.rem_parts = 0; g_last_split_parts = 0; }
-    // fp32 storage: one instantiation per matrix arithmetic (exact fp32 MFMA, 3 or 6 split-bf16 terms)
-    // three-term data gradient: weights pre-split once per launch (PSB)
-    bool psb = false;
-    if constexpr (sizeof(T) == 4 && MODE == MODE_DGRAD) {
-      g_last_presplit = 0;
-      if (p.split == 3) {
-        if (p.w_ps) { psb = true; g_last_presplit = 1; }
-        else {
-          const void* ws = presplit_weights(p.w, p.N, p.K, stream);
-          if (ws) { p.w = ws; psb = true; g_last_presplit = 1; }
-        }
-      }
-    }
-    if (p.x_ps && !psb) { g_igemm_fail = 1; return; }      // a pre-split operand cannot be read as floats: refuse (the entry point reports it)
-    // split-fp16 forward (13): fp16 weight planes times 2^F16_WSCALE_LOG2, once per launch; no scratch -> six bf16 terms
-    if constexpr (sizeof(T) == 4 && MODE == MODE_FWD) {
-      if (p.split == 13) {
-        if (p.w_ps) psb = true;
-        else {
-          const void* ws = presplit_weights(p.w, p.N, p.K, stream, true);
-          if (ws) { p.w = ws; psb = true; } else p.split = 6;
-        }
-      }
-    }
-    if (p.w_ps && !psb) { g_igemm_fail = 1; return; }      // pre-split weights on a launch that would read them as floats (other terms): refuse
-    // fused BatchNorm-backward-reduce epilogue with its mask mode / accumulate flag compiled in (EPS instantiations, bf16):
-    // 1 = (mode 2, store), 3 = (mode 4, store), 4 = (mode 4, accumulate); SIMCLR_BNEPI_SPECIAL=0 (read per launch) = generic
-    int eps = 0;
-    if (sizeof(T) == 2 && MODE == MODE_DGRAD && p.bn_mode) {
-      if (p.bn_mode == 2 && !p.accumulate) eps = 1;
-      else if (p.bn_mode == 4) eps = p.accumulate ? 4 : 3;
-      const char* e = getenv("SIMCLR_BNEPI_SPECIAL");
-      if (e && atoi(e) == 0) eps = 0;
-    }
-#define LPE(BNv, EXv, EPSv) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, true, true, EXv, false, false, 0, false, false, 0, EPSv>), dim3(pg), dim3(256), plds, stream, p)
-#define LPX(BNv, STv, BEv, EXv)                                                                                              \
-    do {                                                                                                                     \
-      if constexpr (sizeof(T) == 4) {                                                                                        \
-        if (psb && p.x_ps) { if constexpr (MODE == MODE_DGRAD && !(EXv)) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, false, false, false, 3, false, true, 0, 0, true>), dim3(pg), dim3(256), plds, stream, p); \
-                             else g_igemm_fail = 1; } \
-        else if (psb) { if constexpr (MODE == MODE_DGRAD) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, EXv, false, false, 3, false, true>), dim3(pg), dim3(256), plds, stream, p); \
-                   else if constexpr (!(BEv) && !(EXv)) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, false, false, false, false, 13, false, true>), dim3(pg), dim3(256), plds, stream, p); } \
-        else if (p.split == 3) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, EXv, false, false, 3>), dim3(pg), dim3(256), plds, stream, p); \
-        else if (p.split == 6) SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, EXv, false, false, 6>), dim3(pg), dim3(256), plds, stream, p); \
-        else SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, EXv>), dim3(pg), dim3(256), plds, stream, p); \
-      } else if ((BNv) == 128 && p.rem_parts >= 2) {                                                                         \
-        SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, 128, 4, 2, STv, BEv, EXv, false, false, 0, true>), dim3(pg), dim3(256), plds, stream, p); \
-      } else {                                                                                                               \
-        SIMCLR_LAUNCH((conv_igemm_persistent<T, MODE, 128, BNv, 4, 2, STv, BEv, EXv>), dim3(pg), dim3(256), plds, stream, p); \
-      }                                                                                                                      \
-    } while (0)
-#define LP(BNv, STv, BEv) LPX(BNv, STv, BEv, false)
-    if (p.fapply) {
-      // the two option sets every fused bottleneck tail uses get instantiations with the options compiled in (FAS);
-      // SIMCLR_FAPPLY_SPECIAL=0 (read per launch: A/B runs, bitwise test) keeps the generic epilogue
-      int fas = 0;
-      if (p.bn_x && p.bn_mode && p.bn_mask && (p.N & 31) == 0) fas = p.bn_mean ? 2 : 1;
-      { const char* e = getenv("SIMCLR_FAPPLY_SPECIAL"); if (e && atoi(e) == 0) fas = 0; }
-      if constexpr (sizeof(T) == 4 && MODE == MODE_FWD) {
-        // fp32 storage: generic options (FAS = 0); three fp16-piece terms with the pre-split weights, six bf16 terms, or exact fp32
-#define LF32(BNv)                                                                                                              \
-        do {                                                                                                                   \
-          if (psb && p.split == 13) SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true, 13, false, true>), dim3(pg), dim3(256), plds, stream, p); \
-          else if (p.split == 6) SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true, 6>), dim3(pg), dim3(256), plds, stream, p); \
-          else if (p.split == 3) SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true, 3>), dim3(pg), dim3(256), plds, stream, p); \
-          else SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true>), dim3(pg), dim3(256), plds, stream, p); \
-        } while (0)
-        if (BN == 64) LF32(64); else LF32(128);
-#undef LF32
-        return;
-      }
-#define LF(BNv)                                                                                                                \
-      do {                                                                                                                     \
-        if (fas == 1) SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true, 0, false, false, 1>), dim3(pg), dim3(256), plds, stream, p); \
-        else if (fas == 2) SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true, 0, false, false, 2>), dim3(pg), dim3(256), plds, stream, p); \
-        else SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE_FWD, 128, BNv, 4, 2, false, false, false, false, true>), dim3(pg), dim3(256), plds, stream, p); \
-      } while (0)
-      if (BN == 64) LF(64); else LF(128);
-#undef LF
-      return;
-    }
-    // 3x3 stride-1: halo-window operand path (one window load per 128-byte channel chunk instead of nine gathers)
-    bool win_now = win3;
-    if constexpr (sizeof(T) == 4) {
-      // fp32 storage: forward = three fp16-piece terms with the pre-split weights; data gradient = three bf16-piece terms with both
-      // operands pre-split, plain or with the fused BatchNorm-backward reduce (the launches a ResNet step makes); everything else gathers
-      if (MODE == MODE_FWD) win_now = win3 && psb && p.split == 13 && !p.bn_mode;
-      else win_now = win3 && psb && p.split == 3 && p.x_ps && (p.bn_mode != 0) == st;
-    }
-    if (win_now) {
-      const int rows = ((128 + 2 * (p.IW + 1)) + 31) / 32 * 32;
-      p.win_j = rows / 32;
-      p.win_bytes = (sizeof(T) == 4 || rows * 128 > 128 * BN * 2) ? rows * 128 : 128 * BN * 2;     // (bf16: doubles as the C staging tile)
-      const size_t wlds = (size_t)p.win_bytes + 2 * BN * 128 + 5 * BN * sizeof(float) + 128 * sizeof(long long) + 128;
-      if constexpr (sizeof(T) == 4) {
-#define LW32(BNv, STv, BEv)                                                                                                   \
-        do {                                                                                                                   \
-          if constexpr (MODE == MODE_FWD) { if constexpr (!(BEv)) SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_FWD, 128, BNv, 4, 2, STv, false, false, true, false, 13, false, true>), dim3(pg), dim3(256), wlds, stream, p); } \
-          else SIMCLR_LAUNCH((conv_igemm_persistent<float, MODE_DGRAD, 128, BNv, 4, 2, STv, BEv, false, true, false, 3, false, true, 0, 0, true>), dim3(pg), dim3(256), wlds, stream, p); \
-        } while (0)
-        if (p.bn_mode) { if (BN == 64) LW32(64, true, true); else LW32(128, true, true); }
-        else if (BN == 64) { if (st) LW32(64, true, false); else LW32(64, false, false); }
-        else { if (st) LW32(128, true, false); else LW32(128, false, false); }
-#undef LW32
-        return;
-      } else {
-#define LW(BNv, STv, BEv)                                                                                                     \
-      do {                                                                                                                     \
-        if ((BNv) == 128 && p.rem_parts >= 2) SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 128, 128, 4, 2, STv, BEv, false, true, false, 0, true>), dim3(pg), dim3(256), wlds, stream, p); \
-        else SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 128, BNv, 4, 2, STv, BEv, false, true>), dim3(pg), dim3(256), wlds, stream, p); \
-      } while (0)
-      if (p.bn_mode && eps == 1 && p.rem_parts < 2) {
-        if (BN == 64) SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 128, 64, 4, 2, true, true, false, true, false, 0, false, false, 0, 1>), dim3(pg), dim3(256), wlds, stream, p);
-        else SIMCLR_LAUNCH((conv_igemm_persistent<uint16_t, MODE, 128, 128, 4, 2, true, true, false, true, false, 0, false, false, 0, 1>), dim3(pg), dim3(256), wlds, stream, p);
-      }
-      else if (p.bn_mode) { if (BN == 64) LW(64, true, true); else LW(128, true, true); }
-      else if (BN == 64) { if (st) LW(64, true, false); else LW(64, false, false); }
-      else { if (st) LW(128, true, false); else LW(128, false, false); }
-#undef LW
-      return;
-      }
-    }
-    if (!p.bn_mode && p.x2) {  // K-extended dgrad, plain epilogue (the conv input is not a BatchNorm output: block entry)
-      if (BN == 64) LPX(64, false, false, true); else LPX(128, false, false, true);
-    } else if (p.bn_mode && p.x2) {   // K-extended dgrad (folded BatchNorm backward of the consumer's output) + fused BN reduce
-      if (eps == 1 && p.rem_parts < 2) { if constexpr (sizeof(T) == 2) { if (BN == 64) LPE(64, true, 1); else LPE(128, true, 1); } }
-      else if (BN == 64) LPX(64, true, true, true); else LPX(128, true, true, true);
-    } else if (p.bn_mode) {    // dgrad with fused BN-backward reduce (statistics = sum dm, sum dm*x^)
-      if ((eps == 1 || eps >= 3) && p.rem_parts < 2) {
-        if constexpr (sizeof(T) == 2) {
-          if (eps == 1) { if (BN == 64) LPE(64, false, 1); else LPE(128, false, 1); }
-          else if (eps == 3) { if (BN == 64) LPE(64, false, 3); else LPE(128, false, 3); }
-          else { if (BN == 64) LPE(64, false, 4); else LPE(128, false, 4); }
-        }
-      }
-      else if (BN == 64) LP(64, true, true); else LP(128, true, true);
-    } else if (BN == 64) { if (st) LP(64, true, false); else LP(64, false, false); }
-    else { if (st) LP(128, true, false); else LP(128, false, false); }
-#undef LP
-#undef LPX
-#undef LPE
-    return;
+  // epilogue: statistics, fused BatchNorm-backward reduce, K-extension (the K-extended dgrad without the reduce keeps no statistics)
+  k.bnepi = p.bn_mode != 0;
+  k.ext = p.x2 != nullptr;
+  k.stats = k.bnepi || (st && !k.ext);
+  if (p.ntaps <= 0 || p.n_tiles > 64) {
+    if (p.x_ps || (p.w_ps && p.ntaps > 0) || p.accumulate == 2) { k.family = IgemmPlan::UNSUPPORTED; return k; }
+    k.family = IgemmPlan::FALLBACK;
+    k.bn = BN; k.stats = st; k.bnepi = k.ext = false;
+    k.grid = ceil_div(p.m_tiles, 8) * 8 * p.n_tiles; k.block = 256;
+    k.lds = 2 * (128 + BN) * 128;
+    const size_t epi = 128 * (BN * 2 + 8) + 128 * sizeof(long long);
+    if (bf16 && epi > k.lds) k.lds = epi;
+    return k;
   }
-  if (p.x_ps || (p.w_ps && p.ntaps > 0) || p.accumulate == 2) { g_igemm_fail = 1; return; }
-#define L(BNv, STv)                                                                                    \
-  do {                                                                                                 \
-    if (no_glds) SIMCLR_LAUNCH((conv_igemm<T, MODE, BNv, STv, false>), dim3(grid), dim3(256), lds, stream, p); \
-    else SIMCLR_LAUNCH((conv_igemm<T, MODE, BNv, STv, true>), dim3(grid), dim3(256), lds, stream, p);          \
-  } while (0)
-  if (BN == 64) { if (st) L(64, true); else L(64, false); }
-  else { if (st) L(128, true); else L(128, false); }
-#undef L
+  // Tile choice: 128x128 / 128x64, 4 waves, 2-stage LDS ring, 2-3 workgroups per CU.  Measured alternatives that were slower on
+  // every ResNet-50 layer (profiles/r01_notes.md): 256x128 with 8 waves (one workgroup per CU), and 3-stage rings with counted
+  // vmcnt for either tile.
+  // 256 x 256 tile, 8 waves of 128 x 64 (one workgroup per CU): half the L2->LDS bytes per FLOP of the 128 x 128 tile
+  // (which needs 64 B/clk/CU from L2 at the MFMA peak -- more than an XCD's L2 delivers) and 0.375 instead of 0.5 KB
+  // of LDS fragment reads per MFMA.  SIMCLR_IGEMM_TILE: 128 / 256 force a tile, unset = igemm_use_256 (measured per
+  // layer class, profiles/r03_notes.md).  The statistics slots of the 128-wide geometry (simclr_conv2d_stats_slots)
+  // are never fewer than this grid's M-slots.
+  const bool wide = bf16 && igemm_use_wide(p, fwd);
+  if (wide || (bf16 && igemm_use_256(p, fwd))) {
+    p.m_tiles = ceil_div(p.M, 256);
+    p.n_tiles = p.N / 256;
+    const int unit = 8 * p.n_tiles;
+    k.grid = min(max(unit, (256 / unit) * unit), ceil_div(p.m_tiles, 8) * unit);
+    k.block = 512;
+    k.tile_floats = (size_t)256 * 256;
+    if (wide) {
+      // eight-phase 256 x 256 tile (csrc/igemm_wide.h): one 8-wave workgroup per CU, 150 KB of LDS
+      k.family = IgemmPlan::WIDE;
+      p.x_bytes = (unsigned)((long long)p.V * p.IH * p.IW * p.pixpitch * 2);
+      const int dist[3] = {8, 128, 136}, chw = p.cls_h * p.cls_w;
+      for (int i = 0; i < 3; ++i) {
+        p.rs_dq[i] = dist[i] / chw;
+        const int r = dist[i] - p.rs_dq[i] * chw;
+        p.rs_drow[i] = r / p.cls_w; p.rs_dcol[i] = r - p.rs_drow[i] * p.cls_w;
+      }
+      // ring 128 KB + BN parameters 4 KB + row offsets 2 KB + per-wave statistics 16 KB + border coordinates 8 KB
+      k.lds = 131072 + 4 * 256 * sizeof(float) + 256 * sizeof(long long) + 8 * 256 * 2 * sizeof(float) + 4 * 512 * sizeof(int);
+      if (can_split) split_tail_plan(p, k.grid, p.ntaps * (p.IC / 64), 1, true);
+      k.flat = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.cs == 1 && p.IH == p.OH && p.IW == p.OW;
+    } else {
+      k.family = IgemmPlan::TILE256;
+      k.bn = 256;
+      k.lds = 2 * (256 + 256) * 128 + 5 * 256 * sizeof(float) + 256 * sizeof(long long) + 8 * 256 * 2 * sizeof(float);
+      k.fapply = p.fapply != 0;
+      if (k.fapply) k.stats = k.bnepi = k.ext = false;
+      else if (can_split) split_tail_plan(p, k.grid, p.ntaps * (p.IC / 64) + (p.x2 ? p.ic2 / 64 : 0), 1);
+      k.tail = p.rem_parts >= 2;
+    }
+    return k;
+  }
+  k.family = IgemmPlan::TILE128;
+  k.bn = BN;
+  int pg, bn_, nt_;
+  igemm_persistent_grid(p.M, p.N, &bn_, &nt_, &pg, narrow);   // 2-3 workgroups per CU, a multiple of 8*n_tiles, at most one per tile
+  k.grid = pg; k.block = 256;
+  k.lds = 2 * (128 + BN) * 128 + 5 * BN * sizeof(float) + 128 * sizeof(long long);
+  // 3x3 stride-1: halo-window operand path (one window load per 128-byte channel chunk instead of nine gathers).  fp32 storage (round 6):
+  // the three-term launches with pre-split weights (A/B of the fp32 path: 143.94 / 144.15 / 144.00 -> 141.75 / 141.58 / 141.22 ms per
+  // step, r06_call35): the forward = three fp16-piece terms, the data gradient = three bf16-piece terms with both operands pre-split,
+  // plain or with the fused BatchNorm-backward reduce (the launches a ResNet step makes); everything else gathers
+  const bool win3 = (bf16 || p.split == 3 || p.split == 13) && !p.fapply && !p.x2 && p.KH == 3 && p.KW == 3 && p.stride == 1 &&
+                    p.pad == 1 && p.cs == 1 && p.ntaps == 9 && p.IH == p.OH && p.IW == p.OW && p.IW <= 62 && p.accumulate < 2;
+  // reduction units the tail can be split in: k-steps, or 64-channel chunks on the halo-window path
+  // (bf16 128 x 128 tiles only: the 64-wide tiles are the short-K streaming layers, the fp32 kernels keep whole tiles)
+  const int bk_elems = 128 / (int)sizeof(T);
+  if (bf16 && BN == 128 && !p.fapply && can_split) {
+    split_tail_plan(p, pg, win3 ? p.IC / bk_elems : p.ntaps * (p.IC / bk_elems) + (p.x2 ? p.ic2 / bk_elems : 0), win3 ? 9 : 1);
+    k.tile_floats = (size_t)128 * BN;
+  } else {
+    p.rem_parts = 0;
+  }
+  k.tail = p.rem_parts >= 2;
+  // fp32 storage: one instantiation per matrix arithmetic (exact fp32 MFMA, 3 or 6 split-bf16 terms, 3 split-fp16 pieces)
+  if (!bf16) {
+    const bool presplit = can_presplit && presplit_enabled(p.N, p.K);
+    // three-term data gradient: weights pre-split once per launch (PSB)
+    if (!fwd && p.split == 3) { k.psb = true; k.presplit = !p.w_ps && presplit; }
+    // split-fp16 forward (13): fp16 weight planes times 2^F16_WSCALE_LOG2, once per launch; no pre-split buffer -> six bf16 terms
+    if (fwd && p.split == 13) { k.psb = true; k.presplit = !p.w_ps && presplit; }
+    if (k.psb && !p.w_ps && !presplit) {
+      k.psb = false;
+      if (fwd) p.split = 6;
+    }
+    // a pre-split operand cannot be read as floats
+    if ((p.x_ps && !k.psb) || (p.w_ps && !k.psb)) { k.family = IgemmPlan::UNSUPPORTED; return k; }
+    k.spl = k.psb || p.split == 3 || p.split == 6 ? p.split : 0;
+    k.psx = k.psb && p.x_ps;
+  }
+  if (p.fapply) {
+    k.fapply = true;
+    k.stats = k.bnepi = k.ext = false;
+    // the two option sets every fused bottleneck tail uses get instantiations with the options compiled in (FAS, bf16)
+    if (bf16 && p.bn_x && p.bn_mode && p.bn_mask && (p.N & 31) == 0) k.fas = p.bn_mean ? 2 : 1;
+    return k;
+  }
+  // fused BatchNorm-backward-reduce epilogue with its mask mode / accumulate flag compiled in (EPS instantiations, bf16, no split tail):
+  // 1 = (mode 2, store), 3 = (mode 4, store), 4 = (mode 4, accumulate)
+  int eps = 0;
+  if (bf16 && !fwd && p.bn_mode && !k.tail) {
+    if (p.bn_mode == 2 && !p.accumulate) eps = 1;
+    else if (p.bn_mode == 4) eps = p.accumulate ? 4 : 3;
+  }
+  k.win = bf16 ? win3 : win3 && k.psb && (fwd ? !p.bn_mode : p.x_ps && (p.bn_mode != 0) == st);
+  if (k.win) {
+    const int rows = ((128 + 2 * (p.IW + 1)) + 31) / 32 * 32;
+    p.win_j = rows / 32;
+    p.win_bytes = (!bf16 || rows * 128 > 128 * BN * 2) ? rows * 128 : 128 * BN * 2;     // (bf16: doubles as the C staging tile)
+    k.lds = (size_t)p.win_bytes + 2 * BN * 128 + 5 * BN * sizeof(float) + 128 * sizeof(long long) + 128;
+    k.eps = eps == 1 ? 1 : 0;
+  } else {
+    k.eps = eps == 1 || (!k.ext && eps >= 3) ? eps : 0;
+    if (k.psx && k.ext) k.family = IgemmPlan::UNSUPPORTED;       // no K-extended kernel reads a pre-split dy
+  }
+  return k;
+}
+
+// ---- launch: the finished plan -> the instantiation with exactly its template arguments ----------------------------------
+// with_consts(f, among<V, v0, v1, ...>{}, x, ...) calls f(std::integral_constant<V, x>{}, ...): each run-time value x becomes the
+// compile-time constant of its list that equals it.  false if a value is not in its list.
+template <typename V, V... Vs> struct among {};
+template <typename F> static bool with_consts(F&& f) { return f(); }
+template <typename V, V... Vs, typename... Rest, typename F>
+static bool with_consts(F&& f, among<V, Vs...>, V x, Rest... rest) {
+  bool hit = false;
+  (void)((x == Vs && (hit = with_consts([&](auto... c) { return f(std::integral_constant<V, Vs>{}, c...); }, rest...), true)) || ...);
+  return hit;
+}
+using Bools = among<bool, false, true>;
+
+// The instantiations that exist.  Epilogues: plain, statistics, fused BatchNorm-backward reduce, K-extended plain / with the reduce.
+static constexpr bool epilogue_exists(bool st, bool be, bool ex) { return (st || !be) && (!ex || st == be); }
+// 128 x BN persistent tile (conv_igemm_persistent<T, MODE, 128, BN, 4, 2, ...>)
+static constexpr bool tile128_exists(bool bf16, bool fwd, int bn, bool st, bool be, bool ex, bool win, bool fa, int spl, bool tail,
+                                     bool psb, int fas, int eps, bool psx) {
+  if (fa)        // fused BatchNorm apply (forward): bf16 with the option sets compiled in (FAS) or not; fp32 per matrix arithmetic
+    return fwd && !st && !be && !ex && !win && !tail && !eps && !psx && (bf16 ? spl == 0 && !psb : fas == 0 && psb == (spl == 13));
+  if (fas || !epilogue_exists(st, be, ex) || (win && ex)) return false;
+  if (bf16)      // split tail on the 128 x 128 tile; mask mode / accumulate of the reduce compiled in (EPS)
+    return spl == 0 && !psb && !psx && (eps ? st && be && !tail && (eps == 1 || (!ex && !win && (eps == 3 || eps == 4))) : !tail || bn == 128);
+  if (tail || eps) return false;
+  // fp32: the halo window = three-term launches with pre-split weights (and a pre-split dy in the data gradient)
+  if (win) return psb && (fwd ? spl == 13 && !be && !psx : spl == 3 && psx);
+  if (psx) return !fwd && !ex && psb && spl == 3;
+  if (psb) return fwd ? spl == 13 && !be && !ex : spl == 3;
+  return spl == 0 || spl == 3 || spl == 6;
+}
+
+// false: no instantiation has the plan's template arguments (a plan_igemm bug, reported like an unsupported launch)
+template <typename T, int MODE>
+static bool launch_plan(const IgemmPlan& k, hipStream_t s) {
+  constexpr bool bf16 = sizeof(T) == 2, fwd = MODE == MODE_FWD;
+  const dim3 g(k.grid), b(k.block);
+  switch (k.family) {
+    case IgemmPlan::FALLBACK:
+      return with_consts([&](auto BN, auto ST) { run_igemm<T, MODE, BN, ST, true>(g, b, k.lds, s, k.p); return true; },
+                         among<int, 64, 128>{}, k.bn, Bools{}, k.stats);
+    case IgemmPlan::WIDE:
+      if constexpr (bf16)
+        return with_consts([&](auto ST, auto BE, auto FLAT) {
+          if constexpr (!epilogue_exists(ST, BE, false)) return false;
+          else { run_wide<MODE, ST, BE, FLAT>(g, b, k.lds, s, k.p); return true; }
+        }, Bools{}, k.stats, Bools{}, k.bnepi, Bools{}, k.flat);
+      return false;
+    case IgemmPlan::TILE256:
+      if constexpr (bf16)
+        return with_consts([&](auto ST, auto BE, auto EX, auto FA, auto TAIL) {
+          if constexpr (FA ? !(fwd && !ST && !BE && !EX && !TAIL) : !epilogue_exists(ST, BE, EX)) return false;
+          else { run_persistent<T, MODE, 256, 256, 8, 2, ST, BE, EX, false, FA, 0, TAIL>(g, b, k.lds, s, k.p); return true; }
+        }, Bools{}, k.stats, Bools{}, k.bnepi, Bools{}, k.ext, Bools{}, k.fapply, Bools{}, k.tail);
+      return false;
+    case IgemmPlan::TILE128: {
+      // per storage only the arguments that vary: bf16 TAIL / FAS / EPS, fp32 SPL / PSB / PSX
+      using Spl = std::conditional_t<bf16, among<int, 0>, among<int, 0, 3, 6, 13>>;
+      using FpBools = std::conditional_t<bf16, among<bool, false>, Bools>;
+      using HBools = std::conditional_t<bf16, Bools, among<bool, false>>;
+      using Fas = std::conditional_t<bf16, among<int, 0, 1, 2>, among<int, 0>>;
+      using Eps = std::conditional_t<bf16, among<int, 0, 1, 3, 4>, among<int, 0>>;
+      return with_consts([&](auto BN, auto ST, auto BE, auto EX, auto WIN, auto FA, auto SPL, auto TAIL, auto PSB, auto FAS, auto EPS, auto PSX) {
+        if constexpr (!tile128_exists(bf16, fwd, BN, ST, BE, EX, WIN, FA, SPL, TAIL, PSB, FAS, EPS, PSX)) return false;
+        else { run_persistent<T, MODE, 128, BN, 4, 2, ST, BE, EX, WIN, FA, SPL, TAIL, PSB, FAS, EPS, PSX>(g, b, k.lds, s, k.p); return true; }
+      }, among<int, 64, 128>{}, k.bn, Bools{}, k.stats, Bools{}, k.bnepi, Bools{}, k.ext, Bools{}, k.win, Bools{}, k.fapply, Spl{}, k.spl,
+         HBools{}, k.tail, FpBools{}, k.psb, Fas{}, k.fas, Eps{}, k.eps, FpBools{}, k.psx);
+    }
+    default:
+      return false;
+  }
+}
+
+// One forward / dgrad launch: plan, resources, launch.  Returns 0, or 1 when the launch cannot honour its operand format.
+template <typename T, int MODE>
+static int launch_igemm_one(const ConvP& p, hipStream_t stream) {
+  bool can_split = true, can_presplit = true;
+  IgemmPlan k = plan_igemm<T, MODE>(p, can_split, can_presplit);
+  if (k.family == IgemmPlan::UNSUPPORTED) return 1;
+  if (k.p.rem_parts >= 2 && !split_tail_scratch(k.p, k.tile_floats, stream)) k = plan_igemm<T, MODE>(p, can_split = false, can_presplit);
+  if (k.presplit) {
+    const void* ws = presplit_weights(k.p.w, k.p.N, k.p.K, stream, k.spl == 13);
+    if (ws) k.p.w = ws;
+    else k = plan_igemm<T, MODE>(p, can_split, can_presplit = false);
+  }
+  if (k.family == IgemmPlan::EMPTY) return 0;
+  if (k.family == IgemmPlan::UNSUPPORTED) return 1;
+  if (k.family != IgemmPlan::FALLBACK) g_last_split_parts = k.p.rem_parts;
+  if (sizeof(T) == 4 && MODE == MODE_DGRAD && k.family == IgemmPlan::TILE128) g_last_presplit = k.psb;
+  return launch_plan<T, MODE>(k, stream) ? 0 : 1;
 }
 
 // Forward and stride-1 dgrad: one class with every tap.  Strided dgrad: one launch per output
 // parity class with only the taps that can contribute (1x1 s2: a single class has work, the
-// other three are zero-filled unless accumulating).
+// other three are zero-filled unless accumulating).  Every class is planned before the first is launched.
 template <typename T, int MODE>
-int launch_igemm(const ConvP& p0, hipStream_t stream) {
+static int launch_igemm(const ConvP& p0, hipStream_t stream) {
   ConvP p = p0;
   if (MODE == MODE_FWD || p.stride == 1) {
     p.cs = 1; p.py = 0; p.px = 0; p.cls_h = p.OH; p.cls_w = p.OW;
@@ -3829,10 +3868,11 @@ int launch_igemm(const ConvP& p0, hipStream_t stream) {
       p.dx_w |= (unsigned long long)(dx + 8) << (4 * t);
     }
     p.M = p.V * p.OH * p.OW;
-    launch_igemm_one<T, MODE>(p, stream);
-    return 0;
+    return launch_igemm_one<T, MODE>(p, stream);
   }
   const int S = p.stride;
+  ConvP cls[4];
+  int n = 0;
   for (int py = 0; py < S; ++py)
     for (int px = 0; px < S; ++px) {
       ConvP q = p;
@@ -3857,9 +3897,47 @@ int launch_igemm(const ConvP& p0, hipStream_t stream) {
       else if (q.ntaps == 0 && p.accumulate) continue;
       if (p.accumulate == 3) q.accumulate = 0;      // sparse store: the classes with taps are plain stores
       if (q.ntaps == 0) q.x_ps = 0;                 // zero fill: the gathered tensor is not read at all
-      launch_igemm_one<T, MODE>(q, stream);
+      if (plan_igemm<T, MODE>(q, true, true).family == IgemmPlan::UNSUPPORTED) return 1;
+      cls[n++] = q;
     }
+  for (int i = 0; i < n; ++i)
+    if (int rc = launch_igemm_one<T, MODE>(cls[i], stream)) return rc;
   return 0;
+}
+
+// What every forward / data-gradient entry point takes from its dtype argument: the storage, the matrix arithmetic of the call
+// (SIMCLR_FMT_TERMS, see terms_of), pre-split weights (SIMCLR_FMT_PS_W: fp32 storage and ps_w_terms terms; 0 = not accepted) and
+// (ps_in) a pre-split gathered operand dy (SIMCLR_FMT_PS_IN: fp32 storage, three terms, Cout % 32 == 0).  fn names the entry point.
+struct ConvCall { int dtype, terms; bool w_ps, x_ps; };
+static int conv_call(const char* fn, int dtype, bool fwd, int ps_w_terms, bool ps_in, int Cout, ConvCall* c) {
+  c->terms = terms_of(&dtype, fwd);
+  SIMCLR_CHECK_ARG(c->terms >= 0, "%s: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)", fn);
+  c->w_ps = ps_w_terms && take_ps_w(&dtype);
+  SIMCLR_CHECK_ARG(!c->w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && c->terms == ps_w_terms),
+                   "%s: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms %d", fn, ps_w_terms);
+  c->x_ps = ps_in && (dtype & SIMCLR_FMT_PS_IN) != 0;
+  if (ps_in) dtype &= 0xff;
+  SIMCLR_CHECK_ARG(!c->x_ps || (dtype == SIMCLR_DT_F32 && c->terms == 3 && Cout % 32 == 0),
+                   "%s: a pre-split dy needs fp32 storage, three backward terms (simclr_set_f32_matmul) and Cout %% 32 == 0", fn);
+  c->dtype = dtype;
+  return 0;
+}
+// The ConvP of a call after its checks: x = the gathered tensor [V, IH, IW, IC], w = [N][KH*KW*IC], y = the output [V, OH, OW, N].
+static int conv_params(const ConvCall& c, const void* x, const void* w, void* y, int V, int IH, int IW, int IC, int OH, int OW, int N,
+                       int KH, int KW, int stride, int pad, ConvP* p) {
+  *p = {};
+  p->zero = zero_page();
+  SIMCLR_CHECK_ARG(p->zero != nullptr, "conv2d: zero page symbol not found");
+  p->w_ps = c.w_ps ? 1 : 0; p->x_ps = c.x_ps ? 1 : 0;
+  p->split = c.terms;
+  p->x = x; p->w = w; p->y = y;
+  p->V = V; p->IH = IH; p->IW = IW; p->IC = IC; p->OH = OH; p->OW = OW; p->N = N;
+  p->KH = KH; p->KW = KW; p->stride = stride; p->pad = pad; p->pixpitch = IC;
+  p->M = V * OH * OW; p->K = KH * KW * IC;
+  return 0;
+}
+template <int MODE> static int launch_conv(int dtype, const ConvP& p, hipStream_t stream) {
+  return dtype == SIMCLR_DT_BF16 ? launch_igemm<uint16_t, MODE>(p, stream) : launch_igemm<float, MODE>(p, stream);
 }
 
 }  // namespace
@@ -3904,10 +3982,9 @@ int simclr_stem_stats_slots(long long M) { return (int)min((M + 127) / 128, 2048
 int simclr_conv2d_fwd(const void* x, const void* w_t, void* y, float* stats, int nslot, int V,
                       int IH, int IW, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride,
                       int pad, int dtype, hipStream_t stream) {
-  const int terms = terms_of(&dtype, true);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_fwd: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  const bool w_ps = take_ps_w(&dtype);
-  SIMCLR_CHECK_ARG(!w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && terms == 13), "conv2d_fwd: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms 13");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_fwd", dtype, true, 13, false, Cout, &c)) return rc;
+  dtype = c.dtype;
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_fwd: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cin % (8 * epc) == 0, "conv2d_fwd: Cin=%d must be a multiple of %d", Cin, 8 * epc);
@@ -3917,19 +3994,10 @@ int simclr_conv2d_fwd(const void* x, const void* w_t, void* y, float* stats, int
   SIMCLR_CHECK_ARG(!stats || nslot > 0, "conv2d_fwd: nslot must be > 0 with stats");
   SIMCLR_CHECK_ARG(KH * KW <= 9, "conv2d_fwd: at most 9 taps (got %dx%d)", KH, KW);
   SIMCLR_CHECK_ARG(y || (stats && dtype == SIMCLR_DT_BF16), "conv2d_fwd: y == NULL (statistics-only pass) needs stats and bf16");
-  ConvP p = {};
-  p.w_ps = w_ps ? 1 : 0;
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = x; p.w = w_t; p.y = y; p.stats = stats; p.nslot = nslot;
-  p.V = V; p.IH = IH; p.IW = IW; p.IC = Cin; p.OH = OH; p.OW = OW; p.N = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = Cin;
-  p.M = V * OH * OW; p.K = KH * KW * Cin;
-  g_igemm_fail = 0;
-  if (dtype == SIMCLR_DT_BF16) launch_igemm<uint16_t, MODE_FWD>(p, stream);
-  else launch_igemm<float, MODE_FWD>(p, stream);
-  SIMCLR_CHECK_ARG(!g_igemm_fail, "conv2d_fwd: no kernel reads pre-split weights on this launch path");
+  ConvP p;
+  if (int rc = conv_params(c, x, w_t, y, V, IH, IW, Cin, OH, OW, Cout, KH, KW, stride, pad, &p)) return rc;
+  p.stats = stats; p.nslot = nslot;
+  SIMCLR_CHECK_ARG(launch_conv<MODE_FWD>(dtype, p, stream) == 0, "conv2d_fwd: no kernel reads pre-split weights on this launch path");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -3943,10 +4011,9 @@ int simclr_conv2d_fwd(const void* x, const void* w_t, void* y, float* stats, int
 int simclr_conv2d_fwd_pivoted(const void* x, const void* w_t, void* y, float* stats, int nslot, float* pivot, int V,
                               int IH, int IW, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride,
                               int pad, int dtype, hipStream_t stream) {
-  const int terms = terms_of(&dtype, true);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_fwd_pivoted: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  const bool w_ps = take_ps_w(&dtype);
-  SIMCLR_CHECK_ARG(!w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && terms == 13), "conv2d_fwd_pivoted: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms 13");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_fwd_pivoted", dtype, true, 13, false, Cout, &c)) return rc;
+  dtype = c.dtype;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_F32, "conv2d_fwd_pivoted: fp32 only (dtype %d)", dtype);
   SIMCLR_CHECK_ARG(Cin % 32 == 0, "conv2d_fwd_pivoted: Cin=%d must be a multiple of 32", Cin);
   SIMCLR_CHECK_ARG(Cout % 4 == 0, "conv2d_fwd_pivoted: Cout=%d must be a multiple of 4", Cout);
@@ -3954,18 +4021,11 @@ int simclr_conv2d_fwd_pivoted(const void* x, const void* w_t, void* y, float* st
   SIMCLR_CHECK_ARG((long long)V * OH * OW < (1ll << 31), "conv2d_fwd_pivoted: M overflows int32");
   SIMCLR_CHECK_ARG(x && w_t && y && stats && pivot && nslot > 0, "conv2d_fwd_pivoted: null argument");
   SIMCLR_CHECK_ARG(KH * KW <= 9, "conv2d_fwd_pivoted: at most 9 taps (got %dx%d)", KH, KW);
-  ConvP p = {};
-  p.w_ps = w_ps ? 1 : 0;
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = x; p.w = w_t; p.y = y; p.stats = stats; p.nslot = nslot;
-  p.V = V; p.IH = IH; p.IW = IW; p.IC = Cin; p.OH = OH; p.OW = OW; p.N = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = Cin;
-  p.M = V * OH * OW; p.K = KH * KW * Cin;
-  // the persistent fp32 kernel is the one that knows about the pivot (launch_igemm_one: n_tiles <= 64, no A/B switches)
-  const bool persistent = Cout <= 64 * 64 && !getenv("SIMCLR_NO_GLDS") && !getenv("SIMCLR_NO_PERSISTENT");
-  if (persistent) {
+  ConvP p;
+  if (int rc = conv_params(c, x, w_t, y, V, IH, IW, Cin, OH, OW, Cout, KH, KW, stride, pad, &p)) return rc;
+  p.stats = stats; p.nslot = nslot;
+  // the persistent fp32 kernel is the one that knows about the pivot (plan_igemm: n_tiles <= 64)
+  if (Cout <= 64 * 64) {
     if (!dry_run())
       hipLaunchKernelGGL(conv_pivot_row, dim3(Cout), dim3(256), 0, stream, (const float*)x, (const float*)w_t, pivot,
                          IH, IW, Cin, Cin, OH, OW, Cout, KH, KW, stride, pad, p.w_ps);
@@ -3973,9 +4033,7 @@ int simclr_conv2d_fwd_pivoted(const void* x, const void* w_t, void* y, float* st
   } else if (!dry_run()) {
     if (hipMemsetAsync(pivot, 0, (size_t)Cout * sizeof(float), stream) != hipSuccess) { simclr_set_error("conv2d_fwd_pivoted: memset failed"); return 2; }
   }
-  g_igemm_fail = 0;
-  launch_igemm<float, MODE_FWD>(p, stream);
-  SIMCLR_CHECK_ARG(!g_igemm_fail, "conv2d_fwd_pivoted: no kernel reads pre-split weights on this launch path");
+  SIMCLR_CHECK_ARG((launch_igemm<float, MODE_FWD>(p, stream)) == 0, "conv2d_fwd_pivoted: no kernel reads pre-split weights on this launch path");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -3992,36 +4050,24 @@ int simclr_conv2d_fwd_bn_apply(const void* x, const void* w_t, void* y, const fl
                                unsigned char* relu_bits, int V, int IH, int IW, int Cin,
                                int OH, int OW, int Cout, int KH, int KW, int stride, int pad, int dtype,
                                hipStream_t stream) {
-  const int terms = terms_of(&dtype, true);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_fwd_bn_apply: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  const bool w_ps = take_ps_w(&dtype);
-  SIMCLR_CHECK_ARG(!w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && terms == 13), "conv2d_fwd_bn_apply: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms 13");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_fwd_bn_apply", dtype, true, 13, false, Cout, &c)) return rc;
+  dtype = c.dtype;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_fwd_bn_apply: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cin % (dtype == SIMCLR_DT_BF16 ? 64 : 32) == 0, "conv2d_fwd_bn_apply: Cin=%d must be a multiple of %d", Cin, dtype == SIMCLR_DT_BF16 ? 64 : 32);
-  SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || (Cout <= 64 * 64 && !getenv("SIMCLR_NO_GLDS") && !getenv("SIMCLR_NO_PERSISTENT")),
-                   "conv2d_fwd_bn_apply: the fp32 epilogue lives in the persistent kernel only");
+  SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || Cout <= 64 * 64, "conv2d_fwd_bn_apply: the fp32 epilogue lives in the persistent kernel only");
   SIMCLR_CHECK_ARG(Cout % 8 == 0, "conv2d_fwd_bn_apply: Cout=%d must be a multiple of 8", Cout);
   SIMCLR_CHECK_ARG(x && w_t && y && scale && shift, "conv2d_fwd_bn_apply: null argument");
   SIMCLR_CHECK_ARG((rscale == nullptr) == (rshift == nullptr) && (!rscale || res), "conv2d_fwd_bn_apply: rscale / rshift come together and need res");
   SIMCLR_CHECK_ARG(V > 0 && OH > 0 && OW > 0 && stride >= 1, "conv2d_fwd_bn_apply: bad geometry");
   SIMCLR_CHECK_ARG((long long)V * OH * OW < (1ll << 31), "conv2d_fwd_bn_apply: M overflows int32");
   SIMCLR_CHECK_ARG(KH * KW <= 9, "conv2d_fwd_bn_apply: at most 9 taps (got %dx%d)", KH, KW);
-  ConvP p = {};
-  p.w_ps = w_ps ? 1 : 0;
-  (void)terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = x; p.w = w_t; p.y = y;
-  p.V = V; p.IH = IH; p.IW = IW; p.IC = Cin; p.OH = OH; p.OW = OW; p.N = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = Cin;
-  p.M = V * OH * OW; p.K = KH * KW * Cin;
+  ConvP p;
+  if (int rc = conv_params(c, x, w_t, y, V, IH, IW, Cin, OH, OW, Cout, KH, KW, stride, pad, &p)) return rc;
+  if (dtype != SIMCLR_DT_F32) p.split = 0;
   p.fapply = 1; p.bn_scale = scale; p.bn_shift = shift; p.bn_x = res; p.bn_mask = relu_bits; p.bn_mode = relu ? 1 : 0;
   p.bn_mean = rscale; p.bn_rstd = rshift;
-  (void)terms;
-  g_igemm_fail = 0;
-  if (dtype == SIMCLR_DT_F32) { p.split = terms; launch_igemm<float, MODE_FWD>(p, stream); }
-  else launch_igemm<uint16_t, MODE_FWD>(p, stream);
-  SIMCLR_CHECK_ARG(!g_igemm_fail, "conv2d_fwd_bn_apply: no kernel reads pre-split weights on this launch path");
+  SIMCLR_CHECK_ARG(launch_conv<MODE_FWD>(dtype, p, stream) == 0, "conv2d_fwd_bn_apply: no kernel reads pre-split weights on this launch path");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4031,15 +4077,10 @@ int simclr_conv2d_fwd_bn_apply(const void* x, const void* w_t, void* y, const fl
 int simclr_conv2d_dgrad(const void* dy, const void* w_d, void* dx, int accumulate, int V, int IH,
                         int IW, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int pad,
                         int dtype, hipStream_t stream) {
-  const int terms = terms_of(&dtype, false);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_dgrad: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  const bool w_ps = take_ps_w(&dtype);
-  SIMCLR_CHECK_ARG(!w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && terms == 3), "conv2d_dgrad: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms 3");
   // dtype | SIMCLR_FMT_PS_IN (fp32, three bf16 backward terms, Cout a multiple of 32): dy is in the pre-split block format (common.h)
-  const bool dy_ps = (dtype & SIMCLR_FMT_PS_IN) != 0;
-  dtype &= 0xff;
-  SIMCLR_CHECK_ARG(!dy_ps || (dtype == SIMCLR_DT_F32 && terms == 3 && Cout % 32 == 0),
-                   "conv2d_dgrad: a pre-split dy needs fp32 storage, three backward terms (simclr_set_f32_matmul) and Cout %% 32 == 0");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_dgrad", dtype, false, 3, true, Cout, &c)) return rc;
+  dtype = c.dtype;
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_dgrad: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cout % (8 * epc) == 0, "conv2d_dgrad: Cout=%d must be a multiple of %d", Cout, 8 * epc);
@@ -4051,20 +4092,10 @@ int simclr_conv2d_dgrad(const void* dy, const void* w_d, void* dx, int accumulat
   SIMCLR_CHECK_ARG(accumulate >= 0 && accumulate <= 3, "conv2d_dgrad: accumulate must be 0 ... 3 (got %d)", accumulate);
   SIMCLR_CHECK_ARG(accumulate != 2 || dtype == SIMCLR_DT_F32, "conv2d_dgrad: accumulate = 2 (sparse earlier data) is an fp32 path");
   SIMCLR_CHECK_ARG(accumulate != 3 || stride == 2, "conv2d_dgrad: accumulate = 3 (sparse store) needs stride 2");
-  ConvP p = {};
-  p.w_ps = w_ps ? 1 : 0;
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = dy; p.w = w_d; p.y = dx; p.stats = nullptr; p.nslot = 1; p.accumulate = accumulate;
-  p.V = V; p.IH = OH; p.IW = OW; p.IC = Cout; p.OH = IH; p.OW = IW; p.N = Cin;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = Cout;
-  p.M = V * IH * IW; p.K = KH * KW * Cout;
-  p.x_ps = dy_ps ? 1 : 0;
-  g_igemm_fail = 0;
-  if (dtype == SIMCLR_DT_BF16) launch_igemm<uint16_t, MODE_DGRAD>(p, stream);
-  else launch_igemm<float, MODE_DGRAD>(p, stream);
-  SIMCLR_CHECK_ARG(!g_igemm_fail, "conv2d_dgrad: no kernel for a pre-split dy on this launch path (pre-split weights unavailable?)");
+  ConvP p;
+  if (int rc = conv_params(c, dy, w_d, dx, V, OH, OW, Cout, IH, IW, Cin, KH, KW, stride, pad, &p)) return rc;
+  p.nslot = 1; p.accumulate = accumulate;
+  SIMCLR_CHECK_ARG(launch_conv<MODE_DGRAD>(dtype, p, stream) == 0, "conv2d_dgrad: no kernel for a pre-split dy on this launch path (pre-split weights unavailable?)");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4079,14 +4110,9 @@ int simclr_conv2d_dgrad_bn(const void* dy, const void* w_d, void* dx, int accumu
                            const float* bn_mean, const float* bn_rstd, int mask_mode, float* stats, int nslot,
                            int V, int IH, int IW, int Cin, int OH, int OW, int Cout, int KH, int KW,
                            int stride, int pad, int dtype, hipStream_t stream) {
-  const int terms = terms_of(&dtype, false);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_dgrad_bn: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  const bool w_ps = take_ps_w(&dtype);
-  SIMCLR_CHECK_ARG(!w_ps || ((dtype & 0xff) == SIMCLR_DT_F32 && terms == 3), "conv2d_dgrad_bn: pre-split weights (SIMCLR_FMT_PS_W) need fp32 storage and terms 3");
-  const bool dy_ps = (dtype & SIMCLR_FMT_PS_IN) != 0;          // see simclr_conv2d_dgrad
-  dtype &= 0xff;
-  SIMCLR_CHECK_ARG(!dy_ps || (dtype == SIMCLR_DT_F32 && terms == 3 && Cout % 32 == 0),
-                   "conv2d_dgrad_bn: a pre-split dy needs fp32 storage, three backward terms (simclr_set_f32_matmul) and Cout %% 32 == 0");
+  ConvCall c;                                                  // SIMCLR_FMT_PS_IN: see simclr_conv2d_dgrad
+  if (int rc = conv_call("conv2d_dgrad_bn", dtype, false, 3, true, Cout, &c)) return rc;
+  dtype = c.dtype;
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_dgrad_bn: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cout % (8 * epc) == 0, "conv2d_dgrad_bn: Cout=%d must be a multiple of %d", Cout, 8 * epc);
@@ -4099,22 +4125,12 @@ int simclr_conv2d_dgrad_bn(const void* dy, const void* w_d, void* dx, int accumu
   SIMCLR_CHECK_ARG(stats && nslot > 0 && (mask_mode == 4 || (bn_x && bn_mean && bn_rstd)), "conv2d_dgrad_bn: null BN argument");
   SIMCLR_CHECK_ARG(mask_mode == 2 || bn_mask, "conv2d_dgrad_bn: mask_mode 1 / 3 / 4 need bn_mask");
   SIMCLR_CHECK_ARG(mask_mode != 2 || (bn_scale && bn_shift), "conv2d_dgrad_bn: mask_mode 2 needs scale/shift");
-  ConvP p = {};
-  p.w_ps = w_ps ? 1 : 0;
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = dy; p.w = w_d; p.y = dx; p.stats = stats; p.nslot = nslot; p.accumulate = accumulate;
-  p.V = V; p.IH = OH; p.IW = OW; p.IC = Cout; p.OH = IH; p.OW = IW; p.N = Cin;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = Cout;
-  p.M = V * IH * IW; p.K = KH * KW * Cout;
+  ConvP p;
+  if (int rc = conv_params(c, dy, w_d, dx, V, OH, OW, Cout, IH, IW, Cin, KH, KW, stride, pad, &p)) return rc;
+  p.stats = stats; p.nslot = nslot; p.accumulate = accumulate;
   p.bn_x = bn_x; p.bn_mask = bn_mask; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
   p.bn_mean = bn_mean; p.bn_rstd = bn_rstd; p.bn_mode = mask_mode;
-  p.x_ps = dy_ps ? 1 : 0;
-  g_igemm_fail = 0;
-  if (dtype == SIMCLR_DT_BF16) launch_igemm<uint16_t, MODE_DGRAD>(p, stream);
-  else launch_igemm<float, MODE_DGRAD>(p, stream);
-  SIMCLR_CHECK_ARG(!g_igemm_fail, "conv2d_dgrad_bn: no kernel for a pre-split dy on this launch path (pre-split weights unavailable?)");
+  SIMCLR_CHECK_ARG(launch_conv<MODE_DGRAD>(dtype, p, stream) == 0, "conv2d_dgrad_bn: no kernel for a pre-split dy on this launch path (pre-split weights unavailable?)");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4130,8 +4146,9 @@ int simclr_conv2d_dgrad_bn_ext(const void* dm, const void* h, const void* w_ext,
                                const float* bn_shift, const float* bn_mean, const float* bn_rstd, int mask_mode,
                                float* stats, int nslot, int V, int H, int W, int Cin, int Cout, int dtype,
                                hipStream_t stream) {
-  const int terms = terms_of(&dtype, false);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_dgrad_bn_ext: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_dgrad_bn_ext", dtype, false, 0, false, Cout, &c)) return rc;
+  dtype = c.dtype;
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_dgrad_bn_ext: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cout % (8 * epc) == 0 && Cin % (8 * epc) == 0, "conv2d_dgrad_bn_ext: Cin=%d / Cout=%d must be multiples of %d", Cin, Cout, 8 * epc);
@@ -4140,19 +4157,14 @@ int simclr_conv2d_dgrad_bn_ext(const void* dm, const void* h, const void* w_ext,
   SIMCLR_CHECK_ARG(dm && h && w_ext && stats && nslot > 0 && (mask_mode == 4 || (bn_x && bn_mean && bn_rstd)), "conv2d_dgrad_bn_ext: null argument");
   SIMCLR_CHECK_ARG(mask_mode == 2 || bn_mask, "conv2d_dgrad_bn_ext: mask_mode 1 / 3 / 4 need bn_mask");
   SIMCLR_CHECK_ARG(mask_mode != 2 || (bn_scale && bn_shift), "conv2d_dgrad_bn_ext: mask_mode 2 needs scale/shift");
-  ConvP p = {};
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = dm; p.w = w_ext; p.y = dx; p.stats = stats; p.nslot = nslot; p.accumulate = accumulate;
-  p.V = V; p.IH = H; p.IW = W; p.IC = Cout; p.OH = H; p.OW = W; p.N = Cin;
-  p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.pixpitch = Cout;
-  p.M = V * H * W; p.K = Cout + Cin;
+  ConvP p;
+  if (int rc = conv_params(c, dm, w_ext, dx, V, H, W, Cout, H, W, Cin, 1, 1, 1, 0, &p)) return rc;
+  p.stats = stats; p.nslot = nslot; p.accumulate = accumulate;
+  p.K = Cout + Cin;
   p.x2 = h; p.ic2 = Cin; p.pixpitch2 = Cin; p.bias = bias;
   p.bn_x = bn_x; p.bn_mask = bn_mask; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
   p.bn_mean = bn_mean; p.bn_rstd = bn_rstd; p.bn_mode = mask_mode;
-  if (dtype == SIMCLR_DT_BF16) launch_igemm<uint16_t, MODE_DGRAD>(p, stream);
-  else launch_igemm<float, MODE_DGRAD>(p, stream);
+  SIMCLR_CHECK_ARG(launch_conv<MODE_DGRAD>(dtype, p, stream) == 0, "conv2d_dgrad_bn_ext: no kernel for this launch");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4161,24 +4173,20 @@ int simclr_conv2d_dgrad_bn_ext(const void* dm, const void* h, const void* w_ext,
 // BatchNorm whose conv input is not itself a BatchNorm output (the projection shortcut at a block entry).
 int simclr_conv2d_dgrad_ext(const void* dm, const void* h, const void* w_ext, const float* bias, void* dx, int accumulate,
                             int V, int H, int W, int Cin, int Cout, int dtype, hipStream_t stream) {
-  const int terms = terms_of(&dtype, false);
-  SIMCLR_CHECK_ARG(terms >= 0, "conv2d_dgrad_ext: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
+  ConvCall c;
+  if (int rc = conv_call("conv2d_dgrad_ext", dtype, false, 0, false, Cout, &c)) return rc;
+  dtype = c.dtype;
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_dgrad_ext: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cout % (8 * epc) == 0 && Cin % (8 * epc) == 0, "conv2d_dgrad_ext: Cin=%d / Cout=%d must be multiples of %d", Cin, Cout, 8 * epc);
   SIMCLR_CHECK_ARG((long long)V * H * W < (1ll << 31), "conv2d_dgrad_ext: M overflows int32");
   SIMCLR_CHECK_ARG(dm && h && w_ext && dx, "conv2d_dgrad_ext: null argument");
-  ConvP p = {};
-  p.split = terms;
-  p.zero = zero_page();
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d: zero page symbol not found");
-  p.x = dm; p.w = w_ext; p.y = dx; p.stats = nullptr; p.nslot = 1; p.accumulate = accumulate;
-  p.V = V; p.IH = H; p.IW = W; p.IC = Cout; p.OH = H; p.OW = W; p.N = Cin;
-  p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.pixpitch = Cout;
-  p.M = V * H * W; p.K = Cout + Cin;
+  ConvP p;
+  if (int rc = conv_params(c, dm, w_ext, dx, V, H, W, Cout, H, W, Cin, 1, 1, 1, 0, &p)) return rc;
+  p.nslot = 1; p.accumulate = accumulate;
+  p.K = Cout + Cin;
   p.x2 = h; p.ic2 = Cin; p.pixpitch2 = Cin; p.bias = bias;
-  if (dtype == SIMCLR_DT_BF16) launch_igemm<uint16_t, MODE_DGRAD>(p, stream);
-  else launch_igemm<float, MODE_DGRAD>(p, stream);
+  SIMCLR_CHECK_ARG(launch_conv<MODE_DGRAD>(dtype, p, stream) == 0, "conv2d_dgrad_ext: no kernel for this launch");
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -162,7 +162,7 @@ def test_class_id_cache_follows_the_label_tensor():
 
 def test_instantiation_table_matches_the_committed_one():
     """which kernel instantiation every (ResNet-50 layer class, launch kind, storage mode) selects is ONE table,
-    produced without a GPU (SIMCLR_DRY_RUN=1: launch_igemm_one takes its decisions and records them instead of launching) and
+    produced without a GPU (SIMCLR_DRY_RUN=1: plan_igemm takes the decisions, the launchers record them instead of launching) and
     committed under profiles/ -- a change of a selection rule shows up here as a diff of that file."""
     import subprocess
     import sys
@@ -175,6 +175,36 @@ def test_instantiation_table_matches_the_committed_one():
     assert r.stdout == want, 'the (layer class -> instantiation) table changed: regenerate profiles/r06_instantiations.txt with tools/instantiation_table.py and review the diff'
     rows = [l for l in want.splitlines() if l and not l.startswith('#')]
     assert len(rows) > 200 and any('conv_igemm_wide' in l for l in rows) and any('elt=4' in l and ', 6>' in l for l in rows)
+
+
+_UNSUPPORTED_STRIDED_DGRAD = r'''
+import ctypes
+from simclr_amd import _lib
+L = _lib.lib()
+FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced in a dry run
+L.conv2d_fwd(FAKE, FAKE, FAKE, None, 0, 8, 14, 14, 256, 14, 14, 512, 1, 1, 1, 0, _lib.DT_BF16, None)
+before = L.conv2d_last_instantiation().decode()
+assert before.startswith('(conv_igemm'), before
+try:
+    # 1x1 stride-2 fp32 dgrad with a pre-split dy and no pre-split weights (SIMCLR_F32_PRESPLIT=0): no kernel reads that dy
+    L.conv2d_dgrad(FAKE, FAKE, FAKE, 0, 8, 14, 14, 256, 7, 7, 512, 1, 1, 2, 0,
+                   _lib.DT_F32 | 0x100 | ((3 + 1) << 12), None)      # SIMCLR_FMT_PS_IN | SIMCLR_FMT_TERMS(3)
+    raise SystemExit('the call did not fail')
+except _lib.SimclrHipError as e:
+    assert 'rc=1' in str(e), e
+assert L.conv2d_last_instantiation().decode() == before, 'a pixel class was launched: ' + L.conv2d_last_instantiation().decode()
+print('ok')
+'''
+
+
+def test_unsupported_strided_dgrad_launches_no_pixel_class():
+    """A strided data gradient plans every pixel class before it launches one: when its operand format has no kernel, the call fails
+    and nothing was launched (the zero-fill classes included)."""
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('SIMCLR_')}
+    env.update(SIMCLR_DRY_RUN='1', SIMCLR_F32_PRESPLIT='0')
+    r = subprocess.run([sys.executable, '-c', _UNSUPPORTED_STRIDED_DGRAD], capture_output=True, text=True, env=env, cwd=ROOT, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stdout + r.stderr[-2000:]
 
 
 def test_product_defaults_are_the_tolerance_meeting_mode():

@@ -4,7 +4,7 @@
     python tools/instantiation_table.py [--views 1024] [--out profiles/r06_instantiations.txt]
 
 Runs WITHOUT a GPU: with SIMCLR_DRY_RUN=1 the convolution entry points of libsimclr_hip.so take every launch decision
-(launch_igemm_one: tile shape, halo window, wide eight-phase tile, split tail, pre-split weights, compile-time epilogue
+(plan_igemm: tile shape, halo window, wide eight-phase tile, split tail, pre-split weights, compile-time epilogue
 specialisations) and record it instead of launching (simclr_conv2d_last_instantiation).  One row per (ResNet-50 1x layer class at
 224 px) x (kind of launch a training step issues for it) x (storage / matrix arithmetic).  tests/test_abi.py regenerates the
 table and compares it with the committed file, so a change of the selection rules is a visible diff, not a silent one.
