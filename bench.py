@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Benchmark of the SimCLR pretraining step on MI355X (BASELINE.json metric: images/sec).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   --dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/<name>.npy (dump_outputs below).
+  --full: also every measurement beside the headline (the JSON line extras below); without it the run sets up, warms up, times
+      the K steps, dumps and prints the line, whose extras are then null.
   N>1 without WORLD_SIZE in the environment: bench.py re-launches itself as
       python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
   (one rank per GPU over RCCL); launched that way by a driver it just runs as one rank.
@@ -26,7 +28,7 @@ event per step boundary is recorded (on the launch stream) -> `step_ms` p10 / me
 per-launch HIP-event profiler (2 events per kernel launch) runs in SEPARATE instrumented steps right
 after the timed region, same process, same data -> `roofline`, `families`, `kernels`, `ntxent`.
 
-JSON line extras:
+JSON line extras (--full only; --no_* below skip single ones):
   roofline      -- dominant kernel family (most GPU time).  Split modes: SURVEY 8(d)'s MINIMUM bytes at 4 B / element against 8 TB/s and
                    the 16-bit MFMA work (fp32 products x terms) against 2.5 PFLOP/s, whichever costs more time is the binding roof
                    (`families` gives forward / data gradient / weight gradient separately).  bf16 / exact fp32: algorithmic FLOPs
@@ -36,6 +38,8 @@ JSON line extras:
   ntxent        -- the fused NT-Xent forward+backward kernels (north_star's named kernel): us, algorithmic
                    GB/s, TFLOP/s and fraction of the fp32-input MFMA peak.
   speed_mode / f32_mode / parity_mode_bf16x6 -- the same step in the other modes (N = 1), same K / W.
+  parity        -- N = 1: every timed mode's step against the reference-source fixtures (measured_parity) -> `north_star_met`.
+  augment       -- N = 1: the two-view augmentation on the device, outside the step.
   allgather     -- N>1: bandwidth of collective A (all-gather of the hidden block) and of the gradient all-reduce.
   cpu_baseline  -- the CPU oracle (torch-CPU restatement of the TF2 reference; TensorFlow is not installed)
                    timed on this box's host cores (rank 0, N=1 only) on BASELINE configs[0] (ResNet-18,
@@ -421,6 +425,9 @@ def main():
     ap.add_argument('--width_multiplier', type=int, default=1)
     ap.add_argument('--sk_ratio', type=float, default=0.0)
     ap.add_argument('--use_blur', action='store_true', help='include the on-device batch_random_blur (reference default)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: instrumented steps (roofline, kernels, ntxent, PMC traffic), the other '
+                         'modes, in-run parity, augmentation, collectives (N > 1) and the CPU baseline; the --no_* options below skip single ones')
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--no_kernel_events', action='store_true', help='skip the instrumented steps (rocprof runs)')
     ap.add_argument('--no_f32', '--no_side', dest='no_f32', action='store_true', help='skip the side measurements of the other modes (bf16 speed mode, exact fp32, bf16x6_3)')
@@ -493,7 +500,7 @@ def main():
 
     # ---- instrumented steps (per-launch HIP events), outside the headline region
     prof = None
-    if not args.no_kernel_events and args.prof_steps > 0:
+    if args.full and not args.no_kernel_events and args.prof_steps > 0:
         prof = ops.KernelProfiler()
         ops.PROFILER = prof
         for _ in range(args.prof_steps):
@@ -503,7 +510,7 @@ def main():
         ops.PROFILER = None
 
     coll = None
-    if strategy is not None:
+    if args.full and strategy is not None:
         coll = collective_bench(strategy, args.per_gpu_batch, dev, int(model._flat_grads.numel()))
         # proof that N ranks took part: an all-reduce of ones over the collective library, and the set of devices the ranks sit on
         ones = torch.ones(1, device=dev)
@@ -662,7 +669,7 @@ def main():
     # by default the FASTEST mode that meets the tolerances (fp32 storage, three fp16 terms forward, three bf16 terms backward).
     side = {}
     headline = (args.dtype, args.f32_matmul if args.dtype == 'f32' else 'exact')
-    if world == 1 and not args.no_f32:
+    if world == 1 and args.full and not args.no_f32:
         del step_fn, data, model
         import gc
 
@@ -707,7 +714,7 @@ def main():
         _o.set_f32_matmul('exact')
 
     parity = None
-    if world == 1 and not args.no_parity:
+    if world == 1 and args.full and not args.no_parity:
         try:
             del step_fn, data, model
         except NameError:
@@ -722,7 +729,7 @@ def main():
             parity = dict(measured_in_run=False, error=repr(e))
 
     augment = None
-    if world == 1:
+    if world == 1 and args.full:
         # the two-view augmentation on the device (tf2/data_util.py:443-475 x 2 views), NOT part of the timed
         # step (inputs are resident); reported so that the input pipeline's rate can be compared with the step's
         try:
@@ -791,7 +798,7 @@ def main():
         'augment': augment,
         'train_metrics': {k: round(v, 5) for k, v in metrics.items()},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline()
     else:
         line['cpu_baseline'] = None

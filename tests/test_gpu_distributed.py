@@ -467,14 +467,14 @@ def test_rccl_collectives_with_one_rank():
 
 
 def test_bench_two_ranks_over_gloo_on_one_gpu():
-    """`python bench.py --gpus 2 --backend gloo`: the self-launch path (torch.distributed.run, one rank per process), the
+    """`python bench.py --gpus 2 --backend gloo --full`: the self-launch path (torch.distributed.run, one rank per process), the
     N > 1 JSON line and the collective micro-benchmark, with both ranks on cuda:0 over gloo."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
-           '--per_gpu_batch', '16', '--image_size', '64', '--no_cpu_baseline', '--no_f32', '--prof_steps', '1']
+           '--per_gpu_batch', '16', '--image_size', '64', '--full', '--no_cpu_baseline', '--no_f32', '--prof_steps', '1']
     env = dict(os.environ)
     env.pop('WORLD_SIZE', None)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)

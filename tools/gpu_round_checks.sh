@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 cd "$R"
 if [ "$MODE" = "quick" ]; then
   timeout 200 python -m pytest tests/test_gpu_kernels.py -m gpu -x -q -k "test_conv_fwd or dgrad or batch_norm or pooling" 2>&1 | tail -3
-  timeout 120 python bench.py --steps 6 --warmup 2 --no_cpu_baseline --no_f32 --no_pmc > "$OUT/bench_quick.json" 2> "$OUT/bench_quick.err"
+  timeout 120 python bench.py --full --steps 6 --warmup 2 --no_cpu_baseline --no_f32 --no_pmc > "$OUT/bench_quick.json" 2> "$OUT/bench_quick.err"
   python -c "import json,sys;d=json.load(open('$OUT/bench_quick.json'));print(d['value'],d['ms_per_step']);[print(k,v) for k,v in d['kernels'].items()]"
   exit 0
 fi
@@ -21,7 +21,7 @@ if [ "$MODE" != "prof" ]; then      # prof: bench line, microbench, rocprofv3 st
 timeout 2400 python -m pytest tests -m gpu -q > "$OUT/pytest_gpu.log" 2>&1; tail -4 "$OUT/pytest_gpu.log"; grep -n "^FAILED" "$OUT/pytest_gpu.log" | head
 fi
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log"
-timeout 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; cut -c1-300 "$OUT/bench.json" | tail -1
+timeout 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; cut -c1-300 "$OUT/bench.json" | tail -1
 timeout 300 python tools/microbench.py --out "$OUT/microbench.json" > "$OUT/microbench.txt" 2>&1
 cd /tmp; export TMPDIR=/tmp
 B="python $R/bench.py --no_cpu_baseline --no_kernel_events --no_f32 --no_pmc"
@@ -38,12 +38,12 @@ timeout 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O
 cd "$R"
 if [ "$MODE" = "full" ]; then
   # BASELINE configs[3] and [4] on one GPU (per-GPU share of the 8-GPU global batch): value, step_mfma_frac, peak HBM
-  timeout 400 python bench.py --resnet_depth 50 --width_multiplier 2 --sk_ratio 0.0625 --steps 8 --warmup 3 --no_cpu_baseline --no_f32 --no_pmc --prof_steps 1 > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"; cut -c1-260 "$OUT/bench_cfg4.json" | tail -1
+  timeout 400 python bench.py --full --resnet_depth 50 --width_multiplier 2 --sk_ratio 0.0625 --steps 8 --warmup 3 --no_cpu_baseline --no_f32 --no_pmc --prof_steps 1 > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"; cut -c1-260 "$OUT/bench_cfg4.json" | tail -1
   # cfg5 at its real per-GPU share (global 2048 / 8 = 256 images): peaks at 192 GB of the 288 GB (104 GB at 128 images, r03_call5)
-  timeout 700 python bench.py --resnet_depth 152 --width_multiplier 3 --sk_ratio 0.0625 --per_gpu_batch 256 --steps 4 --warmup 2 --no_cpu_baseline --no_f32 --no_pmc --prof_steps 1 > "$OUT/bench_cfg5_b256.json" 2> "$OUT/bench_cfg5_b256.err"; cut -c1-260 "$OUT/bench_cfg5_b256.json" | tail -1
+  timeout 700 python bench.py --full --resnet_depth 152 --width_multiplier 3 --sk_ratio 0.0625 --per_gpu_batch 256 --steps 4 --warmup 2 --no_cpu_baseline --no_f32 --no_pmc --prof_steps 1 > "$OUT/bench_cfg5_b256.json" 2> "$OUT/bench_cfg5_b256.err"; cut -c1-260 "$OUT/bench_cfg5_b256.json" | tail -1
 fi
 if [ "$MODE" = "full" ]; then
   # collective C on one GPU: two ranks over gloo sharing cuda:0, with and without the peer-mapped statistics exchange
-  SIMCLR_PEER_STATS=1 timeout 400 python bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --per_gpu_batch 64 --no_cpu_baseline --no_f32 --no_pmc --no_kernel_events > "$OUT/bench_2rank_peer.json" 2> "$OUT/bench_2rank_peer.err"; cut -c1-200 "$OUT/bench_2rank_peer.json" | tail -1
+  SIMCLR_PEER_STATS=1 timeout 400 python bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --per_gpu_batch 64 --no_cpu_baseline --no_f32 --no_pmc --no_kernel_events > "$OUT/bench_2rank_peer.json" 2> "$OUT/bench_2rank_peer.err"; cut -c1-200 "$OUT/bench_2rank_peer.json" | tail -1
 fi
 ls "$OUT"
