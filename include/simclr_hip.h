@@ -407,6 +407,15 @@ int simclr_conv2d_dgrad_bn_ext(const void* dm, const void* h, const void* w_ext,
 size_t simclr_augment_workspace_bytes(int b, int views, int H, int W);
 int simclr_augment_views(const void* src, int src_dtype, const float* params, void* workspace, float* out, int b,
                          int views, int Hs, int Ws, int H, int W, simclr_stream_t stream);
+/* The same pipeline from PACKED variable-size records (the on-disk array format of simclr_amd/data.py): `packed` holds
+ * packed_bytes bytes of uint8 RGB images, HWC, tightly packed, back to back; table is a DEVICE array [b][3] = {byte offset,
+ * height, width} of image i, read at packed + offset with row pitch 3 * width.  params, workspace
+ * (simclr_augment_workspace_bytes) and out as above; out is bitwise what simclr_augment_views writes for the same pixels and
+ * draws.  A record that does not lie inside packed_bytes yields zeros and a crop box is clamped into its image: no table or
+ * parameter content causes a read outside the buffer. */
+int simclr_augment_views_ragged(const unsigned char* packed, long long packed_bytes, const long long* table,
+                                const float* params, void* workspace, float* out, int b, int views, int H, int W,
+                                simclr_stream_t stream);
 
 /* ---- collective C without a collective library: tf2/resnet.py:50-60 (SyncBatchNormalization moment all-reduce) -------
  * One-shot exchange over peer-mapped memory (csrc/comm.hip): every rank owns a mailbox all peers map through hipIpc;

@@ -7,6 +7,7 @@
 // tf.image.sample_distorted_bounding_box, flip / jitter / grayscale coins, op order, factors) and arrive as a
 // parameter table [b][views][16]; the kernels do the pixel work.  Pure HBM streaming:
 //   K1 crop + bicubic resize + flip : 16 taps per output pixel, source image mostly L2 resident      -> tmp [b*views][H][W][3] f32
+//      (two front ends: a dense canvas [b][Hs][Ws][3], or packed variable-size records + a table -- aug_crop_resize_flip_ragged)
 //   K2 mean of the partially jittered image per (image, view, channel) -- tf.image.adjust_contrast needs the mean of
 //      the image AS IT IS when contrast is applied, i.e. after the ops that precede it in the random order
 //   K3 the jitter chain (each op followed by clip to [0,1]), grayscale, final clip                     -> out [b][H][W][3*views] f32
@@ -17,6 +18,7 @@
 
 namespace {
 
+constexpr long long kMaxSide = 1 << 20;   // ragged records: larger sides are refused (3 * h * w stays far inside 64 bits)
 constexpr int kP = 16;   // floats per (image, view) parameter record:
 // 0 crop_y 1 crop_x 2 crop_h 3 crop_w 4 flip 5 jitter_on 6..9 perm 10 brightness 11 contrast 12 saturation 13 hue 14 gray_on
 
@@ -86,6 +88,59 @@ __global__ __launch_bounds__(256) void aug_crop_resize_flip(const S* __restrict_
     }
     const int dx = p[4] > 0.f ? W - 1 - ox : ox;                       // tf.image.random_flip_left_right
     float* o = tmp + (((long long)iv * H + oy) * W + dx) * 3;
+    o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
+  }
+}
+
+// Second front end of the same pipeline: the batch arrives as PACKED records -- images of any size back to back, tightly packed
+// HWC uint8 -- with a device table [b][3] = (byte offset, height, width); image i is read at packed + table[i][0] with row
+// pitch 3 * table[i][2].  Taps, weights and summation order are aug_crop_resize_flip<unsigned char>'s, so tmp is bitwise what
+// the canvas kernel writes for the same pixels and draws.  Nothing in `table` or `params` can move a read outside
+// [packed, packed + packed_bytes): a record that does not fit the buffer yields zeros, and the crop box is clamped into its image.
+__global__ __launch_bounds__(256) void aug_crop_resize_flip_ragged(const unsigned char* __restrict__ packed, long long packed_bytes,
+                                                                   const long long* __restrict__ table,
+                                                                   const float* __restrict__ params, float* __restrict__ tmp,
+                                                                   int b, int views, int H, int W) {
+  const long long total = (long long)b * views * H * W;
+  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total; t += gridDim.x * 256ll) {
+    const int ox = (int)(t % W);
+    const int oy = (int)((t / W) % H);
+    const int iv = (int)(t / ((long long)W * H));
+    const int img = iv / views;
+    const float* p = params + (long long)iv * kP;
+    const long long off = table[img * 3ll], ih = table[img * 3ll + 1], iw = table[img * 3ll + 2];
+    const int dx = p[4] > 0.f ? W - 1 - ox : ox;                       // tf.image.random_flip_left_right
+    float* o = tmp + (((long long)iv * H + oy) * W + dx) * 3;
+    const bool fits = off >= 0 && ih > 0 && iw > 0 && ih <= kMaxSide && iw <= kMaxSide && off <= packed_bytes &&
+                      3 * ih * iw <= packed_bytes - off;
+    if (!fits) {
+      o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+      continue;
+    }
+    const int Hs = (int)ih, Ws = (int)iw;
+    const int cy = min(max((int)p[0], 0), Hs - 1), cx = min(max((int)p[1], 0), Ws - 1);
+    const int ch = min(max((int)p[2], 1), Hs - cy), cw = min(max((int)p[3], 1), Ws - cx);
+    int iy[4], ix[4];
+    float wy[4], wx[4];
+    cubic_weights(oy, (float)ch / (float)H, ch, iy, wy);
+    cubic_weights(ox, (float)cw / (float)W, cw, ix, wx);
+    const unsigned char* base = packed + off;
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      float row[3] = {0.f, 0.f, 0.f};
+      const unsigned char* rp = base + (long long)(cy + iy[a]) * Ws * 3;
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4) {
+        const unsigned char* q = rp + (long long)(cx + ix[c4]) * 3;   // the three bytes of a tap are adjacent
+        // explicit fused multiply-adds: the canvas kernel's 60 tap updates all compile to v_fma_f32 (checked in its ISA); spelled
+        // out here so that no vectoriser choice can turn one of them into a multiply and an add, which rounds differently
+        row[0] = fmaf(wx[c4], ld_src<unsigned char>(q), row[0]);
+        row[1] = fmaf(wx[c4], ld_src<unsigned char>(q + 1), row[1]);
+        row[2] = fmaf(wx[c4], ld_src<unsigned char>(q + 2), row[2]);
+      }
+      acc[0] = fmaf(wy[a], row[0], acc[0]); acc[1] = fmaf(wy[a], row[1], acc[1]); acc[2] = fmaf(wy[a], row[2], acc[2]);
+    }
     o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
   }
 }
@@ -222,6 +277,29 @@ int simclr_augment_views(const void* src, int src_dtype, const float* params, vo
   else
     hipLaunchKernelGGL((aug_crop_resize_flip<float>), dim3(grid), dim3(256), 0, stream, (const float*)src, params, tmp,
                        b, views, Hs, Ws, H, W);
+  SIMCLR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(aug_color_mean, dim3(b * views), dim3(256), 0, stream, tmp, params, mean, H * W);
+  SIMCLR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(aug_color_apply, dim3(grid), dim3(256), 0, stream, tmp, params, mean, out, b, views, H * W);
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+// packed: `packed_bytes` bytes of uint8 RGB records; table: device [b][3] long long = (byte offset, height, width) of image i;
+// params / workspace / out as simclr_augment_views.  Same colour kernels, so out is bitwise the canvas path's for the same
+// pixels and draws.  Records or crop boxes that do not fit are clamped by the kernel (never read out of bounds); callers
+// validate the host copy of the table first (simclr_amd/ops.py::augment_views_ragged).
+int simclr_augment_views_ragged(const unsigned char* packed, long long packed_bytes, const long long* table,
+                                const float* params, void* workspace, float* out, int b, int views, int H, int W,
+                                hipStream_t stream) {
+  SIMCLR_CHECK_ARG(packed && table && params && workspace && out, "augment_views_ragged: null argument");
+  SIMCLR_CHECK_ARG(packed_bytes > 0 && b > 0 && views > 0 && H > 0 && W > 0, "augment_views_ragged: bad shape");
+  float* tmp = (float*)workspace;
+  float* mean = tmp + (size_t)b * views * H * W * 3;
+  const long long total = (long long)b * views * H * W;
+  const int grid = (int)min((total + 255) / 256, 1ll << 20);
+  hipLaunchKernelGGL(aug_crop_resize_flip_ragged, dim3(grid), dim3(256), 0, stream, packed, packed_bytes, table, params, tmp,
+                     b, views, H, W);
   SIMCLR_CHECK_LAUNCH();
   hipLaunchKernelGGL(aug_color_mean, dim3(b * views), dim3(256), 0, stream, tmp, params, mean, H * W);
   SIMCLR_CHECK_LAUNCH();

@@ -6,7 +6,9 @@
   pipeline (random-resized-crop with bicubic resize, flip, colour jitter in random order, random grayscale;
   tf2/data_util.py:53-320, :362-390, :443-499 and the two-views concat of tf2/data.py:52-62) for a whole batch of
   decoded images at once -- at >6 000 images/s per GPU a host tf.data-style pipeline is the limiter.
-  The tfds reader / JPEG decode stay outside (out of scope).
+  Each has a `_ragged` form that reads a batch as packed variable-size records `(packed, table)` instead of a dense
+  canvas: what the input pipeline (simclr_amd/data.py) feeds from the on-disk array format.  tfds / TFRecord readers and
+  JPEG decode at training time stay outside (out of scope); tools/make_array_dataset.py converts once.
 
 Random draws (crop boxes, coins, op order, factors; sigma and selectors of the blur) come from numpy / torch
 generators: parity with the reference is distributional for the draws and exact (tested against the oracle,
@@ -214,3 +216,43 @@ def preprocess_for_eval_batch(images, height, width, crop=True, sizes=None):
     p = np.zeros((b, 1, len(PARAM_FIELDS)), np.float32)
     p[:, 0, 0:4] = center_crop_boxes(hs, ws, height, width) if crop else np.stack([0 * hs, 0 * ws, hs, ws], 1)
     return preprocess_for_train_batch(images, height, width, params=p)
+
+
+# --------------------------------------------------------------------------- the same, from packed variable-size records
+def preprocess_for_train_batch_ragged(packed, table, height, width, color_jitter_strength=0., crop=True, flip=True,
+                                      impl='simclrv2', views=1, params=None, table_dev=None):
+    """preprocess_for_train_batch for a batch held as packed records.  packed: device uint8 [nbytes], the images HWC,
+    tightly packed, back to back; table: HOST int64 [b, 3] = (byte offset, height, width) per image (checked before the
+    launch, ops.augment_views_ragged).  No canvas, no padding: the bytes are what the on-disk format holds.
+    Returns float32 [b, height, width, 3*views], bitwise the canvas function's result for the same images and draws."""
+    if impl != 'simclrv2':
+        raise ValueError('Unknown impl {} for random brightness.'.format(impl))
+    table = np.asarray(table)
+    b = table.shape[0]
+    if params is None:
+        params = draw_train_params(b, table[:, 1], table[:, 2], height, width, color_jitter_strength, crop, flip, views)
+    if not torch.is_tensor(params):
+        params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
+    params = params.to(packed.device, non_blocking=True)
+    return ops.augment_views_ragged(packed, table, params.contiguous(), height, width, table_dev=table_dev)
+
+
+def two_view_batch_ragged(packed, table, height, width, color_jitter_strength=1.0, params=None, table_dev=None):
+    """two_view_batch (tf2/data.py:52-62) from packed records -> [b, height, width, 6]."""
+    return preprocess_for_train_batch_ragged(packed, table, height, width, color_jitter_strength, views=2, params=params,
+                                             table_dev=table_dev)
+
+
+def eval_params(heights, widths, height, width, crop=True):
+    """The parameter table [b, 1, 16] of preprocess_for_eval: the central crop box (or the whole image), nothing else."""
+    hs, ws = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
+    p = np.zeros((hs.shape[0], 1, len(PARAM_FIELDS)), np.float32)
+    p[:, 0, 0:4] = center_crop_boxes(hs, ws, height, width) if crop else np.stack([0 * hs, 0 * ws, hs, ws], 1)
+    return p
+
+
+def preprocess_for_eval_batch_ragged(packed, table, height, width, crop=True, table_dev=None):
+    """preprocess_for_eval_batch (tf2/data_util.py:478-499) from packed records -> [b, height, width, 3]."""
+    table = np.asarray(table)
+    p = eval_params(table[:, 1], table[:, 2], height, width, crop)
+    return preprocess_for_train_batch_ragged(packed, table, height, width, params=p, table_dev=table_dev)

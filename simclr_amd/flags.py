@@ -80,6 +80,11 @@ _DEFS = [
                                      "'exact': 'f16x3' falls back to it there."),
     ('head_dtype', 'same', str, "MI355X build: dtype of the projection / supervised heads: 'same' (= compute_dtype) or 'f32' "
                                 "(the heads are 0.2 % of the FLOPs; fp32 there keeps the loss gradient exact)."),
+    # the input pipeline of simclr_amd/data.py (--dataset other than 'synthetic')
+    ('data_seed', 0, int, 'MI355X build: seed of the per-epoch permutations and of the augmentation draws; the batch of a step depends on '
+                          '(data_seed, step, replica) only, so a resumed run continues the same data.'),
+    ('input_threads', 2, int, 'MI355X build: host threads that gather the records of the next batches into pinned buffers.'),
+    ('prefetch_batches', 2, int, 'MI355X build: batches gathered ahead of the one the step consumes.'),
 ]
 
 

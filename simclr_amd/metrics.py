@@ -61,16 +61,27 @@ class Accuracy:
         self._hits = None
         self._count = 0
 
-    def update_state(self, y_true, y_pred):
-        h = (y_true.reshape(-1) == y_pred.reshape(-1)).sum().to(torch.float64).reshape(1)
+    def update_state(self, y_true, y_pred, sample_weight=None):
+        self._add(y_true.reshape(-1) == y_pred.reshape(-1), sample_weight)
+
+    def _add(self, hit, sample_weight):
+        """sample_weight (optional, one per sample; stays on the device): hits and count are weighted sums, so a padded eval
+        batch whose padding carries weight 0 counts every example once."""
+        if sample_weight is None:
+            h = hit.sum().to(torch.float64).reshape(1)
+            self._count = self._count + hit.numel()
+        else:
+            w = sample_weight.reshape(-1).to(torch.float64)
+            h = (hit.reshape(-1).to(torch.float64) * w).sum().reshape(1)
+            self._count = self._count + w.sum().reshape(1)
         self._hits = h if self._hits is None else self._hits + h
-        self._count += y_true.numel()
 
     def totals(self):
         """(hits, count) as a fp64 tensor -- what a multi-replica eval all-reduces."""
         dev = self._hits.device if self._hits is not None else 'cpu'
         h = self._hits if self._hits is not None else torch.zeros(1, dtype=torch.float64)
-        return torch.cat([h.to(dev), torch.tensor([float(self._count)], dtype=torch.float64, device=dev)])
+        c = self._count if torch.is_tensor(self._count) else torch.tensor([float(self._count)], dtype=torch.float64)
+        return torch.cat([h.to(dev), c.to(dev)])
 
     def result(self):
         t = self.totals()
@@ -85,19 +96,17 @@ class TopKCategoricalAccuracy(Accuracy):
         self.k = k
         super().__init__(name)
 
-    def update_state(self, y_true, y_pred):
+    def update_state(self, y_true, y_pred, sample_weight=None):
         target = y_true.argmax(1)
         tv = y_pred.gather(1, target[:, None])
-        hit = (y_pred > tv).sum(1) < self.k
-        h = hit.sum().to(torch.float64).reshape(1)
-        self._hits = h if self._hits is None else self._hits + h
-        self._count += y_true.shape[0]
+        self._add((y_pred > tv).sum(1) < self.k, sample_weight)
 
 
-def update_finetune_metrics_eval(label_top_1_accuracy_metrics, label_top_5_accuracy_metrics, outputs, labels):
-    """tf2/metrics.py:58-62.  outputs: dense logits [b, C]; labels: one-hot [b, C]."""
-    label_top_1_accuracy_metrics.update_state(labels.argmax(1), outputs.argmax(1))
-    label_top_5_accuracy_metrics.update_state(labels, outputs)
+def update_finetune_metrics_eval(label_top_1_accuracy_metrics, label_top_5_accuracy_metrics, outputs, labels, weights=None):
+    """tf2/metrics.py:58-62.  outputs: dense logits [b, C]; labels: one-hot [b, C]; weights: optional per-sample weights
+    (0 for the padding of a last eval batch)."""
+    label_top_1_accuracy_metrics.update_state(labels.argmax(1), outputs.argmax(1), weights)
+    label_top_5_accuracy_metrics.update_state(labels, outputs, weights)
 
 
 def update_pretrain_metrics_train(contrast_loss, contrast_acc, contrast_entropy, loss, logits_con, labels_con):

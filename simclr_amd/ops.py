@@ -953,6 +953,45 @@ def augment_views(src, params, H, W, out=None):
     return out
 
 
+def check_ragged_table(table, packed_bytes):
+    """Host check of a ragged batch's table [b, 3] = (byte offset, height, width): every record must lie inside the packed
+    buffer.  Returns the table as a contiguous int64 array; raises ValueError naming the first bad row."""
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(table), dtype=np.int64)
+    if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] == 0:
+        raise ValueError('augment_views_ragged: table must be [b, 3] (byte offset, height, width), got shape %s' % (t.shape,))
+    off, h, w = t[:, 0], t[:, 1], t[:, 2]
+    bad = (off < 0) | (h <= 0) | (w <= 0) | (h > (1 << 20)) | (w > (1 << 20))
+    end = off + 3 * np.where(bad, 0, h) * np.where(bad, 0, w)
+    bad |= end > int(packed_bytes)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError('augment_views_ragged: table row %d (offset %d, height %d, width %d) does not lie inside the packed '
+                         'buffer of %d bytes' % (i, off[i], h[i], w[i], int(packed_bytes)))
+    return t
+
+
+def augment_views_ragged(packed, table, params, H, W, out=None, table_dev=None):
+    """packed: device uint8 [nbytes], images HWC back to back; table: HOST int64 [b, 3] = (byte offset, height, width),
+    checked here before anything is launched; params [b, views, 16] float32 on the device.  table_dev: the table already
+    on the device (the input pipeline ships it in the batch's one copy); otherwise it is uploaded.
+    Returns [b, H, W, 3*views] float32 in [0,1], bitwise augment_views' result for the same pixels and draws."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise TypeError('augment_views_ragged: packed must be a 1-D uint8 tensor')
+    t = check_ragged_table(table, packed.numel())
+    b = t.shape[0]
+    assert params.dtype == torch.float32 and params.shape[0] == b and params.shape[2] == 16
+    views = params.shape[1]
+    if table_dev is None:
+        table_dev = torch.from_numpy(t).to(packed.device, non_blocking=True)
+    assert table_dev.dtype == torch.int64 and table_dev.numel() == 3 * b
+    if out is None:
+        out = torch.empty(b, H, W, 3 * views, device=packed.device, dtype=torch.float32)
+    ws = _workspace(lib().augment_workspace_bytes(b, views, H, W), packed.device, key='augment')
+    lib().augment_views_ragged(_p(packed), packed.numel(), _p(table_dev), _p(params), _p(ws), _p(out), b, views, H, W, _s())
+    return out
+
+
 # ---------------------------------------------------------------- BatchNorm backward folded into the producing 1x1 conv
 def bn_fold_coeffs(scale, mean, rstd, c1, c2):
     C = scale.shape[0]

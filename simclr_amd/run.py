@@ -4,9 +4,10 @@
 kernels: model forward, contrastive + supervised losses, metrics, weight decay, loss / R,
 backward (hand-written, replaces tape.gradient :621), cross-replica gradient SUM (implicit in
 apply_gradients :614-622; here a bucketed RCCL all-reduce overlapped with the rest of the
-backward pass), LARS.  `main` accepts the reference's flags (simclr_amd/flags.py); the tfds
-input pipeline, checkpoint manager, eval loop and SavedModel export (run.py:241-553) are out of
-scope -- `--dataset=synthetic` feeds random two-view batches of the right shape.
+backward pass), LARS.  `main` accepts the reference's flags (simclr_amd/flags.py) and mirrors the
+driver (run.py:450-664): `--dataset=synthetic` feeds random two-view batches of the right shape,
+any other `--dataset` is read from `--data_dir` in the array format of simclr_amd/data.py
+(tfds / TFRecord readers and JPEG decode are out of scope, as is the SavedModel export).
 """
 import json
 import logging
@@ -312,10 +313,13 @@ def perform_evaluation(model, data, eval_steps, ckpt, strategy, model_dir=None):
         restored = True
         outputs = supervised_head_outputs.dense()
         l = labels['labels']
-        metrics.update_finetune_metrics_eval(label_top_1_accuracy, label_top_5_accuracy, outputs, l)   # :383-384
+        # 'mask': per-sample weights of a padded last batch (simclr_amd/data.py); absent = every sample counts
+        metrics.update_finetune_metrics_eval(label_top_1_accuracy, label_top_5_accuracy, outputs, l, labels.get('mask'))   # :383-384
         reg_loss = model_lib.add_weight_decay(model, adjust_per_optimizer=True)      # :385
         regularization_loss.update_state(reg_loss)
         logging.info('Completed eval for %d / %d steps', i + 1, eval_steps)
+    if hasattr(data, 'close'):
+        data.close()                     # the input pipeline's worker threads
     # replicas evaluate disjoint shards: the accuracies are ratios of summed counts
     if strategy is not None and num_replicas(strategy) > 1:
         for m in (label_top_1_accuracy, label_top_5_accuracy):
@@ -340,25 +344,42 @@ def perform_evaluation(model, data, eval_steps, ckpt, strategy, model_dir=None):
 
 
 def main(argv):
-    """tf2/run.py:450-664 for --dataset=synthetic: train (with checkpoints every checkpoint_steps /
-    checkpoint_epochs and resume from model_dir), eval, or train_then_eval."""
+    """tf2/run.py:450-664: train (with checkpoints every checkpoint_steps / checkpoint_epochs and resume from
+    model_dir), eval, or train_then_eval -- on synthetic batches (--dataset=synthetic) or on the array dataset
+    <data_dir>/<dataset> (simclr_amd/data.py), whose training stream starts at the restored global step."""
     from .checkpoint import try_restore_from_checkpoint
+    from . import data as data_lib
     import math
     FLAGS.parse(argv)
     logging.basicConfig(level=logging.INFO)
+    builder = None
+    if FLAGS.dataset != 'synthetic':
+        # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter
+        builder = data_lib.ArrayDatasetBuilder(FLAGS.dataset, FLAGS.data_dir)                 # :471-472
+        for sp in ([FLAGS.train_split] if FLAGS.mode != 'eval' else []) + ([FLAGS.eval_split] if FLAGS.mode != 'train' else []):
+            builder.split(sp)
     strategy = init_distributed()
     R = num_replicas(strategy)
     rank0 = strategy is None or strategy.rank == 0
-    if FLAGS.dataset != 'synthetic':
-        raise NotImplementedError('only --dataset=synthetic is available offline (no tfds); '
-                                  'feed real data through make_single_step from your own pipeline')
-    num_classes = 10 if FLAGS.image_size <= 32 else 1000
-    num_train_examples = 50000 if FLAGS.image_size <= 32 else 1281167
-    num_eval_examples = 10000 if FLAGS.image_size <= 32 else 50000
+    if builder is not None:
+        num_classes = builder.info.features['label'].num_classes                              # :475
+        num_train_examples = builder.info.splits[FLAGS.train_split].num_examples if FLAGS.train_split in builder.info.splits else 0
+        num_eval_examples = builder.info.splits[FLAGS.eval_split].num_examples if FLAGS.eval_split in builder.info.splits else 0
+    else:
+        num_classes = 10 if FLAGS.image_size <= 32 else 1000
+        num_train_examples = 50000 if FLAGS.image_size <= 32 else 1281167
+        num_eval_examples = 10000 if FLAGS.image_size <= 32 else 50000
     train_steps = model_lib.get_train_steps(num_train_examples)
     eval_steps = FLAGS.eval_steps or int(math.ceil(num_eval_examples / FLAGS.eval_batch_size))   # :476-478
     epoch_steps = int(round(num_train_examples / FLAGS.train_batch_size))                     # :479
     checkpoint_steps = FLAGS.checkpoint_steps or (FLAGS.checkpoint_epochs * epoch_steps)      # :486-487
+    if builder is not None and FLAGS.mode != 'train':
+        eval_steps = min(eval_steps, data_lib.eval_num_steps(num_eval_examples, FLAGS.eval_batch_size))   # one pass at most
+
+    def eval_data():
+        if builder is not None:
+            return data_lib.build_distributed_dataset(builder, FLAGS.eval_batch_size, False, strategy)
+        return synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device, seed=100 + rep)
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
@@ -369,8 +390,7 @@ def main(argv):
         from .checkpoint import CheckpointManager, Checkpoint                            #  the latest checkpoint)
         mgr = CheckpointManager(Checkpoint(model=model), FLAGS.model_dir, FLAGS.keep_checkpoint_max)
         ckpt = FLAGS.checkpoint or mgr.latest_checkpoint
-        data = synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device, seed=100 + rep)
-        result = perform_evaluation(model, data, eval_steps, ckpt, strategy, FLAGS.model_dir)
+        result = perform_evaluation(model, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
@@ -379,8 +399,10 @@ def main(argv):
     optimizer = model_lib.build_optimizer(learning_rate)
     step_fn = make_single_step(model, optimizer, strategy)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
-    data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep,
-                             views=1 if FLAGS.train_mode == 'finetune' else 2)
+    data = None
+    if builder is None:
+        data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep,
+                                 views=1 if FLAGS.train_mode == 'finetune' else 2)
     manager = None
     summary_writer = metrics.JsonlSummaryWriter(FLAGS.model_dir) if (FLAGS.model_dir and rank0) else None   # :526
     log_every = FLAGS.checkpoint_steps or 10
@@ -395,6 +417,9 @@ def main(argv):
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)
+    if builder is not None:
+        # the batch of step s depends on (data_seed, s, replica) only: starting at the restored step continues the same data
+        data = data_lib.build_distributed_dataset(builder, FLAGS.train_batch_size, True, strategy, start_step=step)
     t0 = time.time()
     while step < train_steps:
         features, labels = next(data)
@@ -427,9 +452,10 @@ def main(argv):
             if strategy is not None:
                 dist.barrier()
     _check_device_health(strategy)       # time-outs of the last steps are reported too (the loop may end between two log intervals)
+    if builder is not None:
+        data.close()
     if FLAGS.mode == 'train_then_eval' and manager is not None:                           # :657-660
-        edata = synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device, seed=100 + rep)
-        result = perform_evaluation(model, edata, eval_steps, manager.latest_checkpoint, strategy, FLAGS.model_dir)
+        result = perform_evaluation(model, eval_data(), eval_steps, manager.latest_checkpoint, strategy, FLAGS.model_dir)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
