@@ -80,6 +80,28 @@ def _trunc_normal(gen, shape, stddev):
     return out
 
 
+# SK_Conv2D's stream arithmetic (tf2/resnet.py:266-277) on given NCHW tensors: Builder.sk_conv2d is written with these, and the
+# kernel-level GPU checks differentiate them in float64 (tests/gpu_checks.py check_sk_kernels).
+def sk_split(x, filters):
+    """:266  tf.stack(tf.split(inputs, 2, channel_axis)): [B,2f,H,W] -> [2,B,f,H,W]."""
+    return torch.stack(torch.split(x, filters, dim=1))
+
+
+def sk_pooled(streams):
+    """:269-270  reduce_mean over H, W of the sum of the streams, keepdims: [2,B,f,H,W] -> [B,f,1,1]."""
+    return streams.sum(0).mean((2, 3), keepdim=True)
+
+
+def sk_mix_weights(logits, filters):
+    """:274-275  softmax over the two streams of the mixing logits: [B,2f,1,1] -> [2,B,f,1,1]."""
+    return torch.softmax(torch.stack(torch.split(logits, filters, dim=1)), dim=0)
+
+
+def sk_mix(streams, mix):
+    """:277  reduce_sum(inputs * mixing, axis=0): -> [B,f,H,W]."""
+    return (streams * mix).sum(0)
+
+
 class Builder:
     """Walks the architecture once; used both to create parameters and to run it.
 
@@ -228,16 +250,15 @@ class Builder:
         self.scope.append(self.namer('sk__conv2d'))
         x = self.conv2d_fixed_padding(x, 2 * filters, 3, strides)          # :264
         x = self.batch_norm_relu(x)                                          # :265
-        streams = torch.stack(torch.split(x, filters, dim=1))                # :266  [2,B,f,H,W]
-        g = streams.sum(0).mean((2, 3), keepdim=True)                        # :269-270
+        streams = sk_split(x, filters)                                       # :266  [2,B,f,H,W]
+        g = sk_pooled(streams)                                               # :269-270
         mid = max(int(filters * self.cfg.sk_ratio), 32)                      # :242
         g = self.plain_conv1x1(g, mid)                                       # :271
         g = self.batch_norm_relu(g)                                          # :272
         mix = self.plain_conv1x1(g, 2 * filters)                             # :273
-        mix = torch.stack(torch.split(mix, filters, dim=1))                  # :274
-        mix = torch.softmax(mix, dim=0)                                      # :275
+        mix = sk_mix_weights(mix, filters)                                   # :274-275
         self.scope.pop()
-        return (streams * mix).sum(0)                                        # :277
+        return sk_mix(streams, mix)                                          # :277
 
     def _shortcut(self, x, filters_out, strides):
         if self.cfg.sk_ratio > 0:   # ResNet-D (:330-344, :400-414)

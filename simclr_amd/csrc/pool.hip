@@ -1211,6 +1211,8 @@ int simclr_bias_softmax_xent(const void* z, const float* bias, const int* labels
 
 int simclr_colsum(const void* x, int rows, int C, int cvalid, float* out, int accumulate, int dtype,
                   hipStream_t stream) {
+  SIMCLR_CHECK_ARG(x && out, "colsum: null argument");
+  SIMCLR_CHECK_ARG(rows > 0 && cvalid > 0 && cvalid <= C, "colsum: bad shape (rows=%d, cvalid=%d, C=%d)", rows, cvalid, C);
   DISPATCH_T(dtype,
              hipLaunchKernelGGL((colsum<uint16_t>), dim3(ceil_div(cvalid, 16)), dim3(256), 0, stream,
                                 (const uint16_t*)x, rows, C, cvalid, out, accumulate),
@@ -1222,6 +1224,11 @@ int simclr_colsum(const void* x, int rows, int C, int cvalid, float* out, int ac
 
 // dtype_in/dtype_out in {f32, bf16}
 int simclr_cast(const void* x, void* y, long long n, int dtype_in, int dtype_out, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(n >= 0, "cast: n=%lld must not be negative", n);
+  if (n == 0) return 0;
+  SIMCLR_CHECK_ARG(x && y, "cast: null argument");
+  SIMCLR_CHECK_ARG((dtype_in == SIMCLR_DT_F32 || dtype_in == SIMCLR_DT_BF16) && (dtype_out == SIMCLR_DT_F32 || dtype_out == SIMCLR_DT_BF16),
+                   "cast: dtypes must be f32 / bf16 (got %d -> %d)", dtype_in, dtype_out);
   const int grid = grid_for(n);
   if (dtype_in == SIMCLR_DT_F32 && dtype_out == SIMCLR_DT_BF16)
     hipLaunchKernelGGL((cast_kernel<float, uint16_t>), dim3(grid), dim3(256), 0, stream, (const float*)x, (uint16_t*)y, n);
@@ -1250,11 +1257,17 @@ int simclr_accumulate_scalars(const float* const* src, const float* scale, int n
 }
 
 int simclr_axpy_f32(float a, const float* x, float* y, long long n, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(n >= 0, "axpy_f32: n=%lld must not be negative", n);
+  if (n == 0) return 0;
+  SIMCLR_CHECK_ARG(x && y, "axpy_f32: null argument");
   hipLaunchKernelGGL(axpy_f32, dim3(grid_for(n)), dim3(256), 0, stream, a, x, y, n);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
 int simclr_l2_loss_f32(const float* x, long long n, float* out, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(n >= 0, "l2_loss_f32: n=%lld must not be negative", n);
+  if (n == 0) return 0;                      // an empty sum adds nothing (and a grid of 0 workgroups is a launch error)
+  SIMCLR_CHECK_ARG(x && out, "l2_loss_f32: null argument");
   hipLaunchKernelGGL(l2_loss_f32, dim3(min(256, ceil_div(n, 1024))), dim3(256), 0, stream, x, n, out);
   SIMCLR_CHECK_LAUNCH();
   return 0;

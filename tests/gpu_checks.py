@@ -5,6 +5,7 @@ oracle (`oracle/`, float64) for the loss / LARS and plain torch-CPU float64 ops
 for conv / BN / pooling.  Used by tests/test_gpu_kernels.py (pytest -m gpu) and
 tools/run_gpu_checks.py (prints everything; first-contact diagnostics).
 """
+import itertools
 import os
 
 import numpy as np
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 from oracle import lars as olars
 from oracle import ntxent as ont
 from simclr_amd import ops
-from simclr_amd._lib import lib
+from simclr_amd._lib import DT_BF16, DT_F32, lib
 
 DEV = 'cuda'
 
@@ -2231,3 +2232,459 @@ def check_reference_pin_step(tag, compute_dtype='f32', f32_matmul='exact', gate=
               worst_rel=float(np.max(np.abs(got_g - want_g) / np.abs(want_g))))
     FLAGS.reset(); RT.reset()
     return res
+
+
+# ------------------------------------------------------------------ selective-kernel unit and the small head kernels
+def _entry(name, err, tol, scale=0.0, numel=1, **kw):
+    """A result whose error measure is not max |got - ref| (a count of mismatches, a ratio to a derived bound)."""
+    d = dict(name=name, err=float(err), tol=float(tol), scale=float(scale), ok=bool(err <= tol), nbad=int(err > tol), numel=numel)
+    d.update(kw)
+    return d
+
+
+def _dn(dtype):
+    return str(dtype).split('.')[-1]
+
+
+def sk_logits(V, f, lpitch, dtype, kind, g):
+    """Mixing logits [V, lpitch] (sigma 3; columns beyond 2f hold values no kernel may read).  'equal': both streams the same logit;
+    'saturated': in the odd rows, seven of eight columns get l1 = l0 + d with d in +-30, +-100, +-200."""
+    l = torch.randn(V, lpitch, generator=g) * 3
+    if kind == 'equal':
+        l[:, f:2 * f] = l[:, :f]
+    elif kind == 'saturated':
+        d = torch.tensor([0., 30., -30., 100., -100., 200., -200., 0.])[torch.arange(f) % 8]
+        rows = torch.arange(V) % 2 == 1
+        l[rows, f:2 * f] = torch.where(d != 0, l[rows, :f] + d, l[rows, f:2 * f])
+    else:
+        assert kind == 'normal', kind
+    return l.to(dtype)
+
+
+def check_sk_kernels(V, H, W, f, lpitch=None, gpitch=None, dtype=torch.float32, logits='normal', seed=0):
+    """simclr_sk_pool_fwd / sk_mix_fwd / sk_mix_bwd_logits / sk_mix_bwd_streams against the oracle's own stream arithmetic
+    (oracle/model_torch.py sk_split ... sk_mix, tf2/resnet.py:266-277) in float64; the gradients are autograd's of
+    <out, dout> + <g, dg[:, :f]>.  Pad columns of g and dl: exactly zero through the wrappers, untouched by the kernels."""
+    from oracle.model_torch import sk_mix, sk_mix_weights, sk_pooled, sk_split
+    lpitch = 2 * f if lpitch is None else lpitch
+    gpitch = f if gpitch is None else gpitch
+    g = torch.Generator().manual_seed(seed)
+    a = torch.relu(torch.randn(V, H, W, 2 * f, generator=g)).to(dtype)             # the streams are a ReLU output
+    l = sk_logits(V, f, lpitch, dtype, logits, g)
+    dout = _rand((V, H, W, f), dtype, g)
+    dg = _rand((V, gpitch), dtype, g)
+    a64 = a.double().permute(0, 3, 1, 2).requires_grad_(True)
+    l64 = l.double()[:, :2 * f].reshape(V, 2 * f, 1, 1).requires_grad_(True)
+    streams = sk_split(a64, f)
+    g_ref = sk_pooled(streams)
+    out_ref = sk_mix(streams, sk_mix_weights(l64, f))
+    ((out_ref * dout.double().permute(0, 3, 1, 2)).sum() + (g_ref.view(V, f) * dg.double()[:, :f]).sum()).backward()
+    ad, ld, dod, dgd = a.to(DEV), l.to(DEV), dout.to(DEV), dg.to(DEV)
+    g_dev = ops.sk_pool_fwd(ad, f, gpitch)
+    out_dev = ops.sk_mix_fwd(ad, ld, f)
+    dl_dev = ops.sk_mix_bwd_logits(ad, ld, dod, f)
+    da_dev = ops.sk_mix_bwd_streams(ld, dod, dgd, f)
+    # The kernels write the first f (2f) columns of a row only; the zeros of the pad columns are the wrapper's (torch.zeros).  Called
+    # directly on sentinel-filled buffers, the kernels must write the same values and leave the pad columns alone.
+    SENT = 7.5
+    g_raw = torch.full((V, gpitch), SENT, device=DEV, dtype=dtype)
+    dl_raw = torch.full((V, lpitch), SENT, device=DEV, dtype=dtype)
+    lib().sk_pool_fwd(ops._p(ad), ops._p(g_raw), V, H * W, f, gpitch, ops.dt(ad), ops._s())
+    lib().sk_mix_bwd_logits(ops._p(ad), ops._p(ld), ops._p(dod), ops._p(dl_raw), V, H * W, f, lpitch, ops.dt(ad), ops._s())
+    torch.cuda.synchronize()
+    tag = 'V%d %dx%d f%d l%d g%d %s %s' % (V, H, W, f, lpitch, gpitch, _dn(dtype), logits)
+    t = _tol(dtype)
+    res = [_res('sk_pool_fwd ' + tag, g_dev[:, :f], g_ref.detach().view(V, f), t, 1e-6),
+           _res('sk_pool_fwd_pad ' + tag, g_dev[:, f:], torch.zeros(V, gpitch - f), 0, 0),
+           _res('sk_mix_fwd ' + tag, out_dev, out_ref.detach().permute(0, 2, 3, 1), t, 1e-6),
+           _res('sk_mix_bwd_logits ' + tag, dl_dev[:, :2 * f], l64.grad.view(V, 2 * f), t, 1e-7),
+           _res('sk_mix_bwd_logits_pad ' + tag, dl_dev[:, 2 * f:], torch.zeros(V, lpitch - 2 * f), 0, 0),
+           _res('sk_mix_bwd_streams ' + tag, da_dev, a64.grad.permute(0, 2, 3, 1), t, 1e-7),
+           _res('sk_pool_fwd_raw ' + tag, g_raw[:, :f], g_dev[:, :f], 0, 0),
+           _res('sk_pool_fwd_raw_pad_untouched ' + tag, g_raw[:, f:], torch.full((V, gpitch - f), SENT), 0, 0),
+           _res('sk_mix_bwd_logits_raw ' + tag, dl_raw[:, :2 * f], dl_dev[:, :2 * f], 0, 0),
+           _res('sk_mix_bwd_logits_raw_pad_untouched ' + tag, dl_raw[:, 2 * f:], torch.full((V, lpitch - 2 * f), SENT), 0, 0)]
+    if logits == 'saturated':
+        # |l1 - l0| >= 90: exp(89) = 4.5e38 is beyond the largest fp32 (3.4e38) and 1 + exp(-89) rounds to 1, so m0 is exactly 0 or 1 in
+        # fp32 and the output is exactly the selected stream's value
+        diff = (l.double()[:, f:2 * f] - l.double()[:, :f]).view(V, 1, 1, f)
+        sel = torch.where(diff > 0, a.double()[..., f:], a.double()[..., :f])
+        hard = (diff.abs() >= 90).expand(V, H, W, f)
+        res.append(_res('sk_mix_fwd_saturated_exact ' + tag, out_dev.double().cpu()[hard], sel[hard], 0, 0))
+        assert int(hard.sum()) > 0
+    return res
+
+
+def check_sk_layer(V, H, Cin, f, stride, f32_matmul='exact', seed=0, margin=1e-5):
+    """resnet.SK_Conv2D (training mode, fp32 storage) forward and backward against Builder.sk_conv2d in float64 on the same weights,
+    BatchNorm parameters and input: the output, dx and the gradient of every variable, each tensor on its own with
+    tol = CAL * err(oracle in float32 vs float64) + 2e-5 * max |ref| (the calibration rule of check_train_step).
+    No ReLU may sit on the fence: the float64 reference must have no BatchNorm pre-activation within margin * max |pre-activation| of
+    zero -- asserted before anything is compared, so nothing needs to be excluded from the comparison."""
+    from collections import OrderedDict
+    from oracle.model_torch import Builder, Config
+    from simclr_amd.flags import FLAGS
+    from simclr_amd.resnet import RT, Act, SK_Conv2D, join_wgrad_stream
+    CAL = 6.0
+    cfg = Config(sk_ratio=0.0625)
+    gx = torch.Generator().manual_seed(seed + 1)
+    x = torch.randn(V, H, H, Cin, generator=gx)
+    b0 = Builder(cfg, seed=seed, randomize_bn=True)
+    with torch.no_grad():
+        o0 = b0.sk_conv2d(x.permute(0, 3, 1, 2), f, stride)
+    dy = torch.randn(tuple(o0.permute(0, 2, 3, 1).shape), generator=gx)
+    params, state = b0.params, b0.state
+
+    def oracle(dtype):
+        p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in params.items())
+        s = OrderedDict((k, v.to(dtype)) for k, v in state.items())
+        b = Builder(cfg, params=p, state=s, dtype=dtype)
+        pre, orig = [], b.batch_norm_relu
+
+        def recording(t, *a, **k):
+            y = orig(t, *a, **k)
+            pre.append(b._last_bn_pre_relu.detach())
+            return y
+        b.batch_norm_relu = recording
+        xi = x.to(dtype).permute(0, 3, 1, 2).requires_grad_(True)
+        out = b.sk_conv2d(xi, f, stride)
+        (out * dy.to(dtype).permute(0, 3, 1, 2)).sum().backward()
+        r = OrderedDict(out=out.detach().permute(0, 2, 3, 1), dx=xi.grad.permute(0, 2, 3, 1))
+        for k, v in p.items():
+            r['d ' + k] = v.grad
+        return r, pre
+
+    r64, pre = oracle(torch.float64)
+    assert len(pre) == 2
+    margins = [float(p.abs().min() / p.abs().max()) for p in pre]
+    assert min(margins) > margin, ('a ReLU of the float64 reference sits within %g * max |pre-activation| of zero (margins %r): '
+                                   'choose another seed' % (margin, margins))
+    r32, _ = oracle(torch.float32)
+
+    FLAGS.reset()
+    FLAGS.update(compute_dtype='f32', sk_ratio=cfg.sk_ratio, f32_matmul=f32_matmul)
+    RT.reset()
+    RT.device = torch.device(DEV)
+    try:
+        sk = SK_Conv2D(f, stride, cfg.sk_ratio)
+        xd, dyd = x.to(DEV), dy.to(DEV)
+        ops.begin_step(DEV)
+        sk(Act(xd, c=Cin), True)                                     # builds the variables
+        ops.end_step()
+        byname = {v.name: v for v in sk.variables}
+        allv = dict(params); allv.update(state)
+        assert sorted(byname) == sorted(allv), (sorted(byname), sorted(allv))
+        for k, v in byname.items():
+            assert tuple(v.value.shape) == tuple(allv[k].shape), (k, v.value.shape, allv[k].shape)
+            v.value.copy_(allv[k].to(DEV))
+        RT.weights_version += 1
+        ops.begin_step(DEV)
+        out = sk(Act(xd, c=Cin), True)
+        assert out.c == f and tuple(out.t.shape) == tuple(dyd.shape)
+        dx = sk.backward(dyd)
+        join_wgrad_stream()
+        torch.cuda.synchronize()
+        got = OrderedDict(out=out.t, dx=dx)
+        for k in params:
+            got['d ' + k] = byname[k].grad
+        tag = 'V%d %d Cin%d f%d s%d %s seed%d' % (V, H, Cin, f, stride, f32_matmul, seed)
+        res = []
+        for k, ref in r64.items():
+            assert got[k] is not None, 'no gradient for %s' % k
+            err = float((got[k].double().cpu() - ref).abs().max())
+            ref_err = float((r32[k].double() - ref).abs().max())
+            scale = float(ref.abs().max())
+            tol = CAL * ref_err + 2e-5 * scale
+            print('sk_layer %-70s err=%.3e ref_err=%.3e tol=%.3e max|ref|=%.3e' % (k + ' ' + tag, err, ref_err, tol, scale), flush=True)
+            res.append(dict(name='sk_layer %s %s' % (k, tag), err=err, tol=tol, scale=scale, ref_err=ref_err, numel=ref.numel(),
+                            ok=bool(err <= tol) and bool(torch.isfinite(got[k]).all()), nbad=int(err > tol), margins=margins))
+        return res
+    finally:
+        ops.end_step()
+        ops.set_f32_matmul('exact')
+        FLAGS.reset(); RT.reset()
+
+
+def check_avgpool_f32_from_bf16(V, H, C, seed=0):
+    """simclr_global_avgpool_fwd_f32: fp32 means of bf16 activations against the float64 mean of the same bf16 values, at the FP32 gate
+    (keeping that precision is what the entry point is for: a mean rounded to bf16 would be off by 2^-9 relative)."""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(V, H, H, C, generator=g) + 0.25).bfloat16()
+    y = ops.global_avgpool_fwd(x.to(DEV), out_dtype=torch.float32)
+    torch.cuda.synchronize()
+    assert y.dtype == torch.float32
+    return [_res('avgpool_fwd_f32_from_bf16 V%d %d C%d' % (V, H, C), y, x.double().mean((1, 2)), _tol(torch.float32))]
+
+
+def check_avgpool_bwd_mask(V, H, C, dtype, seed=0):
+    """simclr_global_avgpool_bwd with mask_src: dx = dy / HW where mask_src > 0, else 0; the mask holds positives, negatives, +0.0, -0.0."""
+    g = torch.Generator().manual_seed(seed)
+    dy = _rand((V, C), dtype, g)
+    mask = torch.randn(V, H, H, C, generator=g)
+    idx = torch.arange(mask.numel()).view(mask.shape)
+    mask[idx % 5 == 1] = 0.0
+    mask[idx % 5 == 3] = -0.0
+    mask = mask.to(dtype)
+    dx = ops.global_avgpool_bwd(dy.to(DEV), H, H, mask_src=mask.to(DEV))
+    torch.cuda.synchronize()
+    on = mask.double() > 0
+    ref = torch.where(on, (dy.double() / (H * H))[:, None, None, :].expand(V, H, H, C), torch.zeros(1, dtype=torch.float64))
+    tag = 'V%d %d C%d %s' % (V, H, C, _dn(dtype))
+    off = dx.cpu()[~on]
+    return [_res('avgpool_bwd_masked ' + tag, dx, ref, _tol(dtype), 1e-7),
+            _res('avgpool_bwd_masked_zeros ' + tag, off, torch.zeros(off.shape), 0, 0)]
+
+
+def _first_argmax(v):
+    """tf.argmax returns the FIRST maximum (tf2/metrics.py)."""
+    n = v.shape[1]
+    cols = torch.arange(n).expand_as(v)
+    return torch.where(v == v.max(1, keepdim=True).values, cols, torch.full_like(cols, n)).min(1).values
+
+
+def check_xent(rows, label_rows, nclass, cpad, dtype, gscale=1.0, mode='normal', seed=0):
+    """simclr_bias_softmax_xent against F.cross_entropy in float64: loss, top-1 accuracy (first maximum wins), dlogits, zero pad columns.
+    mode: 'normal' (sigma 3) | 'zero' (all logits and biases zero: every row an arg-max tie) | 'tie_cross' (columns 6 and 71 share the
+    maximum: different lanes, a lane owns the columns c % 64) | 'tie_same' (columns 6 and 70: the same lane) | 'large' (magnitude 80).
+    The kernel adds into `out`: it is called twice on an un-zeroed `out`."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(rows, cpad, generator=g) * 3
+    bias = 0.1 * torch.randn(nclass, generator=g)
+    labels = torch.randint(0, nclass, (label_rows,), generator=g).int()
+    if mode == 'zero':
+        z[:, :nclass] = 0
+        bias[:] = 0
+        labels[::2] = 0
+    elif mode in ('tie_cross', 'tie_same'):
+        lo, hi = (6, 71) if mode == 'tie_cross' else (6, 70)
+        assert nclass > hi
+        z = z.clamp(-8, 8)
+        z[:, lo] = 11.75; z[:, hi] = 11.75                 # 11.75 + 0.25 = 12 exactly in bf16 and fp32: a true tie, above everything else
+        bias[lo] = 0.25; bias[hi] = 0.25
+        # most rows carry the lower tied column as their label, a few the higher one: the accuracy tells which of the two won
+        idx = torch.arange(label_rows)
+        labels[idx % 4 <= 1] = lo
+        labels[idx % 4 == 3] = hi
+    elif mode == 'large':
+        z = torch.where(torch.rand(rows, cpad, generator=g) < 0.5, -80.0, 80.0) + torch.randn(rows, cpad, generator=g)
+    else:
+        assert mode == 'normal', mode
+    z = z.to(dtype)
+    lab = labels.long()[torch.arange(rows) % label_rows]
+    zr = (z.double()[:, :nclass] + bias.double()).requires_grad_(True)
+    loss = F.cross_entropy(zr, lab)
+    loss.backward()
+    acc = (_first_argmax(zr.detach()) == lab).double().mean()
+    if mode in ('tie_cross', 'tie_same'):
+        n_lo, n_hi = int((lab == lo).sum()), int((lab == hi).sum())
+        assert float(acc) == n_lo / rows and n_lo >= n_hi + 2, (n_lo, n_hi, rows)       # "the higher column wins" would give n_hi / rows
+    init = torch.tensor([0.5, 0.25])
+    out = init.clone().to(DEV)
+    zd, bd, ld = z.to(DEV), bias.to(DEV), labels.to(DEV)
+    dl = ops.bias_softmax_xent(zd, bd, ld, nclass, gscale, out)
+    dl2 = ops.bias_softmax_xent(zd, bd, ld, nclass, gscale, out)
+    torch.cuda.synchronize()
+    tag = '%d(%d)x%d(%d) %s g%g %s' % (rows, label_rows, nclass, cpad, _dn(dtype), gscale, mode)
+    t = _tol(dtype)
+    o = out.double().cpu()
+    # out[0] and out[1] are each built by 2 * rows float atomic adds (order not fixed) onto the initial value; every add rounds to
+    # 2^-24 of a running value that stays below the final one (all terms >= 0, the accuracy ends at most at init + 2), so
+    # |err| <= 2 * rows * 2^-24 * final: for the accuracy that is the whole error (hits / rows are the same fp32 terms in any order) and
+    # still ~1000 times below one wrong row (1 / rows); the loss is held to the project's fp32 gate, which covers that sum (1.5e-5 of the
+    # final value at 126 rows) plus the fp32 evaluation of each row's log-sum-exp.
+    acc_bound = 2 * rows * 2.0 ** -24 * (float(init[1]) + 2.0)
+    return [_res('xent_loss_two_calls ' + tag, o[0], init[0].double() + 2 * loss.detach(), _tol(torch.float32)),
+            _res('xent_acc_two_calls ' + tag, o[1], init[1].double() + 2 * acc, 0, acc_bound),
+            _res('xent_dlogits ' + tag, dl[:, :nclass], zr.grad * gscale, t, 1e-7),
+            _res('xent_dlogits_pad ' + tag, dl[:, nclass:], torch.zeros(rows, cpad - nclass), 0, 0),
+            _res('xent_dlogits_repeat ' + tag, dl2, dl, 0, 0)]
+
+
+def check_colsum(rows, C, cvalid, dtype, seed=0):
+    """simclr_colsum: fp32 column sums of an fp32 / bf16 matrix at the fp32 gate 2e-5 * max |ref| (the output is fp32 and pre-rounded bf16
+    inputs are exact, so only the fp32 summation order is left).  accumulate=1 adds onto a non-zero out; elements at and beyond cvalid
+    keep a sentinel; two calls are bitwise equal.
+    The kernel adds rows/16 values per lane and joins 16 lanes, so per column |err| <= (rows/16 + 16) * 2^-24 * sum_r |x[r][c]|.  The
+    inputs are N(1, 1): sum |x| ~ 1.17 rows and |ref| ~ rows, so that worst case is 6e-8 * 1.17 * (rows/16 + 16) of max |ref| --
+    1.1e-6 at 15 rows, 5.5e-6 at 1000 rows: at least 3.6 times under the gate even if every rounding went the same way."""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(rows, C, generator=g) + 1.0).to(dtype)
+    ref = x.double().sum(0)[:cvalid]
+    SENT = 7.5
+    o1 = torch.full((C,), SENT, device=DEV)
+    o2 = torch.full((C,), SENT, device=DEV)
+    xd = x.to(DEV)
+    ops.colsum(xd, cvalid, o1)
+    ops.colsum(xd, cvalid, o2)
+    init = torch.randn(C, generator=g) * 3
+    o3 = init.clone().to(DEV)
+    ops.colsum(xd, cvalid, o3, accumulate=True)
+    torch.cuda.synchronize()
+    tag = '%dx%d(%d) %s' % (rows, cvalid, C, _dn(dtype))
+    t = _tol(torch.float32)
+    return [_res('colsum ' + tag, o1[:cvalid], ref, t),
+            _res('colsum_sentinel ' + tag, o1[cvalid:], torch.full((C - cvalid,), SENT), 0, 0),
+            _entry('colsum_bitwise_repeat ' + tag, 0.0 if torch.equal(o1, o2) else 1.0, 0.0),
+            _res('colsum_accumulate ' + tag, o3[:cvalid], init.double()[:cvalid] + ref, t),
+            _res('colsum_accumulate_sentinel ' + tag, o3[cvalid:], init[cvalid:], 0, 0)]
+
+
+def cast_classes():
+    """fp32 bit patterns by class: every binade with random mantissas, exact round-to-nearest-even ties in both directions, +-0,
+    subnormals, the largest finite value (rounds to inf in bf16), +-inf, NaNs."""
+    g = torch.Generator().manual_seed(0)
+    sign = torch.tensor([0, 1], dtype=torch.int64).view(2, 1, 1) << 31
+    expo = torch.arange(1, 255, dtype=torch.int64).view(1, 254, 1) << 23
+    mant = torch.randint(0, 1 << 23, (1, 1, 16), generator=g)
+    binades = (sign | expo | mant).reshape(-1)
+    hi = torch.randint(0, 1 << 15, (4096,), generator=g) << 16                  # sign cleared; any exponent below inf / NaN territory
+    hi = hi[(hi >> 23) < 254]
+    ties = torch.cat([hi | 0x8000, hi | 0x8000 | (1 << 31), hi | 0x7fff, hi | 0x8001])   # ties (even and odd kept bit), and their neighbours
+    zeros = torch.tensor([0x00000000, 0x80000000], dtype=torch.int64)
+    sub = torch.cat([torch.randint(1, 1 << 23, (512,), generator=g), torch.tensor([1, 0x7fffff, 0x8000, 0x18000, 0x7f8000, 0x7fffff | (1 << 31)])])
+    top = torch.tensor([0x7f7fffff, 0xff7fffff, 0x7f7f8000, 0x7f7f7fff])
+    inf = torch.tensor([0x7f800000, 0xff800000])
+    nan = torch.tensor([0x7fc00000, 0xffc00000, 0x7f800001, 0x7fc12345, 0xffffffff])
+
+    def f32(bits):
+        return torch.from_numpy((bits & 0xffffffff).numpy().astype(np.uint32).view(np.float32).copy())
+    return dict(binades=f32(binades), ties=f32(ties), zeros=f32(zeros), subnormals=f32(sub), largest_finite=f32(top), inf=f32(inf),
+                nan=f32(nan))
+
+
+def _bits_mismatch(got, ref):
+    """Number of elements that differ bitwise; a NaN only has to be a NaN (payload not compared)."""
+    got, ref = got.cpu(), ref.cpu()
+    view = torch.int16 if got.element_size() == 2 else torch.int32
+    both_nan = torch.isnan(got) & torch.isnan(ref)
+    return int(((got.view(view) != ref.view(view)) & ~both_nan).sum())
+
+
+def check_cast_classes():
+    """simclr_cast fp32 -> bf16 bitwise against torch's CPU .bfloat16() (round to nearest even) per class of value; bf16 -> fp32 over all
+    65536 bit patterns and the two same-type copies exact."""
+    res = []
+    for name, v in cast_classes().items():
+        got = ops.cast(v.to(DEV), torch.bfloat16)
+        torch.cuda.synchronize()
+        res.append(_entry('cast_f32_bf16 ' + name, _bits_mismatch(got, v.bfloat16()), 0, numel=v.numel()))
+        same = ops.cast(v.to(DEV), torch.float32)
+        torch.cuda.synchronize()
+        res.append(_entry('cast_f32_f32 ' + name, _bits_mismatch(same, v), 0, numel=v.numel()))
+    allb = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    up = ops.cast(allb.to(DEV), torch.float32)
+    same = ops.cast(allb.to(DEV), torch.bfloat16)
+    torch.cuda.synchronize()
+    res.append(_entry('cast_bf16_f32 all_patterns', _bits_mismatch(up, allb.float()), 0, numel=65536))
+    res.append(_entry('cast_bf16_bf16 all_patterns', _bits_mismatch(same, allb), 0, numel=65536))
+    return res
+
+
+def check_cast_sizes(n, seed=0):
+    """n elements into a caller-supplied larger `out`: the first n are the conversion, the rest keep a sentinel."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, generator=g) * torch.pow(10.0, torch.rand(n, generator=g) * 8 - 4)
+    res = []
+    for src, dst in ((torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32), (torch.float32, torch.float32),
+                     (torch.bfloat16, torch.bfloat16)):
+        xs = x.to(src)
+        out = torch.full((n + 70,), -3.0, dtype=dst, device=DEV)
+        r = ops.cast(xs.to(DEV), dst, out=out)
+        torch.cuda.synchronize()
+        assert r is out
+        tag = '%s_%s n=%d' % (_dn(src), _dn(dst), n)
+        res.append(_entry('cast ' + tag, _bits_mismatch(out[:n], xs.to(dst)), 0, numel=n))
+        res.append(_entry('cast_sentinel ' + tag, _bits_mismatch(out[n:], torch.full((70,), -3.0, dtype=dst)), 0, numel=70))
+    return res
+
+
+def check_axpy(n, a=0.3, seed=0):
+    """simclr_axpy_f32: y = fma(a, x, y), one rounding per element, so |err| <= 2^-24 |ref| against float64 with `a` the fp32 value the ABI
+    receives.  y is close to -a * x, so the results cancel to a small remainder of either sign; elements of y past n keep their value."""
+    g = torch.Generator().manual_seed(seed)
+    a32 = float(np.float32(a))
+    x = torch.randn(n, generator=g) * 4
+    y = (-(a32 * x.double()) * (1 + 1e-3 * torch.randn(n, generator=g).double())).float()
+    y[::7] = x[::7]                                                    # and some elements that do not cancel
+    yd = torch.cat([y, torch.full((5,), 9.0)]).to(DEV)
+    ops.axpy_f32(a, x.to(DEV), yd)
+    torch.cuda.synchronize()
+    ref = a32 * x.double() + y.double()
+    got = yd.double().cpu()
+    bound = 2.0 ** -24 * ref.abs()
+    excess = float(((got[:n] - ref).abs() - bound).max())
+    return [_entry('axpy_f32 n=%d (max |err| - 2^-24 |ref|)' % n, excess, 0.0, scale=float(ref.abs().max()), numel=n,
+                   cancelled=int((ref.abs() < 1e-2 * (a32 * x.double()).abs()).sum())),
+            _res('axpy_f32_tail n=%d' % n, got[n:], torch.full((5,), 9.0), 0, 0)]
+
+
+def check_l2_loss(n, seed=0):
+    """simclr_l2_loss_f32 adds 0.5 * sum x^2 onto a non-zero out.  The kernel keeps float64 partials per workgroup, rounds each to fp32
+    once and adds it with one float atomic: (blocks + 1) * 2^-24 relative (all terms are positive), blocks = min(256, ceil(n / 1024))."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, generator=g) * torch.pow(10.0, torch.rand(n, generator=g) * 5 - 3)      # magnitudes 1e-3 ... 1e2
+    init = 3.25
+    out = torch.full((1,), init, device=DEV)
+    ops.l2_loss_f32(x.to(DEV), out)
+    torch.cuda.synchronize()
+    ref = init + 0.5 * float((x.double() ** 2).sum())
+    blocks = min(256, (n + 1023) // 1024)
+    return [_entry('l2_loss_f32 n=%d' % n, abs(float(out.double().cpu()[0]) - ref), (blocks + 1) * 2.0 ** -24 * ref, scale=ref, numel=n)]
+
+
+def check_accumulate_scalars(n, seed=0):
+    """simclr_accumulate_scalars: dst[i] += scale[i] * *src[i], copy[i] = the scaled term, total[0] = the sum of the masked terms, for every
+    combination of dst / total / copy present or absent, with and without scales, total_mask empty / full / a strict subset.  The sources
+    are slices of one tensor and `total` a slice of the same tensor, as model.py calls it.  Reference: the same sums in float64; sequential
+    fp32 adds (a contracted multiply-add allowed) stay within n * 2^-23 * sum |terms|."""
+    g = torch.Generator().manual_seed(seed)
+    full = (1 << n) - 1
+    subset = 0b0101010101010101 & full if n > 1 else 0
+    worst = dict(dst=0.0, copy=0.0, total=0.0)
+    untouched = 0
+    count = 0
+    for has_dst, has_total, has_copy, with_scales, mask in itertools.product((False, True), (False, True), (False, True), (False, True),
+                                                                             sorted({0, full, subset})):
+        bank = (torch.randn(n + 1, generator=g) * 5).to(DEV)
+        bank0 = bank.double().cpu()
+        srcs = [bank[i:i + 1] for i in range(n)]
+        scales = [float(np.float32(s)) for s in (torch.randn(n, generator=g) * 2).tolist()] if with_scales else None
+        dst0 = torch.randn(n, generator=g) * 5
+        dst = dst0.clone().to(DEV) if has_dst else None
+        copy = torch.full((n,), -7.0, device=DEV) if has_copy else None
+        ops.accumulate_scalars(srcs, dst=dst, scales=scales, total=bank[n:n + 1] if has_total else None,
+                               total_mask=mask, copy=copy)
+        torch.cuda.synchronize()
+        v = bank0[:n] * (torch.tensor(scales, dtype=torch.float64) if with_scales else 1.0)
+        u = n * 2.0 ** -23
+        if has_dst:
+            b = u * (dst0.double().abs() + v.abs())
+            worst['dst'] = max(worst['dst'], float(((dst.double().cpu() - (dst0.double() + v)).abs() / b).max()))
+        if has_copy:
+            worst['copy'] = max(worst['copy'], float(((copy.double().cpu() - v).abs() / (u * v.abs())).max()))
+        sel = torch.tensor([(mask >> i) & 1 for i in range(n)], dtype=torch.bool)
+        after = bank.double().cpu()
+        if has_total:
+            tref = float(v[sel].sum())
+            terr = abs(float(after[n]) - tref)
+            b = u * float(v[sel].abs().sum())
+            worst['total'] = max(worst['total'], terr / b if b > 0 else (0.0 if terr == 0 else float('inf')))
+        else:
+            untouched += int(after[n] != bank0[n])
+        untouched += int((after[:n] != bank0[:n]).sum())         # the sources are never written
+        count += 1
+    return [_entry('accumulate_scalars_%s n=%d (err / bound)' % (k, n), w, 1.0, numel=count) for k, w in worst.items()] + \
+           [_entry('accumulate_scalars_untouched n=%d' % n, untouched, 0, numel=count)]
+
+
+def check_empty_launches():
+    """n == 0: simclr_cast, simclr_axpy_f32 and simclr_l2_loss_f32 return 0 and touch nothing."""
+    x = torch.full((8,), 2.0, device=DEV)
+    y = torch.full((8,), 5.0, device=DEV)
+    yb = torch.full((8,), 5.0, device=DEV, dtype=torch.bfloat16)
+    L = lib()
+    rc = [L.cast(ops._p(x), ops._p(yb), 0, DT_F32, DT_BF16, ops._s()), L.axpy_f32(1.0, ops._p(x), ops._p(y), 0, ops._s()),
+          L.l2_loss_f32(ops._p(x), 0, ops._p(y), ops._s())]
+    torch.cuda.synchronize()
+    return [_entry('empty_launch_status', sum(abs(r) for r in rc), 0),
+            _res('empty_launch_untouched', torch.cat([x, y, yb.float()]), torch.cat([torch.full((8,), 2.0), torch.full((16,), 5.0)]), 0, 0)]

@@ -71,6 +71,33 @@ def main():
         run(gc.check_pool, 2, 15, 64, dt)
         run(gc.check_sup_head, 64, 1000, 1008, dt)
         run(gc.check_sup_head, 16, 10, 16, dt)
+    # the selective-kernel unit and the small head kernels (tests/test_gpu_sk_and_small_kernels.py)
+    for dt in (F32, BF):
+        for (V, H, W, f, lp, gp) in [(4, 7, 7, 512, None, None), (2, 56, 56, 64, None, None), (3, 4, 4, 72, 192, 128), (130, 3, 3, 64, None, None)]:
+            run(gc.check_sk_kernels, V, H, W, f, lp, gp, dt)
+        run(gc.check_sk_kernels, 3, 4, 4, 72, 192, 128, dt, logits='equal')
+        run(gc.check_sk_kernels, 3, 4, 4, 72, 192, 128, dt, logits='saturated')
+        run(gc.check_avgpool_bwd_mask, 4, 7, 2048, dt)
+        for mode in ('normal', 'zero', 'tie_cross', 'tie_same', 'large'):
+            run(gc.check_xent, 63, 63, 1000, 1008, dt, mode=mode)
+            run(gc.check_xent, 10, 5, 1000, 1008, dt, gscale=0.5, mode=mode)
+        for rows in (1, 15, 17, 1000):
+            run(gc.check_colsum, rows, 1008, 1000, dt)
+    run(gc.check_sk_kernels, 3, 5, 5, 4, 64, 64, F32)
+    for mm in ('exact', 'f16x3_3'):
+        run(gc.check_sk_layer, 3, 14, 64, 64, 2, f32_matmul=mm, seed=4)
+        run(gc.check_sk_layer, 4, 7, 64, 64, 1, f32_matmul=mm, seed=11)
+    run(gc.check_avgpool_f32_from_bf16, 4, 7, 2048)
+    run(gc.check_avgpool_f32_from_bf16, 2, 56, 64)
+    run(gc.check_cast_classes)
+    for n in (1, 257, (1 << 20) + 3):
+        run(gc.check_cast_sizes, n)
+        run(gc.check_axpy, n)
+    for n in (1, 1025, 2048000):
+        run(gc.check_l2_loss, n)
+    for n in (1, 5, 16):
+        run(gc.check_accumulate_scalars, n)
+    run(gc.check_empty_launches)
     nfail = sum(1 for r in results if not r['ok'])
     print('TOTAL %d checks, %d failed' % (len(results), nfail), flush=True)
     os.makedirs('gpurun_out', exist_ok=True)
