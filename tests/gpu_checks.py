@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from oracle import lars as olars
 from oracle import ntxent as ont
+from tests import bn_pool_reference as bpr
 from simclr_amd import ops
 from simclr_amd._lib import DT_BF16, DT_F32, lib
 
@@ -541,19 +542,20 @@ def check_blur(b, H, k=2, seed=0):
     return [_res('batch_blur b%d %dpx k%d' % (b, H, k), y, ref, 0, 2e-6)]
 
 
-def check_avgpool2(V, H, C, stride, dtype, seed=0):
-    """ResNet-D shortcut pool vs the oracle's restatement of AveragePooling2D (tf2/resnet.py:330-338)."""
+def check_avgpool2(V, H, C, stride, dtype, seed=0, W=None):
+    """ResNet-D shortcut pool vs the oracle's restatement of AveragePooling2D (tf2/resnet.py:330-338).  W: map width (default H)."""
     from oracle.model_torch import Builder, Config
+    W = H if W is None else W
     g = torch.Generator().manual_seed(seed)
-    x = _rand((V, H, H, C), dtype, g)
+    x = _rand((V, H, W, C), dtype, g)
     xr = x.double().permute(0, 3, 1, 2).requires_grad_(True)
     yr = Builder(Config(sk_ratio=0.0625)).avg_pool(xr, stride)
     dy = _rand(tuple(yr.permute(0, 2, 3, 1).shape), dtype, g)
     yr.backward(dy.double().permute(0, 3, 1, 2))
     y = ops.avgpool2_fwd(x.to(DEV), stride)
-    dx = ops.avgpool2_bwd(dy.to(DEV), H, H, stride)
+    dx = ops.avgpool2_bwd(dy.to(DEV), H, W, stride)
     torch.cuda.synchronize()
-    tag = 'V%d %d C%d s%d %s' % (V, H, C, stride, str(dtype).split('.')[-1])
+    tag = 'V%d %s C%d s%d %s' % (V, H if W == H else '%dx%d' % (H, W), C, stride, str(dtype).split('.')[-1])
     t = _tol(dtype)
     return [_res('avgpool2_fwd ' + tag, y, yr.detach().permute(0, 2, 3, 1), t, 1e-6),
             _res('avgpool2_bwd ' + tag, dx, xr.grad.permute(0, 2, 3, 1), t, 1e-6)]
@@ -2688,3 +2690,384 @@ def check_empty_launches():
     torch.cuda.synchronize()
     return [_entry('empty_launch_status', sum(abs(r) for r in rc), 0),
             _res('empty_launch_untouched', torch.cat([x, y, yb.float()]), torch.cat([torch.full((8,), 2.0), torch.full((16,), 5.0)]), 0, 0)]
+
+
+# ------------------------------------------------------------------ BatchNorm and stem max-pool kernels on exact lattices
+# (tests/test_gpu_bn_and_stem_pool.py).  Inputs come from tests/bn_pool_reference.py: every intermediate of the kernels' fp32 arithmetic
+# is exactly representable, each check first asserts that on the CPU (float32 evaluation == float64 evaluation), and then compares with
+# tolerance 0.
+def _bitwise(name, got, want, **kw):
+    """got == want element for element (tolerance 0; a NaN is a mismatch).  Prints the first mismatching indices with got / want."""
+    g = torch.as_tensor(got).detach().cpu().double()
+    w = torch.as_tensor(want).detach().cpu().double().reshape(g.shape)
+    bad = ~(g == w)
+    nbad = int(bad.sum())
+    err = 0.0
+    if nbad:
+        diff = (g - w).abs()[bad]
+        err = float(diff.max()) if bool(torch.isfinite(diff).all()) else float('inf')
+        err = max(err, 5e-324)
+        for idx in bad.nonzero()[:6].tolist():
+            print('  MISMATCH %s %s got=%r want=%r' % (name, tuple(idx), float(g[tuple(idx)]), float(w[tuple(idx)])))
+    return _entry(name, err, 0.0, scale=float(w.abs().max()) if w.numel() else 0.0, numel=g.numel(), nbad=nbad, **kw)
+
+
+def _guards(name, *checks):
+    """No guard band of the listed _guarded buffers was written."""
+    return _entry(name + ' guard bands untouched', sum(c() for c in checks), 0.0)
+
+
+def _dev(t, dtype):
+    return t.to(dtype).to(DEV).contiguous()
+
+
+def _assert_shares(L, ksz=None, stride=None, pooled=False, tied=True):
+    s = bpr.lattice_shares(L, ksz or 3, stride or 2)
+    assert s['scale_neg'] >= 0.01 and s['scale_zero'] >= 0.01, s
+    if L['x'].numel() >= 4096:
+        assert s['pre_zero'] >= 0.01, s
+    if pooled:
+        assert s['win_zero'] >= 0.05, s
+        assert s['win_tied_pos'] >= 0.05 or not tied, s
+    return s
+
+
+def check_bn_stream_lattice(rows, C, dtype, seed=0):
+    """simclr_bn_apply, simclr_bn_bwd_reduce and simclr_bn_bwd_apply with lattice scale / shift / mean / rstd / c1 / c2 handed straight
+    to the kernels: every output bitwise equal to the float64 reference rounded once to the storage type; fp32 slot sums exact."""
+    L = bpr.lattice((rows, C), seed=seed + rows, names=('x', 'dy', 'res', 'msk'))
+    bpr.assert_survives(L, dtype)
+    _assert_shares(L)
+    if rows * C >= 4096:
+        assert float((L['msk'] == 0).double().mean()) > 0.01 and float((L['msk'] < 0).double().mean()) > 0.2
+    epc = 8 if dtype == torch.bfloat16 else 4
+    cpr = C // epc
+    tag = '%dx%d %s' % (rows, C, _dn(dtype))
+    dtc = DT_BF16 if dtype == torch.bfloat16 else DT_F32
+    x, dy, rs, mk = (_dev(L[k], dtype) for k in ('x', 'dy', 'res', 'msk'))
+    P = {k: _dev(L[k], torch.float32) for k in ('scale', 'shift', 'mean', 'rstd', 'c1', 'c2', 'rscale', 'rshift')}
+    p, s = ops._p, ops._s()
+    res = []
+    sh = torch.arange(epc, dtype=torch.int32)
+    for relu in (0, 1):
+        for res_mode in (0, 1, 2):
+            want = bpr.round_to(bpr.assert_exact(lambda d: bpr.bn_apply_ref(L, relu, res_mode, d), 'bn_apply'), dtype)
+            y, yc = _guarded((rows, C), dtype)
+            bits, bc = _guarded((rows, cpr), torch.uint8)
+            lib().bn_apply(p(x), p(P['scale']), p(P['shift']), p(rs) if res_mode else None, p(P['rscale']) if res_mode == 2 else None,
+                           p(P['rshift']) if res_mode == 2 else None, p(y), p(bits), rows, C, relu, dtc, s)
+            torch.cuda.synchronize()
+            t2 = 'bn_apply relu=%d res=%d %s' % (relu, res_mode, tag)
+            want_bits = ((want.reshape(rows, cpr, epc) > 0).to(torch.int32) << sh).sum(-1)
+            res += [_bitwise(t2, y, want), _bitwise(t2 + ' relu_bits', bits, want_bits), _guards(t2, yc, bc)]
+    perm = bpr.row_perm(rows)
+    nslot = lib().bn_bwd_reduce_slots(rows, C, dtc)
+    for mode in (0, 1, 2):
+        dm = bpr.assert_exact(lambda d: bpr.bn_masked_dy(L, mode, d), 'dm')
+        s1, s2, dx = bpr.assert_exact(lambda d: bpr.bn_bwd_ref(L, bpr.bn_masked_dy(L, mode, d), d, perm), 'bn_bwd')
+        if mode and rows * C >= 4096:        # the mask kills gradient exactly where its source is 0 (mode 1) / x*scale+shift is 0 (mode 2)
+            src = L['msk'] if mode == 1 else L['x'] * L['scale'] + L['shift']
+            assert int(((src == 0) & (L['dy'] != 0)).sum()) > 0 and not bool(dm[src <= 0].any())
+        part, pc = _guarded((nslot, 2, C), torch.float32, fill=torch.zeros(nslot, 2, C))
+        lib().bn_bwd_reduce(p(dy), p(x), p(mk) if mode == 1 else None, p(P['scale']), p(P['shift']), p(P['mean']), p(P['rstd']),
+                            rows, C, mode, p(part), nslot, dtc, s)
+        t2 = 'bn_bwd mode=%d %s' % (mode, tag)
+        res += [_bitwise(t2 + ' reduce sums (%d slots)' % nslot, part.double().sum(0), torch.stack([s1, s2]))]
+        for want_masked in (True, False):
+            dxd, dc = _guarded((rows, C), dtype)
+            dmd, mc = _guarded((rows, C), dtype)
+            lib().bn_bwd_apply(p(dy), p(x), p(mk) if mode == 1 else None, p(P['scale']), p(P['shift']), p(P['mean']), p(P['rstd']),
+                               p(P['c1']), p(P['c2']), rows, C, mode, p(dxd), p(dmd) if want_masked else None, dtc, s)
+            torch.cuda.synchronize()
+            res += [_bitwise(t2 + ' dx (dmasked %s)' % ('written' if want_masked else 'NULL'), dxd, bpr.round_to(dx, dtype)),
+                    _guards(t2 + ' apply', dc, mc, pc)]
+            if want_masked:
+                res.append(_bitwise(t2 + ' dmasked', dmd, bpr.round_to(dm, dtype)))
+        if dtype == torch.float32 and C % 32 == 0 and C <= 1024:
+            dps, _ = ops.bn_bwd_apply(dy, x, mk if mode == 1 else None, P['scale'], P['shift'], P['mean'], P['rstd'], P['c1'], P['c2'],
+                                      mode, ps_out=True)
+            torch.cuda.synchronize()
+            assert ops.ps_kind(dps) == 'b16'
+            _, hi, lo = ps_decode(dps)
+            want_hi = dx.float().bfloat16().double()
+            res += [_bitwise(t2 + ' pre-split hi', hi, want_hi), _bitwise(t2 + ' pre-split lo', lo, (dx - want_hi).float().bfloat16().double())]
+    return res
+
+
+def check_bn_bwd_reduce_slot_counts(rows, C, dtype, seed=0):
+    """simclr_bn_bwd_reduce called with a caller-chosen slot count: fewer slots than workgroups (float atomics into slot workgroup % nslot)
+    and at least as many (one plain store per slot; slots beyond the grid stay zero).  Lattice sums are exact, so every grouping of the
+    workgroups gives the same bits."""
+    L = bpr.lattice((rows, C), seed=seed, names=('x', 'dy', 'msk'))
+    bpr.assert_survives(L, dtype)
+    dtc = DT_BF16 if dtype == torch.bfloat16 else DT_F32
+    grid = lib().bn_bwd_reduce_slots(rows, C, dtc)
+    assert grid >= 8, grid
+    x, dy = _dev(L['x'], dtype), _dev(L['dy'], dtype)
+    P = {k: _dev(L[k], torch.float32) for k in ('scale', 'shift', 'mean', 'rstd')}
+    s1, s2, _ = bpr.assert_exact(lambda d: bpr.bn_bwd_ref(L, bpr.bn_masked_dy(L, 2, d), d, bpr.row_perm(rows)), 'bn_bwd')
+    want = torch.stack([s1, s2])
+    res = []
+    for nslot in (1, 3, grid - 1, grid, grid + 5):
+        part, pc = _guarded((nslot, 2, C), torch.float32, fill=torch.zeros(nslot, 2, C))
+        lib().bn_bwd_reduce(ops._p(dy), ops._p(x), None, ops._p(P['scale']), ops._p(P['shift']), ops._p(P['mean']), ops._p(P['rstd']),
+                            rows, C, 2, ops._p(part), nslot, dtc, ops._s())
+        torch.cuda.synchronize()
+        tag = 'bn_bwd_reduce %dx%d %s nslot=%d (grid %d)' % (rows, C, _dn(dtype), nslot, grid)
+        res += [_bitwise(tag, part.double().sum(0), want), _guards(tag, pc)]
+        if nslot > grid:
+            res.append(_bitwise(tag + ' slots beyond the grid stay zero', part[grid:], torch.zeros(nslot - grid, 2, C)))
+        if nslot >= grid:      # own-slot branch: every workgroup's slot holds something (no slot is skipped, none shared)
+            res.append(_entry(tag + ' every workgroup wrote its slot', int((part[:grid].abs().sum((1, 2)) == 0).sum()), 0.0))
+    return res
+
+
+def _slots_on_device(pc):
+    """partial [nslot, 2, C] on the device with one slot of large sentinels on either side: a slot walk that reads one slot too far (or
+    one too early) does not reproduce the sums."""
+    nslot, _, C = pc.shape
+    buf = torch.full((nslot + 2, 2, C), 3.0e6, device=DEV, dtype=torch.float32)
+    buf[1:nslot + 1] = pc.to(DEV)
+    return buf[1:nslot + 1]
+
+
+def check_bn_slot_kernels(nslot, C, seed=0):
+    """simclr_bn_reduce_slots / _pivoted (bitwise), simclr_bn_finalize (fused slot path == two-launch path bitwise; against float64 within
+    the ulp bounds derived in bn_pool_reference.bn_finalize_ref) and simclr_bn_bwd_finalize (bitwise) on integer-valued slots."""
+    import numpy as np
+    g = torch.Generator().manual_seed(seed + 7 * nslot + C)
+    const = (0, C - 1)
+    pc = bpr.slot_partials(nslot, C, seed=seed + nslot, constant_channels=const)
+    pd = _slots_on_device(pc)
+    sums64 = pc.double().sum(0)
+    assert bool((pc.double().cumsum(0)[-1] == sums64).all())
+    tag = 'nslot=%d C=%d' % (nslot, C)
+    res = []
+    p, s = ops._p, ops._s()
+    # ---- slot reduction
+    sums_d, sc = _guarded((2, C), torch.float64)
+    lib().bn_reduce_slots(p(pd), nslot, C, p(sums_d), s)
+    pivot = bpr.quarters((C,), 2, g)
+    count = 16 * nslot
+    pv_d, vc = _guarded((2, C), torch.float64)
+    pivot_d = _dev(pivot, torch.float32)
+    lib().bn_reduce_slots_pivoted(p(pd), nslot, C, p(pivot_d), float(count), p(pv_d), s)
+    torch.cuda.synchronize()
+    want_pv = torch.stack([sums64[0] + count * pivot, sums64[1] + 2.0 * pivot * sums64[0] + count * pivot * pivot])
+    # exactness of the pivoted moments in fp64: every term is a dyadic rational far below 2^53 times its granularity 2^-18
+    assert bool((want_pv * 2 ** 18 == (want_pv * 2 ** 18).round()).all()) and float(want_pv.abs().max()) < 2 ** 34
+    res += [_bitwise('bn_reduce_slots ' + tag, sums_d, sums64), _bitwise('bn_reduce_slots_pivoted ' + tag, pv_d, want_pv),
+            _guards('bn_reduce_slots ' + tag, sc, vc)]
+    # ---- finalize: (count, gamma/beta, moving statistics, eps)
+    gamma, beta = bpr.quarters((C,), 2, g).float() + 0.125, bpr.quarters((C,), 2, g).float()
+    mm0, mv0 = bpr.quarters((C,), 2, g).float(), (bpr.quarters((C,), 2, g).abs() + 0.25).float()
+    gamma_d, beta_d = gamma.to(DEV), beta.to(DEV)
+    for name, cnt, with_gb, with_mov, eps in [('local count', count, True, True, 1e-5), ('global count, no gamma/beta/moving, eps 1e-3', 3 * count, False, False, 1e-3),
+                                              ('no gamma/beta', count, False, True, 1e-5), ('no moving', 2 * count, True, False, 1.001e-5)]:
+        outs = []
+        for fused in (True, False):
+            o = [_guarded((C,), torch.float32) for _ in range(4)]
+            mm, mv = (mm0.to(DEV), mv0.to(DEV)) if with_mov else (None, None)
+            lib().bn_finalize(None if fused else p(sums_d), p(pd) if fused else None, nslot if fused else 0, float(cnt), C,
+                              p(gamma_d) if with_gb else None, p(beta_d) if with_gb else None, p(mm), p(mv), 0.9, eps,
+                              p(o[0][0]), p(o[1][0]), p(o[2][0]), p(o[3][0]), s)
+            torch.cuda.synchronize()
+            outs.append(dict(mean=o[0][0], rstd=o[1][0], scale=o[2][0], shift=o[3][0], moving_mean=mm, moving_var=mv))
+            res.append(_guards('bn_finalize %s %s fused=%d' % (name, tag, fused), *[c for _, c in o]))
+        ref, tol, info = bpr.bn_finalize_ref(sums64, cnt, gamma if with_gb else None, beta if with_gb else None,
+                                             mm0 if with_mov else None, mv0 if with_mov else None, 0.9, eps)
+        if cnt == count:
+            assert bool(info['clamped'][list(const)].all()) and int(info['clamped'].sum()) == len(set(const))
+            assert bool((ref['rstd'][list(const)] == 1.0 / np.sqrt(float(np.float32(eps)))).all())
+        assert float(info['kappa'].max()) < 2.0 ** -30          # the fp64 cancellation is far below one fp32 ulp on this data
+        for k in ref:
+            t2 = 'bn_finalize %s [%s] %s' % (k, name, tag)
+            res.append(_bitwise(t2 + ' fused slots == two launches', outs[0][k], outs[1][k]))
+            err = (outs[0][k].double().cpu() - ref[k]).abs()
+            ratio = torch.where(tol[k] > 0, err / tol[k].clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float('inf'))))
+            ratio = torch.where(torch.isfinite(outs[0][k].double().cpu()), ratio, torch.full_like(ratio, float('inf')))
+            res.append(_entry(t2 + ' vs float64, err / derived ulp bound', float(ratio.max()), 1.0, numel=C,
+                              worst_ulps=float((err / (bpr.U32 * ref[k].abs().clamp_min(1e-300))).max())))
+    # ---- backward finalize: dgamma / dbeta from the LOCAL sums, c1 / c2 from the GLOBAL ones (integer slots: every sum below is exact)
+    pb = bpr.slot_partials(nslot, C, seed=seed + nslot + 500)
+    pbd = _slots_on_device(pb)
+    loc = pb.double().sum(0)
+    gl = bpr.slot_partials(nslot, C, seed=seed + nslot + 1000).double().sum(0) + loc
+    loc_d, gl_d = loc.to(DEV), gl.to(DEV)
+    gcount = 2 * count + 3
+    dg0, db0 = bpr.quarters((C,), 4, g).float(), bpr.quarters((C,), 4, g).float()
+
+    def run(local, glob, slots, acc, with_dg, with_db):
+        dg, db = dg0.to(DEV), db0.to(DEV)
+        c1, k1 = _guarded((C,), torch.float32)
+        c2, k2 = _guarded((C,), torch.float32)
+        lib().bn_bwd_finalize(p(local), p(glob), p(slots), nslot if slots is not None else 0, float(gcount), C, p(dg) if with_dg else None,
+                              p(db) if with_db else None, acc, p(c1), p(c2), s)
+        torch.cuda.synchronize()
+        return dict(dgamma=dg, dbeta=db, c1=c1, c2=c2), k1, k2
+    for name, acc, with_dg, with_db in [('acc=0', 0, True, True), ('acc=1', 1, True, True), ('dgamma NULL', 1, False, True), ('dbeta NULL', 0, True, False)]:
+        t2 = 'bn_bwd_finalize %s %s' % (name, tag)
+        want = dict(dgamma=(dg0.double() if acc or not with_dg else 0) + (loc[1] if with_dg else 0),           # NULL: the buffer keeps dg0
+                    dbeta=(db0.double() if acc or not with_db else 0) + (loc[0] if with_db else 0))
+        got, k1, k2 = run(loc_d, gl_d, None, acc, with_dg, with_db)
+        res += [_bitwise(t2 + ' %s (local sums)' % k, got[k], want[k]) for k in ('dgamma', 'dbeta')]
+        res += [_bitwise(t2 + ' c1 (global sums)', got['c1'], (gl[0] / gcount).float()), _bitwise(t2 + ' c2 (global sums)', got['c2'], (gl[1] / gcount).float()),
+                _guards(t2, k1, k2)]
+        # fused slots (single replica: local == global == the slots) == the sums path handed (local, local), bitwise
+        fused, k1, k2 = run(None, None, pbd, acc, with_dg, with_db)
+        same, k3, k4 = run(loc_d, loc_d, None, acc, with_dg, with_db)
+        res += [_bitwise(t2 + ' %s fused slots == sums path' % k, fused[k], same[k]) for k in fused]
+        res += [_bitwise(t2 + ' %s fused slots' % k, fused[k], want[k]) for k in ('dgamma', 'dbeta')]
+        res += [_bitwise(t2 + ' c1 fused slots', fused['c1'], (loc[0] / gcount).float()), _bitwise(t2 + ' c2 fused slots', fused['c2'], (loc[1] / gcount).float()),
+                _guards(t2 + ' fused', k1, k2, k3, k4)]
+    return res
+
+
+def check_bn_fold_lattice(K, N, dtype, seed=0):
+    """simclr_bn_fold_coeffs / bn_sums_from_gram / bn_fold_s2 / bn_fold_pre / bn_fold_post on lattice operands: the fp64-accumulated
+    outputs bitwise, the fp32 fmaf outputs bitwise (their float32 evaluation on the CPU equals the float64 one: asserted)."""
+    g = torch.Generator().manual_seed(seed + K * 1000 + N)
+    L = bpr.lattice_params(N, g)
+    w, t1, gw, dw0 = (bpr.quarters((K, N), 4, g) for _ in range(4))
+    q = bpr.quarters((K, K), 4, g)
+    cs = torch.randint(-8, 9, (K,), generator=g).double()
+    cs64_d, cs32_d = cs.to(DEV), cs.float().to(DEV)
+    s0 = torch.randint(-64, 65, (N,), generator=g).double()
+    bpr.assert_survives(dict(w=w, q=q), dtype)
+    tag = 'K=%d N=%d %s' % (K, N, _dn(dtype))
+    dtc = DT_BF16 if dtype == torch.bfloat16 else DT_F32
+    p, s = ops._p, ops._s()
+    P = {k: _dev(L[k], torch.float32) for k in ('scale', 'mean', 'rstd', 'c1', 'c2')}
+    wd, w32, t1d, gwd, qd = _dev(w, dtype), _dev(w, torch.float32), _dev(t1, torch.float32), _dev(gw, torch.float32), _dev(q, torch.float32)
+    a, b, d = bpr.assert_exact(lambda dt_: bpr.bn_fold_coeffs_ref(L, dt_), 'fold_coeffs')
+    res = []
+    # coeffs
+    o = [_guarded((N,), torch.float32) for _ in range(3)]
+    lib().bn_fold_coeffs(p(P['scale']), p(P['mean']), p(P['rstd']), p(P['c1']), p(P['c2']), p(o[0][0]), p(o[1][0]), p(o[2][0]), N, s)
+    torch.cuda.synchronize()
+    res += [_bitwise('bn_fold_coeffs %s %s' % (k, tag), t[0], v) for k, t, v in zip('abd', o, (a, b, d))] + [_guards('bn_fold_coeffs ' + tag, *[c for _, c in o])]
+    # sums from the Gram matrix (fp32 weights whatever the storage type), column sums as fp64 or fp32
+    want_g = torch.stack([(cs[:, None] * w).sum(0), (gw * w).sum(0)])
+    for kind in ('cs64', 'cs32'):
+        sd, c0 = _guarded((2, N), torch.float64)
+        lib().bn_sums_from_gram(p(gwd), p(w32), p(cs64_d) if kind == 'cs64' else None, p(cs32_d) if kind == 'cs32' else None,
+                                K, N, p(sd), s)
+        torch.cuda.synchronize()
+        res += [_bitwise('bn_sums_from_gram %s %s' % (kind, tag), sd, want_g), _guards('bn_sums_from_gram %s %s' % (kind, tag), c0)]
+    # sum(dm x^) from t1 = h^T dm
+    sd, c0 = _guarded((2, N), torch.float64, fill=torch.stack([s0, torch.full((N,), -77.0, dtype=torch.float64)]))
+    lib().bn_fold_s2(p(t1d), p(wd), p(P['mean']), p(P['rstd']), p(sd), K, N, dtc, s)
+    torch.cuda.synchronize()
+    res += [_bitwise('bn_fold_s2 ' + tag, sd, torch.stack([s0, L['rstd'] * ((w * t1).sum(0) - L['mean'] * s0)])), _guards('bn_fold_s2 ' + tag, c0)]
+    # pre: a, b, d, wb = w b (fp32), wext[:, :N] = T(w a), e = fp32(sum_j w d); the K columns behind stay untouched
+    wb = bpr.assert_exact(lambda dt_: w.to(dt_) * bpr.bn_fold_coeffs_ref(L, dt_)[1], 'fold_pre wb')
+    wa = bpr.assert_exact(lambda dt_: w.to(dt_) * bpr.bn_fold_coeffs_ref(L, dt_)[0], 'fold_pre wext')
+    assert torch.equal(wa.to(dtype).double(), wa)
+    o = [_guarded((N,), torch.float32) for _ in range(3)]
+    wbd, c1_ = _guarded((K, N), torch.float32)
+    wext, c2_ = _guarded((K, N + K), dtype, fill=torch.full((K, N + K), 99.0).to(dtype))
+    ed, c3_ = _guarded((K,), torch.float32)
+    lib().bn_fold_pre(p(wd), p(P['scale']), p(P['mean']), p(P['rstd']), p(P['c1']), p(P['c2']), p(o[0][0]), p(o[1][0]), p(o[2][0]), p(wbd),
+                      p(wext), p(ed), K, N, dtc, s)
+    torch.cuda.synchronize()
+    res += [_bitwise('bn_fold_pre %s %s' % (k, tag), t[0], v) for k, t, v in zip('abd', o, (a, b, d))]
+    res += [_bitwise('bn_fold_pre wb ' + tag, wbd, wb), _bitwise('bn_fold_pre wext[:, :N] ' + tag, wext[:, :N], wa),
+            _bitwise('bn_fold_pre wext[:, N:] untouched ' + tag, wext[:, N:], torch.full((K, K), 99.0)),
+            _bitwise('bn_fold_pre e ' + tag, ed, (w * d).sum(1).float()), _guards('bn_fold_pre ' + tag, c1_, c2_, c3_, *[c for _, c in o])]
+    # post: dw = a t1 + b gw + cs (x) d (+ dw), wext[:, N:] = T(q^T) unless wext and q are NULL
+    ad, bd, dd = (_dev(v, torch.float32) for v in (a, b, d))
+    for kind, acc, with_q in [('cs64', 0, True), ('cs32', 1, True), ('cs64', 1, False), ('cs32', 0, False)]:
+        want = bpr.assert_exact(lambda dt_: bpr.bn_fold_post_ref(a, b, d, t1, gw, cs, dw0 if acc else None, dt_), 'fold_post dw')
+        dw, c1_ = _guarded((K, N), torch.float32, fill=dw0.float())
+        wext, c2_ = _guarded((K, N + K), dtype, fill=torch.full((K, N + K), 99.0).to(dtype))
+        lib().bn_fold_post(p(t1d), p(gwd), p(cs64_d) if kind == 'cs64' else None, p(cs32_d) if kind == 'cs32' else None,
+                           p(ad), p(bd), p(dd), p(qd) if with_q else None, p(dw), p(wext) if with_q else None, K, N, acc, dtc, s)
+        torch.cuda.synchronize()
+        t2 = 'bn_fold_post %s acc=%d q=%d %s' % (kind, acc, with_q, tag)
+        res += [_bitwise(t2 + ' dw', dw, want), _bitwise(t2 + ' wext[:, :N] untouched', wext[:, :N], torch.full((K, N), 99.0)),
+                _bitwise(t2 + ' wext[:, N:]', wext[:, N:], q.t() if with_q else torch.full((K, K), 99.0)), _guards(t2, c1_, c2_)]
+    return res
+
+
+def check_stem_pool_lattice(V, H, W, C, dtype, ksz=3, stride=2, seed=0):
+    """simclr_bnrelu_maxpool_fwd / maxpool_bwd / bn_bwd_reduce_pool / bn_bwd_apply_pool and the un-fused sequence maxpool_bwd ->
+    bn_bwd_reduce -> bn_bwd_apply (mask mode 2) on lattice data against the explicit first-max-tap reference: values, the tap id of every
+    window, every gradient element and the slot sums, all bitwise."""
+    from simclr_amd._lib import SimclrHipError
+    L = bpr.lattice((V, H, W, C), seed=seed, names=('x',))
+    OH, pt, _ = bpr.same_pad(H, ksz, stride)
+    OW, pl, _ = bpr.same_pad(W, ksz, stride)
+    assert (OH, pt) == ops.same_pad(H, ksz, stride) and (OW, pl) == ops.same_pad(W, ksz, stride)
+    L['dy'] = bpr.quarters((V, OH, OW, C), 4, torch.Generator().manual_seed(seed + 1))
+    bpr.assert_survives(L, dtype)
+    shares = _assert_shares(L, ksz, stride, pooled=True, tied=H * W > 1)       # a one-pixel map has one tap per window: nothing can tie
+    ref = bpr.assert_exact(lambda d: bpr.bnrelu_maxpool_ref(L['x'], L['scale'], L['shift'], L['dy'], ksz, stride, d), 'maxpool')
+    rows = V * H * W
+    s1, s2, dx = bpr.assert_exact(lambda d: bpr.bn_bwd_ref(L, bpr.bnrelu_maxpool_ref(L['x'], L['scale'], L['shift'], L['dy'], ksz, stride, d)['dpre'],
+                                                           d, bpr.row_perm(rows)), 'pool bn_bwd')
+    for k in ('y', 'dact'):       # exact in the storage type too: the bf16 un-fused path rounds nothing away
+        assert torch.equal(ref[k].to(dtype).double(), ref[k])
+    want_sums = torch.stack([s1, s2])
+    want_dx = bpr.round_to(dx, dtype)
+    epc = 8 if dtype == torch.bfloat16 else 4
+    dtc = DT_BF16 if dtype == torch.bfloat16 else DT_F32
+    tag = 'V%d %dx%d C%d k%d s%d %s (tied %.0f%%, zero %.0f%%)' % (V, H, W, C, ksz, stride, _dn(dtype), 100 * shares['win_tied_pos'], 100 * shares['win_zero'])
+    x, dy = _dev(L['x'], dtype), _dev(L['dy'], dtype)
+    P = {k: _dev(L[k], torch.float32) for k in ('scale', 'shift', 'mean', 'rstd', 'c1', 'c2')}
+    p, s = ops._p, ops._s()
+    geo = (V, H, W, C, OH, OW, ksz, stride, pt, pl)
+    # forward: the ABI with guard bands, then the wrapper (its own geometry) with and without tap ids
+    y, yc = _guarded((V, OH, OW, C), dtype)
+    arg, ac = _guarded((V, OH, OW, C), torch.uint8)
+    lib().bnrelu_maxpool_fwd(p(x), p(P['scale']), p(P['shift']), p(y), p(arg), *geo, dtc, s)
+    y2, arg2 = ops.bnrelu_maxpool_fwd(x, P['scale'], P['shift'], ksz, stride)
+    y3, arg3 = ops.bnrelu_maxpool_fwd(x, P['scale'], P['shift'], ksz, stride, want_arg=False)
+    torch.cuda.synchronize()
+    assert arg3 is None
+    res = [_bitwise('maxpool_fwd value ' + tag, y, ref['y']), _bitwise('maxpool_fwd tap ids (every window) ' + tag, arg, ref['tap']),
+           _bitwise('maxpool_fwd wrapper value ' + tag, y2, ref['y']), _bitwise('maxpool_fwd wrapper tap ids ' + tag, arg2, ref['tap']),
+           _bitwise('maxpool_fwd want_arg=False value ' + tag, y3, ref['y']), _guards('maxpool_fwd ' + tag, yc, ac)]
+    # max-pool backward: the whole tensor, no "active" mask
+    da, dc = _guarded((V, H, W, C), dtype)
+    lib().maxpool_bwd(p(dy), p(arg), p(da), *geo, dtc, s)
+    torch.cuda.synchronize()
+    res += [_bitwise('maxpool_bwd ' + tag, da, ref['dact']), _guards('maxpool_bwd ' + tag, dc)]
+    # fused reduce
+    cpr = C // epc
+    nslot = lib().bn_bwd_pool_slots(rows, C, dtc)
+    part, pc = _guarded((nslot, 2, C), torch.float32, fill=torch.full((nslot, 2, C), 3.0))       # every slot must be written
+    call = lambda: lib().bn_bwd_reduce_pool(p(dy), p(arg), p(x), p(P['scale']), p(P['shift']), p(P['mean']), p(P['rstd']), *geo, p(part), nslot, dtc, s)
+    if cpr <= 256 and 256 % cpr == 0:
+        call()
+        torch.cuda.synchronize()
+        res += [_bitwise('bn_bwd_reduce_pool sums (%d slots) %s' % (nslot, tag), part.double().sum(0), want_sums), _guards('bn_bwd_reduce_pool ' + tag, pc)]
+        pw = ops.bn_bwd_reduce_pool(dy, arg, x, P['scale'], P['shift'], P['mean'], P['rstd'], ksz, stride)
+        res.append(_bitwise('bn_bwd_reduce_pool wrapper ' + tag, pw.double().sum(0), want_sums))
+    else:
+        msg = ''
+        try:
+            call()
+        except SimclrHipError as e:
+            msg = str(e)
+        torch.cuda.synchronize()
+        res += [_entry('bn_bwd_reduce_pool refuses C=%d %s: %r' % (C, tag, msg), 0.0 if 'bn_bwd_reduce_pool: C=%d not supported' % C in msg else 1.0, 0.0),
+                _bitwise('bn_bwd_reduce_pool refusal launched nothing ' + tag, part, torch.full((nslot, 2, C), 3.0)), _guards('bn_bwd_reduce_pool ' + tag, pc)]
+    # fused apply
+    dxf, fc = _guarded((V, H, W, C), dtype)
+    lib().bn_bwd_apply_pool(p(dy), p(arg), p(x), p(P['scale']), p(P['shift']), p(P['mean']), p(P['rstd']), p(P['c1']), p(P['c2']), p(dxf), *geo, dtc, s)
+    torch.cuda.synchronize()
+    res += [_bitwise('bn_bwd_apply_pool ' + tag, dxf, want_dx), _guards('bn_bwd_apply_pool ' + tag, fc)]
+    if dtype == torch.float32 and C % 32 == 0:
+        dps = ops.bn_bwd_apply_pool(dy, arg, x, P['scale'], P['shift'], P['mean'], P['rstd'], P['c1'], P['c2'], ksz, stride, ps_out=True)
+        torch.cuda.synchronize()
+        _, hi, lo = ps_decode(dps)
+        want_hi = dx.float().bfloat16().double()
+        res += [_bitwise('bn_bwd_apply_pool pre-split hi ' + tag, hi, want_hi),
+                _bitwise('bn_bwd_apply_pool pre-split lo ' + tag, lo, (dx - want_hi).float().bfloat16().double())]
+    # the un-fused sequence, from the max-pool backward as stored
+    pu = ops.bn_bwd_reduce(da, x, None, P['scale'], P['shift'], P['mean'], P['rstd'], 2)
+    dxu, _ = ops.bn_bwd_apply(da, x, None, P['scale'], P['shift'], P['mean'], P['rstd'], P['c1'], P['c2'], 2)
+    torch.cuda.synchronize()
+    res += [_bitwise('unfused bn_bwd_reduce sums ' + tag, pu.double().sum(0), want_sums), _bitwise('unfused bn_bwd_apply ' + tag, dxu, want_dx),
+            _bitwise('fused dx == unfused dx ' + tag, dxf, dxu)]
+    return res

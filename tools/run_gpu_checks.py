@@ -98,6 +98,22 @@ def main():
     for n in (1, 5, 16):
         run(gc.check_accumulate_scalars, n)
     run(gc.check_empty_launches)
+    # BatchNorm and stem max-pool kernels on exact lattices, tolerance 0 (tests/test_gpu_bn_and_stem_pool.py)
+    for dt, widths in ((F32, (4, 96, 192, 1024, 6144)), (BF, (8, 96, 384, 2048, 6144))):
+        for C in widths:
+            for rows in (3, 515):
+                run(gc.check_bn_stream_lattice, rows, C, dt)
+        run(gc.check_bn_bwd_reduce_slot_counts, 515, 192 if dt == F32 else 384, dt)
+        for (K, N) in [(5, 300), (64, 40)]:
+            run(gc.check_bn_fold_lattice, K, N, dt)
+        for (V, H, W, C) in [(2, 6, 10, 64), (3, 7, 5, 128), (1, 9, 16, 192), (2, 1, 1, 64), (1, 2, 3, 256), (2, 15, 15, 64)]:
+            run(gc.check_stem_pool_lattice, V, H, W, C, dt)
+        for (V, H, W, C, k, s) in [(2, 7, 9, 64, 2, 2), (2, 7, 9, 64, 3, 1), (2, 7, 9, 64, 5, 3), (2, 7, 9, 192, 3, 1), (2, 9, 9, 1024, 5, 3)]:
+            run(gc.check_stem_pool_lattice, V, H, W, C, dt, ksz=k, stride=s)
+        for (H, W, s) in [(7, 4, 2), (5, 8, 2), (7, 4, 1), (4, 7, 1)]:
+            run(gc.check_avgpool2, 2, H, 192, s, dt, W=W)
+    for nslot, C in [(1, 8), (33, 40), (129, 64), (160, 40), (768, 2048)]:
+        run(gc.check_bn_slot_kernels, nslot, C)
     nfail = sum(1 for r in results if not r['ok'])
     print('TOTAL %d checks, %d failed' % (len(results), nfail), flush=True)
     os.makedirs('gpurun_out', exist_ok=True)
