@@ -349,6 +349,17 @@ int simclr_bias_softmax_xent(const void* z, const float* bias, const int* labels
 int simclr_colsum(const void* x, int rows, int C, int cvalid, float* out, int accumulate, int dtype,
                   simclr_stream_t stream);
 
+/* ---- distillation (self-training) tail: add_kd_loss, tf2/colabs/distillation_self_training.ipynb:803-808, with the teacher
+ * agreement of the step at :908-919.  s = zs + bias_s (student), t = zt + bias_t (teacher), T = temperature:
+ *   out[0] += T^2 * mean_rows(-sum_c softmax(t/T)_c log softmax(s/T)_c);  out[1] += share of rows with argmax s == argmax t (first
+ *   maximum wins); dlogits[row][c] = T * (softmax(s/T)_c - softmax(t/T)_c) * gscale / rows in the student's dtype, 0 for
+ *   nclass <= c < cpad_s.  Row pitches cpad_s, cpad_t >= nclass and storage dtypes dtype_s, dtype_t are independent; pad columns of
+ *   the inputs are never read; either bias may be NULL; fp32 arithmetic with both row maxima subtracted.  out is added to: the caller
+ *   zeroes it (as for simclr_bias_softmax_xent). */
+int simclr_kd_softmax_xent(const void* zs, const float* bias_s, const void* zt, const float* bias_t, int rows, int nclass,
+                           int cpad_s, int cpad_t, float temperature, float gscale, void* dlogits, float* out,
+                           int dtype_s, int dtype_t, simclr_stream_t stream);
+
 /* ---- small helpers ------------------------------------------------------------------------------ */
 /* dtype hand-over between the fp32 heads / loss and the T-typed encoder (tf2/model.py:262-266) */
 int simclr_cast(const void* x, void* y, long long n, int dtype_in, int dtype_out, simclr_stream_t stream);

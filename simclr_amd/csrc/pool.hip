@@ -816,6 +816,99 @@ __global__ void bias_softmax_xent(const T* __restrict__ z, const float* __restri
   }
 }
 
+// Distillation tail: s = zs + bias_s (student), t = zt + bias_t (teacher), p = softmax(t / T), q = softmax(s / T);
+// loss row = T^2 * (-sum_c p_c log q_c) = T^2 * (log sum_c e^{a_c} - sum_c p_c a_c) with a_c = (s_c - max s) / T;
+// dlogits = T * (q - p) * gscale / rows, padded classes (>= nclass) get 0.  One wave per row, fp32 throughout, both row maxima
+// subtracted.  out[0] += loss contribution, out[1] += rows whose two arg-maxima agree (first maximum wins; atomics; caller zeroes).
+// NREG > 0: the row (nclass <= 64 * NREG) stays in registers -- s and t are read once and serve all three passes;
+// NREG == 0: any nclass, the inputs are read again in every pass.  The maximum is subtracted BEFORE the division by T: the
+// difference of two logits is exact or rounded relative to itself, so the exponents near 0 -- the ones that matter -- keep
+// their absolute accuracy at |s| = 80, T = 0.1, where s / T alone would already be rounded to 6e-5.
+template <typename TS, typename TT, int NREG>
+__global__ __launch_bounds__(256) void kd_softmax_xent(const TS* __restrict__ zs, const float* __restrict__ bias_s,
+                                                       const TT* __restrict__ zt, const float* __restrict__ bias_t,
+                                                       int rows, int nclass, int cpad_s, int cpad_t, float T, float gscale,
+                                                       TS* __restrict__ dlogits, float* __restrict__ out) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const TS* sr = zs + (long long)row * cpad_s;
+  const TT* tr = zt + (long long)row * cpad_t;
+  TS* dr = dlogits + (long long)row * cpad_s;
+  const float invT = 1.f / T;
+  auto ld_s = [&](int c) { return Elem<TS>::ld(sr + c) + (bias_s ? bias_s[c] : 0.f); };
+  auto ld_t = [&](int c) { return Elem<TT>::ld(tr + c) + (bias_t ? bias_t[c] : 0.f); };
+  constexpr int NR = NREG > 0 ? NREG : 1;
+  float a[NR], b[NR];
+  // pass 1: row maxima and arg-maxima of s and t
+  float ms = -INFINITY, mt = -INFINITY; int as = 0x7fffffff, at = 0x7fffffff;
+  if constexpr (NREG > 0) {
+#pragma unroll
+    for (int k = 0; k < NREG; ++k) {
+      const int c = lane + 64 * k;
+      a[k] = b[k] = 0.f;
+      if (c < nclass) {
+        const float vs = ld_s(c), vt = ld_t(c);
+        if (vs > ms) { ms = vs; as = c; }
+        if (vt > mt) { mt = vt; at = c; }
+        a[k] = vs; b[k] = vt;
+      }
+    }
+  } else {
+    for (int c = lane; c < nclass; c += 64) {
+      const float vs = ld_s(c), vt = ld_t(c);
+      if (vs > ms) { ms = vs; as = c; }
+      if (vt > mt) { mt = vt; at = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float oms = __shfl_xor(ms, o, 64); const int oas = __shfl_xor(as, o, 64);
+    if (oms > ms || (oms == ms && oas < as)) { ms = oms; as = oas; }
+    const float omt = __shfl_xor(mt, o, 64); const int oat = __shfl_xor(at, o, 64);
+    if (omt > mt || (omt == mt && oat < at)) { mt = omt; at = oat; }
+  }
+  // pass 2: sq = sum e^a, sp = sum e^b, cr = sum e^b a   (a = (s - max s) / T, b = (t - max t) / T)
+  float sq = 0.f, sp = 0.f, cr = 0.f;
+  if constexpr (NREG > 0) {
+#pragma unroll
+    for (int k = 0; k < NREG; ++k) {
+      if (lane + 64 * k < nclass) {
+        const float da = (a[k] - ms) * invT, eb = expf((b[k] - mt) * invT);
+        sq += expf(da); sp += eb; cr += eb * da;
+      }
+    }
+  } else {
+    for (int c = lane; c < nclass; c += 64) {
+      const float da = (ld_s(c) - ms) * invT, eb = expf((ld_t(c) - mt) * invT);
+      sq += expf(da); sp += eb; cr += eb * da;
+    }
+  }
+  sq = wave_sum(sq); sp = wave_sum(sp); cr = wave_sum(cr);
+  const float rq = 1.f / sq, rp = 1.f / sp;
+  const float g = T * gscale / (float)rows;
+  // pass 3: the gradient; the pad columns of the student's pitch are written as 0
+  if constexpr (NREG > 0) {
+#pragma unroll
+    for (int k = 0; k < NREG; ++k) {
+      const int c = lane + 64 * k;
+      if (c < cpad_s)
+        Elem<TS>::st(dr + c, c < nclass ? (expf((a[k] - ms) * invT) * rq - expf((b[k] - mt) * invT) * rp) * g : 0.f);
+    }
+    for (int c = lane + 64 * NREG; c < cpad_s; c += 64) Elem<TS>::st(dr + c, 0.f);
+  } else {
+    for (int c = lane; c < cpad_s; c += 64) {
+      float d = 0.f;
+      if (c < nclass) d = (expf((ld_s(c) - ms) * invT) * rq - expf((ld_t(c) - mt) * invT) * rp) * g;
+      Elem<TS>::st(dr + c, d);
+    }
+  }
+  if (lane == 0) {
+    atomicAdd(out, T * T * (logf(sq) - cr * rp) / (float)rows);
+    atomicAdd(out + 1, (as == at ? 1.f : 0.f) / (float)rows);
+  }
+}
+
 // out[c] (+)= sum over rows of x[row][c]   (bias gradient)
 template <typename T>
 __global__ __launch_bounds__(256) void colsum(const T* __restrict__ x, int rows, int C, int cvalid, float* __restrict__ out,
@@ -900,6 +993,19 @@ int grid_for(long long n) {
 
 #define DISPATCH_T(dtype, EXPR_BF16, EXPR_F32) \
   do { if ((dtype) == SIMCLR_DT_BF16) { EXPR_BF16; } else { EXPR_F32; } } while (0)
+
+template <typename TS, typename TT>
+static void kd_launch(const void* zs, const float* bias_s, const void* zt, const float* bias_t, int rows, int nclass,
+                      int cpad_s, int cpad_t, float T, float gscale, void* dlogits, float* out, hipStream_t stream) {
+  const dim3 grid(ceil_div(rows, 4)), block(256);
+#define KD_GO(NREG)                                                                                                        \
+  hipLaunchKernelGGL((kd_softmax_xent<TS, TT, NREG>), grid, block, 0, stream, (const TS*)zs, bias_s, (const TT*)zt, bias_t, \
+                     rows, nclass, cpad_s, cpad_t, T, gscale, (TS*)dlogits, out)
+  if (nclass <= 128) KD_GO(2);            // CIFAR-sized label sets: two registers per operand
+  else if (nclass <= 1024) KD_GO(16);     // ImageNet: 16 strided reads per lane and operand, kept across the three passes
+  else KD_GO(0);
+#undef KD_GO
+}
 
 extern "C" {
 
@@ -1205,6 +1311,27 @@ int simclr_bias_softmax_xent(const void* z, const float* bias, const int* labels
              hipLaunchKernelGGL((bias_softmax_xent<float>), dim3(ceil_div(rows, 4)), dim3(256), 0, stream,
                                 (const float*)z, bias, labels, rows, label_rows, nclass, cpad, gscale,
                                 (float*)dlogits, out));
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] += mean distillation loss, out[1] += share of rows whose student and teacher arg-maxima agree (caller zeroes out[0..1])
+int simclr_kd_softmax_xent(const void* zs, const float* bias_s, const void* zt, const float* bias_t, int rows, int nclass,
+                           int cpad_s, int cpad_t, float temperature, float gscale, void* dlogits, float* out,
+                           int dtype_s, int dtype_t, hipStream_t stream) {
+  SIMCLR_CHECK_ARG(zs && zt && dlogits && out, "kd_softmax_xent: null argument (zs, zt, dlogits and out are required)");
+  SIMCLR_CHECK_ARG(rows > 0 && nclass > 0, "kd_softmax_xent: bad shape (rows=%d, nclass=%d)", rows, nclass);
+  SIMCLR_CHECK_ARG(cpad_s >= nclass && cpad_t >= nclass, "kd_softmax_xent: row pitch below nclass=%d (cpad_s=%d, cpad_t=%d)",
+                   nclass, cpad_s, cpad_t);
+  SIMCLR_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "kd_softmax_xent: temperature=%g must be positive and finite",
+                   (double)temperature);
+  SIMCLR_CHECK_ARG((dtype_s == SIMCLR_DT_F32 || dtype_s == SIMCLR_DT_BF16) && (dtype_t == SIMCLR_DT_F32 || dtype_t == SIMCLR_DT_BF16),
+                   "kd_softmax_xent: dtypes must be SIMCLR_DT_F32 or SIMCLR_DT_BF16 (got %d, %d)", dtype_s, dtype_t);
+  const bool sb = dtype_s == SIMCLR_DT_BF16, tb = dtype_t == SIMCLR_DT_BF16;
+  if (sb && tb) kd_launch<uint16_t, uint16_t>(zs, bias_s, zt, bias_t, rows, nclass, cpad_s, cpad_t, temperature, gscale, dlogits, out, stream);
+  else if (sb) kd_launch<uint16_t, float>(zs, bias_s, zt, bias_t, rows, nclass, cpad_s, cpad_t, temperature, gscale, dlogits, out, stream);
+  else if (tb) kd_launch<float, uint16_t>(zs, bias_s, zt, bias_t, rows, nclass, cpad_s, cpad_t, temperature, gscale, dlogits, out, stream);
+  else kd_launch<float, float>(zs, bias_s, zt, bias_t, rows, nclass, cpad_s, cpad_t, temperature, gscale, dlogits, out, stream);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -6,6 +6,7 @@ spellings, defaults and `--name=value` / `--noname` command-line syntax behind a
 module-level `FLAGS` namespace.  TPU flags are accepted and ignored.
 """
 import argparse
+import contextlib
 
 # The product default of f32_matmul is the fast tolerance-meeting mode.  SIMCLR_DEFAULT_F32_MATMUL overrides the DEFAULT only (tests/conftest.py
 # sets it to 'exact': the test-suite pins the arithmetic it tests explicitly and calibrated its fp32 gates on the exact fp32-input MFMA).
@@ -85,6 +86,17 @@ _DEFS = [
                           '(data_seed, step, replica) only, so a resumed run continues the same data.'),
     ('input_threads', 2, int, 'MI355X build: host threads that gather the records of the next batches into pinned buffers.'),
     ('prefetch_batches', 2, int, 'MI355X build: batches gathered ahead of the one the step consumes.'),
+    # self-training / distillation (the third SimCLRv2 stage, tf2/colabs/distillation_self_training.ipynb): a frozen fine-tuned teacher
+    # supplies the targets of the student's fine-tuning step
+    ('teacher_checkpoint', None, str, 'MI355X build: checkpoint of a fine-tuned model (supervised head included).  When set, --train_mode=finetune '
+                                      'distils that frozen teacher into the student: the loss of a step is add_kd_loss(student logits, teacher '
+                                      'logits, distill_temperature) on the step\'s images, labels are not read.  Every teacher variable must be '
+                                      'in the file with its shape.  Ignored by --mode=eval.'),
+    ('distill_temperature', 1.0, float, 'MI355X build: temperature T of the distillation loss T^2 * CE(softmax(teacher / T), student / T).'),
+    ('teacher_resnet_depth', None, int, "MI355X build: depth of the teacher's ResNet (default: --resnet_depth)."),
+    ('teacher_width_multiplier', None, int, "MI355X build: width multiplier of the teacher (default: --width_multiplier)."),
+    ('teacher_sk_ratio', None, float, "MI355X build: selective-kernel ratio of the teacher (default: --sk_ratio)."),
+    ('teacher_ft_proj_selector', None, int, 'MI355X build: projection-head layer the teacher\'s supervised head reads (default: --ft_proj_selector).'),
 ]
 
 
@@ -114,6 +126,18 @@ class _Flags:
                 raise AttributeError('Unknown flag %r' % k)
             setattr(self, k, v)
         return self
+
+    @contextlib.contextmanager
+    def override(self, **kw):
+        """Flag values for the duration of a `with` block: a second model of another configuration (the distillation teacher) is
+        built and called under it, while everything else keeps reading the process's flags."""
+        old = {k: getattr(self, k) for k in kw}
+        self.update(**kw)
+        try:
+            yield self
+        finally:
+            for k, v in old.items():
+                setattr(self, k, v)
 
     def parse(self, argv):
         """absl-style parsing: --name=value, --name value, --flag / --noflag for booleans."""

@@ -127,6 +127,9 @@ class LinearLayer(Layer):  # tf2/model.py:119-154
         """Compute copies of the fp32 master weight in the dtype of the layer's input."""
         if self._version == RT.weights_version and getattr(self, '_dtype', None) == dtype:
             return
+        if not self.trainable and self._version >= 0 and getattr(self, '_frozen_key', None) == (RT.frozen_version, dtype):
+            return                  # frozen (the distillation teacher): the optimizer step did not change this weight
+        self._frozen_key = None if self.trainable else (RT.frozen_version, dtype)
         w4 = self.kernel.value.view(1, 1, self.cin, self.nout)
         if self.npad == self.nout:
             self.w_t = ops.prep_weights(w4, 0, dtype)
@@ -384,6 +387,12 @@ class Model(Layer):
             sel = FLAGS.ft_proj_selector if FLAGS.proj_head_mode != 'none' else 0
             self.supervised_head.linear_layer.build(feats[sel])
 
+    def release(self):
+        super().release()
+        rm = self.resnet_model
+        rm.endpoints.clear()
+        rm._final = rm._pool = None
+
     _wd_grad_scale = 1.0   # set to 1/num_replicas by the step (loss / R, tf2/run.py:617)
 
     def allocate_flat_grads(self):
@@ -401,3 +410,60 @@ class Model(Layer):
         self._flat_order = vs
         self._flat_offsets = offs
         return flat
+
+
+def teacher_flag_values():
+    """The flag values the distillation teacher is built and called under: its own architecture flags (--teacher_*, each defaulting
+    to the student's), the structure of a fine-tuned model, everything else shared with the student."""
+    def pick(name):
+        v = getattr(FLAGS, 'teacher_' + name)
+        return getattr(FLAGS, name) if v is None else v
+    return dict(train_mode='finetune', fine_tune_after_block=-1, resnet_depth=pick('resnet_depth'),
+                width_multiplier=pick('width_multiplier'), sk_ratio=pick('sk_ratio'), ft_proj_selector=pick('ft_proj_selector'))
+
+
+class Teacher:
+    """The frozen fine-tuned network of the self-training stage (tf2/colabs/distillation_self_training.ipynb:908-919): a second Model
+    in the process, built under `teacher_flag_values()` and under the variable names it has when built alone (RT.fresh_names), so that
+    its own checkpoint restores by name and the student's names and initial values are those of a run without a teacher.  The whole
+    model is `trainable = False`; a call is an inference forward (moving BatchNorm statistics) that keeps no activations.
+
+    Construct it BEFORE the student: its one build-forward runs here.  `checkpoint`: restored strictly -- a teacher variable that the
+    file lacks or holds with another shape raises, the supervised head included."""
+
+    def __init__(self, num_classes, checkpoint=None, image_size=None):
+        self.flag_values = teacher_flag_values()
+        size = image_size or FLAGS.image_size
+        with FLAGS.override(**self.flag_values), RT.fresh_names():
+            self.model = Model(num_classes)
+            self.model.trainable = False
+            for l in _all_layers(self.model):
+                l.inference_only = True
+            # variables exist only after the first forward pass (lazy build)
+            self.model(torch.zeros(2, size, size, 3, device=RT.device), training=False)
+            self.model.release()
+        if checkpoint:
+            self.restore(checkpoint)
+
+    def restore(self, path):
+        from .checkpoint import Checkpoint
+        status = Checkpoint(model=self.model).restore(path, model_only=True)
+        if status.missing_in_checkpoint or status.shape_mismatch:
+            raise ValueError('teacher checkpoint %s does not hold the teacher (flags %s): missing variables %s, variables of another '
+                             'shape (name, in the file, in the model) %s'
+                             % (path, self.flag_values, status.missing_in_checkpoint[:8], status.shape_mismatch[:8]))
+        return status
+
+    def __call__(self, features):
+        """features [b, H, W, 3] -> SupLogits of the frozen teacher."""
+        with FLAGS.override(**self.flag_values):
+            _, logits = self.model(features, training=False)
+        self.model.release()
+        return logits
+
+
+def _all_layers(layer):
+    out = [layer]
+    for l in layer.sublayers():
+        out.extend(_all_layers(l))
+    return out

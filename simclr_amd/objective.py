@@ -194,3 +194,21 @@ def add_supervised_loss(labels, logits):
     loss = _Loss(out[0:1], lambda grad_scale=None: dlogits)
     loss.acc = out[1:2]
     return loss
+
+
+def add_kd_loss(student_logits, teacher_logits, temperature):
+    """Distillation loss of the self-training stage (tf2/colabs/distillation_self_training.ipynb:803-808):
+    temperature^2 * mean over the local batch of CE(softmax(teacher / temperature), student / temperature).
+
+    student_logits, teacher_logits: model.SupLogits of the same rows.  Returns a loss scalar with .backward() -> dlogits (gradient
+    wrt the student's logits, in their layout) and `.acc`, the share of rows whose student and teacher arg-maxima agree."""
+    if student_logits.num_classes != teacher_logits.num_classes:
+        raise ValueError('add_kd_loss: the student has %d classes, the teacher %d'
+                         % (student_logits.num_classes, teacher_logits.num_classes))
+    out = ops.step_scalars(2, student_logits.z.device)
+    gscale = 1.0 / num_replicas(RT.strategy)                    # loss / R, tf2/run.py:617
+    dlogits = ops.kd_softmax_xent(student_logits.z, student_logits.bias, teacher_logits.z, teacher_logits.bias,
+                                  student_logits.num_classes, temperature, gscale, out)
+    loss = _Loss(out[0:1], lambda grad_scale=None: dlogits)
+    loss.acc = out[1:2]
+    return loss

@@ -894,6 +894,17 @@ def bias_softmax_xent(z, bias, labels, nclass, gscale, out):
     return dlogits
 
 
+def kd_softmax_xent(zs, bias_s, zt, bias_t, nclass, temperature, gscale, out):
+    """Distillation loss of student rows zs [rows, cpad_s] against teacher rows zt [rows, cpad_t] (simclr_kd_softmax_xent): adds the
+    loss into out[0] and the teacher agreement into out[1], returns dlogits in the student's layout.  Either bias may be None."""
+    rows, cpad_s = zs.shape
+    assert zt.dim() == 2 and zt.shape[0] == rows, (tuple(zs.shape), tuple(zt.shape))
+    dlogits = torch.empty_like(zs)
+    lib().kd_softmax_xent(_p(zs), _p(bias_s), _p(zt), _p(bias_t), rows, nclass, cpad_s, zt.shape[1], float(temperature),
+                          float(gscale), _p(dlogits), _p(out), dt(zs), dt(zt), _s())
+    return dlogits
+
+
 def colsum(x, cvalid, out, accumulate=False):
     rows, C = x.shape
     lib().colsum(_p(x), rows, C, cvalid, _p(out), int(accumulate), dt(x), _s())

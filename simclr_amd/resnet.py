@@ -20,6 +20,7 @@ shortcut :330-338/:400-408) are built; channel counts that are not a multiple of
 dim, 32*w stem) are zero-padded internally.  Not built (fail loudly): SE (se_ratio>0, :280-311),
 DropBlock (:81-157, unreachable in the reference too), channels_first.
 """
+import contextlib
 import math
 import weakref
 
@@ -73,9 +74,25 @@ class _Runtime:
         """The optimizer updated the TRAINABLE weights: frozen layers (fine_tune_after_block) keep their compute copies."""
         self._weights_version += 1
 
-    def frozen_key(self):
-        """What a frozen layer's compute copies depend on besides its (unchanging) master weight."""
-        return (self.frozen_version, self.dtype) + tuple(ops._TERMS)
+    def frozen_key(self, layer=None):
+        """What a frozen layer's compute copies depend on besides its (unchanging) master weight.  A layer of an inference-only
+        model (the distillation teacher) never reads the pre-split copies that belong to an arithmetic mode, and it shares the
+        process with a student whose steps select another mode: its key leaves the mode out, so neither model's refresh rewrites
+        the teacher's copies."""
+        key = (self.frozen_version, self.dtype)
+        return key if getattr(layer, 'inference_only', False) else key + tuple(ops._TERMS)
+
+    @contextlib.contextmanager
+    def fresh_names(self):
+        """Build a second model under the names (and initial values) it would have alone in the process: empty name counters and
+        scope inside the block; the counters, the scope and the seed of the surrounding build are restored afterwards.  Nothing
+        else of the runtime is touched -- the registered convolutions of every model stay."""
+        saved = (self.counters, self.scope, self.seed)
+        self.counters, self.scope = {}, []
+        try:
+            yield self
+        finally:
+            self.counters, self.scope, self.seed = saved
 
     def const(self, C, value):
         """Cached constant fp32 vector on the device (means 0 / rstd 1 for plain column sums)."""
@@ -92,9 +109,8 @@ class _Runtime:
         self.convs = [r for r in self.convs if r() is not None]      # weak references: models may have been dropped
         convs = [r() for r in self.convs]
         convs = [c for c in convs if c is not None and c.kernel is not None]
-        fk = self.frozen_key()
         # frozen layers' copies are made once per (restore, storage mode, arithmetic mode), not after every optimizer step
-        convs = [c for c in convs if c.trainable or getattr(c, '_frozen_key', None) != fk]
+        convs = [c for c in convs if c.trainable or getattr(c, '_frozen_key', None) != self.frozen_key(c)]
         entries = [(c.kernel.value, c.cin_p, c.cout_p) for c in convs]
         if self._conv_batch is None or not self._conv_batch.matches(entries, self.dtype):
             self._conv_batch = ops.WeightPairBatch(entries, self.dtype)
@@ -102,7 +118,7 @@ class _Runtime:
             c.w_t, c.w_d = w_t, w_d
             c._version = self.weights_version
             c._dtype = self.dtype
-            c._frozen_key = None if c.trainable else fk
+            c._frozen_key = None if c.trainable else self.frozen_key(c)
 
     def wgrad_stream(self):
         """Side stream for the weight-gradient kernels (SIMCLR_WGRAD_STREAM=1), else None."""
@@ -511,12 +527,12 @@ class Conv2dFixedPadding(Layer):  # tf2/resnet.py:183-208
     def _refresh(self, stem_geo=None):
         if self._version == RT.weights_version and getattr(self, '_dtype', None) == RT.dtype:
             return
-        if not self.trainable and self._version >= 0 and getattr(self, '_frozen_key', None) == RT.frozen_key():
+        if not self.trainable and self._version >= 0 and getattr(self, '_frozen_key', None) == RT.frozen_key(self):
             return                  # frozen (fine_tune_after_block): the optimizer step did not change this weight
         w = self.kernel.value
         if stem_geo is not None:
             self.w_s = ops.prep_weights(w, 2, RT.dtype, stem_geo['KHP'], stem_geo['KWP'], cout_p=self.cout_p)
-            self._frozen_key = None if self.trainable else RT.frozen_key()
+            self._frozen_key = None if self.trainable else RT.frozen_key(self)
         else:
             # first refresh of a layer (lazy build during the first forward) or a layer outside the registry (built under
             # an earlier RT.reset()): its own launch; afterwards every version bump refreshes ALL layers with one launch

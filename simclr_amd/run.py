@@ -31,7 +31,9 @@ def build_metrics():
     names = ['train/weight_decay', 'train/total_loss']
     if FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
-    if FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
+    if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
+        names += ['train/distill_loss', 'train/distill_agreement']       # distillation: the teacher replaces the labels
+    elif FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
         names += ['train/supervised_loss', 'train/supervised_acc']
     for n in names:
         m[n] = metrics.Mean(n)
@@ -98,21 +100,50 @@ class GradSync:
         self.works = []
 
 
-def make_single_step(model, optimizer, strategy, all_metrics=None):
-    """Returns single_step(features, labels) -- tf2/run.py:557-622."""
-    m = all_metrics if all_metrics is not None else build_metrics()
+def check_distillation_flags():
+    """A teacher needs the fine-tuning path: raise before any device work otherwise.  --mode=eval ignores the teacher flags."""
+    if FLAGS.teacher_checkpoint and FLAGS.mode != 'eval':
+        if FLAGS.train_mode != 'finetune':
+            raise ValueError('--teacher_checkpoint distils into the fine-tuning path: it requires --train_mode=finetune (got %r)'
+                             % FLAGS.train_mode)
+        if not FLAGS.distill_temperature > 0:
+            raise ValueError('--distill_temperature must be positive (got %r)' % FLAGS.distill_temperature)
+        return True
+    return False
+
+
+def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None):
+    """Returns single_step(features, labels) -- tf2/run.py:557-622.
+    teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
+    loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
+    tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
+    if teacher is not None and FLAGS.train_mode != 'finetune':
+        raise ValueError('a distillation teacher requires train_mode=finetune (got %r)' % FLAGS.train_mode)
+    if all_metrics is not None:
+        m = all_metrics
+    elif teacher is not None:
+        m = {n: metrics.Mean(n) for n in ('train/weight_decay', 'train/total_loss', 'train/distill_loss', 'train/distill_agreement')}
+    else:
+        m = build_metrics()
     state = {'sync': None}
     RT.strategy = strategy
 
     def single_step(features, labels):
         ops.begin_step(features.device)
+        teacher_logits = None
+        if teacher is not None:
+            # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
+            # training arithmetic again, for the rest of the step
+            teacher_logits = teacher(features)
         projection_head_outputs, supervised_head_outputs = model(features, training=True)   # :577-578
         R = num_replicas(strategy)
         con_loss = sup_loss = None
         sup_box = {}
 
         def supervised_part():
-            if supervised_head_outputs is not None:
+            if teacher_logits is not None:
+                sup_box['loss'] = obj_lib.add_kd_loss(supervised_head_outputs, teacher_logits, FLAGS.distill_temperature)
+            elif supervised_head_outputs is not None:
                 l = labels['labels'] if isinstance(labels, dict) else labels
                 # pretraining: labels are reused for both views (tf2/run.py:599-600: l = concat([l, l], 0)); finetune: one view
                 sup_box['loss'] = obj_lib.add_supervised_loss(labels=l, logits=supervised_head_outputs)   # :601
@@ -179,9 +210,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
             vals['train/contrast_entropy'] = logits_con.contrast_entropy.reshape(-1)[:1]
+        sup_names = ('train/distill_loss', 'train/distill_agreement') if teacher is not None else \
+                    ('train/supervised_loss', 'train/supervised_acc')
         if sup_loss is not None:
-            vals['train/supervised_loss'] = sup_loss.value.reshape(-1)[:1]
-            vals['train/supervised_acc'] = sup_loss.acc.reshape(-1)[:1]
+            vals[sup_names[0]] = sup_loss.value.reshape(-1)[:1]
+            vals[sup_names[1]] = sup_loss.acc.reshape(-1)[:1]
         names = [nm for nm in order if nm in vals]
         # one launch: bank[index(name)] += value(name); the metrics absent this step keep their sums
         srcs = [vals.get(nm, state['zero']) for nm in order]
@@ -198,10 +231,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None):
             con_loss.value = at['train/contrast_loss']
             if 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
-        if sup_loss is not None and 'train/supervised_loss' in at:
-            sup_loss.value = at['train/supervised_loss']
-            if 'train/supervised_acc' in at:
-                sup_loss.acc = at['train/supervised_acc']
+        if sup_loss is not None and sup_names[0] in at:
+            sup_loss.value = at[sup_names[0]]
+            if sup_names[1] in at:
+                sup_loss.acc = at[sup_names[1]]
         if torch.is_tensor(weight_decay) and 'train/weight_decay' in at:
             weight_decay = at['train/weight_decay']
         return dict(con_loss=con_loss, sup_loss=sup_loss, weight_decay=weight_decay, total_loss=total,
@@ -352,6 +385,7 @@ def main(argv):
     import math
     FLAGS.parse(argv)
     logging.basicConfig(level=logging.INFO)
+    distill = check_distillation_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
         # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter
@@ -383,6 +417,9 @@ def main(argv):
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
+    # the teacher is built, run once and restored BEFORE the student exists: the student's names and initial values are those of a
+    # run without a teacher
+    teacher = model_lib.Teacher(num_classes, FLAGS.teacher_checkpoint) if distill else None
     model = model_lib.Model(num_classes)
     rep = 0 if strategy is None else strategy.rank
 
@@ -397,7 +434,7 @@ def main(argv):
 
     learning_rate = model_lib.WarmUpAndCosineDecay(FLAGS.learning_rate, num_train_examples)
     optimizer = model_lib.build_optimizer(learning_rate)
-    step_fn = make_single_step(model, optimizer, strategy)
+    step_fn = make_single_step(model, optimizer, strategy, teacher=teacher)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
     if builder is None:
