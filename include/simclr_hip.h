@@ -99,6 +99,44 @@ int simclr_ntxent_wide_bwd(const float* z_local, const float* z_all, int n, int 
 int simclr_ntxent_wide_logits_ab(const float* z_local, const float* z_all, int n, int N, int D, int terms,
                                  float temperature, float* logits_ab, simclr_stream_t stream);
 
+/* ---- generalized contrastive loss (csrc/gcl.hip): colabs/intriguing_properties/generalized_contrastive_loss.ipynb ----
+ * loss = loss_scaling * (align + lambda_weight * dist_match), the notebook's `generalized_contrastive_loss` cell.
+ * z_local [2n, D] = this replica's two views stacked, z_all [2N, D] = every replica's view-1 rows, then every replica's view-2 rows
+ * (the NT-Xent layout), N = R*n.  D in {64, 128, 256}, any n >= 1.  No atomics: bitwise run-to-run deterministic. */
+size_t simclr_gcl_lse_workspace_bytes(int n, int N, int D);    /* 0 for a shape the kernels refuse */
+/* dist='logsumexp' (the cell's `get_logsumexp_loss` + the alignment term): out[0] = loss, out[1] = align = mean((z1 - z2)^2) / 2,
+ * out[2] = dist_match = mean_i(logsumexp_j(z_i.z_j / T) - log D) over the 2n local rows and ALL 2N columns (self column included,
+ * nothing masked; the constant is the log of the hidden width, as the cell takes shape(states)[1]).  row_stats [2n] is kept for the
+ * backward; the workspace holds one fwd/bwd pair. */
+int simclr_gcl_lse_fwd(const float* z_local, const float* z_all, int n, int N, int D, float temperature, float lambda_weight,
+                       float loss_scaling, float* out, float* row_stats, void* workspace, simclr_stream_t stream);
+/* tape.gradient of that cell: dz_local [2n, D] = query-side gradient + the alignment gradient, dz_all [2N, D] = key-side gradient
+ * (to be reduce-scattered like simclr_ntxent_bwd's), both times grad_scale.  rank = replica id (where the local rows sit in z_all).
+ * skip_self != 0 leaves out the term of every local row's OWN column, 2 coeff softmax_ii z_i in total: for l2-normalised rows it is
+ * radial, the normalisation backward (simclr_l2norm_bwd) annihilates it, and next to it (softmax_ii ~ 1 at small temperatures) the
+ * tangential gradient would lose its low bits in fp32.  Pass 0 when the rows are not normalised: there the term is part of the gradient. */
+int simclr_gcl_lse_bwd(const float* z_local, const float* z_all, int n, int N, int D, float temperature, float lambda_weight,
+                       float loss_scaling, int rank, int skip_self, const float* row_stats, float grad_scale, float* dz_local,
+                       float* dz_all, void* workspace, simclr_stream_t stream);
+/* dist='normal' / 'uniform' (the cell's `get_swd_loss`, its O(M^2) one-hot `sort` replaced by a sort): Pt, Qt [D, M] fp32 = the
+ * projected hiddens / prior, one contiguous row per projected dimension, M <= 8192.  Every row of both is sorted ascending (equal keys of
+ * Pt by row index: numpy.argsort(kind='stable')); dP[perm[k], c] = coeff * (P_sorted[c, k] - Q_sorted[c, k]) into a [M, D] row-major
+ * tensor, col_loss[c] = sum_k (Q_sorted - P_sorted)^2, perm [D, M] int32 (may be null) = the sorting permutation of Pt's rows. */
+int simclr_swd_sort_match(const float* Pt, const float* Qt, int M, int D, float coeff, float* dP, float* col_loss, int* perm,
+                          simclr_stream_t stream);
+/* The rest of `get_swd_loss` + the cell's last lines: out[0] = loss, out[1] = align, out[2] = dist_match = sum_c col_loss[c] / (D M)
+ * (reduce_mean over [D, M]), summed in a fixed order. */
+int simclr_gcl_swd_out(const float* col_loss, const float* z_local, int n, int M, int D, float lambda_weight, float loss_scaling, float* out,
+                       simclr_stream_t stream);
+/* tape.gradient of the SWD cell wrt the local rows: g_all [2N, D] = d dist_match / d z_all (every replica computes the identical
+ * global term, so no collective follows); dz_local [2n, D] = lambda_weight * loss_scaling * grad_scale * R * (own rows of g_all) + the
+ * alignment gradient +-(z1 - z2) / (n D) * loss_scaling * grad_scale. */
+int simclr_gcl_swd_bwd(const float* g_all, const float* z_local, int n, int N, int D, int rank, float lambda_weight, float loss_scaling,
+                       float grad_scale, float* dz_local, simclr_stream_t stream);
+/* C [M, N] = A [M, K] B [N, K]^T, fp32 row-major, any M and N, K a multiple of 16, exact f32 MFMA: the cell's two
+ * matmul(., rand_w) projections and their transposes (simclr_small_gemm_nt_f32 needs M and N multiples of 16). */
+int simclr_gcl_gemm_nt(const float* A, const float* B, float* C, int M, int N, int K, simclr_stream_t stream);
+
 /* ---- LARS: tf2/lars_optimizer.py:83-137 (_resource_apply_dense), all tensors in 2 launches ---- */
 /* table: device int64[5*T] = {w ptrs | g ptrs | v ptrs | numel | flags(bit0 use_weight_decay :139-148,
  * bit1 do_layer_adaptation :150-157)}; chunks: device int64[2*num_chunks] = (tensor id, element

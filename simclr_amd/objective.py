@@ -7,6 +7,9 @@ l2-normalise -> RCCL all-gather of the hidden block (replacing the scatter + all
 matrix cores.  The [n,N] logits and [n,2N] one-hot labels the reference returns are never
 materialised on the hot path: `logits_con` / `labels_con` are lazy handles that also carry the
 fused contrast accuracy / entropy (tf2/metrics.py:28-35); call `.dense()` for real tensors.
+
+`generalized_contrastive_loss` is the loss of colabs/intriguing_properties/generalized_contrastive_loss.ipynb (alignment + a
+distribution-matching term: decoupled NT-Xent, or sliced Wasserstein against a normal / uniform prior) on the kernels of csrc/gcl.hip.
 """
 import torch
 
@@ -159,6 +162,144 @@ def add_contrastive_loss(hidden, hidden_norm=True, temperature=1.0, strategy=Non
     labels_con = LazyLabels(n, n * R, rank, z.device)
     loss.normalized = z
     return loss, logits_con, labels_con
+
+
+GCL_DISTS = ('logsumexp', 'normal', 'uniform')
+_GCL_STEP = [0]
+
+
+def set_gcl_step(step):
+    """The global step the next generalized_contrastive_loss call draws its projection basis and prior for (run.single_step sets it
+    from optimizer.iterations, which a checkpoint restores)."""
+    _GCL_STEP[0] = int(step)
+
+
+def _gcl_seed(seed, step, stream):
+    return (int(seed) * 0x9E3779B97F4A7C15 + int(step) * 4 + stream) & 0x7FFFFFFFFFFFFFFF
+
+
+def gcl_draws(D, M, dist, seed, step, device):
+    """(rand_w [D, D], prior [M, D]) of one step: a function of (seed, step) only -- identical on every replica, the same after a resume.
+    rand_w: a random orthogonal matrix with torch.nn.init.orthogonal_'s construction (QR of a normal matrix, columns signed by
+    diag(R)), made on the host and copied asynchronously; prior: N(0, 1) ('normal') or U(-1, 1) ('uniform') from a device generator.
+    Nothing here waits for the device."""
+    g = torch.Generator(device='cpu').manual_seed(_gcl_seed(seed, step, 0))
+    q, r = torch.linalg.qr(torch.randn(D, D, generator=g))
+    q = q * torch.sign(torch.diagonal(r)).unsqueeze(0)
+    if torch.device(device).type == 'cuda':
+        q = q.contiguous().pin_memory()
+    rand_w = q.to(device, non_blocking=True)
+    gd = torch.Generator(device=device).manual_seed(_gcl_seed(seed, step, 1))
+    if dist == 'normal':
+        prior = torch.randn(M, D, generator=gd, device=device, dtype=torch.float32)
+    else:
+        prior = torch.rand(M, D, generator=gd, device=device, dtype=torch.float32).mul_(2.0).sub_(1.0)
+    return rand_w, prior
+
+
+def generalized_contrastive_loss(hidden1, hidden2, lambda_weight=1.0, temperature=1.0, dist='normal', hidden_norm=True, loss_scaling=1.0,
+                                 strategy=None, overlap=None, rand_w=None, prior=None):
+    """Generalized contrastive loss (colabs/intriguing_properties/generalized_contrastive_loss.ipynb):
+    loss_scaling * (alignment + lambda_weight * distribution matching).
+
+    Args:
+      hidden1, hidden2: float32 device tensors [n, D], the two views of the local batch; D in {64, 128, 256}.
+      lambda_weight: weight of the distribution-matching term.
+      temperature: temperature of the 'logsumexp' term (unused by the SWD priors).
+      dist: 'logsumexp' (decoupled NT-Xent over the global batch), 'normal' or 'uniform' (sliced Wasserstein distance between the
+        global batch and an N(0, 1) / U(-1, 1) prior, at most 8192 global rows).
+      hidden_norm: l2-normalise the hiddens (and the SWD prior) first.
+      loss_scaling: factor on the whole loss.
+      strategy, overlap: as add_contrastive_loss (the hidden block is gathered asynchronously; overlap() runs meanwhile).
+      rand_w [D, D], prior [2N, D]: the SWD projection basis and prior samples; drawn by gcl_draws(FLAGS.gcl_seed, step) when None.
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> gradient wrt [hidden1; hidden2], [2n, D]) and the device
+      scalars .align and .dist_match; SWD losses also carry .perm ([D, 2N] int32, the sorting permutation of every projected dimension).
+    """
+    if dist not in GCL_DISTS:
+        raise ValueError('Unknown prior {}'.format(dist))
+    assert hidden1.dtype == torch.float32 and hidden1.dim() == 2 and hidden1.shape == hidden2.shape
+    n, D = hidden1.shape
+    ops._gcl_check_dim(D)
+    hidden = torch.cat([hidden1, hidden2], 0)
+    return generalized_loss_of_block(hidden, lambda_weight, temperature, dist, hidden_norm, loss_scaling, strategy, overlap, rand_w, prior)
+
+
+def generalized_loss_of_block(hidden, lambda_weight=1.0, temperature=1.0, dist='normal', hidden_norm=True, loss_scaling=1.0, strategy=None,
+                              overlap=None, rand_w=None, prior=None):
+    """generalized_contrastive_loss on the stacked block [hidden1; hidden2] (what the projection head returns)."""
+    if dist not in GCL_DISTS:
+        raise ValueError('Unknown prior {}'.format(dist))
+    hidden = hidden.contiguous()
+    D = hidden.shape[1]
+    ops._gcl_check_dim(D)
+    if hidden_norm:
+        z, inv = ops.l2norm_fwd(hidden)
+    else:
+        z, inv = hidden, None
+    n = z.shape[0] // 2
+    R, rank = num_replicas(strategy), replica_id(strategy)
+    M = 2 * n * R
+    if dist != 'logsumexp' and M > ops.SWD_MAX_ROWS:
+        raise ValueError('the sliced-Wasserstein sort holds at most %d global rows (2 x global batch) per column, got %d' % (ops.SWD_MAX_ROWS, M))
+    pending = gather_hidden(z, strategy, async_op=True)
+    if dist != 'logsumexp' and (rand_w is None or prior is None):
+        w_d, p_d = gcl_draws(D, M, dist, getattr(FLAGS, 'gcl_seed', 0), _GCL_STEP[0], z.device)
+        rand_w = w_d if rand_w is None else rand_w
+        prior = p_d if prior is None else prior
+    if overlap is not None:
+        overlap()
+    z_all = pending()
+    state = {}
+
+    def finish_local(dz_local):
+        if hidden_norm:
+            return ops.l2norm_bwd(z, inv, dz_local)
+        return dz_local
+
+    if dist == 'logsumexp':
+        out, row_stats, ws = ops.gcl_lse_fwd(z, z_all, temperature, lambda_weight, loss_scaling)
+
+        def backward_start(grad_scale=1.0):
+            # normalised rows: the self column's radial term is left to the normalisation backward, which removes it exactly
+            dz_local, dz_all = ops.gcl_lse_bwd(z, z_all, temperature, row_stats, grad_scale, ws, lambda_weight, loss_scaling,
+                                               rank=rank, skip_self=bool(hidden_norm))
+            state['dz_local'] = dz_local
+            state['slot'] = scatter_hidden_grad(dz_all, strategy, async_op=True)   # transpose of the concat, as NT-Xent's
+
+        def backward_finish():
+            dz_local, dz_slot = state.pop('dz_local'), state.pop('slot')()
+            ops.axpy_f32(1.0, dz_slot, dz_local)
+            return finish_local(dz_local)
+        perm = None
+    else:
+        assert tuple(rand_w.shape) == (D, D) and tuple(prior.shape) == (M, D), 'rand_w must be [D, D] and prior [2N, D]'
+        w = rand_w.contiguous()
+        wt = w.t().contiguous()
+        q = ops.l2norm_fwd(prior.contiguous())[0] if hidden_norm else prior.contiguous()
+        pt = ops.gcl_gemm_nt(wt, z_all)                       # [D, M] = (z_all W)^T
+        qt = ops.gcl_gemm_nt(wt, q)
+        # d mean_{D x M}((Q_sorted - P_sorted)^2) / d P_sorted = 2 (P_sorted - Q_sorted) / (D M)
+        dp, col_loss, perm = ops.swd_sort_match(pt, qt, 2.0 / (D * M), want_perm=True)
+        out = ops.gcl_swd_out(col_loss, z, M, lambda_weight, loss_scaling)
+
+        def backward_start(grad_scale=1.0):
+            g_all = ops.gcl_gemm_nt(dp, w)                    # [M, D] = dP W^T
+            # every replica holds the identical global term: its own rows' gradient needs no collective
+            state['dz_local'] = ops.gcl_swd_bwd(g_all, z, rank, grad_scale, lambda_weight, loss_scaling)
+
+        def backward_finish():
+            return finish_local(state.pop('dz_local'))
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.align, loss.dist_match = out[1:2], out[2:3]
+    loss.perm = perm
+    loss.normalized = z
+    return loss
 
 
 _CLASS_ID_CACHE = {}

@@ -248,6 +248,95 @@ def ntxent_wide_logits_ab(z_local, z_all, temperature):
     return out
 
 
+# ---------------------------------------------------------------- generalized contrastive loss (csrc/gcl.hip)
+GCL_DIMS = (64, 128, 256)           # hidden widths the generalized-loss kernels are instantiated for (no padding: log D is in the loss)
+SWD_MAX_ROWS = 8192                 # global rows (2N) a column sort holds in LDS
+
+
+def _gcl_check_dim(D):
+    if D not in GCL_DIMS:
+        raise ValueError('the generalized contrastive loss supports hidden widths %s (got %d)' % ('/'.join(map(str, GCL_DIMS)), D))
+
+
+def gcl_lse_workspace(n, N, D, device):
+    _gcl_check_dim(D)
+    nbytes = lib().gcl_lse_workspace_bytes(n, N, D)
+    assert nbytes > 0, 'gcl_lse_workspace: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+
+
+def gcl_lse_fwd(z_local, z_all, temperature, lambda_weight=1.0, loss_scaling=1.0, ws=None):
+    """Decoupled NT-Xent forward.  Returns out = [loss, align, dist_match] (device), row_stats [2n], the workspace."""
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    assert z_local.dtype == torch.float32 and z_all.dtype == torch.float32 and z_all.shape[1] == D
+    _gcl_check_dim(D)
+    if ws is None:
+        ws = gcl_lse_workspace(n, N, D, z_local.device)
+    out = step_scalars(4, z_local.device)
+    row_stats = torch.empty(2 * n, device=z_local.device, dtype=torch.float32)
+    _launch('gcl_lse_fwd', 8.0 * n * N * D, 4.0 * (2 * n + 2 * N) * D,
+            lambda: lib().gcl_lse_fwd(_p(z_local), _p(z_all), n, N, D, float(temperature), float(lambda_weight), float(loss_scaling),
+                                      _p(out), _p(row_stats), _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def gcl_lse_bwd(z_local, z_all, temperature, row_stats, grad_scale, ws, lambda_weight=1.0, loss_scaling=1.0, rank=0, skip_self=False):
+    """skip_self: leave out the (radial) term of every row's own column -- for l2-normalised rows, whose normalisation backward removes
+    it anyway (include/simclr_hip.h)."""
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    _gcl_check_dim(D)
+    dz_local = torch.empty_like(z_local)
+    dz_all = torch.empty_like(z_all)
+    _launch('gcl_lse_bwd', 16.0 * n * N * D, 2.0 * (2 * n + 2 * N) * D * 4,
+            lambda: lib().gcl_lse_bwd(_p(z_local), _p(z_all), n, N, D, float(temperature), float(lambda_weight), float(loss_scaling),
+                                      int(rank), int(bool(skip_self)), _p(row_stats), float(grad_scale), _p(dz_local), _p(dz_all), _p(ws), _s()))
+    return dz_local, dz_all
+
+
+def gcl_gemm_nt(A, B):
+    """A [M, K] fp32, B [N, K] fp32 -> A B^T [M, N] fp32 (exact f32 MFMA), any M and N, K a multiple of 16."""
+    M, K = A.shape
+    N = B.shape[0]
+    assert A.dtype == torch.float32 and B.dtype == torch.float32 and B.shape[1] == K
+    C = torch.empty(M, N, device=A.device, dtype=torch.float32)
+    _launch('gcl_gemm_nt', 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N), lambda: lib().gcl_gemm_nt(_p(A), _p(B), _p(C), M, N, K, _s()))
+    return C
+
+
+def swd_sort_match(Pt, Qt, coeff, want_perm=False):
+    """Pt, Qt [D, M] fp32 (one row per projected dimension).  Returns dP [M, D] (= coeff * (P_sorted - Q_sorted) scattered back to row
+    order), col_loss [D] and, on request, perm [D, M] int32 (the stable sorting permutation of every row of Pt)."""
+    D, M = Pt.shape
+    assert Pt.dtype == torch.float32 and Qt.dtype == torch.float32 and tuple(Qt.shape) == (D, M)
+    if M > SWD_MAX_ROWS:
+        raise ValueError('the sliced-Wasserstein sort holds at most %d global rows (2 x global batch) per column, got %d' % (SWD_MAX_ROWS, M))
+    dP = torch.empty(M, D, device=Pt.device, dtype=torch.float32)
+    col_loss = torch.empty(D, device=Pt.device, dtype=torch.float32)
+    perm = torch.empty(D, M, device=Pt.device, dtype=torch.int32) if want_perm else None
+    logm = max(1, (M - 1).bit_length())
+    _launch('swd_sort_match', 3.0 * D * M * logm * (logm + 1), 4.0 * 3 * D * M,
+            lambda: lib().swd_sort_match(_p(Pt), _p(Qt), M, D, float(coeff), _p(dP), _p(col_loss), _p(perm), _s()))
+    return dP, col_loss, perm
+
+
+def gcl_swd_out(col_loss, z_local, M, lambda_weight=1.0, loss_scaling=1.0):
+    """out = [loss, align, dist_match] of an SWD loss from the column losses of swd_sort_match."""
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    out = step_scalars(4, z_local.device)
+    lib().gcl_swd_out(_p(col_loss), _p(z_local), n, M, D, float(lambda_weight), float(loss_scaling), _p(out), _s())
+    return out
+
+
+def gcl_swd_bwd(g_all, z_local, rank, grad_scale, lambda_weight=1.0, loss_scaling=1.0):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = g_all.shape[0] // 2
+    dz_local = torch.empty_like(z_local)
+    lib().gcl_swd_bwd(_p(g_all), _p(z_local), n, N, D, rank, float(lambda_weight), float(loss_scaling), float(grad_scale), _p(dz_local), _s())
+    return dz_local
+
+
 # ---------------------------------------------------------------- conv / dense
 def prep_weights(w_hwio, mode, dtype, khp=0, kwp=0, out=None, cin_p=0, cout_p=0):
     """fp32 HWIO master -> compute copy.  cin_p / cout_p: zero-padded channel dims of the copy."""

@@ -25,11 +25,36 @@ from .flags import FLAGS
 from .resnet import RT, join_wgrad_stream
 
 
+def generalized_loss_on():
+    """--contrastive_loss=generalized replaces NT-Xent in the pretraining step; train_mode=finetune has no contrastive loss and ignores it."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'generalized' and FLAGS.train_mode == 'pretrain'
+
+
+def check_contrastive_loss_flags():
+    """Raise before any device work when the pretraining loss flags name something the kernels do not cover."""
+    if FLAGS.contrastive_loss not in ('ntxent', 'generalized'):
+        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' (got %r)" % FLAGS.contrastive_loss)
+    if not generalized_loss_on() or FLAGS.mode == 'eval':
+        return False
+    if FLAGS.gcl_dist not in obj_lib.GCL_DISTS:
+        raise ValueError('Unknown prior {}'.format(FLAGS.gcl_dist))
+    if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.GCL_DIMS:
+        raise ValueError('--contrastive_loss=generalized needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
+                         'the generalized-loss kernels are instantiated for those widths only'
+                         % ('/'.join(map(str, ops.GCL_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+    if FLAGS.gcl_dist != 'logsumexp' and 2 * FLAGS.train_batch_size > ops.SWD_MAX_ROWS:
+        raise ValueError('--gcl_dist=%s sorts the 2 x train_batch_size global rows of every projected dimension in LDS: '
+                         'train_batch_size <= %d (got %d)' % (FLAGS.gcl_dist, ops.SWD_MAX_ROWS // 2, FLAGS.train_batch_size))
+    return True
+
+
 def build_metrics():
     """The metric set of tf2/run.py:534-549."""
     m = {}
     names = ['train/weight_decay', 'train/total_loss']
-    if FLAGS.train_mode == 'pretrain':
+    if FLAGS.train_mode == 'pretrain' and generalized_loss_on():
+        names += ['train/contrast_loss', 'train/align_loss', 'train/dist_loss']   # the generalized loss has no logits to score
+    elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
         names += ['train/distill_loss', 'train/distill_agreement']       # distillation: the teacher replaces the labels
@@ -127,6 +152,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
         m = build_metrics()
     state = {'sync': None}
     RT.strategy = strategy
+    generalized = check_contrastive_loss_flags()
 
     def single_step(features, labels):
         ops.begin_step(features.device)
@@ -150,9 +176,17 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
         if projection_head_outputs is not None:
             outputs = projection_head_outputs
             # collective A (all-gather of the hidden block) is in flight while the supervised loss is computed
-            con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(                # :582-586
-                outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
-                overlap=supervised_part)
+            if generalized:
+                # the draws of the SWD priors are a function of (gcl_seed, global step): the restored step continues them
+                obj_lib.set_gcl_step(getattr(optimizer, 'iterations', 0))
+                logits_con = None
+                con_loss = obj_lib.generalized_loss_of_block(
+                    outputs, lambda_weight=FLAGS.gcl_lambda, temperature=FLAGS.temperature, dist=FLAGS.gcl_dist,
+                    hidden_norm=FLAGS.hidden_norm, loss_scaling=FLAGS.gcl_loss_scaling, strategy=strategy, overlap=supervised_part)
+            else:
+                con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
+                    outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
+                    overlap=supervised_part)
         else:
             supervised_part()
         sup_loss = sup_box.get('loss')
@@ -206,7 +240,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 ([sup_loss.value.reshape(-1)[:1]] if sup_loss is not None else [])
         ops.accumulate_scalars(terms, total=total, total_mask=(1 << len(terms)) - 1)
         vals = {'train/weight_decay': wd_t, 'train/total_loss': total}
-        if con_loss is not None:
+        if con_loss is not None and generalized:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/align_loss'] = con_loss.align.reshape(-1)[:1]
+            vals['train/dist_loss'] = con_loss.dist_match.reshape(-1)[:1]
+        elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
             vals['train/contrast_entropy'] = logits_con.contrast_entropy.reshape(-1)[:1]
@@ -229,7 +267,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
         at = {nm: keep[i:i + 1] for i, nm in enumerate(order) if nm in vals}
         if con_loss is not None and 'train/contrast_loss' in at:
             con_loss.value = at['train/contrast_loss']
-            if 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
+            if generalized and 'train/align_loss' in at and 'train/dist_loss' in at:
+                con_loss.align, con_loss.dist_match = at['train/align_loss'], at['train/dist_loss']
+            elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:
             sup_loss.value = at[sup_names[0]]
@@ -386,6 +426,7 @@ def main(argv):
     FLAGS.parse(argv)
     logging.basicConfig(level=logging.INFO)
     distill = check_distillation_flags()
+    check_contrastive_loss_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
         # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -267,6 +267,41 @@ def main():
                 n, N, D, t_f, ff / t_f / 1e6, t_b, fb / t_b / 1e6), flush=True)
             res.append(dict(layer='ntxent wide n%d N%d D%d' % (n, N, D), fwd_us=t_f, bwd_us=t_b, fwd_flops=ff, bwd_flops=fb))
             del zl, za, ws, out, rs
+    if 'gcl' in what:
+        # generalized contrastive loss (csrc/gcl.hip) at the NT-Xent table's shapes, beside NT-Xent's exact sweeps: the decoupled sweep, and
+        # the SWD launches (two projections + sort-and-match + reduce | back-projection + combine) where 2N <= 8192 rows fit a column sort
+        for (n, N) in [(512, 512), (512, 4096), (256, 2048), (4096, 4096)]:
+            D = 128
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            row = dict(layer='gcl n%d N%d' % (n, N),
+                       ntxent_fwd_us=timeit(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws), args.iters),
+                       ntxent_bwd_us=timeit(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws), args.iters))
+            gws = ops.gcl_lse_workspace(n, N, D, dev)
+            _, grs, _ = ops.gcl_lse_fwd(zl, za, 0.1, ws=gws)
+            row['lse_fwd_us'] = timeit(lambda: ops.gcl_lse_fwd(zl, za, 0.1, ws=gws), args.iters)
+            row['lse_bwd_us'] = timeit(lambda: ops.gcl_lse_bwd(zl, za, 0.1, grs, 1.0, gws, skip_self=True), args.iters)
+            M = 2 * N
+            if M <= ops.SWD_MAX_ROWS:
+                w = torch.linalg.qr(torch.randn(D, D))[0].contiguous().to(dev)
+                wt = w.t().contiguous()
+                prior = torch.nn.functional.normalize(torch.randn(M, D, device=dev), dim=1)
+
+                def swd_fwd():
+                    pt, qt = ops.gcl_gemm_nt(wt, za), ops.gcl_gemm_nt(wt, prior)
+                    dp, cl, _ = ops.swd_sort_match(pt, qt, 2.0 / (D * M))
+                    ops.gcl_swd_out(cl, zl, M)
+                    return pt, qt, dp
+                pt, qt, dp = swd_fwd()
+                row['swd_fwd_us'] = timeit(swd_fwd, args.iters)
+                row['swd_sort_us'] = timeit(lambda: ops.swd_sort_match(pt, qt, 2.0 / (D * M)), args.iters)
+                row['swd_bwd_us'] = timeit(lambda: ops.gcl_swd_bwd(ops.gcl_gemm_nt(dp, w), zl, 0, 1.0), args.iters)
+            print('gcl n=%d N=%d: ' % (n, N) + ' '.join('%s %.0f' % (k[:-3], v) for k, v in row.items() if k != 'layer') + ' (us)', flush=True)
+            res.append(row)
+            del zl, za, ws, gws
     if 'lars' in what:
         from simclr_amd.lars_optimizer import LARSOptimizer, Variable
         sizes = []
