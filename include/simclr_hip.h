@@ -488,6 +488,35 @@ int simclr_comm_destroy(void* mailbox);
 int simclr_comm_stats_allreduce(const double* in, double* out, int count, void* const* peers, int rank, int world,
                                 int max_doubles, unsigned seq, int* status, simclr_stream_t stream);
 
+/* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
+ * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
+ * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the
+ * reference's units -- elements, or (image, channel) planes when min(dropblock_size, W) == W, where the pattern is [V,1,1,C] and is
+ * written broadcast over the plane.  percent_ones = float(count[0]) / float(count[1]) is formed on the device by the consumers. */
+/* tf2/resnet.py:111-153.  keep_thresh = fp32(1 - gamma) (gamma = seed_drop_rate, :113-114, computed by the caller in double): a valid
+ * block centre keeps its seed bit iff fp32(keep_thresh + u) >= 1.  noise (nullable): the uniform [0,1) fp32 tensor [V,H,W,C] to read u
+ * from (tests); NULL: u of element i (linear NHWC index) = (32 bits >> 8) * 2^-24 with the 32 bits = the low (i even) / high (i odd)
+ * half of splitmix64's output function applied to key + (i/2 + 1) * 0x9E3779B97F4A7C15 -- no state, nothing read.  The count is an
+ * integer sum: bitwise repeatable.  Refused: H != W, C % 8 != 0, H = W > 178 (one workgroup stages an (image, 8- or 32-channel)
+ * plane twice in LDS, 2 x 32000 bytes: every map of the network up to image_size 448, 112 x 112, fits), null bits / count. */
+int simclr_dropblock_mask(const float* noise, long long key, int V, int H, int W, int C, int dropblock_size, float keep_thresh,
+                          unsigned char* bits, void* count, simclr_stream_t stream);
+/* tf2/resnet.py:155-156: y = x / percent_ones * pattern (true division, then the multiply; fp32 arithmetic on fp32 or bf16 storage),
+ * x, y [rows, C].  Applied to dy it is the gradient (pattern and percent_ones are constants to tape.gradient).  percent_ones == 0
+ * gives NaN / inf as in the reference. */
+int simclr_dropblock_apply(const void* x, const unsigned char* bits, const void* count, void* y, long long rows, int C, int dtype,
+                           simclr_stream_t stream);
+/* tf2/resnet.py:482-487 with the DropBlock sites of :468-472 (a = bn3's output) and :424-427 (b = the shortcut) in front of the add:
+ * out = relu(a / pa * ma + b / pb * mb), relu(o) = o < 0 ? 0 : o (NaN passes).  relu_bits (nullable): the ReLU mask in the format
+ * simclr_bn_apply(relu_bits) writes (one byte per 16-byte chunk of out). */
+int simclr_dropblock_tail_fwd(const void* a, const unsigned char* bits_a, const void* count_a, const void* b, const unsigned char* bits_b,
+                              const void* count_b, void* out, unsigned char* relu_bits, long long rows, int C, int dtype,
+                              simclr_stream_t stream);
+/* tape.gradient of the above: g = relu bit ? dout : 0;  da = g / pa * ma;  db = g / pb * mb, both written in one pass. */
+int simclr_dropblock_tail_bwd(const void* dout, const unsigned char* relu_bits, const unsigned char* bits_a, const void* count_a,
+                              const unsigned char* bits_b, const void* count_b, void* da, void* db, long long rows, int C, int dtype,
+                              simclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

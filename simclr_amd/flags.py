@@ -106,7 +106,50 @@ _DEFS = [
     ('gcl_lambda', 1.0, float, 'MI355X build: weight of the distribution-matching term (lambda_weight).'),
     ('gcl_loss_scaling', 1.0, float, 'MI355X build: factor on the whole generalized loss (loss_scaling).'),
     ('gcl_seed', 0, int, 'MI355X build: seed of the SWD projection basis and prior samples; the draws of a step depend on (gcl_seed, step) only.'),
+    # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
+    ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
+                                      "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),
+    ('dropblock_size', None, int, 'MI355X build: DropBlock block size; required when any keep probability is active.'),
+    ('dropblock_seed', 0, int, 'MI355X build: seed of the DropBlock noise; the draws of a site depend on (dropblock_seed, step, replica, site) only.'),
 ]
+
+
+def parse_dropblock_keep_probs(text):
+    """--dropblock_keep_probs -> the `dropblock_keep_probs` argument of resnet(): None for the empty default, else a list of four
+    entries, None ('none' / '1': off) or a float in (0, 1).  ValueError for anything else."""
+    if text is None or (isinstance(text, str) and not text.strip()):
+        return None
+    if isinstance(text, (list, tuple)):
+        parts = list(text)
+    else:
+        parts = [t.strip() for t in str(text).split(',')]
+    if len(parts) != 4:
+        raise ValueError('--dropblock_keep_probs needs four comma-separated values, one per block group (got %r)' % (text,))
+    out = []
+    for t in parts:
+        if t is None or (isinstance(t, str) and t.lower() == 'none'):
+            out.append(None)
+            continue
+        try:
+            v = float(t)
+        except ValueError:
+            raise ValueError("--dropblock_keep_probs: %r is neither a number nor 'none'" % (t,))
+        if not 0.0 < v <= 1.0:
+            raise ValueError('--dropblock_keep_probs: a keep probability lies in (0, 1] (got %r)' % (t,))
+        out.append(None if v == 1.0 else v)
+    return out
+
+
+def check_dropblock_flags(flags=None):
+    """The `dropblock_keep_probs` / `dropblock_size` arguments of resnet() from the flags; raises ValueError -- before any device
+    work -- for a malformed list, or an active keep probability without a positive --dropblock_size."""
+    flags = FLAGS if flags is None else flags
+    probs = parse_dropblock_keep_probs(getattr(flags, 'dropblock_keep_probs', ''))
+    size = getattr(flags, 'dropblock_size', None)
+    if probs is not None and any(p is not None for p in probs):
+        if size is None or int(size) < 1:
+            raise ValueError('--dropblock_keep_probs=%s needs a positive --dropblock_size (got %r)' % (flags.dropblock_keep_probs, size))
+    return probs, size
 
 
 class _Flags:

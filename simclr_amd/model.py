@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import data_util, lars_optimizer, ops, optimizers, resnet
-from .flags import FLAGS
+from .flags import FLAGS, check_dropblock_flags
 from .lars_optimizer import Variable
 from .resnet import RT, Act, Layer, PackedInput, scope
 
@@ -262,9 +262,11 @@ class Model(Layer):
     def __init__(self, num_classes, **kwargs):
         RT.strategy = kwargs.get('strategy', RT.strategy)
         with scope('model'):
+            keep_probs, dropblock_size = check_dropblock_flags()
             self.resnet_model = resnet.resnet(resnet_depth=FLAGS.resnet_depth,
                                               width_multiplier=FLAGS.width_multiplier,
-                                              cifar_stem=FLAGS.image_size <= 32)
+                                              cifar_stem=FLAGS.image_size <= 32,
+                                              dropblock_keep_probs=keep_probs, dropblock_size=dropblock_size)
             self._projection_head = ProjectionHead()
             self.supervised_head = None
             if FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
@@ -419,7 +421,8 @@ def teacher_flag_values():
         v = getattr(FLAGS, 'teacher_' + name)
         return getattr(FLAGS, name) if v is None else v
     return dict(train_mode='finetune', fine_tune_after_block=-1, resnet_depth=pick('resnet_depth'),
-                width_multiplier=pick('width_multiplier'), sk_ratio=pick('sk_ratio'), ft_proj_selector=pick('ft_proj_selector'))
+                width_multiplier=pick('width_multiplier'), sk_ratio=pick('sk_ratio'), ft_proj_selector=pick('ft_proj_selector'),
+                dropblock_keep_probs='')        # the teacher never trains: no DropBlock site
 
 
 class Teacher:

@@ -6,6 +6,7 @@ All tensors must be CUDA (ROCm) tensors, contiguous.
 """
 import ctypes
 import os
+import struct
 
 import torch
 
@@ -1233,3 +1234,68 @@ def conv2d_dgrad_ext(dm, h, wext, bias, out=None, accumulate=False):
             fn=lambda: lib().conv2d_dgrad_ext(_p(dm), _p(h), _p(wext), _p(bias), _p(out), int(accumulate), V, H, W, K, N,
                                               dt(dm) | _tb(), _s()))
     return out
+
+
+# ---------------------------------------------------------------- DropBlock (csrc/dropblock.hip, tf2/resnet.py:81-157)
+def dropblock_gamma(keep_prob, width, dropblock_size):
+    """(k, seed_drop_rate) of tf2/resnet.py:111-114, in Python double as the reference computes it."""
+    k = min(dropblock_size, width)
+    return k, (1.0 - keep_prob) * width**2 / k**2 / (width - k + 1)**2
+
+
+def dropblock_keep_thresh(gamma):
+    """fp32(1 - gamma), the constant of tf2/resnet.py:130-131 (round to nearest, as tf.cast of the Python double)."""
+    return struct.unpack('f', struct.pack('f', 1.0 - gamma))[0]
+
+
+def dropblock_mask(shape, keep_prob, dropblock_size, key=0, noise=None, device=None):
+    """The block pattern of one site for an activation of `shape` [V,H,W,C]: (bits uint8 [V,H,W,C/8], count int64 [2] = ones, size).
+    noise: fp32 [V,H,W,C] uniform tensor to read (tests); None: generated in the kernel from `key` (64 bits) and the element index."""
+    V, H, W, C = shape
+    if H != W:
+        raise ValueError('Input tensor with width!=height is not supported.')          # :108-109
+    device = noise.device if noise is not None else device
+    k, gamma = dropblock_gamma(keep_prob, W, dropblock_size)
+    bits = torch.empty(V, H, W, max(C // 8, 1), device=device, dtype=torch.uint8)
+    count = torch.empty(2, device=device, dtype=torch.int64)
+    key = int(key) & 0xFFFFFFFFFFFFFFFF
+    key = key - (1 << 64) if key >= (1 << 63) else key
+    lib().dropblock_mask(_p(noise), key, V, H, W, C, int(dropblock_size), dropblock_keep_thresh(gamma), _p(bits), _p(count), _s())
+    return bits, count
+
+
+def dropblock_apply(x, bits, count, out=None):
+    """x / percent_ones * pattern (forward; applied to dy, the backward)."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    y = torch.empty_like(x) if out is None else out
+    nbytes = 2.0 * x.numel() * x.element_size() + x.numel() / 8
+    _launch('dropblock_apply', 2.0 * x.numel(), nbytes,
+            lambda: lib().dropblock_apply(_p(x), _p(bits), _p(count), _p(y), rows, C, dt(x), _s()))
+    return y
+
+
+def dropblock_tail_fwd(a, bits_a, count_a, b, bits_b, count_b, want_bits=True):
+    """relu(a / pa * ma + b / pb * mb) -> (out, ReLU bits in bn_apply's format | None)."""
+    assert a.shape == b.shape and a.dtype == b.dtype
+    C = a.shape[-1]
+    rows = a.numel() // C
+    out = torch.empty_like(a)
+    rb = torch.empty(rows, C // (16 // a.element_size()), device=a.device, dtype=torch.uint8) if want_bits else None
+    nbytes = 3.0 * a.numel() * a.element_size() + a.numel() * 3 / 8
+    _launch('dropblock_tail_fwd', 6.0 * a.numel(), nbytes,
+            lambda: lib().dropblock_tail_fwd(_p(a), _p(bits_a), _p(count_a), _p(b), _p(bits_b), _p(count_b), _p(out), _p(rb), rows, C,
+                                             dt(a), _s()))
+    return out, rb
+
+
+def dropblock_tail_bwd(dout, relu_bits, bits_a, count_a, bits_b, count_b):
+    """Gradient of dropblock_tail_fwd wrt (a, b)."""
+    C = dout.shape[-1]
+    rows = dout.numel() // C
+    da, db = torch.empty_like(dout), torch.empty_like(dout)
+    nbytes = 3.0 * dout.numel() * dout.element_size() + dout.numel() * 3 / 8
+    _launch('dropblock_tail_bwd', 4.0 * dout.numel(), nbytes,
+            lambda: lib().dropblock_tail_bwd(_p(dout), _p(relu_bits), _p(bits_a), _p(count_a), _p(bits_b), _p(count_b), _p(da), _p(db),
+                                             rows, C, dt(dout), _s()))
+    return da, db

@@ -17,8 +17,10 @@ MI355X-first differences (numerically equivalent to the reference graph):
     stem conv needs no bounds checks.
 Selective kernels (sk_ratio>0: SK_Conv2D resnet.py:217-277, ResNet-D stem :566-591 and avg-pool
 shortcut :330-338/:400-408) are built; channel counts that are not a multiple of 64 (SK squeeze
-dim, 32*w stem) are zero-padded internally.  Not built (fail loudly): SE (se_ratio>0, :280-311),
-DropBlock (:81-157, unreachable in the reference too), channels_first.
+dim, 32*w stem) are zero-padded internally.  DropBlock (:81-157) is built for the bottleneck blocks (its four sites, :424-487): the
+block pattern is a bit tensor made by one kernel per site from a stateless generator keyed by (dropblock_seed, global step, replica,
+site), and a block with an active keep probability takes its own un-fused route (BottleneckBlock._call_dropblock); keep_prob None / 1.0
+launches nothing and keeps every fusion.  Not built (fail loudly): SE (se_ratio>0, :280-311), channels_first.
 """
 import contextlib
 import math
@@ -792,9 +794,79 @@ class IdentityLayer(Layer):  # tf2/resnet.py:211-214
         return inputs
 
 
-def _no_dropblock(keep_prob, size):
-    if keep_prob is not None and keep_prob != 1.0:
-        raise NotImplementedError('DropBlock (tf2/resnet.py:81-157) is not part of the hot path')
+_DROPBLOCK_STEP = [0]
+_MASK64 = (1 << 64) - 1
+
+
+def set_dropblock_step(step):
+    """The global step the DropBlock sites of the next forward pass draw their noise for (run.single_step sets it from
+    optimizer.iterations, which a checkpoint restores: a resumed run continues bitwise)."""
+    _DROPBLOCK_STEP[0] = int(step)
+
+
+def _mix64(z):
+    z &= _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def dropblock_key(seed, step, replica, site):
+    """The 64-bit key of one site's noise in one step: a chain of splitmix64 mixes over (seed, step, replica, site), so that changing
+    any one of them changes every draw."""
+    k = _mix64(int(seed) + 0x9E3779B97F4A7C15)
+    for v in (step, replica, site):
+        k = _mix64(k + (int(v) + 1) * 0x9E3779B97F4A7C15)
+    return k
+
+
+def dropblock_active(keep_prob):
+    """keep_prob None: the reference's layer returns its input (:97-98); 1.0: gamma = 0, the pattern is all ones and percent_ones = 1,
+    so x / 1 * 1 = x exactly -- neither launches anything."""
+    return keep_prob is not None and keep_prob != 1.0
+
+
+class DropBlock(Layer):  # tf2/resnet.py:81-157
+    """One DropBlock site.  `site`: its ordinal among the active sites in construction order (part of the noise key).  The forward keeps
+    the pattern bits and the (ones, size) count in `saved` for `backward`; `release()` drops them."""
+
+    def __init__(self, keep_prob, dropblock_size, data_format='channels_last', **kwargs):
+        if data_format != 'channels_last':
+            raise ValueError('MI355X build supports channels_last only')
+        self.keep_prob = keep_prob
+        self.dropblock_size = dropblock_size
+        self.data_format = data_format
+        self.site = RT.counters.get('drop_block', 0)
+        self._name = RT.path(RT.unique('drop_block'))
+        self.saved = None
+        self.last_count = None
+
+    def key(self):
+        from .comm import replica_id
+        return dropblock_key(getattr(FLAGS, 'dropblock_seed', 0), _DROPBLOCK_STEP[0], replica_id(RT.strategy), self.site)
+
+    def make_mask(self, act):
+        """Pattern bits + count for the activation `act` (kept in `saved`); launches simclr_dropblock_mask only."""
+        if self.dropblock_size is None:
+            raise ValueError('DropBlock with keep_prob=%r needs a dropblock_size' % (self.keep_prob,))
+        if act.shape[-1] != act.c:
+            raise NotImplementedError('DropBlock on a zero-padded activation (%d of %d channels)' % (act.c, act.shape[-1]))
+        bits, count = ops.dropblock_mask(act.shape, self.keep_prob, self.dropblock_size, key=self.key(), device=act.t.device)
+        self.saved = dict(bits=bits, count=count)
+        self.last_count = count          # 16 bytes, kept after the backward: what a health check or a test reads
+        return bits, count
+
+    def __call__(self, net, training):
+        if not training or not dropblock_active(self.keep_prob):                 # :97-98
+            return net
+        bits, count = self.make_mask(net)
+        return Act(ops.dropblock_apply(net.t, bits, count), c=net.c)
+
+    def backward(self, dy):
+        """Pattern and percent_ones are constants to the gradient: dnet = dout / percent_ones * block_pattern."""
+        sv = self.saved
+        self.saved = None
+        return ops.dropblock_apply(dy, sv['bits'], sv['count'])
 
 
 # --------------------------------------------------------------------------- blocks
@@ -978,11 +1050,17 @@ class ResidualBlock(Layer):  # tf2/resnet.py:314-382
 class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
     def __init__(self, filters, strides, use_projection=False, data_format='channels_last',
                  dropblock_keep_prob=None, dropblock_size=None, **kwargs):
-        _no_dropblock(dropblock_keep_prob, dropblock_size)
         if FLAGS.se_ratio > 0:
             raise NotImplementedError('SE_Layer (tf2/resnet.py:280-311) not built')
+        self.dropblock = None
         with scope(RT.unique('bottleneck_block')):
             self.shortcut = _Shortcut(4 * filters, strides, data_format) if use_projection else None
+            if dropblock_active(dropblock_keep_prob):
+                if dropblock_size is None:
+                    raise ValueError('dropblock_keep_prob=%r needs a dropblock_size' % (dropblock_keep_prob,))
+                # the four sites in the reference's construction order: shortcut (:424-427), after bn1 + ReLU (:436-440), after
+                # bn2 + ReLU / the SK unit (:454-458), after bn3 (:468-472)
+                self.dropblock = [DropBlock(dropblock_keep_prob, dropblock_size, data_format) for _ in range(4)]
             self.conv1 = Conv2dFixedPadding(filters=filters, kernel_size=1, strides=1, data_format=data_format)
             self.bn1 = BatchNormRelu(data_format=data_format)
             self.sk = None
@@ -996,7 +1074,62 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
             self.conv3 = Conv2dFixedPadding(filters=4 * filters, kernel_size=1, strides=1, data_format=data_format)
             self.bn3 = BatchNormRelu(relu=False, init_zero=True, data_format=data_format)
 
+    def _call_dropblock(self, inputs, training):
+        """The training forward of a block with an active keep probability (:478-487).  No fusion reaches across a DropBlock site: the
+        shortcut's BatchNorm is applied stand-alone, conv3's output is stored, bn3 is applied without add or ReLU, and one kernel
+        closes the block: relu(dropblock(bn3) + dropblock(shortcut)), the two sites' patterns applied in its loads."""
+        db_sc, db1, db2, db3 = self.dropblock
+        sc, sc_bn, h = _block_entry(self, inputs, training)
+        if sc_bn is not None:
+            sc = ops.bn_apply(sc, sc_bn[0], sc_bn[1], False)
+        h = db1(h, training)
+        if self.sk is not None:
+            h = self.sk(h, training)
+        else:
+            h = self.bn2(self.conv2(h, training), training)
+        h = db2(h, training)
+        self.fused_tail = False
+        a = self.bn3(self.conv3(h, training), training, relu=False)
+        ma, ca = db3.make_mask(a)
+        mb, cb = db_sc.make_mask(Act(sc, c=a.c))
+        y, self.relu_bits = ops.dropblock_tail_fwd(a.t, ma, ca, sc, mb, cb, want_bits=self.trainable)
+        self.out = y
+        return Act(y, c=a.c)
+
+    def _backward_dropblock(self, dout, dout_partial, prev_tail, need_dx):
+        """Backward of _call_dropblock: plain (un-fused) data gradients and BatchNorm backward passes, the DropBlock backward in front
+        of bn2's / bn1's; a `prev_tail` handed over by a preceding block without DropBlock is still honoured by conv1's data gradient."""
+        if dout_partial is not None:
+            raise RuntimeError('a block on the DropBlock route received a fused tail reduction (its tail_info() is None)')
+        db_sc, db1, db2, db3 = self.dropblock
+        da, db = ops.dropblock_tail_bwd(dout, self.relu_bits, db3.saved['bits'], db3.saved['count'],
+                                        db_sc.saved['bits'], db_sc.saved['count'])
+        db3.saved = db_sc.saved = None
+        self.out = self.relu_bits = None
+        if self.shortcut is not None:
+            dx = self.shortcut.backward(db, need_dx=need_dx)
+        else:
+            dx = db if need_dx else None
+        dh3, _ = self.bn3.backward(da, mask_mode=0)
+        d2 = db2.backward(self.conv3.backward(dh3))
+        if self.sk is not None:
+            d1 = self.sk.backward(d2)
+        else:
+            dh2, _ = self.bn2.backward(d2)
+            d1 = self.conv2.backward(dh2)
+        dh1, _ = self.bn1.backward(db1.backward(d1))
+        if not need_dx:
+            self.conv1.backward(dh1, need_dx=False)
+            return None, None
+        if prev_tail is not None:
+            return self.conv1.backward(dh1, dx_out=dx, accumulate=True, fuse_bn=prev_tail)
+        self.conv1.backward(dh1, dx_out=dx, accumulate=True)
+        return dx, None
+
     def __call__(self, inputs, training):
+        self._on_dropblock_route = bool(training and self.dropblock is not None)
+        if self._on_dropblock_route:
+            return self._call_dropblock(inputs, training)
         sc, sc_bn, h = _block_entry(self, inputs, training)
         if self.sk is not None:
             h = self.sk(h, training)
@@ -1023,6 +1156,8 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
         return out
 
     def _foldable(self):
+        if getattr(self, '_on_dropblock_route', False):
+            return False
         return self.sk is None and not self.conv3.padded and _bn_fold_enabled()
 
     def _fused_tail(self, training, sc_bn, h):
@@ -1042,11 +1177,15 @@ class BottleneckBlock(Layer):  # tf2/resnet.py:385-487
                 and self._foldable() and _bn_s2_enabled() and (level >= 2 or (level == 1 and sc_bn is None)))
 
     def tail_info(self):
+        if getattr(self, '_on_dropblock_route', False):
+            return None      # the tail is not relu(bn3(.) + shortcut): the consuming block fuses no reduce for it
         # foldable tail: the consumer's dgrad epilogue only masks and sums dm (no read of this block's conv3 output)
         return self.bn3.fusion_info(mask_src=self.out, sums_only=self._foldable() and _bn_s2_enabled())
 
     def backward(self, dout, dout_partial=None, prev_tail=None, need_dx=True):
         """See ResidualBlock.backward.  Returns (dx, partial-or-None)."""
+        if getattr(self, '_on_dropblock_route', False):
+            return self._backward_dropblock(dout, dout_partial, prev_tail, need_dx)
         fold = dout_partial is not None and self._foldable()
         if getattr(self, 'fused_tail', False) and not fold:
             raise RuntimeError('bottleneck block ran the fused conv3 + bn3 forward (conv3 output not stored) but its '

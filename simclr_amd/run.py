@@ -21,8 +21,8 @@ from . import metrics, ops
 from . import model as model_lib
 from . import objective as obj_lib
 from .comm import Strategy, collectives_on, num_replicas
-from .flags import FLAGS
-from .resnet import RT, join_wgrad_stream
+from .flags import FLAGS, check_dropblock_flags
+from .resnet import RT, join_wgrad_stream, set_dropblock_step
 
 
 def generalized_loss_on():
@@ -153,9 +153,13 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
     state = {'sync': None}
     RT.strategy = strategy
     generalized = check_contrastive_loss_flags()
+    dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
 
     def single_step(features, labels):
         ops.begin_step(features.device)
+        if dropblock:
+            # the noise of a DropBlock site is a function of (dropblock_seed, global step, replica, site): the restored step continues it
+            set_dropblock_step(getattr(optimizer, 'iterations', 0))
         teacher_logits = None
         if teacher is not None:
             # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
@@ -427,6 +431,7 @@ def main(argv):
     logging.basicConfig(level=logging.INFO)
     distill = check_distillation_flags()
     check_contrastive_loss_flags()
+    check_dropblock_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
         # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter

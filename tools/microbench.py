@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,dropblock]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -302,6 +302,34 @@ def main():
             print('gcl n=%d N=%d: ' % (n, N) + ' '.join('%s %.0f' % (k[:-3], v) for k, v in row.items() if k != 'layer') + ' (us)', flush=True)
             res.append(row)
             del zl, za, ws, gws
+    if 'dropblock' in what:
+        # the four DropBlock kernels (csrc/dropblock.hip) at the sites of block groups 3 and 4, in fp32 and bf16 storage, as GB/s of
+        # the bytes each must move (tensors once, bit tensors once; the mask kernel reads nothing and writes one bit per element),
+        # beside simclr_bn_apply on the same tensor
+        for (H, C) in [(14, 1024), (14, 256), (7, 2048)]:
+            for sdt in (torch.float32, torch.bfloat16):
+                x = torch.randn(V, H, H, C, device=dev).to(sdt)
+                r = torch.randn(V, H, H, C, device=dev).to(sdt)
+                y = torch.empty_like(x)
+                scale = torch.rand(C, device=dev) + 0.5; shift = torch.randn(C, device=dev) * 0.1
+                nb = x.numel() * x.element_size()
+                mb = x.numel() / 8
+                ba, ca = ops.dropblock_mask(tuple(x.shape), 0.9, 7, key=1, device=dev)
+                bb, cb = ops.dropblock_mask(tuple(x.shape), 0.9, 7, key=2, device=dev)
+                _, rb = ops.dropblock_tail_fwd(x, ba, ca, r, bb, cb)
+                t_bn = timeit(lambda: ops.bn_apply(x, scale, shift, True, out=y), args.iters)
+                t_m = timeit(lambda: ops.dropblock_mask(tuple(x.shape), 0.9, 7, key=1, device=dev), args.iters)
+                t_a = timeit(lambda: ops.dropblock_apply(x, ba, ca, out=y), args.iters)
+                t_tf = timeit(lambda: ops.dropblock_tail_fwd(x, ba, ca, r, bb, cb), args.iters)
+                t_tb = timeit(lambda: ops.dropblock_tail_bwd(x, rb, ba, ca, bb, cb), args.iters)
+                row = dict(layer='dropblock %dx%d C%d %s' % (H, H, C, 'f32' if sdt == torch.float32 else 'bf16'), tensor_bytes=nb,
+                           bn_apply_us=t_bn, bn_apply_gbs=2 * nb / t_bn / 1e3, mask_us=t_m, mask_gbs=mb / t_m / 1e3,
+                           apply_us=t_a, apply_gbs=(2 * nb + mb) / t_a / 1e3,
+                           tail_fwd_us=t_tf, tail_fwd_gbs=(3 * nb + 2 * mb + rb.numel()) / t_tf / 1e3,
+                           tail_bwd_us=t_tb, tail_bwd_gbs=(3 * nb + 2 * mb + rb.numel()) / t_tb / 1e3)
+                print(row['layer'] + ': ' + ' '.join('%s %.0f' % (k, v) for k, v in row.items() if k not in ('layer', 'tensor_bytes')), flush=True)
+                res.append(row)
+                del x, r, y, ba, bb, rb
     if 'lars' in what:
         from simclr_amd.lars_optimizer import LARSOptimizer, Variable
         sizes = []
