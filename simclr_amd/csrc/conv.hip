@@ -20,6 +20,7 @@
 // BatchNorm statistics (tf2/resnet.py:50-60) reduce with 4 xor-shuffles in the epilogue.
 #include "common.h"
 #include <stdlib.h>
+#include <string.h>
 #include <mutex>
 #include <type_traits>
 
@@ -3345,6 +3346,66 @@ static void run_persistent(dim3 grid, dim3 block, size_t lds, hipStream_t stream
                        grid, block, lds, stream, p);
 }
 
+// The weight-gradient, Gram and pre-split stem launches write the same kind of record (role = wgrad | gram | stem_wgrad_ps): the
+// kernel with its template arguments (trailing arguments that equal their defaults left out), the split-K geometry of its
+// parameter struct, and -- appended by run_slab_reduce -- the grid of the slab reduction that follows it.
+struct WgradRec { int k_tiles, n_tiles, splits, chunks_per_split, xcd_map; };
+static WgradRec rec_of(const WgradP& p) { return {p.k_tiles, p.n_tiles, p.splits, p.chunks_per_split, p.xcd_map}; }
+static WgradRec rec_of(const Wgrad3P& p) { return {p.ci_tiles, p.co_tiles, p.splits, p.chunks_per_split, 1}; }   // (a tile spans all nine taps)
+static WgradRec rec_of(const StemWgP& p) { return {1, 1, p.splits, p.chunks_per_split, 0}; }
+static void record_wgrad(const char* kern, int elt, const char* role, unsigned grid, unsigned block, size_t lds, const WgradRec& r) {
+  snprintf(g_last_inst, sizeof(g_last_inst), "(%s) elt=%d role=%s grid=%u block=%u lds=%zu k_tiles=%d n_tiles=%d splits=%d chunks_per_split=%d xcd_map=%d",
+           kern, elt, role, grid, block, lds, r.k_tiles, r.n_tiles, r.splits, r.chunks_per_split, r.xcd_map);
+}
+
+template <typename T, int BKW, int BNW, bool MT = false>
+static void run_wgrad(const char* role, unsigned grid, unsigned block, size_t lds, hipStream_t stream, const WgradP& p) {
+  char name[128];
+  snprintf(name, sizeof(name), MT ? "conv_wgrad<%s, %d, %d, true>" : "conv_wgrad<%s, %d, %d>", type_name<T>(), BKW, BNW);
+  record_wgrad(name, (int)sizeof(T), role, grid, block, lds, rec_of(p));
+  if (!dry_run()) hipLaunchKernelGGL((conv_wgrad<T, BKW, BNW, MT>), dim3(grid), dim3(block), lds, stream, p);
+}
+
+template <typename T, int BKW, int BNW, int BRM, int STAGES, int WK = 2, int WNN = 2, bool GRAM = false, bool MT = false, int SPL = 0, int PSD = 0>
+static void run_wgrad_dma(const char* role, unsigned grid, unsigned block, size_t lds, hipStream_t stream, const WgradP& p) {
+  const int opt[6] = {WK, WNN, GRAM, MT, SPL, PSD}, dflt[6] = {2, 2, 0, 0, 0, 0};
+  const bool is_bool[6] = {false, false, true, true, false, false};
+  int n = 6;
+  while (n > 0 && opt[n - 1] == dflt[n - 1]) --n;
+  char name[160];
+  int len = snprintf(name, sizeof(name), "conv_wgrad_dma<%s, %d, %d, %d, %d", type_name<T>(), BKW, BNW, BRM, STAGES);
+  for (int i = 0; i < n; ++i)
+    len += is_bool[i] ? snprintf(name + len, sizeof(name) - len, ", %s", tf(opt[i])) : snprintf(name + len, sizeof(name) - len, ", %d", opt[i]);
+  snprintf(name + len, sizeof(name) - len, ">");
+  record_wgrad(name, (int)sizeof(T), role, grid, block, lds, rec_of(p));
+  if (!dry_run())
+    hipLaunchKernelGGL((conv_wgrad_dma<T, BKW, BNW, BRM, STAGES, WK, WNN, GRAM, MT, SPL, PSD>), dim3(grid), dim3(block), lds, stream, p);
+}
+
+template <int ST> static void run_wgrad3x3_bf16(unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Wgrad3P& q) {
+  char name[64];
+  snprintf(name, sizeof(name), "conv_wgrad3x3_bf16<%d>", ST);
+  record_wgrad(name, 2, "wgrad", grid, block, lds, rec_of(q));
+  if (!dry_run()) hipLaunchKernelGGL(conv_wgrad3x3_bf16<ST>, dim3(grid), dim3(block), lds, stream, q);
+}
+static void run_wgrad3x3_f32ps(unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Wgrad3P& q) {
+  record_wgrad("conv_wgrad3x3_f32ps", 4, "wgrad", grid, block, lds, rec_of(q));
+  if (!dry_run()) hipLaunchKernelGGL(conv_wgrad3x3_f32ps, dim3(grid), dim3(block), lds, stream, q);
+}
+template <int STAGES> static void run_stem_wgrad_ps(unsigned grid, unsigned block, size_t lds, hipStream_t stream, const StemWgP& p) {
+  char name[64];
+  snprintf(name, sizeof(name), "stem_wgrad_ps<7, 2, %d>", STAGES);
+  record_wgrad(name, 4, "stem_wgrad_ps", grid, block, lds, rec_of(p));
+  if (!dry_run()) hipLaunchKernelGGL((stem_wgrad_ps<7, 2, STAGES>), dim3(grid), dim3(block), lds, stream, p);
+}
+// out [numel] (+)= the sum of the `splits` fp32 slabs a weight-gradient kernel left in the workspace; appends its grid to the record
+static void run_slab_reduce(const void* slabs, int splits, long long numel, float* out, int accumulate, hipStream_t stream) {
+  const int grid = max(1, (int)ceil_div(numel / 4, 16));
+  const size_t len = strlen(g_last_inst);
+  snprintf(g_last_inst + len, sizeof(g_last_inst) - len, " reduce_grid=%d", grid);
+  if (!dry_run()) hipLaunchKernelGGL(slab_reduce, dim3(grid), dim3(256), 0, stream, (const float*)slabs, splits, numel, out, accumulate);
+}
+
 static const void* zero_page() {
   static void* zp = nullptr;
   if (dry_run()) return (const void*)&g_last_inst;          // never dereferenced: nothing is launched in a dry run
@@ -3940,6 +4001,251 @@ template <int MODE> static int launch_conv(int dtype, const ConvP& p, hipStream_
   return dtype == SIMCLR_DT_BF16 ? launch_igemm<uint16_t, MODE>(p, stream) : launch_igemm<float, MODE>(p, stream);
 }
 
+
+// ---- weight gradient: ONE plan per launch, shared by the workspace functions and the launchers --------------------------------
+// plan_wgrad / plan_gram / plan_stem_wgrad_ps decide everything about one split-K launch from its shape, storage type and operand
+// format alone: the kernel family, tile, ring depth, pixels per chunk, the pixel-range split, grid / block / LDS.  The launchers only
+// fill the kernel's parameter struct from the plan; the *_workspace_bytes functions ask the same plan for the slab count.  Every
+// SIMCLR_* switch of the weight gradient is read here, per launch (a sweep may flip it between two calls of one process).
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// pixel ranges of a split-K launch: ~target workgroups in total, at most `cap` ranges of whole `br`-pixel chunks
+static int wgrad_splits(long long M, int K, int N, int bkw, int bnw, int br, int* chunks_per_split, int cap, int target) {
+  const int tiles = ceil_div(K, bkw) * ceil_div(N, bnw);
+  const int nchunks = ceil_div(M, br);
+  // a multiple of 8 pixel ranges so that the XCD-aware mapping (one pixel range per XCD at a time) keeps all 8 XCDs equally loaded
+  int splits = max(1, min(nchunks, target / max(1, tiles)));
+  if (nchunks >= 8) splits = min(nchunks / 8 * 8, max(8, (splits + 7) / 8 * 8));
+  splits = min(splits, cap);
+  *chunks_per_split = ceil_div(nchunks, splits);
+  int eff = ceil_div(nchunks, *chunks_per_split);
+  // keep the effective split count a multiple of 8 when possible
+  while (nchunks >= 8 && eff % 8 != 0 && *chunks_per_split > 1) {
+    --*chunks_per_split;
+    eff = ceil_div(nchunks, *chunks_per_split);
+    if (eff > cap) { ++*chunks_per_split; eff = ceil_div(nchunks, *chunks_per_split); break; }
+  }
+  return eff;
+}
+
+struct WgradShape { int V, IH, IW, Cin, pixpitch, OH, OW, Cout, KH, KW, stride, pad; };
+struct WgradPlan {
+  enum Family {
+    UNSUPPORTED,        // a pre-split dy on a launch that only the register-staged kernels serve
+    NINE_TAP_BF16,      // conv_wgrad3x3_bf16: 64 x 64 channels x all nine taps per workgroup
+    NINE_TAP_F32PS,     // conv_wgrad3x3_f32ps: the same on fp32 storage, three terms, pre-split dy
+    TILE256_BF16,       // conv_wgrad_dma 256 x 256, one 8-wave workgroup per CU
+    TILE256_F32,        // ... fp32 storage, three terms, pre-split dy, eight waves along k
+    STEM_DMA_BF16,      // packed stem, all kernel rows in one 256-row k-tile, over LDS-DMA
+    STEM_DMA_F32,       // ... fp32 storage under split-bf16 terms
+    STEM_MT,            // ... register-staged (conv_wgrad<T, 256, 64, true>)
+    REG_STAGED,         // conv_wgrad<T, bkw, bnw>
+    DMA_RING,           // conv_wgrad_dma<T, bkw, bnw, ...>: LDS-DMA ring of `stages` chunks
+    GRAM,               // conv_wgrad_dma<..., GRAM = true>: h^T h, one tile spans all channels
+    STEM_PS             // stem_wgrad_ps
+  } family;
+  int bkw, bnw;                         // tile: k rows x output channels
+  int stages, br;                       // LDS ring depth, pixels per reduction chunk
+  int hpp;                              // nine-tap kernels: pixels of the activation window
+  int splits, chunks_per_split;         // pixel ranges (= fp32 slabs in the workspace), chunks per range
+  int k_tiles, n_tiles, xcd_map;
+  unsigned grid, block;
+  size_t lds;
+};
+
+// a pre-split dy (SIMCLR_FMT_PS_IN): fp32 storage, three bf16 backward terms, whole 64 / 32-channel blocks, 16-byte aligned pixels
+static bool wgrad_takes_presplit(const WgradShape& s, int dtype, int terms) {
+  return dtype == SIMCLR_DT_F32 && terms == 3 && s.Cin % 64 == 0 && s.Cout % 32 == 0 && (s.pixpitch * 4) % 16 == 0;
+}
+
+static WgradPlan plan_wgrad(const WgradShape& s, int dtype, int terms, bool dy_ps) {
+  WgradPlan k = {};
+  const bool bf = dtype == SIMCLR_DT_BF16;
+  const int esz = bf ? 2 : 4, taps = s.KH * s.KW, K = taps * s.Cin, N = s.Cout;
+  const long long M = (long long)s.V * s.OH * s.OW;
+  const bool aligned = (s.pixpitch * esz) % 16 == 0;           // 16-byte pixels: what the LDS-DMA loads need
+  k.block = 256;
+  // nine-tap 3x3 kernel: default for every eligible layer (stride 1, 7 <= W, whole 64-channel blocks; bf16, or fp32 storage with three
+  // terms and a pre-split dy); measured against the per-tap kernels at 1024 views (profiles/r03_notes.md): 56^2 645 -> 516 us, 28^2 463
+  // -> 381, 14^2 387 -> 367, 7^2 360 -> 349.  SIMCLR_WGRAD_3X3=0 switches back.
+  if (env_int("SIMCLR_WGRAD_3X3", 1) > 0 && s.KH == 3 && s.KW == 3 && s.stride == 1 && s.pad == 1 && s.IH == s.OH && s.IW == s.OW &&
+      s.Cin % 64 == 0 && s.Cout % 64 == 0 && s.IW >= 7 && (bf ? aligned : (terms == 3 && dy_ps))) {
+    const int br = bf ? 64 : 32;
+    const int hpp = (br + 2 * s.IW + 2 + 31) / 32 * 32;        // a chunk with a halo of W + 1 pixels either side
+    const size_t stage = (size_t)(hpp + br) * 64 * esz;        // window + gradient chunk, 64 channels each
+    // bf16: two stages must fit, a three-deep ring wherever two workgroups of it fit a CU (round 3: -0.1 ms per step); fp32: two
+    // workgroups of two stages per CU (W <= 47: 28^2, 14^2, 7^2)
+    if ((bf ? 2 : 4) * stage <= 160 * 1024) {
+      k.family = bf ? WgradPlan::NINE_TAP_BF16 : WgradPlan::NINE_TAP_F32PS;
+      k.bkw = 64; k.bnw = 64; k.br = br; k.hpp = hpp;
+      k.stages = (bf && 2 * 3 * stage <= 160 * 1024) ? 3 : 2;
+      k.k_tiles = s.Cin / 64; k.n_tiles = N / 64;
+      const int tiles = k.k_tiles * k.n_tiles;
+      // SIMCLR_WGRAD3_BLOCKS overrides the total workgroup target.  Measured (us at 1024 views, targets 512 / 768 / 1024 / 1536 / 2048):
+      // 56^2 437 517 434 425 418 | 28^2 362 440 370 450 507 | 14^2 323 379 344 371 515 | 7^2 295 311 312 340 378 -> one full round of 512
+      // (2 per CU), more ranges only for the single-tile 64 -> 64 layer; partial rounds (768, 1536) are the worst choice
+      const int want = min(bf ? 4096 : 2048, max(8, env_int("SIMCLR_WGRAD3_BLOCKS", tiles == 1 ? 2048 : 512)));
+      k.splits = wgrad_splits(M, s.Cin, N, 64, 64, br, &k.chunks_per_split, 2048, want);
+      k.xcd_map = 1;
+      k.grid = tiles * ceil_div(k.splits, 8) * 8;
+      k.lds = k.stages * stage;
+      return k;
+    }
+  }
+  k.bkw = (s.Cin % 128 == 0) ? 128 : (s.Cin % 64 == 0 ? 64 : 32);
+  k.bnw = (N % 128 == 0 || N > 128) ? 128 : 64;
+  if (k.bkw == 32) k.bnw = 64;
+  if (s.Cin % 256 == 0 && N % 256 == 0 && aligned) {
+    // 256 x 256 tile (one 8-wave workgroup per CU, half the L2->LDS bytes per FLOP): measured per layer (tools/diag_conv.py --wgrad) a
+    // win for the long reductions and the 256-channel 3x3 layers, a loss for the short ones (7x7, 14x14 1x1) where it leaves too few
+    // workgroups.  SIMCLR_WGRAD_256=0 keeps the 128 x 128 tile.
+    if (bf && env_int("SIMCLR_WGRAD_256", 1) != 0 && (M >= 500000 || (taps == 9 && M >= 150000 && s.Cin == 256))) k.bkw = k.bnw = 256;
+    // fp32 storage, pre-split gradient, stride-1 1x1 layers: eight waves along k (32 k-rows x all 256 columns each: the activation
+    // operand split once per workgroup, 8 LDS-DMA instructions per wave for 96 MFMAs instead of 48).  Per layer at 1024 views: 28^2
+    // 512->256 713 -> 673 us, 14^2 1024->512 659 -> 620, 1024->256 361 -> 358, 256->1024 366 -> 360, 7^2 340 -> 331 / 350 -> 340
+    if (!bf && terms == 3 && dy_ps && s.stride == 1 && taps == 1) k.bkw = k.bnw = 256;
+  }
+  // stem (packed input, 32 elements per kernel row): all kernel rows in ONE 256-row k-tile, so dY is read once
+  const bool stem = k.bkw == 32 && s.Cin == 32 && K <= 256 && N <= 64;
+  if (stem) { k.bkw = 256; k.bnw = 64; }
+  // SIMCLR_WGRAD_CFG: 1 = LDS-DMA ring, 64-pixel chunks x 2 stages (default); 2 = 32-pixel chunks x 3 stages for the 128 x 128 tile
+  // (3 workgroups / CU), 3 stages elsewhere; 3 = 32-pixel chunks x 4 stages; 0 = register-staged kernel.  bf16 only beyond 1.
+  int cfg = env_int("SIMCLR_WGRAD_CFG", -1);
+  if (cfg < 0 || (!bf && cfg > 1)) cfg = 1;
+  // 32-row tiles, the stem and sources that are not 16-byte aligned keep the register-staged kernel; the 256 x 256 tile has none
+  if (k.bkw == 32 || stem || !aligned) cfg = 0;
+  const bool big = k.bkw == 128 && k.bnw == 128, big256 = k.bkw == 256 && !stem;
+  if (big256 && cfg == 0) cfg = 1;
+  if (dy_ps && cfg == 0) return k;                             // UNSUPPORTED
+  const int brm = ((cfg >= 2 && big) || (big256 && bf)) ? 1 : 2;
+  k.stages = big256 ? (bf ? 4 : 2) : (cfg <= 1 ? 2 : (big ? (cfg == 2 ? 3 : 4) : 3));
+  k.br = (bf ? 32 : 16) * brm;
+  // workgroup target: 512 for the 256 x 256 tile (two rounds of 256 instead of three of 512); bf16 1024 (round 5 sweep, ms per step at
+  // 768 / 1024 / 1536 / 2048 / 3072: 64.1 / 63.7 / 63.9 / 64.6 / 65.1 -- fewer, longer pixel ranges write fewer fp32 slabs); fp32 1536
+  // (parity mode 190.5 / 187.4 / 187.2 at 1024 / 1536 / 2048).  SIMCLR_WGRAD_BLOCKS overrides the last two.  The stem: up to 1024 ranges.
+  const int target = stem ? 1024 : (k.bkw == 256 ? 512 : env_int("SIMCLR_WGRAD_BLOCKS", bf ? 1024 : 1536));
+  k.splits = wgrad_splits(M, K, N, k.bkw, k.bnw, k.br, &k.chunks_per_split, stem ? 1024 : 256, target);
+  k.k_tiles = ceil_div(K, k.bkw);
+  k.n_tiles = ceil_div(N, k.bnw);
+  // XCD-aware mapping: with the LDS-DMA kernel a win (or neutral) on every ResNet-50 layer; the register-staged kernel keeps the old
+  // size rule
+  k.xcd_map = cfg != 0 || M >= 1500000 || (M >= 500000 && taps == 1 && s.stride == 1);
+#ifdef SIMCLR_DIAG
+  { const char* e = getenv("SIMCLR_WGRAD_XCD"); if (e && atoi(e) >= 0) k.xcd_map = atoi(e); }
+#endif
+  k.family = big256 ? (bf ? WgradPlan::TILE256_BF16 : WgradPlan::TILE256_F32) : cfg == 0 ? WgradPlan::REG_STAGED : WgradPlan::DMA_RING;
+  if (big256) k.block = 512;
+  if (stem) {
+    const bool packed = s.KW == 1 && s.pad == 0 && s.pixpitch == 4;
+    k.family = WgradPlan::STEM_MT;
+    if (bf && packed && s.stride % 2 == 0 && s.IW % 2 == 0) {
+      // over LDS-DMA: stride 2 on an even-width packed image makes every source 16-byte aligned; 64-pixel chunks x 2 stages
+      k.family = WgradPlan::STEM_DMA_BF16;
+    } else if (!bf && packed && terms != 0 && env_int("SIMCLR_STEM_SPLIT", 1) != 0) {
+      // fp32 stem under split-bf16 terms: a packed pixel is 4 floats = 16 bytes, so every source of the multi-tap k-tile is 16-byte
+      // aligned at ANY stride / width; 32-pixel chunks x 2 stages, 8 waves (4 along the 256 k-rows x 2 along n: the 4-wave shape
+      // spills ~100 registers).  SIMCLR_STEM_WGRAD_STAGES=3 (three terms): a three-deep ring (120 KB).  The exact fp32 arithmetic
+      // keeps the register-staged kernel.
+      k.family = WgradPlan::STEM_DMA_F32;
+      k.block = 512;
+      if (terms == 3 && env_int("SIMCLR_STEM_WGRAD_STAGES", 2) == 3) k.stages = 3;
+    }
+    if (k.family != WgradPlan::STEM_MT) k.xcd_map = 1;
+  }
+  k.grid = k.k_tiles * k.n_tiles * (k.xcd_map ? ceil_div(k.splits, 8) * 8 : k.splits);
+  k.lds = (size_t)k.stages * k.br * (k.bkw + k.bnw) * esz;
+  return k;
+}
+
+// Gram launch (simclr_conv2d_gram): K in {64, 128, 256}, one tile spans all channels, the activation is streamed once
+static WgradPlan plan_gram(long long M, int K, int dtype) {
+  WgradPlan k = {};
+  const bool bf = dtype == SIMCLR_DT_BF16;
+  k.family = WgradPlan::GRAM;
+  k.bkw = k.bnw = K;
+  // 4-stage ring of 64-pixel (bf16) chunks holding the activation tile only: three chunks in flight per workgroup
+  k.stages = 4;
+  k.br = (bf ? 64 : 32) / (K == 256 ? 2 : 1);
+  // one tile per pixel range: up to 1024 workgroups (4 per CU) share the streaming; 512 of the eight-wave 256-channel tile
+  const int ranges = K == 256 ? 512 : 1024;
+  k.splits = wgrad_splits(M, K, K, K, K, k.br, &k.chunks_per_split, ranges, ranges);
+  k.k_tiles = 1; k.n_tiles = 1; k.xcd_map = 1;
+  k.grid = ceil_div(k.splits, 8) * 8;
+  k.block = K == 256 ? 512 : 256;
+  k.lds = (size_t)k.stages * k.br * K * (bf ? 2 : 4);
+  return k;
+}
+
+// pre-split stem weight gradient (simclr_stem_wgrad_ps)
+static WgradPlan plan_stem_wgrad_ps(int V, int OH, int OW) {
+  WgradPlan k = {};
+  k.family = WgradPlan::STEM_PS;
+  k.bkw = 7 * 32; k.bnw = 64; k.br = 32;
+  const long long chunks = (long long)V * OH * ((OW + 31) / 32);       // 32-pixel segments of the output rows
+  // four two-wave workgroups per CU (two per SIMD pair), every one of them resident for the whole launch
+  const int want = (int)max(1ll, min((long long)max(8, min(env_int("SIMCLR_STEM_WGRAD_BLOCKS", 1024), 1024)), chunks));
+  k.chunks_per_split = (int)((chunks + want - 1) / want);
+  k.splits = (int)((chunks + k.chunks_per_split - 1) / k.chunks_per_split);
+  k.stages = env_int("SIMCLR_STEM_WGRAD_PS_STAGES", 2) == 3 ? 3 : 2;
+  k.k_tiles = 1; k.n_tiles = 1;
+  k.grid = k.splits; k.block = 128;
+  k.lds = (size_t)k.stages * ((7 * 70 + 63) / 64 + 8) * 1024;          // window (7 rows x 70 packed pixels) + gradient chunk per stage
+  return k;
+}
+
+template <int A, int B> struct WgradTile { static constexpr int BKW = A, BNW = B; };
+// f(WgradTile<bkw, bnw>()) for the five tiles of the register-staged and LDS-DMA ring kernels
+template <typename F> static void with_wgrad_tile(int bkw, int bnw, F&& f) {
+  if (bkw == 128 && bnw == 128) f(WgradTile<128, 128>());
+  else if (bkw == 128) f(WgradTile<128, 64>());
+  else if (bkw == 64 && bnw == 128) f(WgradTile<64, 128>());
+  else if (bkw == 64) f(WgradTile<64, 64>());
+  else f(WgradTile<32, 64>());
+}
+
+static void launch_wgrad(const WgradPlan& k, bool bf, hipStream_t stream, const WgradP& p) {
+  const unsigned g = k.grid;
+  const size_t l = k.lds;
+  switch (k.family) {
+    case WgradPlan::TILE256_BF16: return run_wgrad_dma<uint16_t, 256, 256, 1, 4, 2, 4>("wgrad", g, k.block, l, stream, p);
+    case WgradPlan::TILE256_F32: return run_wgrad_dma<float, 256, 256, 2, 2, 8, 1, false, false, 3, 1>("wgrad", g, k.block, l, stream, p);
+    case WgradPlan::STEM_DMA_BF16: return run_wgrad_dma<uint16_t, 256, 64, 2, 2, 2, 2, false, true>("wgrad", g, k.block, l, stream, p);
+    case WgradPlan::STEM_DMA_F32:
+      if (p.split != 3) return run_wgrad_dma<float, 256, 64, 2, 2, 4, 2, false, true, 6>("wgrad", g, k.block, l, stream, p);
+      if (k.stages == 3) return run_wgrad_dma<float, 256, 64, 2, 3, 4, 2, false, true, 3>("wgrad", g, k.block, l, stream, p);
+      return run_wgrad_dma<float, 256, 64, 2, 2, 4, 2, false, true, 3>("wgrad", g, k.block, l, stream, p);
+    case WgradPlan::STEM_MT:
+      if (bf) return run_wgrad<uint16_t, 256, 64, true>("wgrad", g, k.block, l, stream, p);
+      return run_wgrad<float, 256, 64, true>("wgrad", g, k.block, l, stream, p);
+    default: break;
+  }
+  with_wgrad_tile(k.bkw, k.bnw, [&](auto tile) {
+    constexpr int A = decltype(tile)::BKW, B = decltype(tile)::BNW;
+    if (k.family == WgradPlan::REG_STAGED) {
+      if (bf) run_wgrad<uint16_t, A, B>("wgrad", g, k.block, l, stream, p);
+      else run_wgrad<float, A, B>("wgrad", g, k.block, l, stream, p);
+    } else if (bf) {
+      if (k.stages == 2) run_wgrad_dma<uint16_t, A, B, 2, 2>("wgrad", g, k.block, l, stream, p);
+      else if constexpr (A == 128 && B == 128) {               // 32-pixel chunks: three workgroups per CU
+        if (k.stages == 3) run_wgrad_dma<uint16_t, 128, 128, 1, 3>("wgrad", g, k.block, l, stream, p);
+        else run_wgrad_dma<uint16_t, 128, 128, 1, 4>("wgrad", g, k.block, l, stream, p);
+      } else run_wgrad_dma<uint16_t, A, B, 2, 3>("wgrad", g, k.block, l, stream, p);
+    } else if (p.split == 3) {
+      // three terms on tiles of >= 64 k-rows: four waves along k (each 32 | 16 k-rows x all columns), so that the activation operand, the
+      // one still split in registers, is split ONCE per workgroup instead of once per column half (96 -> 48 VALU per 48 MFMAs; round 6:
+      // family 39.93 -> 38.54 ms); a plain fp32 gradient is split in LDS once per chunk (PSD = 2: 37.40 -> 37.21 ms)
+      if constexpr (A >= 64) {
+        if (p.dy_ps) run_wgrad_dma<float, A, B, 2, 2, 4, 1, false, false, 3, 1>("wgrad", g, k.block, l, stream, p);
+        else run_wgrad_dma<float, A, B, 2, 2, 4, 1, false, false, 3, 2>("wgrad", g, k.block, l, stream, p);
+      } else {
+        if (p.dy_ps) run_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3, 1>("wgrad", g, k.block, l, stream, p);
+        else run_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3>("wgrad", g, k.block, l, stream, p);
+      }
+    } else if (p.split == 6) run_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 6>("wgrad", g, k.block, l, stream, p);
+    else run_wgrad_dma<float, A, B, 2, 2>("wgrad", g, k.block, l, stream, p);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -4191,80 +4497,21 @@ int simclr_conv2d_dgrad_ext(const void* dm, const void* h, const void* w_ext, co
   return 0;
 }
 
-size_t simclr_conv2d_wgrad_workspace_bytes(int V, int OH, int OW, int Cin, int Cout, int KH, int KW,
-                                           int dtype);
-
-static int wgrad_splits(long long M, int K, int N, int bkw, int bnw, int br, int* chunks_per_split, int cap = 256,
-                        int want = 0) {
-  const int tiles = ceil_div(K, bkw) * ceil_div(N, bnw);
-  const int nchunks = ceil_div(M, br);
-  // ~1024-2048 workgroups in total; a multiple of 8 pixel ranges so that the XCD-aware mapping (one
-  // pixel range per XCD at a time) keeps all 8 XCDs equally loaded
-  static const int target_env = getenv("SIMCLR_WGRAD_BLOCKS") ? atoi(getenv("SIMCLR_WGRAD_BLOCKS")) : 1536;
-  // 256 x 256 tiles run one 8-wave workgroup per CU: two rounds of 256 instead of three rounds of 512
-  const int target = want > 0 ? want : (bkw == 256 ? 512 : target_env);
-  int splits = max(1, min(nchunks, target / max(1, tiles)));
-  if (nchunks >= 8) splits = min(nchunks / 8 * 8, max(8, (splits + 7) / 8 * 8));
-  splits = min(splits, cap);
-  *chunks_per_split = ceil_div(nchunks, splits);
-  int eff = ceil_div(nchunks, *chunks_per_split);
-  // keep the effective split count a multiple of 8 when possible
-  while (nchunks >= 8 && eff % 8 != 0 && *chunks_per_split > 1) {
-    --*chunks_per_split;
-    eff = ceil_div(nchunks, *chunks_per_split);
-    if (eff > cap) { ++*chunks_per_split; eff = ceil_div(nchunks, *chunks_per_split); break; }
-  }
-  return eff;
-}
-// nine-tap 3x3 kernel: default for every eligible layer (bf16, stride 1, 7 <= W, whole 64-channel blocks); measured
-// against the per-tap kernels at 1024 views (profiles/r03_notes.md): 56^2 645 -> 516 us, 28^2 463 -> 381, 14^2 387 -> 367,
-// 7^2 360 -> 349; SIMCLR_WGRAD_3X3=0 switches back (read per call so that a test can compare both in-process)
-static bool wgrad_use_3x3(int dtype, long long M, int Cin, int Cout, int KH, int KW, int stride, int pad, int IH, int IW,
-                          int OH, int OW, int pixpitch) {
-  const char* e = getenv("SIMCLR_WGRAD_3X3");
-  if (e && atoi(e) <= 0) return false;
-  return dtype == SIMCLR_DT_BF16 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && IH == OH && IW == OW &&
-         Cin % 64 == 0 && Cout % 64 == 0 && (pixpitch * 2) % 16 == 0 && IW >= 7 && ((64 + 2 * IW + 2 + 31) / 32 * 32 + 64) * 128 * 2 <= 160 * 1024;
-}
-static bool wgrad_use_256() {
-#ifdef SIMCLR_DIAG
-  const char* e = getenv("SIMCLR_WGRAD_256");       // per launch: sweeps
-  return !e || atoi(e) != 0;
-#else
-  static const bool on = !getenv("SIMCLR_WGRAD_256") || atoi(getenv("SIMCLR_WGRAD_256")) != 0;
-  return on;
-#endif
-}
-static void wgrad_tile(int Cin, int Cout, int dtype, long long M, int taps, int* bkw, int* bnw, bool f32ps256 = false) {
-  *bkw = (Cin % 128 == 0) ? 128 : (Cin % 64 == 0 ? 64 : 32);
-  *bnw = (Cout % 128 == 0 || Cout > 128) ? 128 : 64;
-  if (*bkw == 32) *bnw = 64;
-  // 256 x 256 tile (one 8-wave workgroup per CU, half the L2->LDS bytes per FLOP): measured per layer
-  // (tools/diag_conv.py --wgrad) a win for the long reductions and the 256-channel 3x3 layers, a loss
-  // for the short ones (7x7, 14x14 1x1) where it leaves too few workgroups.
-  if (dtype == SIMCLR_DT_BF16 && Cin % 256 == 0 && Cout % 256 == 0 && wgrad_use_256() &&
-      (M >= 500000 || (taps == 9 && M >= 150000 && Cin == 256))) { *bkw = 256; *bnw = 256; }
-  // fp32 storage, pre-split gradient, 1x1 layers of 256-channel multiples: 256 x 256 tile, eight waves along k (32 k-rows x all 256 columns
-  // each: the activation operand split once per workgroup, 8 LDS-DMA instructions per wave for 96 MFMAs instead of 48), one workgroup per
-  // CU.  Per layer at 1024 views (r06_call48): 28^2 512->256 713 -> 673 us, 14^2 1024->512 659 -> 620, 1024->256 361 -> 358, 256->1024
-  // 366 -> 360, 7^2 340 -> 331 / 350 -> 340; no layer loses
-  if (f32ps256 && taps == 1 && Cin % 256 == 0 && Cout % 256 == 0) { *bkw = 256; *bnw = 256; }
-}
-
-size_t simclr_conv2d_wgrad_workspace_bytes(int V, int OH, int OW, int Cin, int Cout, int KH, int KW,
-                                           int dtype) {
-  int bkw, bnw, cps;
-  wgrad_tile(Cin, Cout, dtype, (long long)V * OH * OW, KH * KW, &bkw, &bnw);
-  // the bf16 kernel variants reduce in chunks of 64 or 32 pixels: size for whichever needs more slabs
-  int splits = wgrad_splits((long long)V * OH * OW, KH * KW * Cin, Cout, bkw, bnw, dtype == SIMCLR_DT_BF16 ? 64 : 32, &cps);
-  splits = max(splits, wgrad_splits((long long)V * OH * OW, KH * KW * Cin, Cout, bkw, bnw, 32, &cps));
-  if (KH == 3 && KW == 3 && Cin % 64 == 0 && Cout % 64 == 0)      // nine-tap kernel: 64x64 tiles of all taps, up to 2048 ranges
-    splits = max(splits, max(wgrad_splits((long long)V * OH * OW, Cin, Cout, 64, 64, 64, &cps, 2048, 4096),
-                             wgrad_splits((long long)V * OH * OW, Cin, Cout, 64, 64, 32, &cps, 2048, 4096)));    // (fp32 nine-tap kernel: 32-pixel chunks)
-  if (dtype != SIMCLR_DT_BF16 && KH * KW == 1 && Cin % 256 == 0 && Cout % 256 == 0)   // fp32 256 x 256 tile on a pre-split gradient: fewer tiles, more ranges
-    splits = max(splits, wgrad_splits((long long)V * OH * OW, Cin, Cout, 256, 256, 32, &cps));
-  if (Cin == 32 && KH * KW * Cin <= 256 && Cout <= 64)            // stem: one 256-row k-tile, up to 1024 pixel ranges
-    splits = max(splits, wgrad_splits((long long)V * OH * OW, KH * KW * Cin, Cout, 256, 64, dtype == SIMCLR_DT_BF16 ? 64 : 32, &cps, 1024, 1024));
+// The caller sizes the workspace from the storage type, M, the channels and the taps alone.  What it does not tell reaches the split
+// count only through the operand format (fp32: backward terms, plain or pre-split dy) and two questions about the geometry -- stride 1 at
+// the same size (nine-tap kernels, fp32 256 x 256 tile)?  16-byte pixels? -- so the answer is the largest plan over all of them.
+size_t simclr_conv2d_wgrad_workspace_bytes(int V, int OH, int OW, int Cin, int Cout, int KH, int KW, int dtype) {
+  int splits = 0;
+  for (int stride = 1; stride <= 2; ++stride)
+    for (int odd_pitch = 0; odd_pitch <= 1; ++odd_pitch) {
+      const WgradShape s = {V, OH * stride, OW * stride, Cin, Cin + odd_pitch, OH, OW, Cout, KH, KW, stride, (KH - 1) / 2};
+      for (int terms : {0, 3, 6})
+        for (int ps = 0; ps <= 1; ++ps) {
+          if (dtype == SIMCLR_DT_BF16 ? (terms != 0 || ps) : (!valid_terms(terms, false) || (ps && !wgrad_takes_presplit(s, dtype, terms)))) continue;
+          const WgradPlan k = plan_wgrad(s, dtype, terms, ps != 0);
+          if (k.family != WgradPlan::UNSUPPORTED) splits = max(splits, k.splits);
+        }
+    }
   return (size_t)splits * KH * KW * Cin * Cout * sizeof(float);
 }
 
@@ -4275,225 +4522,47 @@ int simclr_conv2d_wgrad(const void* x, const void* dy, float* dw, int accumulate
                         int KW, int stride, int pad, int dtype, hipStream_t stream) {
   const int terms = terms_of(&dtype, false);
   SIMCLR_CHECK_ARG(terms >= 0, "conv2d_wgrad: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
-  // dtype | SIMCLR_FMT_PS_IN (fp32, three bf16 backward terms, Cin a multiple of 64, Cout of 32, 16-byte aligned pixels): dy is in
-  // the pre-split block format (common.h)
+  // dtype | SIMCLR_FMT_PS_IN: dy is in the pre-split block format (common.h)
   const bool dy_ps = (dtype & SIMCLR_FMT_PS_IN) != 0;
   dtype &= 0xff;
-  SIMCLR_CHECK_ARG(!dy_ps || (dtype == SIMCLR_DT_F32 && terms == 3 && Cin % 64 == 0 && Cout % 32 == 0 && (pixpitch * 4) % 16 == 0),
+  const WgradShape s = {V, IH, IW, Cin, pixpitch, OH, OW, Cout, KH, KW, stride, pad};
+  SIMCLR_CHECK_ARG(!dy_ps || wgrad_takes_presplit(s, dtype, terms),
                    "conv2d_wgrad: a pre-split dy needs fp32 storage, three backward terms, Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%d Cout=%d)", Cin, Cout);
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_wgrad: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cin % 32 == 0, "conv2d_wgrad: Cin=%d must be a multiple of 32", Cin);
   SIMCLR_CHECK_ARG(Cout % 8 == 0, "conv2d_wgrad: Cout=%d must be a multiple of 8", Cout);
   SIMCLR_CHECK_ARG((long long)V * OH * OW < (1ll << 31), "conv2d_wgrad: M overflows int32");
-  WgradP p = {};
-  p.x = x; p.dy = dy; p.dw = (float*)workspace;
-  p.V = V; p.IH = IH; p.IW = IW; p.IC = Cin; p.OH = OH; p.OW = OW; p.N = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = pixpitch;
-  p.M = V * OH * OW; p.K = KH * KW * Cin;
-  if (wgrad_use_3x3(dtype, p.M, Cin, Cout, KH, KW, stride, pad, IH, IW, OH, OW, pixpitch)) {
+  const WgradPlan k = plan_wgrad(s, dtype, terms, dy_ps);
+  SIMCLR_CHECK_ARG(k.family != WgradPlan::UNSUPPORTED, "conv2d_wgrad: no pre-split kernel on the register-staged path");
+  const void* zero = zero_page();
+  SIMCLR_CHECK_ARG(zero != nullptr, "conv2d_wgrad: zero page symbol not found");
+  const int M = V * OH * OW, K = KH * KW * Cin;
+  if (k.family == WgradPlan::NINE_TAP_BF16 || k.family == WgradPlan::NINE_TAP_F32PS) {
     Wgrad3P q = {};
-    q.x = x; q.dy = dy; q.dw = (float*)workspace; q.zero = zero_page();
-    SIMCLR_CHECK_ARG(q.zero != nullptr, "conv2d_wgrad: zero page symbol not found");
-    q.V = V; q.H = IH; q.W = IW; q.IC = Cin; q.N = Cout; q.pixpitch = pixpitch; q.M = p.M;
-    q.ci_tiles = Cin / 64; q.co_tiles = Cout / 64;
-    // pixel ranges (SIMCLR_WGRAD3_BLOCKS overrides the total workgroup target), at most 2048 ranges
-    // measured (us at 1024 views, targets 512 / 768 / 1024 / 1536 / 2048): 56^2 437 517 434 425 418 | 28^2 362 440 370 450
-    // 507 | 14^2 323 379 344 371 515 | 7^2 295 311 312 340 378 -> one full round of 512 (2 per CU), more ranges only
-    // for the single-tile 64 -> 64 layer; partial rounds (768, 1536) are the worst choice
-    const int tiles3 = (Cin / 64) * (Cout / 64);
-    // (never more than the 4096 simclr_conv2d_wgrad_workspace_bytes sizes the slabs for)
-    const int want3 = min(4096, max(8, getenv("SIMCLR_WGRAD3_BLOCKS") ? atoi(getenv("SIMCLR_WGRAD3_BLOCKS")) : (tiles3 == 1 ? 2048 : 512)));
-    q.splits = wgrad_splits(p.M, Cin, Cout, 64, 64, 64, &q.chunks_per_split, 2048, want3);
-    q.hpp = (64 + 2 * IW + 2 + 31) / 32 * 32;
-    const int tiles = q.ci_tiles * q.co_tiles;
-    const int grid3 = tiles * ceil_div(q.splits, 8) * 8;
-    const size_t stage3 = (size_t)(q.hpp + 64) * 128;
-    constexpr bool ring3 = true;          // three-deep ring wherever two workgroups of it fit a CU (round 3: -0.1 ms per step)
-    if (ring3 && 2 * 3 * stage3 <= 160 * 1024)
-      hipLaunchKernelGGL(conv_wgrad3x3_bf16<3>, dim3(grid3), dim3(256), 3 * stage3, stream, q);
-    else
-      hipLaunchKernelGGL(conv_wgrad3x3_bf16<2>, dim3(grid3), dim3(256), 2 * stage3, stream, q);
-    SIMCLR_CHECK_LAUNCH();
-    const long long numel3 = (long long)p.K * p.N;
-    hipLaunchKernelGGL(slab_reduce, dim3(max(1, (int)ceil_div(numel3 / 4, 16))), dim3(256), 0, stream,
-                       (const float*)workspace, q.splits, numel3, dw, accumulate);
-    SIMCLR_CHECK_LAUNCH();
-    return 0;
-  }
-  // fp32 storage, three backward terms, pre-split gradient: the nine-tap kernel for the 3x3 stride-1 layers whose window fits two
-  // workgroups per CU (W <= 47: 28^2, 14^2, 7^2); SIMCLR_WGRAD_3X3=0 keeps the per-tap kernel (read per call, as for bf16)
-  {
-    const char* e3 = getenv("SIMCLR_WGRAD_3X3");
-    const int hpp = (32 + 2 * IW + 2 + 31) / 32 * 32;
-    if (!(e3 && atoi(e3) <= 0) && dtype == SIMCLR_DT_F32 && terms == 3 && dy_ps && KH == 3 && KW == 3 && stride == 1 && pad == 1 &&
-        IH == OH && IW == OW && Cin % 64 == 0 && Cout % 64 == 0 && IW >= 7 && 2 * 2 * (hpp + 32) * 256 <= 160 * 1024) {
-      Wgrad3P q = {};
-      q.x = x; q.dy = dy; q.dw = (float*)workspace; q.zero = zero_page();
-      SIMCLR_CHECK_ARG(q.zero != nullptr, "conv2d_wgrad: zero page symbol not found");
-      q.V = V; q.H = IH; q.W = IW; q.IC = Cin; q.N = Cout; q.pixpitch = pixpitch; q.M = p.M;
-      q.ci_tiles = Cin / 64; q.co_tiles = Cout / 64;
-      const int tiles3 = q.ci_tiles * q.co_tiles;
-      const int want3 = min(2048, max(8, getenv("SIMCLR_WGRAD3_BLOCKS") ? atoi(getenv("SIMCLR_WGRAD3_BLOCKS")) : (tiles3 == 1 ? 2048 : 512)));
-      q.splits = wgrad_splits(p.M, Cin, Cout, 64, 64, 32, &q.chunks_per_split, 2048, want3);
-      q.hpp = hpp;
-      const int grid3 = tiles3 * ceil_div(q.splits, 8) * 8;
-      hipLaunchKernelGGL(conv_wgrad3x3_f32ps, dim3(grid3), dim3(256), (size_t)2 * (hpp + 32) * 256, stream, q);
-      SIMCLR_CHECK_LAUNCH();
-      const long long numel3 = (long long)p.K * p.N;
-      hipLaunchKernelGGL(slab_reduce, dim3(max(1, (int)ceil_div(numel3 / 4, 16))), dim3(256), 0, stream,
-                         (const float*)workspace, q.splits, numel3, dw, accumulate);
-      SIMCLR_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  int bkw, bnw;
-  constexpr bool f32_256 = true;
-  wgrad_tile(Cin, Cout, dtype, p.M, KH * KW, &bkw, &bnw, f32_256 && dtype == SIMCLR_DT_F32 && terms == 3 && dy_ps && stride == 1);
-  if ((pixpitch * (dtype == SIMCLR_DT_BF16 ? 2 : 4)) % 16 != 0 && bkw == 256) { bkw = 128; bnw = 128; }
-  // stem (packed input, 32 elements per kernel row): all kernel rows in ONE 256-row k-tile, so dY is read once
-  constexpr bool stem_mt_on = true;
-  const bool stem_mt = stem_mt_on && bkw == 32 && Cin == 32 && p.K <= 256 && Cout <= 64;
-  if (stem_mt) { bkw = 256; bnw = 64; }
-  // kernel variant: 1 = LDS-DMA ring, 64-pixel chunks x 2 stages; 2 = 32-pixel chunks x 3 stages for the
-  // 128x128 tile (3 workgroups/CU), 3 stages elsewhere; 3 = 32-pixel chunks x 4 stages; 0 = register-staged
-  // kernel (kept for A/B runs: SIMCLR_WGRAD_CFG).
-#ifdef SIMCLR_DIAG
-  const int cfg_env = getenv("SIMCLR_WGRAD_CFG") ? atoi(getenv("SIMCLR_WGRAD_CFG")) : -1;   // per launch: sweeps
-#else
-  static const int cfg_env = getenv("SIMCLR_WGRAD_CFG") ? atoi(getenv("SIMCLR_WGRAD_CFG")) : -1;
-#endif
-  int cfg = cfg_env >= 0 ? cfg_env : 1;
-  if (dtype != SIMCLR_DT_BF16 && cfg > 1) cfg = 1;
-  // the stem's packed input (pixel pitch 4 elements) gives 8-byte-aligned sources: keep the register-staged kernel
-  if (bkw == 32 || stem_mt || (pixpitch * (dtype == SIMCLR_DT_BF16 ? 2 : 4)) % 16 != 0) cfg = 0;
-  const bool big = bkw == 128 && bnw == 128;
-  const bool big256 = bkw == 256 && !stem_mt;
-  if (big256 && cfg == 0) cfg = 1;
-  const bool bf = dtype == SIMCLR_DT_BF16;
-  const int brm = ((cfg >= 2 && big) || (big256 && bf)) ? 1 : 2;
-  const int stages = big256 ? (bf ? 4 : 2) : (cfg <= 1 ? 2 : (big ? (cfg == 2 ? 3 : 4) : 3));
-  const int br = (dtype == SIMCLR_DT_BF16 ? 32 : 16) * brm;
-  // workgroup target of the bf16 launches: 1024 (round 5 sweep, interleaved pairs on one box, ms per step at 768 / 1024 / 1536 / 2048 /
-  // 3072: 64.1 / 63.7 / 63.9 / 64.6 / 65.1 -- fewer, longer pixel ranges write fewer fp32 slabs); the fp32 launches keep the 1536 of
-  // SIMCLR_WGRAD_BLOCKS' default (parity mode 190.5 / 187.4 / 187.2 at 1024 / 1536 / 2048).  The workspace is sized for 1536.
-  static const bool blocks_env = getenv("SIMCLR_WGRAD_BLOCKS") != nullptr;
-  const int want_wg = (dtype == SIMCLR_DT_BF16 && !blocks_env && bkw != 256) ? 1024 : 0;
-  p.splits = stem_mt ? wgrad_splits(p.M, p.K, p.N, bkw, bnw, br, &p.chunks_per_split, 1024, 1024)
-                     : wgrad_splits(p.M, p.K, p.N, bkw, bnw, br, &p.chunks_per_split, 256, want_wg);
-  p.k_tiles = ceil_div(p.K, bkw);
-  p.n_tiles = ceil_div(p.N, bnw);
-  // XCD-aware mapping: with the LDS-DMA kernel a win (or neutral) on every ResNet-50 layer; the register-staged
-  // kernel (cfg 0: stem) keeps the old size rule
-  p.xcd_map = cfg != 0 || (p.M >= 1500000) || (p.M >= 500000 && KH * KW == 1 && stride == 1);
-#ifdef SIMCLR_DIAG
-  { const char* e = getenv("SIMCLR_DIAG"); p.diag = e ? atoi(e) : 0; }
-  { const char* e = getenv("SIMCLR_WGRAD_XCD"); if (e && atoi(e) >= 0) p.xcd_map = atoi(e); }
-#endif
-  p.zero = zero_page();
-  p.split = terms;
-  p.dy_ps = dy_ps ? 1 : 0;
-  SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d_wgrad: zero page symbol not found");
-  SIMCLR_CHECK_ARG(!dy_ps || (cfg != 0 && !stem_mt), "conv2d_wgrad: no pre-split kernel on the register-staged path");
-  const int grid = p.k_tiles * p.n_tiles * (p.xcd_map ? ceil_div(p.splits, 8) * 8 : p.splits);
-  const size_t esz = dtype == SIMCLR_DT_BF16 ? 2 : 4;
-  const size_t lds = (size_t)(cfg == 0 ? 2 : stages) * br * (bkw + bnw) * esz;
-#define LW(TT, A, B) hipLaunchKernelGGL((conv_wgrad<TT, A, B>), dim3(grid), dim3(256), lds, stream, p)
-#define LD(TT, A, B, M_, S_) hipLaunchKernelGGL((conv_wgrad_dma<TT, A, B, M_, S_>), dim3(grid), dim3(256), lds, stream, p)
-  // stem over LDS-DMA: stride 2 on an even-width packed image makes every source 16-byte aligned
-  constexpr bool stem_dma_on = true;
-  const bool stem_dma = stem_mt && stem_dma_on && dtype == SIMCLR_DT_BF16 && KW == 1 && pad == 0 && stride % 2 == 0 && IW % 2 == 0 &&
-                        pixpitch == 4 && Cin == 32;
-  // fp32 stem under split-bf16 terms: a packed pixel is 4 floats = 16 bytes, so every source of the multi-tap k-tile is 16-byte
-  // aligned at ANY stride / width; 32-pixel chunks x 2 stages.  The exact fp32 arithmetic keeps the register-staged kernel.
-  static const bool stem_split_on = !getenv("SIMCLR_STEM_SPLIT") || atoi(getenv("SIMCLR_STEM_SPLIT")) != 0;
-  const bool stem_dma_f32 = stem_mt && stem_dma_on && stem_split_on && dtype == SIMCLR_DT_F32 && p.split != 0 && KW == 1 && pad == 0 &&
-                            pixpitch == 4 && Cin == 32;
-  if (big256 && !bf) {
-    hipLaunchKernelGGL((conv_wgrad_dma<float, 256, 256, 2, 2, 8, 1, false, false, 3, 1>), dim3(grid), dim3(512), lds, stream, p);
-  } else if (big256) {
-    hipLaunchKernelGGL((conv_wgrad_dma<uint16_t, 256, 256, 1, 4, 2, 4>), dim3(grid), dim3(512), lds, stream, p);
-  } else if (stem_dma_f32) {
-    const size_t lds_s = (size_t)2 * 32 * (256 + 64) * 4;      // 2 stages x 32 pixels x (256 + 64) fp32
-    p.xcd_map = 1;
-    const int grid_s = p.k_tiles * p.n_tiles * ceil_div(p.splits, 8) * 8;
-    // 8 waves (4 along the 256 k-rows x 2 along n): 4 k-fragments and 4 LDS-DMA source states per wave -- the 4-wave shape keeps 8 + 8
-    // of them next to the split fragments and spills ~100 registers
-    // SIMCLR_STEM_WGRAD_STAGES=3: a three-deep ring (120 KB) -- two 32-pixel chunks in flight behind the one being multiplied
-    static const int stem_stages = getenv("SIMCLR_STEM_WGRAD_STAGES") ? atoi(getenv("SIMCLR_STEM_WGRAD_STAGES")) : 2;
-    if (p.split == 3 && stem_stages == 3)
-      hipLaunchKernelGGL((conv_wgrad_dma<float, 256, 64, 2, 3, 4, 2, false, true, 3>), dim3(grid_s), dim3(512), lds_s / 2 * 3, stream, p);
-    else if (p.split == 3) hipLaunchKernelGGL((conv_wgrad_dma<float, 256, 64, 2, 2, 4, 2, false, true, 3>), dim3(grid_s), dim3(512), lds_s, stream, p);
-    else hipLaunchKernelGGL((conv_wgrad_dma<float, 256, 64, 2, 2, 4, 2, false, true, 6>), dim3(grid_s), dim3(512), lds_s, stream, p);
-  } else if (stem_dma) {
-    const size_t lds_s = (size_t)2 * 64 * (256 + 64) * 2;      // 2 stages x 64 pixels x (256 + 64) bf16
-    p.xcd_map = 1;
-    const int grid_s = p.k_tiles * p.n_tiles * ceil_div(p.splits, 8) * 8;
-    hipLaunchKernelGGL((conv_wgrad_dma<uint16_t, 256, 64, 2, 2, 2, 2, false, true>), dim3(grid_s), dim3(256), lds_s, stream, p);
-  } else if (stem_mt) {
-    if (dtype == SIMCLR_DT_BF16) hipLaunchKernelGGL((conv_wgrad<uint16_t, 256, 64, true>), dim3(grid), dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((conv_wgrad<float, 256, 64, true>), dim3(grid), dim3(256), lds, stream, p);
-  } else if (cfg == 0) {
-    if (dtype == SIMCLR_DT_BF16) {
-      if (bkw == 128 && bnw == 128) LW(uint16_t, 128, 128);
-      else if (bkw == 128) LW(uint16_t, 128, 64);
-      else if (bkw == 64 && bnw == 128) LW(uint16_t, 64, 128);
-      else if (bkw == 64) LW(uint16_t, 64, 64);
-      else LW(uint16_t, 32, 64);
-    } else {
-      if (bkw == 128 && bnw == 128) LW(float, 128, 128);
-      else if (bkw == 128) LW(float, 128, 64);
-      else if (bkw == 64 && bnw == 128) LW(float, 64, 128);
-      else if (bkw == 64) LW(float, 64, 64);
-      else LW(float, 32, 64);
-    }
-  } else if (dtype != SIMCLR_DT_BF16) {
-    // settled A/B switches of round 6 (profiles/r06_notes.md sections 16, 17): four waves along k on a pre-split gradient (family 39.93 ->
-    // 38.54 ms), plain fp32 gradients split in LDS (37.40 -> 37.21 ms)
-    constexpr bool wk4 = true, ldsps = true;
-#define LDS_(A, B)                                                                                                          \
-    do {                                                                                                                     \
-      if (p.split == 3 && p.dy_ps) {                                                                                         \
-        /* pre-split gradient: four waves along k (each 32 | 16 k-rows x all columns) -- the activation operand, the one still split in   \
-           registers, is then split ONCE per workgroup instead of once per column half (96 -> 48 VALU per 48 MFMAs) */                      \
-        if constexpr ((A) >= 64) { if (wk4) hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 4, 1, false, false, 3, 1>), dim3(grid), dim3(256), lds, stream, p); \
-                                   else hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3, 1>), dim3(grid), dim3(256), lds, stream, p); } \
-        else hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3, 1>), dim3(grid), dim3(256), lds, stream, p); \
-      }                                                                                                                      \
-      else if (p.split == 3) {                                                                                               \
-        /* plain fp32 gradient: split in LDS once per chunk (PSD = 2), then the pre-split kernel's loop with four waves along k */         \
-        if constexpr ((A) >= 64 && (B) % 32 == 0) { if (ldsps) hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 4, 1, false, false, 3, 2>), dim3(grid), dim3(256), lds, stream, p); \
-                                   else hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3>), dim3(grid), dim3(256), lds, stream, p); } \
-        else hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 3>), dim3(grid), dim3(256), lds, stream, p); \
-      }                                                                                                                      \
-      else if (p.split == 6) hipLaunchKernelGGL((conv_wgrad_dma<float, A, B, 2, 2, 2, 2, false, false, 6>), dim3(grid), dim3(256), lds, stream, p); \
-      else LD(float, A, B, 2, 2);                                                                                            \
-    } while (0)
-    if (bkw == 128 && bnw == 128) LDS_(128, 128);
-    else if (bkw == 128) LDS_(128, 64);
-    else if (bkw == 64 && bnw == 128) LDS_(64, 128);
-    else if (bkw == 64) LDS_(64, 64);
-    else LDS_(32, 64);
-#undef LDS_
-  } else if (stages == 2) {
-    if (bkw == 128 && bnw == 128) LD(uint16_t, 128, 128, 2, 2);
-    else if (bkw == 128) LD(uint16_t, 128, 64, 2, 2);
-    else if (bkw == 64 && bnw == 128) LD(uint16_t, 64, 128, 2, 2);
-    else if (bkw == 64) LD(uint16_t, 64, 64, 2, 2);
-    else LD(uint16_t, 32, 64, 2, 2);
+    q.x = x; q.dy = dy; q.dw = (float*)workspace; q.zero = zero;
+    q.V = V; q.H = IH; q.W = IW; q.IC = Cin; q.N = Cout; q.pixpitch = pixpitch; q.M = M;
+    q.ci_tiles = k.k_tiles; q.co_tiles = k.n_tiles;
+    q.splits = k.splits; q.chunks_per_split = k.chunks_per_split; q.hpp = k.hpp;
+    if (k.family == WgradPlan::NINE_TAP_F32PS) run_wgrad3x3_f32ps(k.grid, k.block, k.lds, stream, q);
+    else if (k.stages == 3) run_wgrad3x3_bf16<3>(k.grid, k.block, k.lds, stream, q);
+    else run_wgrad3x3_bf16<2>(k.grid, k.block, k.lds, stream, q);
   } else {
-    if (big && stages == 3) LD(uint16_t, 128, 128, 1, 3);
-    else if (big) LD(uint16_t, 128, 128, 1, 4);
-    else if (bkw == 128) LD(uint16_t, 128, 64, 2, 3);
-    else if (bkw == 64 && bnw == 128) LD(uint16_t, 64, 128, 2, 3);
-    else if (bkw == 64) LD(uint16_t, 64, 64, 2, 3);
-    else LD(uint16_t, 32, 64, 2, 3);
+    WgradP p = {};
+    p.x = x; p.dy = dy; p.dw = (float*)workspace; p.zero = zero;
+    p.V = V; p.IH = IH; p.IW = IW; p.IC = Cin; p.OH = OH; p.OW = OW; p.N = Cout;
+    p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pixpitch = pixpitch;
+    p.M = M; p.K = K;
+    p.splits = k.splits; p.chunks_per_split = k.chunks_per_split;
+    p.k_tiles = k.k_tiles; p.n_tiles = k.n_tiles; p.xcd_map = k.xcd_map;
+    p.split = terms;
+    p.dy_ps = dy_ps ? 1 : 0;
+#ifdef SIMCLR_DIAG
+    { const char* e = getenv("SIMCLR_DIAG"); p.diag = e ? atoi(e) : 0; }
+#endif
+    launch_wgrad(k, dtype == SIMCLR_DT_BF16, stream, p);
   }
-#undef LD
-#undef LW
   SIMCLR_CHECK_LAUNCH();
-  const long long numel = (long long)p.K * p.N;
-  hipLaunchKernelGGL(slab_reduce, dim3(max(1, (int)ceil_div(numel / 4, 16))), dim3(256), 0, stream,
-                     (const float*)workspace, p.splits, numel, dw, accumulate);
+  run_slab_reduce(workspace, k.splits, (long long)K * Cout, dw, accumulate, stream);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4502,56 +4571,41 @@ int simclr_conv2d_wgrad(const void* x, const void* dy, float* dw, int accumulate
 // (Gram matrix row-major, then the K column sums).  K in {64, 128, 256}: one tile spans all channels, the activation
 // is streamed ONCE.  workspace: simclr_conv2d_gram_workspace_bytes.
 size_t simclr_conv2d_gram_workspace_bytes(long long M, int K, int dtype) {
-  int cps;
-  const int br = (dtype == SIMCLR_DT_BF16 ? 64 : 32);
-  const int splits = wgrad_splits(M, K, K, K, K, K == 256 ? br / 2 : br, &cps, K == 256 ? 512 : 1024, K == 256 ? 512 : 1024);
-  return (size_t)splits * ((size_t)K * K + K) * sizeof(float);
+  return (size_t)plan_gram(M, K, dtype).splits * ((size_t)K * K + K) * sizeof(float);
 }
 int simclr_conv2d_gram(const void* h, float* out, void* workspace, long long M, int K, int dtype, hipStream_t stream) {
   // fp32 storage: dtype may carry the matrix-arithmetic field (SIMCLR_FMT_TERMS) of the forward pass this Gram matrix serves.  Exact
   // arithmetic -> exact fp32 MFMA; any split mode -> SIX bf16-piece terms (fp32-level products at 2.7x the fp32 MFMA rate: the Gram
-  // launches were the last exact-fp32 matrix work of the fast parity step)
+  // launches were the last exact-fp32 matrix work of the fast parity step; step 140.16 -> 139.71 ms in three pairs, every gate of the
+  // fused-tail / fold / step tests unchanged)
   const int terms = terms_of(&dtype, true);
   SIMCLR_CHECK_ARG(terms >= 0, "conv2d_gram: bad matrix-arithmetic field in dtype (SIMCLR_FMT_TERMS)");
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_gram: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(K == 64 || K == 128 || (K == 256 && dtype == SIMCLR_DT_BF16), "conv2d_gram: K=%d not supported (64, 128, bf16 256)", K);
   SIMCLR_CHECK_ARG(M > 0 && M < (1ll << 31), "conv2d_gram: bad M");
+  const WgradPlan k = plan_gram(M, K, dtype);
   WgradP p = {};
   p.x = h; p.dy = h; p.dw = (float*)workspace;
   p.V = 1; p.IH = 1; p.IW = (int)M; p.IC = K; p.OH = 1; p.OW = (int)M; p.N = K;
   p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.pixpitch = K;
   p.M = (int)M; p.K = K;
-  const int br = (dtype == SIMCLR_DT_BF16 ? 64 : 32) / (K == 256 ? 2 : 1);
-  // one tile per pixel range: up to 1024 workgroups (4 per CU) share the streaming
-  p.splits = wgrad_splits(M, K, K, K, K, br, &p.chunks_per_split, K == 256 ? 512 : 1024, K == 256 ? 512 : 1024);
-  p.k_tiles = 1; p.n_tiles = 1; p.xcd_map = 1;
+  p.splits = k.splits; p.chunks_per_split = k.chunks_per_split;
+  p.k_tiles = k.k_tiles; p.n_tiles = k.n_tiles; p.xcd_map = k.xcd_map;
   p.zero = zero_page();
   SIMCLR_CHECK_ARG(p.zero != nullptr, "conv2d_gram: zero page symbol not found");
-  const int grid = ceil_div(p.splits, 8) * 8;
-  const size_t esz = dtype == SIMCLR_DT_BF16 ? 2 : 4;
-  if (K == 256) {
-    const size_t lds = (size_t)4 * br * K * esz;
-    hipLaunchKernelGGL((conv_wgrad_dma<uint16_t, 256, 256, 1, 4, 2, 4, true>), dim3(grid), dim3(512), lds, stream, p);
+  if (K == 256) run_wgrad_dma<uint16_t, 256, 256, 1, 4, 2, 4, true>("gram", k.grid, k.block, k.lds, stream, p);
+  else if (dtype == SIMCLR_DT_BF16) {
+    if (K == 64) run_wgrad_dma<uint16_t, 64, 64, 2, 4, 2, 2, true>("gram", k.grid, k.block, k.lds, stream, p);
+    else run_wgrad_dma<uint16_t, 128, 128, 2, 4, 2, 2, true>("gram", k.grid, k.block, k.lds, stream, p);
+  } else if (terms != 0) {
+    if (K == 64) run_wgrad_dma<float, 64, 64, 2, 4, 2, 2, true, false, 6>("gram", k.grid, k.block, k.lds, stream, p);
+    else run_wgrad_dma<float, 128, 128, 2, 4, 2, 2, true, false, 6>("gram", k.grid, k.block, k.lds, stream, p);
   } else {
-    // 4-stage ring of 64-pixel (bf16) chunks holding the activation tile only: three chunks in flight per workgroup
-    const size_t lds = (size_t)4 * br * K * esz;
-    if (dtype == SIMCLR_DT_BF16) {
-      if (K == 64) hipLaunchKernelGGL((conv_wgrad_dma<uint16_t, 64, 64, 2, 4, 2, 2, true>), dim3(grid), dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((conv_wgrad_dma<uint16_t, 128, 128, 2, 4, 2, 2, true>), dim3(grid), dim3(256), lds, stream, p);
-    } else {
-      // (A/B on one box, r06_call52: step 140.16 -> 139.71 ms in three pairs; every gate of the fused-tail / fold / step tests unchanged)
-      if (terms != 0) {
-        if (K == 64) hipLaunchKernelGGL((conv_wgrad_dma<float, 64, 64, 2, 4, 2, 2, true, false, 6>), dim3(grid), dim3(256), lds, stream, p);
-        else hipLaunchKernelGGL((conv_wgrad_dma<float, 128, 128, 2, 4, 2, 2, true, false, 6>), dim3(grid), dim3(256), lds, stream, p);
-      }
-      else if (K == 64) hipLaunchKernelGGL((conv_wgrad_dma<float, 64, 64, 2, 4, 2, 2, true>), dim3(grid), dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((conv_wgrad_dma<float, 128, 128, 2, 4, 2, 2, true>), dim3(grid), dim3(256), lds, stream, p);
-    }
+    if (K == 64) run_wgrad_dma<float, 64, 64, 2, 4, 2, 2, true>("gram", k.grid, k.block, k.lds, stream, p);
+    else run_wgrad_dma<float, 128, 128, 2, 4, 2, 2, true>("gram", k.grid, k.block, k.lds, stream, p);
   }
   SIMCLR_CHECK_LAUNCH();
-  const long long numel = (long long)K * K + K;
-  hipLaunchKernelGGL(slab_reduce, dim3(max(1, (int)ceil_div(numel / 4, 16))), dim3(256), 0, stream,
-                     (const float*)workspace, p.splits, numel, out, 0);
+  run_slab_reduce(workspace, k.splits, (long long)K * K + K, out, 0, stream);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -4701,17 +4755,8 @@ int simclr_presplit_packed(const void* xp, void* xq, long long npix, hipStream_t
 }
 // 1 if simclr_stem_wgrad_ps has a kernel for this stem (the 7x7 / stride-2 ImageNet stem with 64 output channels)
 int simclr_stem_wgrad_ps_supported(int KH, int KWP, int stride, int Cout) { return KH == 7 && KWP == 8 && stride == 2 && Cout == 64; }
-static int stem_wgrad_ps_splits(long long chunks, int* cps) {
-  // four two-wave workgroups per CU (two per SIMD pair), every one of them resident for the whole launch
-  static const int want_env = getenv("SIMCLR_STEM_WGRAD_BLOCKS") ? atoi(getenv("SIMCLR_STEM_WGRAD_BLOCKS")) : 1024;
-  const int want = (int)max(1ll, min((long long)max(8, min(want_env, 1024)), chunks));
-  *cps = (int)((chunks + want - 1) / want);
-  return (int)((chunks + *cps - 1) / *cps);
-}
 size_t simclr_stem_wgrad_ps_workspace_bytes(int V, int OH, int OW, int KH) {
-  int cps;
-  const long long chunks = (long long)V * OH * ((OW + 31) / 32);
-  return (size_t)stem_wgrad_ps_splits(chunks, &cps) * KH * 32 * 64 * sizeof(float);
+  return (size_t)plan_stem_wgrad_ps(V, OH, OW).splits * KH * 32 * 64 * sizeof(float);
 }
 // xq: simclr_presplit_packed of the packed views [V][HP][WP][4]; dy_ps [V*OH*OW][64] in the pre-split block format;
 // dw_kn: fp32 [KH*KWP*4][64] (what simclr_unpack_stem_dw reads); accumulate != 0: dw_kn += result.
@@ -4724,18 +4769,14 @@ int simclr_stem_wgrad_ps(const void* xq, const void* dy_ps, float* dw_kn, int ac
   StemWgP p = {};
   p.xq = xq; p.dy = dy_ps; p.dw = (float*)workspace; p.zero = zero_page();
   SIMCLR_CHECK_ARG(p.zero != nullptr, "stem_wgrad_ps: zero page symbol not found");
+  const WgradPlan k = plan_stem_wgrad_ps(V, OH, OW);
   p.HP = HP; p.WP = WP; p.OH = OH; p.OW = OW; p.segs = (OW + 31) / 32;
-  const long long chunks = (long long)V * OH * p.segs;
-  p.chunks = (int)chunks;
-  p.splits = stem_wgrad_ps_splits(chunks, &p.chunks_per_split);
-  static const int stages_env = getenv("SIMCLR_STEM_WGRAD_PS_STAGES") ? atoi(getenv("SIMCLR_STEM_WGRAD_PS_STAGES")) : 2;
-  constexpr int stage_bytes = ((7 * 70 + 63) / 64 + 8) * 1024;
-  if (stages_env == 3) hipLaunchKernelGGL((stem_wgrad_ps<7, 2, 3>), dim3(p.splits), dim3(128), 3 * stage_bytes, stream, p);
-  else hipLaunchKernelGGL((stem_wgrad_ps<7, 2, 2>), dim3(p.splits), dim3(128), 2 * stage_bytes, stream, p);
+  p.chunks = V * OH * p.segs;
+  p.splits = k.splits; p.chunks_per_split = k.chunks_per_split;
+  if (k.stages == 3) run_stem_wgrad_ps<3>(k.grid, k.block, k.lds, stream, p);
+  else run_stem_wgrad_ps<2>(k.grid, k.block, k.lds, stream, p);
   SIMCLR_CHECK_LAUNCH();
-  const long long numel = (long long)KH * 32 * 64;
-  hipLaunchKernelGGL(slab_reduce, dim3(max(1, (int)ceil_div(numel / 4, 16))), dim3(256), 0, stream, (const float*)workspace, p.splits,
-                     numel, dw_kn, accumulate);
+  run_slab_reduce(workspace, k.splits, (long long)KH * 32 * 64, dw_kn, accumulate, stream);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -972,18 +972,19 @@ def check_ps_weight_pieces(Cin, Cout, k, seed=0):
         ops.set_f32_matmul('exact')
 
 
-def check_wgrad_workspace_bound(V, H, Cin, Cout, k, matmul='f16x3_3', ps=True, seed=0):
+def check_wgrad_workspace_bound(V, H, Cin, Cout, k, matmul='f16x3_3', ps=True, seed=0, dtype=torch.float32):
     """simclr_conv2d_wgrad writes its split-K slabs into a caller-provided workspace of simclr_conv2d_wgrad_workspace_bytes: every kernel
     variant the launcher may pick (per-tap, nine-tap with 32-pixel chunks, the 256 x 256 tile) must stay inside it.  The workspace here is
     EXACTLY that size, followed by a poisoned guard region that must come back untouched, and the result must equal the one computed
-    with the library's shared (larger) scratch buffer."""
+    with the library's shared (larger) scratch buffer.  dtype: storage type of x and dy (a pre-split dy is an fp32 format)."""
     from simclr_amd._lib import lib
+    assert dtype == torch.float32 or not ps
     ops.set_f32_matmul(matmul)
     try:
         g = torch.Generator(device=DEV).manual_seed(seed)
         pad = (k - 1) // 2
-        x = torch.randn(V, H, H, Cin, device=DEV, generator=g)
-        dy = torch.randn(V, H, H, Cout, device=DEV, generator=g) * 1e-3
+        x = torch.randn(V, H, H, Cin, device=DEV, generator=g).to(dtype)
+        dy = (torch.randn(V, H, H, Cout, device=DEV, generator=g) * 1e-3).to(dtype)
         if ps:
             one, zero = torch.ones(Cout, device=DEV), torch.zeros(Cout, device=DEV)
             dy, _ = ops.bn_bwd_apply(dy, dy, None, one, zero, zero, one, zero, zero, 0, ps_out=True)
@@ -995,10 +996,35 @@ def check_wgrad_workspace_bound(V, H, Cin, Cout, k, matmul='f16x3_3', ps=True, s
         lib().conv2d_wgrad(ops._p(x), ops._pp(dy), ops._p(out), 0, ops._p(buf), V, H, H, Cin, Cin, H, H, Cout, k, k, 1, pad,
                            ops.dt(x) | (ops.FMT_PS_IN if ops.ps_kind(dy) else 0) | ops._tb(), ops._s())
         torch.cuda.synchronize()
-        tag = 'V%d %dx%d %d->%d k%d %s' % (V, H, H, Cin, Cout, k, 'ps' if ps else 'plain')
+        tag = 'V%d %dx%d %d->%d k%d %s %s %s' % (V, H, H, Cin, Cout, k, 'ps' if ps else 'plain', str(dtype).split('.')[-1], matmul)
         tail = buf[(nbytes + 3) // 4:]
         return [_res('wgrad_ws_guard_untouched ' + tag, tail, torch.full_like(tail, 12345.0), 0.0),
                 _res('wgrad_ws_same_result ' + tag, out, ref, 0.0)]
+    finally:
+        ops.set_f32_matmul('exact')
+
+
+def check_gram_workspace_bound(M, K, dtype, matmul='f16x3_3', seed=0):
+    """The Gram counterpart of check_wgrad_workspace_bound: simclr_conv2d_gram with a workspace of EXACTLY
+    simclr_conv2d_gram_workspace_bytes, followed by a poisoned guard region that must come back untouched; the result equals
+    ops.conv2d_gram's (the same deterministic kernel on the library's shared scratch buffer) bit for bit."""
+    from simclr_amd._lib import lib
+    ops.set_f32_matmul(matmul)
+    try:
+        g = torch.Generator(device=DEV).manual_seed(seed)
+        h = torch.randn(M, K, device=DEV, generator=g).to(dtype)
+        gm, cs = ops.conv2d_gram(h)
+        nbytes = lib().conv2d_gram_workspace_bytes(M, K, ops.dt(h))
+        guard = 1 << 20
+        buf = torch.full(((nbytes + 3) // 4 + guard,), 12345.0, device=DEV, dtype=torch.float32)
+        out = torch.empty(K * K + K, device=DEV, dtype=torch.float32)
+        lib().conv2d_gram(ops._p(h), ops._p(out), ops._p(buf), M, K, ops.dt(h) | (ops._tf() if dtype == torch.float32 else 0), ops._s())
+        torch.cuda.synchronize()
+        tag = 'M%d K%d %s %s' % (M, K, str(dtype).split('.')[-1], matmul)
+        tail = buf[(nbytes + 3) // 4:]
+        return [_res('gram_ws_guard_untouched ' + tag, tail, torch.full_like(tail, 12345.0), 0.0),
+                _res('gram_ws_same_matrix ' + tag, out[:K * K], gm.reshape(-1), 0.0),
+                _res('gram_ws_same_colsum ' + tag, out[K * K:], cs, 0.0)]
     finally:
         ops.set_f32_matmul('exact')
 

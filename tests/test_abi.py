@@ -177,6 +177,134 @@ def test_instantiation_table_matches_the_committed_one():
     assert len(rows) > 200 and any('conv_igemm_wide' in l for l in rows) and any('elt=4' in l and ', 6>' in l for l in rows)
 
 
+def test_wgrad_instantiation_table_matches_the_committed_one():
+    """The weight-gradient side of the same table (tools/instantiation_table.py --what wgrad): which kernel, tile, split count and
+    slab-reduction grid every (layer class, operand format) selects, the stem and the Gram launches included."""
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'instantiation_table.py'), '--what', 'wgrad'], capture_output=True, text=True,
+                       timeout=300, env={k: v for k, v in os.environ.items() if not k.startswith('SIMCLR_')})
+    assert r.returncode == 0, r.stderr[-2000:]
+    want = open(os.path.join(ROOT, 'profiles', 'wgrad_instantiations.txt')).read()
+    assert r.stdout == want, 'the weight-gradient table changed: regenerate profiles/wgrad_instantiations.txt with tools/instantiation_table.py --what wgrad and review the diff'
+    rows = [l for l in want.splitlines() if l and not l.startswith('#')]
+    assert len(rows) == 5 * 25 + 4 + 1 + 14 and all('splits=' in l and 'reduce_grid=' in l for l in rows)
+    for kern in ('conv_wgrad3x3_bf16<3>', 'conv_wgrad3x3_f32ps', 'conv_wgrad_dma<uint16_t, 256, 256', 'conv_wgrad_dma<float, 256, 256', 'conv_wgrad<',
+                 'stem_wgrad_ps<7, 2, 2>', 'role=gram'):
+        assert any(kern in l for l in rows), kern
+
+
+# Every weight-gradient, Gram and pre-split stem launch of a sweep over shapes and operand formats, in a dry run: the split count of the
+# record times the slab size must fit the workspace the matching *_workspace_bytes function reports.  Prints the number of launches checked
+# and the number the entry point refused (a pre-split dy while SIMCLR_WGRAD_CFG=0 forces the register-staged kernels: nothing is launched).
+_WGRAD_WORKSPACE_SWEEP = r'''
+import ctypes, re, sys
+sys.path.insert(0, 'tools')
+from simclr_amd import _lib
+from instantiation_table import LAYERS, WGRAD_MODES, GRAM_MODES, PS_IN, stem_geometry
+L = _lib.lib()
+FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced in a dry run
+splits = lambda: int(re.search(r' splits=(\d+) ', L.conv2d_last_instantiation().decode()).group(1))
+shapes = {(H, Cin, Cout, k, s) for _, H, Cin, Cout, k, s, _ in LAYERS}
+shapes |= {(14, 32, 64, 3, 1), (14, 32, 64, 1, 1), (28, 32, 32, 3, 2)}                                   # Cin = 32
+shapes |= {(14, Cin, Cout, k, 1) for Cin in (64, 256) for Cout in (8, 72, 192) for k in (1, 3)}        # Cout 8, 72, 192
+shapes |= {(28, 128, 128, 3, 2), (28, 512, 1024, 1, 2), (14, 64, 192, 3, 2)}                             # stride 2
+n = refused = 0
+for V in (1, 3, 8, 40, 1024):
+    for mode, dtype, flags in WGRAD_MODES:
+        for H, Cin, Cout, k, s in sorted(shapes):
+            if flags & PS_IN and (Cin % 64 or Cout % 32):
+                continue                                   # the entry point accepts a pre-split dy for these channel counts only
+            pad = (k - 1) // 2
+            OH = (H + (k - 1) - k) // s + 1
+            try:
+                L.conv2d_wgrad(FAKE, FAKE, FAKE, 0, FAKE, V, H, H, Cin, Cin, OH, OH, Cout, k, k, s, pad, dtype | flags, None)
+            except _lib.SimclrHipError as e:               # SIMCLR_WGRAD_CFG=0: the register-staged kernels read no pre-split dy
+                assert flags & PS_IN and 'no pre-split kernel on the register-staged path' in str(e), e
+                refused += 1
+                continue
+            have = L.conv2d_wgrad_workspace_bytes(V, OH, OH, Cin, Cout, k, k, dtype)
+            assert splits() * k * k * Cin * Cout * 4 <= have, (V, mode, H, Cin, Cout, k, s, L.conv2d_last_instantiation(), have)
+            n += 1
+        if not flags & PS_IN:                              # the packed stem: 7 kernel rows x 32 packed elements, pixel pitch 4
+            for Hs in (32, 224):
+                OH, HP, WP = stem_geometry(Hs)
+                L.conv2d_wgrad(FAKE, FAKE, FAKE, 0, FAKE, V, HP, WP, 32, 4, OH, OH, 64, 7, 1, 2, 0, dtype | flags, None)
+                have = L.conv2d_wgrad_workspace_bytes(V, OH, OH, 32, 64, 7, 1, dtype)
+                assert splits() * 7 * 32 * 64 * 4 <= have, (V, mode, 'stem', Hs, L.conv2d_last_instantiation(), have)
+                n += 1
+    for Hs in (32, 224):
+        OH, HP, WP = stem_geometry(Hs)
+        L.stem_wgrad_ps(FAKE, FAKE, FAKE, 0, FAKE, V, HP, WP, OH, OH, 64, 7, 8, 2, None)
+        have = L.stem_wgrad_ps_workspace_bytes(V, OH, OH, 7)
+        assert splits() * 7 * 32 * 64 * 4 <= have, (V, 'stem_wgrad_ps', Hs, L.conv2d_last_instantiation(), have)
+        n += 1
+    for mode, dtype, flags in GRAM_MODES:
+        for K in (64, 128, 256):
+            for H in (7, 28, 56):
+                if K == 256 and dtype != _lib.DT_BF16:
+                    continue
+                L.conv2d_gram(FAKE, FAKE, FAKE, V * H * H, K, dtype | flags, None)
+                have = L.conv2d_gram_workspace_bytes(V * H * H, K, dtype)
+                assert splits() * (K * K + K) * 4 <= have, (V, mode, 'gram', K, H, L.conv2d_last_instantiation(), have)
+                n += 1
+print('ok', n, refused)
+'''
+
+_WGRAD_SWEEP_SETTINGS = [{}, {'SIMCLR_WGRAD_BLOCKS': '64'}, {'SIMCLR_WGRAD_BLOCKS': '4096'}, {'SIMCLR_WGRAD3_BLOCKS': '8'},
+                         {'SIMCLR_WGRAD3_BLOCKS': '100000'}, {'SIMCLR_WGRAD_256': '0'}, {'SIMCLR_WGRAD_3X3': '0'}, {'SIMCLR_WGRAD_CFG': '0'},
+                         {'SIMCLR_WGRAD_CFG': '2'}, {'SIMCLR_WGRAD_CFG': '3'}]
+
+
+@pytest.mark.parametrize('setting', _WGRAD_SWEEP_SETTINGS, ids=lambda d: ','.join('%s=%s' % kv for kv in d.items()) or 'defaults')
+def test_every_weight_gradient_launch_fits_its_workspace(setting):
+    """simclr_conv2d_wgrad_workspace_bytes / _gram_workspace_bytes / simclr_stem_wgrad_ps_workspace_bytes size the split-K slabs with
+    the plan the launcher itself follows: no launch of the sweep -- layer classes at 1 ... 1024 views, Cin = 32, Cout 8 / 72 / 192,
+    stride 2, the packed stem, every operand format -- under any weight-gradient switch needs more slabs than its workspace holds."""
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('SIMCLR_')}
+    env.update(setting, SIMCLR_DRY_RUN='1')
+    r = subprocess.run([sys.executable, '-c', _WGRAD_WORKSPACE_SWEEP], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith('ok '), r.stdout + r.stderr[-2000:]
+    checked, refused = map(int, r.stdout.split()[1:])
+    assert checked + refused == 1125 and (refused == 0 or setting == {'SIMCLR_WGRAD_CFG': '0'}), r.stdout      # none was skipped
+
+
+_WGRAD_SWITCHES_PER_LAUNCH = r'''
+import ctypes, os
+from simclr_amd import _lib
+L = _lib.lib()
+FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced in a dry run
+
+
+def wgrad(V, H, Cin, Cout):
+    L.conv2d_wgrad(FAKE, FAKE, FAKE, 0, FAKE, V, H, H, Cin, Cin, H, H, Cout, 1, 1, 1, 0, _lib.DT_BF16, None)
+    return L.conv2d_last_instantiation().decode()
+
+
+os.environ['SIMCLR_WGRAD_CFG'] = '0'
+a = wgrad(8, 14, 256, 512)
+del os.environ['SIMCLR_WGRAD_CFG']
+b = wgrad(8, 14, 256, 512)
+assert a != b and a.startswith('(conv_wgrad<uint16_t, 128, 128>)') and b.startswith('(conv_wgrad_dma<uint16_t, 128, 128, 2, 2>)'), (a, b)
+os.environ['SIMCLR_WGRAD_256'] = '0'
+a = wgrad(1024, 28, 512, 256)            # M = 802 816 rows, 256-channel multiples: the 256 x 256 tile by default
+del os.environ['SIMCLR_WGRAD_256']
+b = wgrad(1024, 28, 512, 256)
+assert a != b and a.startswith('(conv_wgrad_dma<uint16_t, 128, 128, 2, 2>)') and b.startswith('(conv_wgrad_dma<uint16_t, 256, 256, 1, 4, 2, 4>)'), (a, b)
+print('ok')
+'''
+
+
+def test_weight_gradient_switches_are_read_per_launch():
+    """plan_wgrad reads its SIMCLR_* switches at every launch, in every build: a sweep that flips one between two calls of one process
+    (tools/diag_conv.py --wgrad, tools/bench_wgrad3x3.py) times two different configurations."""
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('SIMCLR_')}
+    env.update(SIMCLR_DRY_RUN='1')
+    r = subprocess.run([sys.executable, '-c', _WGRAD_SWITCHES_PER_LAUNCH], capture_output=True, text=True, env=env, cwd=ROOT, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stdout + r.stderr[-2000:]
+
+
 _UNSUPPORTED_STRIDED_DGRAD = r'''
 import ctypes
 from simclr_amd import _lib

@@ -559,6 +559,22 @@ def test_weight_gradient_stays_inside_its_workspace(V, H, Cin, Cout, k, ps):
     _assert(gc.check_wgrad_workspace_bound(V, H, Cin, Cout, k, ps=ps))
 
 
+@pytest.mark.parametrize('V,H,Cin,Cout,k,dtype,matmul', [(30, 14, 64, 64, 3, BF, 'exact'),     # bf16 nine-tap kernel, ONE tile
+                                                          (8, 14, 256, 512, 1, BF, 'exact'),    # bf16 1x1: LDS-DMA ring, 128 x 128 tile
+                                                          (4, 28, 128, 128, 3, F32, 'exact')])  # exact fp32 arithmetic, plain dy, per-tap
+def test_weight_gradient_stays_inside_its_workspace_other_formats(V, H, Cin, Cout, k, dtype, matmul):
+    """The paths the pre-split cases above do not reach: bf16 storage and the exact fp32 arithmetic."""
+    from tests import gpu_checks as gc
+    _assert(gc.check_wgrad_workspace_bound(V, H, Cin, Cout, k, matmul=matmul, ps=False, dtype=dtype))
+
+
+@pytest.mark.parametrize('K,dtype', [(64, F32), (128, F32), (256, BF)])
+def test_gram_stays_inside_its_workspace(K, dtype):
+    """simclr_conv2d_gram on a workspace of exactly simclr_conv2d_gram_workspace_bytes (both from plan_gram): guard untouched, same bits."""
+    from tests import gpu_checks as gc
+    _assert(gc.check_gram_workspace_bound(8 * 14 * 14, K, dtype))
+
+
 @pytest.mark.parametrize('Cin,Cout,k', [(64, 64, 1), (128, 96, 3)])
 def test_presplit_weight_pieces_equal_torch_rounding(Cin, Cout, k):
     from tests import gpu_checks as gc

@@ -2,12 +2,17 @@
 """(layer class -> kernel instantiation) table of the forward / data-gradient convolution launches.
 
     python tools/instantiation_table.py [--views 1024] [--out profiles/r06_instantiations.txt]
+    python tools/instantiation_table.py --what wgrad [--out profiles/wgrad_instantiations.txt]
 
 Runs WITHOUT a GPU: with SIMCLR_DRY_RUN=1 the convolution entry points of libsimclr_hip.so take every launch decision
 (plan_igemm: tile shape, halo window, wide eight-phase tile, split tail, pre-split weights, compile-time epilogue
 specialisations) and record it instead of launching (simclr_conv2d_last_instantiation).  One row per (ResNet-50 1x layer class at
 224 px) x (kind of launch a training step issues for it) x (storage / matrix arithmetic).  tests/test_abi.py regenerates the
 table and compares it with the committed file, so a change of the selection rules is a visible diff, not a silent one.
+
+--what wgrad: the same for the weight-gradient side -- simclr_conv2d_wgrad per layer class and operand format (bf16; fp32 with every
+backward term count; fp32, three terms, pre-split dy), the 7x7 stem as the multi-tap call and as simclr_stem_wgrad_ps, and the Gram
+launches of the fused bottleneck tail.  Each record ends with the split-K geometry and the grid of the slab reduction.
 """
 import argparse
 import ctypes
@@ -96,6 +101,67 @@ def rows(views):
     return out
 
 
+# weight-gradient operand formats: (name, storage dtype, flags of the dtype argument); SIMCLR_FMT_TERMS(t) = (t + 1) << 12
+TERMS = lambda t: (t + 1) << 12
+PS_IN = 0x100
+WGRAD_MODES = [('bf16', 1, 0), ('f32 exact', 0, TERMS(0)), ('f32 bf16x3', 0, TERMS(3)), ('f32 bf16x6', 0, TERMS(6)),
+               ('f32 bf16x3 pre-split dy', 0, TERMS(3) | PS_IN)]
+# (name, K, H of the activation, launches per step): the fused bottleneck tail's Gram matrices at the row counts of the 56^2 and 28^2
+# blocks (conv3 reads 64 channels in the three 56^2 blocks, 128 in the four 28^2 blocks; x0 = no ResNet-50 1x launch, the rule only)
+GRAMS = [('gram 64 @56', 64, 56, 3), ('gram 128 @28', 128, 28, 4), ('gram 64 @28', 64, 28, 0), ('gram 128 @56', 128, 56, 0),
+         ('gram 256 @56', 256, 56, 0), ('gram 256 @28', 256, 28, 0)]
+GRAM_MODES = [('bf16', 1, 0), ('f32 exact', 0, TERMS(0)), ('f32 split', 0, TERMS(13))]
+
+
+def stem_geometry(H=224, k=7, s=2):
+    """simclr_amd.ops.stem_geometry for the 7x7 / stride-2 stem: packed image HP x WP, 8 taps per packed kernel row."""
+    OH = (H + (k - 1) - k) // s + 1
+    HP = max((OH - 1) * s + k, H + (k - 1) // 2)
+    WP = (max((OH - 1) * s + 8, H + (k - 1) // 2) + 1) // 2 * 2
+    return OH, HP, WP
+
+
+def wgrad_rows(views):
+    os.environ['SIMCLR_DRY_RUN'] = '1'
+    from simclr_amd._lib import lib, SimclrHipError
+    L = lib()
+    out = []
+    last = lambda: L.conv2d_last_instantiation().decode()
+    V = views
+    try:
+        for mode, dtype, flags in WGRAD_MODES:
+            for name, H, Cin, Cout, k, s, cnt in LAYERS:
+                pad = (k - 1) // 2
+                OH = (H + (k - 1) - k) // s + 1
+                L.conv2d_wgrad(FAKE, FAKE, FAKE, 0, FAKE, V, H, H, Cin, Cin, OH, OH, Cout, k, k, s, pad, dtype | flags, None)
+                out.append((mode, name, cnt, 'wgrad', last()))
+            if not flags & PS_IN:        # the packed stem: one 'tap' per kernel row of 8 x 4 packed elements, pixel pitch 4
+                OH, HP, WP = stem_geometry()
+                L.conv2d_wgrad(FAKE, FAKE, FAKE, 0, FAKE, V, HP, WP, 32, 4, OH, OH, 64, 7, 1, 2, 0, dtype | flags, None)
+                out.append((mode, 'stem 7x7 s2 3->64', 1, 'stem wgrad (multi-tap)', last()))
+        OH, HP, WP = stem_geometry()
+        L.stem_wgrad_ps(FAKE, FAKE, FAKE, 0, FAKE, V, HP, WP, OH, OH, 64, 7, 8, 2, None)
+        out.append(('f32 bf16x3 pre-split dy', 'stem 7x7 s2 3->64', 1, 'stem wgrad (pre-split operands)', last()))
+        for mode, dtype, flags in GRAM_MODES:
+            for name, K, H, cnt in GRAMS:
+                if K == 256 and dtype != 1:
+                    continue
+                L.conv2d_gram(FAKE, FAKE, FAKE, V * H * H, K, dtype | flags, None)
+                out.append((mode, name, cnt, 'gram', last()))
+    finally:
+        os.environ.pop('SIMCLR_DRY_RUN', None)
+    return out
+
+
+def render_wgrad(views):
+    lines = ['# weight-gradient / Gram kernel instantiation per (ResNet-50 1x layer class, operand format) at %d views' % views,
+             '# generated by tools/instantiation_table.py --what wgrad (SIMCLR_DRY_RUN=1: decisions only, no device); columns:',
+             '# operand format | layer class | launches per step of this class | launch kind | instantiation record', '']
+    for mode, name, cnt, kind, inst in wgrad_rows(views):
+        lines.append(' | '.join([mode, name, 'x%d' % cnt, kind, inst]))
+    return '\n'.join(lines) + '\n'
+
+
 def render(views):
     lines = ['# forward / data-gradient kernel instantiation per (ResNet-50 1x layer class, launch kind, storage mode) at %d views' % views,
              '# generated by tools/instantiation_table.py (SIMCLR_DRY_RUN=1: decisions only, no device); columns:',
@@ -109,8 +175,9 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--views', type=int, default=1024)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--what', choices=['igemm', 'wgrad'], default='igemm', help='forward / data-gradient table (default) or weight-gradient table')
     a = ap.parse_args()
-    txt = render(a.views)
+    txt = render_wgrad(a.views) if a.what == 'wgrad' else render(a.views)
     if a.out:
         open(a.out, 'w').write(txt)
         print('wrote %d rows to %s' % (txt.count('\n') - 4, a.out))
