@@ -137,6 +137,25 @@ int simclr_gcl_swd_bwd(const float* g_all, const float* z_local, int n, int N, i
  * matmul(., rand_w) projections and their transposes (simclr_small_gemm_nt_f32 needs M and N multiples of 16). */
 int simclr_gcl_gemm_nt(const float* A, const float* B, float* C, int M, int N, int K, simclr_stream_t stream);
 
+/* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
+/* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
+ * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.
+ * Row i of top_val [Q, k] fp32 / top_idx [Q, k] int32 = the first k pairs of the total order "similarity descending, bank index
+ * ascending", in that order; a NaN similarity orders below every number.  1 <= k <= 256 (a candidate list is sorted in LDS),
+ * k <= N < 2^31, D a multiple of 16, Q >= 1.  The [Q, N] matrix is never written: a workgroup keeps the k best of a bank slab of
+ * simclr_knn_slab_rows() rows per query, a second launch merges the slabs; workspace = Q * ceil(N / slab) * k * 8 bytes.  No
+ * floating-point atomics; bitwise repeatable. */
+int simclr_knn_slab_rows(void);
+size_t simclr_knn_workspace_bytes(int Q, int N, int D, int k);
+int simclr_knn_topk(const float* q, const float* bank, int Q, int N, int D, int k, float* top_val, int* top_idx, void* workspace,
+                    simclr_stream_t stream);
+/* top_val [Q, k] as written by simclr_knn_topk, top_label [Q, k] int32 = the neighbours' class ids.  w_r = exp((top_val[i,r] -
+ * top_val[i,0]) / temperature) in fp32; score_c = the sum of w_r over the neighbours of class c, added in ascending rank order r.
+ * pred [Q, 5] int32 / score [Q, 5] fp32 = the five best classes by "score descending, class id ascending" (classes without a neighbour
+ * score 0); with fewer than five classes the unused entries are -1 / 0.  The class scores live in LDS: 1 <= num_classes <= 32768. */
+int simclr_knn_vote(const float* top_val, const int* top_label, int Q, int k, int num_classes, float temperature, int* pred, float* score,
+                    simclr_stream_t stream);
+
 /* ---- LARS: tf2/lars_optimizer.py:83-137 (_resource_apply_dense), all tensors in 2 launches ---- */
 /* table: device int64[5*T] = {w ptrs | g ptrs | v ptrs | numel | flags(bit0 use_weight_decay :139-148,
  * bit1 do_layer_adaptation :150-157)}; chunks: device int64[2*num_chunks] = (tensor id, element

@@ -111,6 +111,13 @@ _DEFS = [
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),
     ('dropblock_size', None, int, 'MI355X build: DropBlock block size; required when any keep probability is active.'),
     ('dropblock_seed', 0, int, 'MI355X build: seed of the DropBlock noise; the draws of a site depend on (dropblock_seed, step, replica, site) only.'),
+    # weighted k-NN evaluation of the frozen encoder (Wu et al. 2018; simclr_amd/knn.py): no trained head
+    ('knn_eval', False, bool, 'MI355X build: --mode=eval / train_then_eval also classify --eval_split by a weighted k-NN vote over the encoder '
+                              'features of --train_split (evaluation preprocessing) and write knn_result.json; runs with or without a linear head.'),
+    ('knn_k', 200, int, 'MI355X build: neighbours per query of the k-NN evaluation (1..256).'),
+    ('knn_temperature', 0.07, float, 'MI355X build: temperature of the k-NN vote weights exp(similarity / temperature).'),
+    ('knn_bank_examples', 0, int, 'MI355X build: examples of --train_split in the k-NN bank: 0 = the whole split, n > 0 = the first n positions of '
+                                  'epoch_permutation(data_seed, 0, N).  --dataset=synthetic: a bank of random images, at most 8 eval batches.'),
 ]
 
 

@@ -312,6 +312,21 @@ class Model(Layer):
             sup_out = self.supervised_head(sup_in, training)                       # stop_gradient, :276-278
         return proj32, sup_out
 
+    def features(self, inputs):
+        """inputs: float32 [b, H, W, 3] in [0,1].  The encoder alone in inference mode (moving BatchNorm statistics, no blur): the
+        pooled `hiddens` the heads read, as float32 [b, C].  Neither head runs, no activation is kept and no variable or moving
+        statistic moves, so a call between two training steps leaves the next step what it is without the call
+        (simclr_amd/knn.py: the frozen features of the weighted k-NN evaluation)."""
+        if inputs.dim() != 4 or inputs.shape[3] != 3:
+            raise ValueError(f'features() reads single-view batches [b, H, W, 3] (got input shape {tuple(inputs.shape)})')
+        ops.select_f32_matmul(inference=True)
+        k, s = self.resnet_model.stem_kernel_stride
+        packed = PackedInput(inputs.contiguous(), 1, k, s, RT.dtype)
+        hiddens = self.resnet_model(packed, training=False)
+        out = ops.cast(hiddens, torch.float32) if hiddens.dtype != torch.float32 else hiddens.clone()
+        self.release()
+        return out
+
     def backward_supervised(self, d_sup):
         """Backward of the linear-eval head alone (its input is stop_gradient'ed, tf2/model.py:276-277)."""
         if d_sup is not None:

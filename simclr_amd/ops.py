@@ -338,6 +338,61 @@ def gcl_swd_bwd(g_all, z_local, rank, grad_scale, lambda_weight=1.0, loss_scalin
     return dz_local
 
 
+# ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
+KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
+KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS
+KNN_MAX_CLASSES = 32768             # the class scores of a query live in LDS
+
+
+def knn_topk(q, bank, k):
+    """q [Q, D], bank [N, D] fp32 -> (top_val [Q, k] fp32, top_idx [Q, k] int32): per query the first k bank rows of the total order
+    "similarity descending, bank index ascending" (exact f32 MFMA, a similarity depends on its two rows only)."""
+    if q.dim() != 2 or bank.dim() != 2 or q.shape[1] != bank.shape[1]:
+        raise ValueError('knn_topk: need q [Q, D] and bank [N, D] (got %s and %s)' % (tuple(q.shape), tuple(bank.shape)))
+    if q.dtype != torch.float32 or bank.dtype != torch.float32:
+        raise ValueError('knn_topk: fp32 features only (got %s and %s)' % (q.dtype, bank.dtype))
+    (Q, D), N, k = q.shape, bank.shape[0], int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError('knn_topk: k must be 1..%d (got %d)' % (KNN_MAX_K, k))
+    if N < k:
+        raise ValueError('knn_topk: the bank has %d rows, fewer than k = %d' % (N, k))
+    if N >= 2 ** 31:
+        raise ValueError('knn_topk: the bank must have fewer than 2^31 rows (got %d)' % N)
+    if D < 16 or D % 16:
+        raise ValueError('knn_topk: the feature width must be a multiple of 16 (got %d)' % D)
+    if Q < 1:
+        raise ValueError('knn_topk: no queries')
+    assert lib().knn_slab_rows() == KNN_SLAB, 'libsimclr_hip.so was built with another slab length: rebuild it'
+    top_val = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    top_idx = torch.empty(Q, k, device=q.device, dtype=torch.int32)
+    ws = _workspace(lib().knn_workspace_bytes(Q, N, D, k), q.device, key='knn')
+    _launch('knn_topk', 2.0 * Q * N * D, 4.0 * (Q + N) * D + 8.0 * Q * k,
+            lambda: lib().knn_topk(_p(q), _p(bank), Q, N, D, k, _p(top_val), _p(top_idx), _p(ws), _s()))
+    return top_val, top_idx
+
+
+def knn_vote(top_val, top_label, num_classes, temperature):
+    """top_val [Q, k] fp32 (descending), top_label [Q, k] int32 -> (pred [Q, 5] int32, score [Q, 5] fp32): the five best classes of the
+    weighted vote exp((s - s_max) / temperature), by "score descending, class id ascending"; -1 / 0 past the number of classes."""
+    if top_val.dim() != 2 or tuple(top_label.shape) != tuple(top_val.shape):
+        raise ValueError('knn_vote: need top_val and top_label of one [Q, k] shape (got %s and %s)' % (tuple(top_val.shape), tuple(top_label.shape)))
+    if top_val.dtype != torch.float32 or top_label.dtype != torch.int32:
+        raise ValueError('knn_vote: need fp32 similarities and int32 labels (got %s and %s)' % (top_val.dtype, top_label.dtype))
+    Q, k = top_val.shape
+    num_classes = int(num_classes)
+    if not 1 <= k <= KNN_MAX_K or Q < 1:
+        raise ValueError('knn_vote: need Q >= 1 and k in 1..%d (got Q=%d k=%d)' % (KNN_MAX_K, Q, k))
+    if not 1 <= num_classes <= KNN_MAX_CLASSES:
+        raise ValueError('knn_vote: num_classes must be 1..%d (got %d)' % (KNN_MAX_CLASSES, num_classes))
+    if not float(temperature) > 0.0:
+        raise ValueError('knn_vote: temperature must be > 0 (got %r)' % (temperature,))
+    pred = torch.empty(Q, 5, device=top_val.device, dtype=torch.int32)
+    score = torch.empty(Q, 5, device=top_val.device, dtype=torch.float32)
+    _launch('knn_vote', 2.0 * Q * k, 8.0 * Q * k + 40.0 * Q,
+            lambda: lib().knn_vote(_p(top_val), _p(top_label), Q, k, num_classes, float(temperature), _p(pred), _p(score), _s()))
+    return pred, score
+
+
 # ---------------------------------------------------------------- conv / dense
 def prep_weights(w_hwio, mode, dtype, khp=0, kwp=0, out=None, cin_p=0, cout_p=0):
     """fp32 HWIO master -> compute copy.  cin_p / cout_p: zero-padded channel dims of the copy."""

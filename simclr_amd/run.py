@@ -137,6 +137,32 @@ def check_distillation_flags():
     return False
 
 
+SYNTHETIC_KNN_BANK_BATCHES = 8     # --dataset=synthetic: eval batches in the k-NN bank (plumbing only; every batch distinct)
+
+
+def check_knn_flags(num_train_examples=None):
+    """--knn_eval (simclr_amd/knn.py), checked before any device work.  Returns the number of bank examples (None with the flag off, or
+    when the size of --train_split is not known yet)."""
+    if not FLAGS.knn_eval:
+        return None
+    if not 1 <= FLAGS.knn_k <= ops.KNN_MAX_K:
+        raise ValueError('--knn_k must be 1..%d (got %d): the top-k kernel sorts a query\'s candidates in LDS' % (ops.KNN_MAX_K, FLAGS.knn_k))
+    if not FLAGS.knn_temperature > 0:
+        raise ValueError('--knn_temperature must be > 0 (got %r)' % (FLAGS.knn_temperature,))
+    if FLAGS.knn_bank_examples < 0:
+        raise ValueError('--knn_bank_examples must be >= 0 (got %d)' % FLAGS.knn_bank_examples)
+    if num_train_examples is None:
+        bank = FLAGS.knn_bank_examples or None
+    else:
+        if FLAGS.knn_bank_examples > num_train_examples:
+            raise ValueError('--knn_bank_examples=%d exceeds the %d examples of --train_split=%s'
+                             % (FLAGS.knn_bank_examples, num_train_examples, FLAGS.train_split))
+        bank = FLAGS.knn_bank_examples or int(num_train_examples)
+    if bank is not None and bank < FLAGS.knn_k:
+        raise ValueError('the k-NN bank would hold %d examples, fewer than --knn_k=%d' % (bank, FLAGS.knn_k))
+    return bank
+
+
 def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
@@ -432,12 +458,18 @@ def main(argv):
     distill = check_distillation_flags()
     check_contrastive_loss_flags()
     check_dropblock_flags()
+    check_knn_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
         # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter
         builder = data_lib.ArrayDatasetBuilder(FLAGS.dataset, FLAGS.data_dir)                 # :471-472
         for sp in ([FLAGS.train_split] if FLAGS.mode != 'eval' else []) + ([FLAGS.eval_split] if FLAGS.mode != 'train' else []):
             builder.split(sp)
+        if FLAGS.knn_eval and FLAGS.mode != 'train':
+            builder.split(FLAGS.train_split)
+            check_knn_flags(builder.info.splits[FLAGS.train_split].num_examples)
+    elif FLAGS.knn_eval:
+        check_knn_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
     strategy = init_distributed()
     R = num_replicas(strategy)
     rank0 = strategy is None or strategy.rank == 0
@@ -460,6 +492,27 @@ def main(argv):
         if builder is not None:
             return data_lib.build_distributed_dataset(builder, FLAGS.eval_batch_size, False, strategy)
         return synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device, seed=100 + rep)
+
+    def knn_evaluation(ckpt, result):
+        """--knn_eval: the weighted k-NN evaluation after perform_evaluation (which may have skipped); the union of both results."""
+        from . import knn as knn_lib
+        # --dataset=synthetic: at most SYNTHETIC_KNN_BANK_BATCHES batches, each drawn once -- a longer bank would only repeat them
+        n_bank = check_knn_flags(num_train_examples if builder is not None else SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        if builder is not None:
+            split = builder.split(FLAGS.train_split, cache=FLAGS.cache_dataset)
+            if FLAGS.knn_bank_examples:
+                sel = knn_lib.knn_bank_indices(FLAGS.data_seed, split.index.shape[0], n_bank)
+                split = data_lib.Split(split.index[sel], split.images)
+            # evaluation preprocessing of the TRAINING split; the last batch is padded with weight 0 and trimmed from the bank
+            bank_data = data_lib.DatasetIterator(split, num_classes, FLAGS.eval_batch_size, False, replica=rep, num_replicas=R,
+                                                 device=RT.device)
+        else:
+            import itertools
+            steps = int(math.ceil(n_bank / FLAGS.eval_batch_size))
+            bank_data = itertools.islice(synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device,
+                                                                seed=7000 + rep, pool=steps), steps)
+        knn_result = knn_lib.perform_knn_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
+        return dict(result or {}, **knn_result)
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
@@ -474,6 +527,8 @@ def main(argv):
         mgr = CheckpointManager(Checkpoint(model=model), FLAGS.model_dir, FLAGS.keep_checkpoint_max)
         ckpt = FLAGS.checkpoint or mgr.latest_checkpoint
         result = perform_evaluation(model, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
+        if FLAGS.knn_eval:
+            result = knn_evaluation(ckpt, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
@@ -539,6 +594,8 @@ def main(argv):
         data.close()
     if FLAGS.mode == 'train_then_eval' and manager is not None:                           # :657-660
         result = perform_evaluation(model, eval_data(), eval_steps, manager.latest_checkpoint, strategy, FLAGS.model_dir)
+        if FLAGS.knn_eval:
+            result = knn_evaluation(manager.latest_checkpoint, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result

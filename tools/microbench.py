@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,dropblock]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -302,6 +302,33 @@ def main():
             print('gcl n=%d N=%d: ' % (n, N) + ' '.join('%s %.0f' % (k[:-3], v) for k, v in row.items() if k != 'layer') + ' (us)', flush=True)
             res.append(row)
             del zl, za, ws, gws
+    if 'knn' in what:
+        # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
+        # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
+        # the same exact-f32 GEMM, which WRITES the dense [Q, N] matrix (for the full bank: on a 131072-row slice, scaled by N / 131072)
+        for (Q, N, D, k) in [(256, 131072, 2048, 200), (256, 1281167, 2048, 200), (256, 131072, 128, 200)]:
+            q = torch.nn.functional.normalize(torch.randn(Q, D, device=dev), dim=1)
+            bank = torch.randn(N, D, device=dev)
+            for lo in range(0, N, 65536):
+                bank[lo:lo + 65536] = torch.nn.functional.normalize(bank[lo:lo + 65536], dim=1)
+            labels = torch.randint(0, 1000, (N,), device=dev, dtype=torch.int32)
+            tv, ti = ops.knn_topk(q, bank, k)
+            tl = labels[ti.long()].contiguous()
+            t_k = timeit(lambda: ops.knn_topk(q, bank, k), args.iters)
+            t_v = timeit(lambda: ops.knn_vote(tv, tl, 1000, 0.07), args.iters)
+            Ns = min(N, 131072)
+            z_local = torch.cat([q, q])                                    # logits_ab reads z_local[:n] and z_all[N:]
+            z_all = torch.cat([bank[:1].expand(Ns, D), bank[:Ns]]).contiguous()
+            t_g = timeit(lambda: ops.ntxent_wide_logits_ab(z_local, z_all, 1.0), args.iters) * (N / Ns)
+            fl = 2.0 * Q * N * D
+            row = dict(layer='knn Q%d N%d D%d k%d' % (Q, N, D, k), topk_us=t_k, topk_tfs=fl / t_k / 1e6, vote_us=t_v,
+                       logits_ab_us=t_g, logits_ab_tfs=fl / t_g / 1e6, logits_ab_scaled_from_rows=Ns, topk_over_logits_ab=t_k / t_g,
+                       workspace_bytes=Q * k * 8 * -(-N // ops.KNN_SLAB))
+            print('knn Q=%d N=%d D=%d k=%d: topk %.0f us (%.1f TF/s) vote %.0f us | dense logits_ab %.0f us (%.1f TF/s%s) | topk / dense %.2f'
+                  % (Q, N, D, k, t_k, row['topk_tfs'], t_v, t_g, row['logits_ab_tfs'], '' if Ns == N else ', scaled from %d rows' % Ns,
+                     row['topk_over_logits_ab']), flush=True)
+            res.append(row)
+            del q, bank, z_all, z_local, tv, ti, tl
     if 'dropblock' in what:
         # the four DropBlock kernels (csrc/dropblock.hip) at the sites of block groups 3 and 4, in fp32 and bf16 storage, as GB/s of
         # the bytes each must move (tensors once, bit tensors once; the mask kernel reads nothing and writes one bit per element),
