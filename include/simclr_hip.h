@@ -137,6 +137,27 @@ int simclr_gcl_swd_bwd(const float* g_all, const float* z_local, int n, int N, i
  * matmul(., rand_w) projections and their transposes (simclr_small_gemm_nt_f32 needs M and N multiples of 16). */
 int simclr_gcl_gemm_nt(const float* A, const float* B, float* C, int M, int N, int K, simclr_stream_t stream);
 
+/* ---- supervised contrastive loss (Khosla et al. 2020, Supervised Contrastive Learning, the L_out^sup form), csrc/supcon.hip ----
+ * NT-Xent with every same-class row of the global batch as a positive.  Layout as simclr_ntxent_fwd: z_local [2n, D] = this replica's
+ * [view-1 rows; view-2 rows], z_all [2N, D] = every replica's view-1 rows, then every replica's view-2 rows, N = R*n.  labels_all [N]
+ * int32 = the class ids of the global batch in z_all's sample order: column j has label labels_all[j mod N].  Local row i (view
+ * v = i / n, sample s = i % n) is global column self(i) = v*N + rank*n + s.
+ *   A(i) = all 2N columns except self(i);  P(i) = {p in A(i): label(p) == label(i)}  (the other view of the image: |P(i)| >= 1)
+ *   l_i  = logsumexp_{a in A(i)}(z_i.z_a / T) - (1 / |P(i)|) sum_{p in P(i)} z_i.z_p / T
+ * The temperature / base_temperature factor of the paper's code is left out: with all labels distinct this is simclr_ntxent_fwd's loss.
+ * D in {64, 128, 256}, any n >= 1; exact fp32-input MFMA, the [2n, 2N] matrix never written, no atomics: bitwise run-to-run
+ * deterministic.  Labels are only compared for equality.  The workspace holds one fwd/bwd pair. */
+size_t simclr_supcon_workspace_bytes(int n, int N, int D);     /* 0 for a shape the kernels refuse */
+/* out[0] = loss = (1 / n) sum_{i < 2n} l_i (the sum of the two per-view means), out[1] = contrast_acc = the share of the 2n rows with
+ * max_{p in P(i)} s_ip >= max_{a in A(i) \ P(i)} s_ia (a row without a non-positive column is a hit), out[2] = contrast_positives =
+ * the mean of |P(i)| over the 2n rows.  row_stats [2n, 2] = {logsumexp over A(i) in the base-2 domain, |P(i)|}, kept for the backward. */
+int simclr_supcon_fwd(const float* z_local, const float* z_all, const int* labels_all, int n, int N, int D, int rank, float temperature,
+                      float* out, float* row_stats, void* workspace, simclr_stream_t stream);
+/* The gradient through the logits: dS_ia = grad_scale / (n T) * (softmax_{A(i)}(s_i)_a - [a in P(i)] / |P(i)|), dS_{i, self(i)} = 0;
+ * dz_local [2n, D] = dS z_all, dz_all [2N, D] = dS^T z_local (to be reduce-scattered like simclr_ntxent_bwd's). */
+int simclr_supcon_bwd(const float* z_local, const float* z_all, const int* labels_all, int n, int N, int D, int rank, float temperature,
+                      const float* row_stats, float grad_scale, float* dz_local, float* dz_all, void* workspace, simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

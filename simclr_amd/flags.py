@@ -98,9 +98,10 @@ _DEFS = [
     ('teacher_sk_ratio', None, float, "MI355X build: selective-kernel ratio of the teacher (default: --sk_ratio)."),
     ('teacher_ft_proj_selector', None, int, 'MI355X build: projection-head layer the teacher\'s supervised head reads (default: --ft_proj_selector).'),
     # generalized contrastive loss (colabs/intriguing_properties/generalized_contrastive_loss.ipynb) in place of NT-Xent for pretraining
-    ('contrastive_loss', 'ntxent', str, "MI355X build: pretraining loss, 'ntxent' (add_contrastive_loss, default) or 'generalized' "
-                                        '(generalized_contrastive_loss: alignment + gcl_lambda x distribution matching; projection width 64, 128 or 256).  '
-                                        'Ignored by --train_mode=finetune.'),
+    ('contrastive_loss', 'ntxent', str, "MI355X build: pretraining loss, 'ntxent' (add_contrastive_loss, default), 'generalized' "
+                                        '(generalized_contrastive_loss: alignment + gcl_lambda x distribution matching; projection width 64, 128 or 256) '
+                                        "or 'supcon' (add_supcon_loss: supervised contrastive loss, every same-class row of the global batch a positive; "
+                                        'projection width 64, 128 or 256).  Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
     ('gcl_lambda', 1.0, float, 'MI355X build: weight of the distribution-matching term (lambda_weight).'),

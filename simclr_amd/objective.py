@@ -10,6 +10,9 @@ fused contrast accuracy / entropy (tf2/metrics.py:28-35); call `.dense()` for re
 
 `generalized_contrastive_loss` is the loss of colabs/intriguing_properties/generalized_contrastive_loss.ipynb (alignment + a
 distribution-matching term: decoupled NT-Xent, or sliced Wasserstein against a normal / uniform prior) on the kernels of csrc/gcl.hip.
+
+`add_supcon_loss` is the supervised contrastive loss of Khosla et al. 2020 (NT-Xent with every same-class row of the global batch as a
+positive) on the kernels of csrc/supcon.hip.
 """
 import torch
 
@@ -319,6 +322,80 @@ def _class_ids(labels):
     import weakref
     _CLASS_ID_CACHE[key] = (weakref.ref(labels), ids)
     return ids
+
+
+def _gather_class_ids(ids, strategy):
+    """[n] int32 class ids of this replica -> (wait-and-get function of) the [N] ids of the global batch in replica order, which is
+    z_all's sample order.  The collective is asynchronous, like gather_hidden's."""
+    if not collectives_on(strategy):
+        return lambda: ids
+    g, work = strategy.all_gather_concat(ids, async_op=True)
+
+    def finish():
+        if work is not None:
+            work.wait()
+        return g
+    return finish
+
+
+def add_supcon_loss(hidden, labels, hidden_norm=True, temperature=1.0, strategy=None, overlap=None):
+    """Supervised contrastive loss (Khosla et al. 2020, Supervised Contrastive Learning, the L_out^sup form) on the kernels of
+    csrc/supcon.hip: NT-Xent with every same-class row of the GLOBAL batch as a positive.
+
+    With A(i) = every column of the gathered block but row i's own and P(i) = the columns of A(i) with row i's label,
+      loss = (1 / n) sum_{i < 2n} [logsumexp_{a in A(i)}(z_i.z_a / T) - (1 / |P(i)|) sum_{p in P(i)} z_i.z_p / T],
+    the sum of the two per-view means, as add_contrastive_loss forms NT-Xent: with all labels of the global batch distinct the loss
+    and its gradient are add_contrastive_loss's.  The temperature / base_temperature factor of the paper's code is left out.
+
+    Args:
+      hidden: float32 device tensor [2n, D] = [view-a rows; view-b rows], D in {64, 128, 256}.
+      labels: one-hot float [n, C] or int class ids [n] of the local batch (both views of an image share its label).
+      hidden_norm, temperature, strategy, overlap: as add_contrastive_loss (the hidden block and the class ids are gathered
+        asynchronously; overlap() runs meanwhile).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> gradient wrt hidden), the device scalars .acc (share of rows
+      whose best positive scores at least as high as their best non-positive) and .positives (mean |P(i)|), and .normalized.
+    """
+    assert hidden.dtype == torch.float32 and hidden.dim() == 2
+    hidden = hidden.contiguous()
+    n, D = hidden.shape[0] // 2, hidden.shape[1]
+    ops._supcon_check_dim(D)
+    ids = _class_ids(labels)
+    if ids.dim() != 1 or ids.shape[0] != n:
+        raise ValueError('add_supcon_loss: %d labels for a local batch of %d (hidden holds both views: [2n, D])' % (ids.shape[0], n))
+    if hidden_norm:
+        z, inv = ops.l2norm_fwd(hidden)
+    else:
+        z, inv = hidden, None
+    rank = replica_id(strategy)
+    pending = gather_hidden(z, strategy, async_op=True)
+    pending_ids = _gather_class_ids(ids, strategy)
+    if overlap is not None:
+        overlap()
+    z_all, ids_all = pending(), pending_ids()
+    out, row_stats, ws = ops.supcon_fwd(z, z_all, ids_all, rank, temperature)
+    state = {}
+
+    def backward_start(grad_scale=1.0):
+        dz_local, dz_all = ops.supcon_bwd(z, z_all, ids_all, rank, temperature, row_stats, grad_scale, ws)
+        state['dz_local'] = dz_local
+        state['slot'] = scatter_hidden_grad(dz_all, strategy, async_op=True)   # transpose of the concat, as NT-Xent's
+
+    def backward_finish():
+        dz_local, dz_slot = state.pop('dz_local'), state.pop('slot')()
+        ops.axpy_f32(1.0, dz_slot, dz_local)
+        if hidden_norm:
+            return ops.l2norm_bwd(z, inv, dz_local)
+        return dz_local
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.acc, loss.positives = out[1:2], out[2:3]
+    loss.normalized = z
+    return loss
 
 
 def add_supervised_loss(labels, logits):

@@ -338,6 +338,60 @@ def gcl_swd_bwd(g_all, z_local, rank, grad_scale, lambda_weight=1.0, loss_scalin
     return dz_local
 
 
+# ---------------------------------------------------------------- supervised contrastive loss (csrc/supcon.hip)
+SUPCON_DIMS = (64, 128, 256)        # hidden widths the supervised contrastive kernels are instantiated for
+
+
+def _supcon_check_dim(D):
+    if D not in SUPCON_DIMS:
+        raise ValueError('the supervised contrastive loss supports hidden widths %s (got %d)' % ('/'.join(map(str, SUPCON_DIMS)), D))
+
+
+def _supcon_check(z_local, z_all, labels_all):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    assert z_local.dtype == torch.float32 and z_all.dtype == torch.float32 and z_all.shape[1] == D
+    _supcon_check_dim(D)
+    if n < 1 or z_local.shape[0] != 2 * n or N < n or N % n != 0 or z_all.shape[0] != 2 * N:
+        raise ValueError('supcon: need z_local [2n, D] with n >= 1 and z_all [2N, D] with N = R*n (got %d and %d rows)'
+                         % (z_local.shape[0], z_all.shape[0]))
+    if labels_all.dtype != torch.int32 or labels_all.dim() != 1 or labels_all.shape[0] != N:
+        raise ValueError('supcon: labels_all must hold the N = %d int32 class ids of the global batch (got %s %s)'
+                         % (N, tuple(labels_all.shape), labels_all.dtype))
+    return n, N, D
+
+
+def supcon_workspace(n, N, D, device):
+    _supcon_check_dim(D)
+    nbytes = lib().supcon_workspace_bytes(n, N, D)
+    assert nbytes > 0, 'supcon_workspace: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+
+
+def supcon_fwd(z_local, z_all, labels_all, rank, temperature, ws=None):
+    """Supervised contrastive forward.  labels_all [N] int32: the class ids of the global batch in z_all's sample order.
+    Returns out = [loss, contrast_acc, contrast_positives] (device), row_stats [2n, 2], the workspace."""
+    n, N, D = _supcon_check(z_local, z_all, labels_all)
+    if ws is None:
+        ws = supcon_workspace(n, N, D, z_local.device)
+    out = step_scalars(4, z_local.device)
+    row_stats = torch.empty(2 * n, 2, device=z_local.device, dtype=torch.float32)
+    _launch('supcon_fwd', 8.0 * n * N * D, 4.0 * (2 * n + 2 * N) * D,
+            lambda: lib().supcon_fwd(_p(z_local), _p(z_all), _p(labels_all), n, N, D, int(rank), float(temperature), _p(out), _p(row_stats),
+                                     _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def supcon_bwd(z_local, z_all, labels_all, rank, temperature, row_stats, grad_scale, ws):
+    n, N, D = _supcon_check(z_local, z_all, labels_all)
+    dz_local = torch.empty_like(z_local)
+    dz_all = torch.empty_like(z_all)
+    _launch('supcon_bwd', 24.0 * n * N * D, 2.0 * (2 * n + 2 * N) * D * 4,
+            lambda: lib().supcon_bwd(_p(z_local), _p(z_all), _p(labels_all), n, N, D, int(rank), float(temperature), _p(row_stats),
+                                     float(grad_scale), _p(dz_local), _p(dz_all), _p(ws), _s()))
+    return dz_local, dz_all
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

@@ -30,10 +30,22 @@ def generalized_loss_on():
     return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'generalized' and FLAGS.train_mode == 'pretrain'
 
 
+def supcon_loss_on():
+    """--contrastive_loss=supcon replaces NT-Xent in the pretraining step by the supervised contrastive loss; train_mode=finetune ignores it."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'supcon' and FLAGS.train_mode == 'pretrain'
+
+
 def check_contrastive_loss_flags():
-    """Raise before any device work when the pretraining loss flags name something the kernels do not cover."""
-    if FLAGS.contrastive_loss not in ('ntxent', 'generalized'):
-        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' (got %r)" % FLAGS.contrastive_loss)
+    """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
+    Returns True for the generalized loss only (supcon_loss_on() tells the supervised contrastive loss)."""
+    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon'):
+        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' (got %r)" % FLAGS.contrastive_loss)
+    if supcon_loss_on() and FLAGS.mode != 'eval':
+        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.SUPCON_DIMS:
+            raise ValueError('--contrastive_loss=supcon needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
+                             'the supervised contrastive kernels are instantiated for those widths only'
+                             % ('/'.join(map(str, ops.SUPCON_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if not generalized_loss_on() or FLAGS.mode == 'eval':
         return False
     if FLAGS.gcl_dist not in obj_lib.GCL_DISTS:
@@ -54,6 +66,8 @@ def build_metrics():
     names = ['train/weight_decay', 'train/total_loss']
     if FLAGS.train_mode == 'pretrain' and generalized_loss_on():
         names += ['train/contrast_loss', 'train/align_loss', 'train/dist_loss']   # the generalized loss has no logits to score
+    elif FLAGS.train_mode == 'pretrain' and supcon_loss_on():
+        names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_positives']
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -179,6 +193,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
     state = {'sync': None}
     RT.strategy = strategy
     generalized = check_contrastive_loss_flags()
+    supcon = supcon_loss_on() and not generalized
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
 
     def single_step(features, labels):
@@ -213,6 +228,12 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 con_loss = obj_lib.generalized_loss_of_block(
                     outputs, lambda_weight=FLAGS.gcl_lambda, temperature=FLAGS.temperature, dist=FLAGS.gcl_dist,
                     hidden_norm=FLAGS.hidden_norm, loss_scaling=FLAGS.gcl_loss_scaling, strategy=strategy, overlap=supervised_part)
+            elif supcon:
+                # the labels define the positives, whether or not the supervised head trains on them too
+                logits_con = None
+                con_loss = obj_lib.add_supcon_loss(
+                    outputs, labels['labels'] if isinstance(labels, dict) else labels, hidden_norm=FLAGS.hidden_norm,
+                    temperature=FLAGS.temperature, strategy=strategy, overlap=supervised_part)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -274,6 +295,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/align_loss'] = con_loss.align.reshape(-1)[:1]
             vals['train/dist_loss'] = con_loss.dist_match.reshape(-1)[:1]
+        elif con_loss is not None and supcon:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
+            vals['train/contrast_positives'] = con_loss.positives.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -299,6 +324,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
             con_loss.value = at['train/contrast_loss']
             if generalized and 'train/align_loss' in at and 'train/dist_loss' in at:
                 con_loss.align, con_loss.dist_match = at['train/align_loss'], at['train/dist_loss']
+            elif supcon and 'train/contrast_acc' in at and 'train/contrast_positives' in at:
+                con_loss.acc, con_loss.positives = at['train/contrast_acc'], at['train/contrast_positives']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:

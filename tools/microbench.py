@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -302,6 +302,41 @@ def main():
             print('gcl n=%d N=%d: ' % (n, N) + ' '.join('%s %.0f' % (k[:-3], v) for k, v in row.items() if k != 'layer') + ' (us)', flush=True)
             res.append(row)
             del zl, za, ws, gws
+    if 'supcon' in what:
+        # supervised contrastive loss (csrc/supcon.hip) beside the closest existing sweeps at the same shapes in the same run: the decoupled
+        # sweep of csrc/gcl.hip and NT-Xent's exact sweeps.  Matrix FLOPs: forward S = 8nND, backward S again + dS K + dS^T Q = 24nND.
+        # Labels: 100 classes drawn at random (about 2N / 100 positives per row).
+        for (n, N) in [(512, 512), (512, 4096)]:
+            D = 128
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            labels = torch.randint(0, 100, (N,), device=dev, dtype=torch.int32)
+            ff, fb = 8.0 * n * N * D, 24.0 * n * N * D
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            gws = ops.gcl_lse_workspace(n, N, D, dev)
+            _, grs, _ = ops.gcl_lse_fwd(zl, za, 0.1, ws=gws)
+            sws = ops.supcon_workspace(n, N, D, dev)
+            _, srs, _ = ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)
+            row = dict(layer='supcon n%d N%d D%d' % (n, N, D), fwd_flops=ff, bwd_flops=fb,
+                       supcon_fwd_us=timeit(lambda: ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws), args.iters),
+                       supcon_bwd_us=timeit(lambda: ops.supcon_bwd(zl, za, labels, 0, 0.1, srs, 1.0, sws), args.iters),
+                       gcl_lse_fwd_us=timeit(lambda: ops.gcl_lse_fwd(zl, za, 0.1, ws=gws), args.iters),
+                       gcl_lse_bwd_us=timeit(lambda: ops.gcl_lse_bwd(zl, za, 0.1, grs, 1.0, gws, skip_self=True), args.iters),
+                       ntxent_fwd_us=timeit(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws), args.iters),
+                       ntxent_bwd_us=timeit(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws), args.iters))
+            for k in ('supcon', 'gcl_lse', 'ntxent'):
+                row[k + '_fwd_tfs'] = ff / row[k + '_fwd_us'] / 1e6
+                row[k + '_bwd_tfs'] = fb / row[k + '_bwd_us'] / 1e6
+            row['supcon_over_gcl_lse_fwd'] = row['supcon_fwd_us'] / row['gcl_lse_fwd_us']
+            row['supcon_over_gcl_lse_bwd'] = row['supcon_bwd_us'] / row['gcl_lse_bwd_us']
+            print('supcon n=%d N=%d D=%d: ' % (n, N, D) + ' | '.join(
+                '%s fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s)' % (k, row[k + '_fwd_us'], row[k + '_fwd_tfs'], row[k + '_bwd_us'], row[k + '_bwd_tfs'])
+                for k in ('supcon', 'gcl_lse', 'ntxent')) + ' | supcon / gcl_lse fwd %.2f bwd %.2f' % (
+                    row['supcon_over_gcl_lse_fwd'], row['supcon_over_gcl_lse_bwd']), flush=True)
+            res.append(row)
+            del zl, za, ws, gws, sws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
