@@ -158,6 +158,39 @@ int simclr_supcon_fwd(const float* z_local, const float* z_all, const int* label
 int simclr_supcon_bwd(const float* z_local, const float* z_all, const int* labels_all, int n, int N, int D, int rank, float temperature,
                       const float* row_stats, float grad_scale, float* dz_local, float* dz_all, void* workspace, simclr_stream_t stream);
 
+/* ---- Barlow Twins loss (Zbontar et al. 2021, Barlow Twins: Self-Supervised Learning via Redundancy Reduction), csrc/barlow.hip ----
+ * The Gram form: with zhat the per-view, per-dimension standardisation of the gathered block over the GLOBAL batch,
+ * C = zhat1^T zhat2 / N ([D, D], never formed), c_i = C_ii, G1 = zhat1 zhat1^T, G2 = zhat2 zhat2^T,
+ *   on_diag = sum_i (1 - c_i)^2,   off_diag = sum_{i != j} C_ij^2 = (1 / N^2) sum_{a, b} G1_ab G2_ab - sum_i c_i^2,
+ *   L = loss_scaling * (on_diag + lambda_weight * off_diag).
+ * Layout as simclr_ntxent_fwd: h_all / zhat_all [2N, D] = every replica's view-1 rows, then every replica's view-2 rows, N = R*n; this
+ * replica's rows are rank*n .. rank*n + n - 1 of each view.  D a multiple of 64 in [64, 8192], any n >= 1.  Exact fp32-input MFMA,
+ * column statistics and loss sums in double in a fixed order, no atomics: bitwise run-to-run deterministic, and everything computed
+ * from the gathered block alone is identical on every replica.  The workspace holds one fwd/bwd pair. */
+size_t simclr_bt_workspace_bytes(int n, int N, int D);          /* 0 for a shape the kernels refuse */
+/* Where simclr_bt_fwd keeps the Gram blocks of the local rows in the workspace: fp32 [2, rows, pitch] from that byte offset, block v
+ * row a column b = zhat_v[rank*n + a] . zhat_v[b]; rows >= n and pitch >= N are padded to the tile with zeros.  0 for a refused shape. */
+size_t simclr_bt_gram_offset_bytes(int n, int N, int D);
+size_t simclr_bt_gram_rows(int n, int N, int D);
+size_t simclr_bt_gram_pitch(int n, int N, int D);
+/* zhat = (h - mu) / sqrt(var + eps) per view and column over the N rows (two passes: mean, then the biased variance from centred
+ * squares, sums in double); rstd [2, D] = 1 / sqrt(var + eps) is kept for simclr_bt_apply.  N = 1 gives zhat = 0. */
+int simclr_bt_standardize(const float* h_all, int N, int D, float eps, float* zhat_all, float* rstd, simclr_stream_t stream);
+/* out[0] = this replica's loss value loss_scaling * (on_diag + lambda_weight * off_diag) with off_diag = R / N^2 * sum_{a local, b}
+ * G1_ab G2_ab - sum_i c_i^2 (the mean over the replicas is L), out[1] = on_diag, out[2] = off_diag. */
+int simclr_bt_fwd(const float* zhat_all, int n, int N, int D, int rank, float lambda_weight, float loss_scaling, float* out,
+                  void* workspace, simclr_stream_t stream);
+/* g_local [2n, D] = grad_scale * R * dL/dzhat of the local rows of both views:
+ *   g1_a = s * (lambda_weight * (2 / N^2) * sum_b G2_ab zhat1_b + d o zhat2_a / N),  d_i = -2 (1 - c_i) - 2 lambda_weight c_i,
+ * s = loss_scaling * grad_scale * R (view 2: G1, zhat2_b, zhat1_a), from the Gram blocks simclr_bt_fwd left in the workspace;
+ * colsums [2 views, 2, D] doubles = the column sums over the local rows of g and of g o zhat, to be summed over the replicas. */
+int simclr_bt_bwd(const float* zhat_all, int n, int N, int D, int rank, float lambda_weight, float loss_scaling, float grad_scale,
+                  void* workspace, float* g_local, double* colsums, simclr_stream_t stream);
+/* The standardisation backward: dh_a = (g_a - colsums[v][0] / N - zhat_a o colsums[v][1] / N) * rstd[v], colsums summed over the
+ * GLOBAL batch; dh [2n, D] = grad_scale * R * dL/dh of the local rows. */
+int simclr_bt_apply(const float* g_local, const float* zhat_all, const float* rstd, const double* colsums, int n, int N, int D, int rank,
+                    float* dh, simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

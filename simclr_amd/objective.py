@@ -13,6 +13,9 @@ distribution-matching term: decoupled NT-Xent, or sliced Wasserstein against a n
 
 `add_supcon_loss` is the supervised contrastive loss of Khosla et al. 2020 (NT-Xent with every same-class row of the global batch as a
 positive) on the kernels of csrc/supcon.hip.
+
+`add_barlow_twins_loss` is the Barlow Twins loss of Zbontar et al. 2021 (redundancy reduction on the cross-correlation of the two views'
+batch-standardised hiddens; no negatives) in its Gram form on the kernels of csrc/barlow.hip.
 """
 import torch
 
@@ -395,6 +398,63 @@ def add_supcon_loss(hidden, labels, hidden_norm=True, temperature=1.0, strategy=
     loss = _Loss(out[0:1], backward, backward_start, backward_finish)
     loss.acc, loss.positives = out[1:2], out[2:3]
     loss.normalized = z
+    return loss
+
+
+def add_barlow_twins_loss(hidden, lambda_weight=0.0051, loss_scaling=1.0, eps=1e-5, strategy=None, overlap=None):
+    """Barlow Twins loss (Zbontar et al. 2021) on the Gram-form kernels of csrc/barlow.hip:
+      loss = loss_scaling * (sum_i (1 - C_ii)^2 + lambda_weight * sum_{i != j} C_ij^2),   C = zhat1^T zhat2 / N,
+    zhat = every dimension of each view standardised over the GLOBAL batch (biased variance, eps inside the root).  No negatives, no
+    temperature and no l2 normalisation.  C [D, D] is never formed: sum_ij C_ij^2 = sum_ab (zhat1_a.zhat1_b)(zhat2_a.zhat2_b) / N^2,
+    and a replica sums its own rows a of that against all columns b.
+
+    Args:
+      hidden: float32 device tensor [2n, D] = [view-a rows; view-b rows], D a multiple of 64 in [64, 8192].
+      lambda_weight: weight of the off-diagonal (redundancy-reduction) term.
+      loss_scaling: factor on the whole loss.
+      eps: added to the variance of the standardisation.
+      strategy, overlap: as add_contrastive_loss (the raw hidden block is gathered asynchronously; overlap() runs meanwhile).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * R * dL/dhidden of the local rows, [2n, D]: with
+      grad_scale = 1 / R and the summed gradient synchronisation a run optimises L itself), the device scalars .on_diag and .off_diag
+      (the raw sums, before lambda_weight and loss_scaling) and .normalized (zhat of the local rows).  The value is this replica's share
+      loss_scaling * (on_diag + lambda_weight * (R / N^2 * sum_{a local, b} G1_ab G2_ab - sum_i C_ii^2)): the mean over the replicas is
+      the loss, as for add_contrastive_loss.
+    """
+    assert hidden.dtype == torch.float32 and hidden.dim() == 2
+    hidden = hidden.contiguous()
+    n, D = hidden.shape[0] // 2, hidden.shape[1]
+    ops._bt_check_dim(D)
+    if n < 1 or hidden.shape[0] != 2 * n:
+        raise ValueError('add_barlow_twins_loss: hidden holds both views, [2n, D] with n >= 1 (got %d rows)' % hidden.shape[0])
+    R, rank = num_replicas(strategy), replica_id(strategy)
+    pending = gather_hidden(hidden, strategy, async_op=True)
+    if overlap is not None:
+        overlap()
+    h_all = pending()
+    # every replica standardises the whole gathered block in one fixed order: statistics and zhat_all are bitwise the same everywhere
+    zhat_all, rstd = ops.bt_standardize(h_all, eps)
+    out, ws = ops.bt_fwd(zhat_all, n, rank, lambda_weight, loss_scaling)
+    state = {}
+
+    def backward_start(grad_scale=1.0):
+        g, colsums = ops.bt_bwd(zhat_all, n, rank, lambda_weight, loss_scaling, grad_scale, ws)
+        if collectives_on(strategy):
+            strategy.all_reduce_sum(colsums)          # the SyncBN statistics route: the means of the standardisation backward are global
+        state['g'], state['colsums'] = g, colsums
+
+    def backward_finish():
+        return ops.bt_apply(state.pop('g'), zhat_all, rstd, state.pop('colsums'), rank)
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.on_diag, loss.off_diag = out[1:2], out[2:3]
+    N = n * R
+    v1 = zhat_all[rank * n:(rank + 1) * n]
+    loss.normalized = zhat_all if R == 1 else torch.cat([v1, zhat_all[N + rank * n:N + (rank + 1) * n]], 0)
     return loss
 
 

@@ -392,6 +392,101 @@ def supcon_bwd(z_local, z_all, labels_all, rank, temperature, row_stats, grad_sc
     return dz_local, dz_all
 
 
+# ---------------------------------------------------------------- Barlow Twins loss (csrc/barlow.hip)
+BT_DIM_STEP, BT_MIN_DIM, BT_MAX_DIM = 64, 64, 8192       # hidden widths the Barlow Twins kernels take: multiples of 64 in [64, 8192]
+BT_EPS = 1e-5
+
+
+def bt_dim_ok(D):
+    return BT_MIN_DIM <= D <= BT_MAX_DIM and D % BT_DIM_STEP == 0
+
+
+def _bt_check_dim(D):
+    if not bt_dim_ok(D):
+        raise ValueError('the Barlow Twins loss supports hidden widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (BT_DIM_STEP, BT_MIN_DIM, BT_MAX_DIM, D))
+
+
+def _bt_check(zhat_all, n, rank):
+    if zhat_all.dtype != torch.float32 or zhat_all.dim() != 2:
+        raise ValueError('barlow: need a float32 [2N, D] block (got %s %s)' % (tuple(zhat_all.shape), zhat_all.dtype))
+    D = zhat_all.shape[1]
+    _bt_check_dim(D)
+    N = zhat_all.shape[0] // 2
+    n, rank = int(n), int(rank)
+    if n < 1 or N < n or N % n != 0 or zhat_all.shape[0] != 2 * N:
+        raise ValueError('barlow: need zhat_all [2N, D] with N = R*n and n >= 1 (got %d rows for n = %d)' % (zhat_all.shape[0], n))
+    if not 0 <= rank < N // n:
+        raise ValueError('barlow: rank %d is not one of the R = %d replicas' % (rank, N // n))
+    return n, N, D, rank
+
+
+def bt_workspace(n, N, D, device):
+    _bt_check_dim(D)
+    nbytes = lib().bt_workspace_bytes(n, N, D)
+    if nbytes == 0:
+        raise ValueError('barlow: need N = R*n with n >= 1 (got n = %d, N = %d)' % (n, N))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def bt_standardize(h_all, eps=BT_EPS):
+    """h_all [2N, D] = [view-1 rows; view-2 rows] of the global batch -> (zhat_all [2N, D], rstd [2, D]): every column of each view
+    standardised over its N rows (biased variance, eps inside the root)."""
+    if h_all.dtype != torch.float32 or h_all.dim() != 2 or h_all.shape[0] < 2 or h_all.shape[0] % 2:
+        raise ValueError('bt_standardize: need a float32 [2N, D] block with N >= 1 (got %s %s)' % (tuple(h_all.shape), h_all.dtype))
+    N, D = h_all.shape[0] // 2, h_all.shape[1]
+    _bt_check_dim(D)
+    zhat = torch.empty_like(h_all)
+    rstd = torch.empty(2, D, device=h_all.device, dtype=torch.float32)
+    _launch('bt_standardize', 10.0 * N * D, 16.0 * N * D,
+            lambda: lib().bt_standardize(_p(h_all), N, D, float(eps), _p(zhat), _p(rstd), _s()), impl_bytes=32.0 * N * D)
+    return zhat, rstd
+
+
+def bt_fwd(zhat_all, n, rank, lambda_weight, loss_scaling=1.0, ws=None):
+    """Barlow Twins forward on the standardised global block.  Returns out = [loss, on_diag, off_diag] (device; the per-replica values
+    of include/simclr_hip.h) and the workspace, which keeps the Gram blocks and c for bt_bwd."""
+    n, N, D, rank = _bt_check(zhat_all, n, rank)
+    if ws is None:
+        ws = bt_workspace(n, N, D, zhat_all.device)
+    out = step_scalars(4, zhat_all.device)
+    _launch('bt_fwd', 4.0 * n * N * D, 4.0 * (2 * N * D + 2 * n * N),
+            lambda: lib().bt_fwd(_p(zhat_all), n, N, D, rank, float(lambda_weight), float(loss_scaling), _p(out), _p(ws), _s()))
+    return out, ws
+
+
+def bt_gram_blocks(ws, n, N, D):
+    """The [2, n, N] fp32 view of the Gram blocks bt_fwd left in `ws`: block v, row a, column b = zhat_v[rank*n + a] . zhat_v[b]."""
+    off, rows, pitch = lib().bt_gram_offset_bytes(n, N, D), lib().bt_gram_rows(n, N, D), lib().bt_gram_pitch(n, N, D)
+    assert rows > 0 and off % 8 == 0, 'bt_gram_blocks: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return ws[off // 8:].view(torch.float32)[:2 * rows * pitch].view(2, rows, pitch)[:, :n, :N]
+
+
+def bt_bwd(zhat_all, n, rank, lambda_weight, loss_scaling, grad_scale, ws):
+    """Returns g_local [2n, D] = grad_scale * R * dL/dzhat of the local rows and colsums [2, 2, D] float64 (the column sums of g and
+    g o zhat over the local rows: sum them over the replicas before bt_apply)."""
+    n, N, D, rank = _bt_check(zhat_all, n, rank)
+    g = torch.empty(2 * n, D, device=zhat_all.device, dtype=torch.float32)
+    colsums = torch.empty(2, 2, D, device=zhat_all.device, dtype=torch.float64)
+    _launch('bt_bwd', 4.0 * n * N * D, 4.0 * (2 * N * D + 2 * n * N + 2 * n * D),
+            lambda: lib().bt_bwd(_p(zhat_all), n, N, D, rank, float(lambda_weight), float(loss_scaling), float(grad_scale), _p(ws), _p(g),
+                                 _p(colsums), _s()))
+    return g, colsums
+
+
+def bt_apply(g_local, zhat_all, rstd, colsums, rank):
+    """The standardisation backward of the local rows: (g - colsums[v, 0] / N - zhat o colsums[v, 1] / N) * rstd[v]."""
+    n = g_local.shape[0] // 2
+    n, N, D, rank = _bt_check(zhat_all, n, rank)
+    if tuple(g_local.shape) != (2 * n, D) or tuple(rstd.shape) != (2, D) or tuple(colsums.shape) != (2, 2, D) or colsums.dtype != torch.float64:
+        raise ValueError('bt_apply: need g_local [2n, D], rstd [2, D] and float64 colsums [2, 2, D] (got %s, %s, %s %s)'
+                         % (tuple(g_local.shape), tuple(rstd.shape), tuple(colsums.shape), colsums.dtype))
+    dh = torch.empty_like(g_local)
+    _launch('bt_apply', 10.0 * n * D, 4.0 * 6 * n * D,
+            lambda: lib().bt_apply(_p(g_local), _p(zhat_all), _p(rstd), _p(colsums), n, N, D, rank, _p(dh), _s()))
+    return dh
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

@@ -35,11 +35,34 @@ def supcon_loss_on():
     return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'supcon' and FLAGS.train_mode == 'pretrain'
 
 
+def barlow_loss_on():
+    """--contrastive_loss=barlow replaces NT-Xent in the pretraining step by the Barlow Twins loss; train_mode=finetune ignores it."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'barlow' and FLAGS.train_mode == 'pretrain'
+
+
+def barlow_loss_width():
+    """Width of the block the Barlow Twins loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none."""
+    if FLAGS.proj_head_mode == 'none':
+        return (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
+    return FLAGS.proj_out_dim
+
+
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() tells the supervised contrastive loss)."""
-    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon'):
-        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' (got %r)" % FLAGS.contrastive_loss)
+    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() tell the other two)."""
+    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow'):
+        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' (got %r)" % FLAGS.contrastive_loss)
+    if barlow_loss_on() and FLAGS.mode != 'eval':
+        if FLAGS.bt_lambda < 0:
+            raise ValueError('--bt_lambda must be >= 0 (got %r)' % (FLAGS.bt_lambda,))
+        if not FLAGS.bt_loss_scaling > 0:
+            raise ValueError('--bt_loss_scaling must be > 0 (got %r)' % (FLAGS.bt_loss_scaling,))
+        width = barlow_loss_width()
+        if not ops.bt_dim_ok(width):
+            raise ValueError('--contrastive_loss=barlow needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
+                             'proj_head_mode=%r, proj_out_dim=%d): the Barlow Twins kernels take those widths only'
+                             % (ops.BT_DIM_STEP, ops.BT_MIN_DIM, ops.BT_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if supcon_loss_on() and FLAGS.mode != 'eval':
         if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.SUPCON_DIMS:
             raise ValueError('--contrastive_loss=supcon needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
@@ -68,6 +91,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/align_loss', 'train/dist_loss']   # the generalized loss has no logits to score
     elif FLAGS.train_mode == 'pretrain' and supcon_loss_on():
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_positives']
+    elif FLAGS.train_mode == 'pretrain' and barlow_loss_on():
+        names += ['train/contrast_loss', 'train/bt_on_diag', 'train/bt_off_diag']     # no logits to score: the two raw sums instead
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -194,6 +219,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
     RT.strategy = strategy
     generalized = check_contrastive_loss_flags()
     supcon = supcon_loss_on() and not generalized
+    barlow = barlow_loss_on() and not generalized
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
 
     def single_step(features, labels):
@@ -234,6 +260,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 con_loss = obj_lib.add_supcon_loss(
                     outputs, labels['labels'] if isinstance(labels, dict) else labels, hidden_norm=FLAGS.hidden_norm,
                     temperature=FLAGS.temperature, strategy=strategy, overlap=supervised_part)
+            elif barlow:
+                logits_con = None
+                con_loss = obj_lib.add_barlow_twins_loss(
+                    outputs, lambda_weight=FLAGS.bt_lambda, loss_scaling=FLAGS.bt_loss_scaling, strategy=strategy, overlap=supervised_part)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -299,6 +329,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
             vals['train/contrast_positives'] = con_loss.positives.reshape(-1)[:1]
+        elif con_loss is not None and barlow:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/bt_on_diag'] = con_loss.on_diag.reshape(-1)[:1]
+            vals['train/bt_off_diag'] = con_loss.off_diag.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -326,6 +360,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 con_loss.align, con_loss.dist_match = at['train/align_loss'], at['train/dist_loss']
             elif supcon and 'train/contrast_acc' in at and 'train/contrast_positives' in at:
                 con_loss.acc, con_loss.positives = at['train/contrast_acc'], at['train/contrast_positives']
+            elif barlow and 'train/bt_on_diag' in at and 'train/bt_off_diag' in at:
+                con_loss.on_diag, con_loss.off_diag = at['train/bt_on_diag'], at['train/bt_off_diag']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:

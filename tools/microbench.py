@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -337,6 +337,44 @@ def main():
                     row['supcon_over_gcl_lse_fwd'], row['supcon_over_gcl_lse_bwd']), flush=True)
             res.append(row)
             del zl, za, ws, gws, sws
+    if 'barlow' in what:
+        # Barlow Twins loss (csrc/barlow.hip) beside NT-Xent at the same (n, N, D) in the same run: the register-resident sweeps at
+        # D = 128, the wide kernels above 256 -- the same exact fp32-input MFMA.  Matrix FLOPs: the two Gram blocks 2 x 2nND = 4nND forward,
+        # the two [n, N] x [N, D] products 4nND backward; NT-Xent 8nND / 24nND.  The forward also writes the [2, n, N] blocks.
+        for (n, N, D) in [(512, 512, 128), (512, 4096, 128), (512, 4096, 2048), (512, 512, 8192)]:
+            h = torch.randn(2 * N, D, device=dev) + 1.0
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            bws = ops.bt_workspace(n, N, D, dev)
+            zhat, rstd = ops.bt_standardize(h)
+            ops.bt_fwd(zhat, n, 0, 0.0051, ws=bws)
+            g, cs = ops.bt_bwd(zhat, n, 0, 0.0051, 1.0, 1.0, bws)
+            nt = 'ntxent_wide' if ops.ntxent_is_wide(D) else 'ntxent'
+            row = dict(layer='barlow n%d N%d D%d' % (n, N, D), ntxent_kernels=nt, bt_flops=4.0 * n * N * D, ntxent_fwd_flops=8.0 * n * N * D,
+                       ntxent_bwd_flops=24.0 * n * N * D, bt_workspace_bytes=bws.numel() * 8,
+                       bt_standardize_us=timeit(lambda: ops.bt_standardize(h), args.iters),
+                       bt_fwd_us=timeit(lambda: ops.bt_fwd(zhat, n, 0, 0.0051, ws=bws), args.iters),
+                       bt_bwd_us=timeit(lambda: ops.bt_bwd(zhat, n, 0, 0.0051, 1.0, 1.0, bws), args.iters),
+                       bt_apply_us=timeit(lambda: ops.bt_apply(g, zhat, rstd, cs, 0), args.iters),
+                       ntxent_fwd_us=timeit(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws), args.iters),
+                       ntxent_bwd_us=timeit(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws), args.iters))
+            row['bt_standardize_gbs'] = 32.0 * N * D / row['bt_standardize_us'] / 1e3       # three reads and one write of [2N, D]
+            row['bt_fwd_tfs'] = row['bt_flops'] / row['bt_fwd_us'] / 1e6
+            row['bt_bwd_tfs'] = row['bt_flops'] / row['bt_bwd_us'] / 1e6
+            row['ntxent_fwd_tfs'] = row['ntxent_fwd_flops'] / row['ntxent_fwd_us'] / 1e6
+            row['ntxent_bwd_tfs'] = row['ntxent_bwd_flops'] / row['ntxent_bwd_us'] / 1e6
+            row['bt_over_ntxent_fwd'] = row['bt_fwd_us'] / row['ntxent_fwd_us']
+            row['bt_over_ntxent_bwd'] = row['bt_bwd_us'] / row['ntxent_bwd_us']
+            print('barlow n=%d N=%d D=%d: standardize %.0f us (%.0f GB/s) fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s) apply %.0f us | %s fwd '
+                  '%.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s) | barlow / ntxent fwd %.2f bwd %.2f'
+                  % (n, N, D, row['bt_standardize_us'], row['bt_standardize_gbs'], row['bt_fwd_us'], row['bt_fwd_tfs'], row['bt_bwd_us'],
+                     row['bt_bwd_tfs'], row['bt_apply_us'], nt, row['ntxent_fwd_us'], row['ntxent_fwd_tfs'], row['ntxent_bwd_us'],
+                     row['ntxent_bwd_tfs'], row['bt_over_ntxent_fwd'], row['bt_over_ntxent_bwd']), flush=True)
+            res.append(row)
+            del h, zl, za, ws, bws, zhat, rstd, g, cs
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
