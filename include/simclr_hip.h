@@ -561,6 +561,30 @@ int simclr_comm_destroy(void* mailbox);
 int simclr_comm_stats_allreduce(const double* in, double* out, int count, void* const* peers, int rank, int world,
                                 int max_doubles, unsigned seq, int* status, simclr_stream_t stream);
 
+/* ---- BYOL on a momentum target network (csrc/byol.hip): Grill et al. 2020, Bootstrap Your Own Latent ----
+ * Exponential moving average of every target tensor towards its online tensor in ONE launch, on the descriptor / chunk tables of
+ * simclr_lars_multi_tensor: table = device int64 [3 * num_tensors], row 0 = target pointers, row 1 = online pointers, row 2 = element
+ * counts (fp32 tensors); chunks[2c] = tensor id, chunks[2c + 1] = element offset, a multiple of simclr_lars_chunk_elems().
+ * t = t + one_minus_tau * (o - t): subtract, multiply and add are rounded separately (no fma), so float32 numpy restates it bit for
+ * bit.  16-byte accesses where both pointers of a chunk are 16-byte aligned, scalar ones otherwise; any element count.
+ * Refused: empty / null tables, one_minus_tau outside [0, 1]. */
+int simclr_ema_multi_tensor(const long long* table, int num_tensors, const long long* chunks, int num_chunks, float one_minus_tau,
+                            simclr_stream_t stream);
+/* q [2b, D] = the online predictor's output, t [2b, D] = the target network's projection, fp32, 16-byte aligned; row r of q pairs with
+ * row p = (r + b) mod 2b of t.  With xhat = x / sqrt(max(sum x^2, 1e-12)) (tf.math.l2_normalize) and l_r = sum_j (qhat_rj - that_pj)^2
+ * (the difference is summed in double; 2 - 2 cos is never formed):
+ *   out[0] = (1 / b) sum_r l_r (the sum of the two per-view means, the convention of NT-Xent here), out[1] = mean_r qhat_r . that_p.
+ * Rows are summed in double in a fixed order: two calls are bitwise equal.  row_stats: device double [2b, 4], kept for simclr_byol_bwd;
+ * row_out: device double [2b, 2] scratch.  Refused (nothing launched): null / misaligned pointers, b < 1, D not a multiple of 64 in
+ * [64, 8192]. */
+int simclr_byol_fwd(const float* q, const float* t, int b, int D, float* out, double* row_stats, double* row_out,
+                    simclr_stream_t stream);
+/* dq [2b, D] fp32 = (grad_scale / b) * d(sum_r l_r) / dq, from the row_stats of simclr_byol_fwd on the same q, t.  A row with
+ * sum q^2 < 1e-12 has the constant norm 1e-6 (the gradient of tf.maximum goes to the epsilon): dq_r = (grad_scale / b) * 2e6 *
+ * (qhat_r - that_p).  t gets no gradient.  Refusals as simclr_byol_fwd. */
+int simclr_byol_bwd(const float* q, const float* t, int b, int D, const double* row_stats, float grad_scale, float* dq,
+                    simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

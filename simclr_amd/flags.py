@@ -103,7 +103,9 @@ _DEFS = [
                                         "or 'supcon' (add_supcon_loss: supervised contrastive loss, every same-class row of the global batch a positive; "
                                         "projection width 64, 128 or 256) or 'barlow' (add_barlow_twins_loss: Barlow Twins, no negatives; loss width "
                                         '= proj_out_dim, or the encoder width with proj_head_mode=none, a multiple of 64 in [64, 8192]; --hidden_norm and '
-                                        '--temperature are ignored with it).  Ignored by --train_mode=finetune.'),
+                                        "--temperature are ignored with it) or 'byol' (add_byol_loss: BYOL on a momentum target network with a predictor "
+                                        'on the online side; loss width as for barlow; always l2-normalised, --hidden_norm and --temperature are ignored).  '
+                                        'Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
     ('gcl_lambda', 1.0, float, 'MI355X build: weight of the distribution-matching term (lambda_weight).'),
@@ -112,6 +114,10 @@ _DEFS = [
     # Barlow Twins (Zbontar et al. 2021) in place of NT-Xent for pretraining
     ('bt_lambda', 0.0051, float, 'MI355X build: weight of the off-diagonal (redundancy-reduction) term of the Barlow Twins loss (lambda_weight).'),
     ('bt_loss_scaling', 1.0, float, 'MI355X build: factor on the whole Barlow Twins loss (loss_scaling).'),
+    # BYOL (Grill et al. 2020) in place of NT-Xent for pretraining: a momentum target network and a predictor on the online side
+    ('byol_tau_base', 0.996, float, 'MI355X build: base decay of the target network\'s moving average; step k of K uses '
+                                    'tau_k = 1 - (1 - byol_tau_base) * (cos(pi k / K) + 1) / 2.  In [0, 1].'),
+    ('byol_pred_hidden_dim', 4096, int, 'MI355X build: hidden width of the BYOL predictor (dense + BN + ReLU, dense): a multiple of 64 in [64, 8192].'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),

@@ -231,6 +231,39 @@ class ProjectionHead(Layer):  # tf2/model.py:157-213
         return d
 
 
+def byol_on():
+    """--contrastive_loss=byol in a pretraining run: the online model carries a predictor and the step needs a TargetNetwork."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'byol' and FLAGS.train_mode == 'pretrain'
+
+
+def projection_width():
+    """Width of the block the pretraining loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none.  The one
+    statement of that rule: the start-up checks of run.check_contrastive_loss_flags and the predictor's output layer both call it."""
+    if FLAGS.proj_head_mode == 'none':
+        return (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
+    return FLAGS.proj_out_dim
+
+
+class PredictionHead(Layer):
+    """The predictor of BYOL (Grill et al. 2020, section 3.3) on the online projection output: dense + BN + ReLU of width
+    byol_pred_hidden_dim, then a dense layer back to the loss width.  The paper's output layer has a bias; LinearLayer without
+    BatchNorm applies none (tf2/model.py:146 creates it only with use_bias=True), and this one is built without.  Trained,
+    weight-decayed and LARS-adapted by the name rules of the projection head's layers."""
+
+    def __init__(self, **kwargs):
+        with scope('prediction_head'):
+            self.linear_layers = [LinearLayer(num_classes=FLAGS.byol_pred_hidden_dim, use_bias=True, use_bn=True, name='l_0'),
+                                  LinearLayer(num_classes=projection_width(), use_bias=False, use_bn=False, name='l_1')]
+
+    def __call__(self, inputs, training):
+        hidden = self.linear_layers[0](inputs, training, relu=True)
+        return self.linear_layers[1](hidden, training)
+
+    def backward(self, dq):
+        """dq: gradient wrt the predictor's output -> gradient wrt its input (the online projection output)."""
+        return self.linear_layers[0].backward(self.linear_layers[1].backward(dq))
+
+
 class SupLogits:
     """Supervised-head output before the bias add; bias + softmax-CE + gradient are one fused
     launch in objective.add_supervised_loss."""
@@ -271,11 +304,14 @@ class Model(Layer):
             self.supervised_head = None
             if FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
                 self.supervised_head = SupervisedHead(num_classes)
+            # BYOL: constructed last, so every other layer keeps the name (and, built after them, the initial value) of an ntxent run
+            self.prediction_head = PredictionHead() if byol_on() else None
         self._flat_grads = None
 
-    def __call__(self, inputs, training):
+    def __call__(self, inputs, training, blur=True):
         """inputs: float32 [b, H, W, 3k] in [0,1].  Returns (projection_head_outputs float32
-        [k*b, proj_out_dim], supervised_head_outputs SupLogits) like tf2/model.py:241-280."""
+        [k*b, proj_out_dim], supervised_head_outputs SupLogits) like tf2/model.py:241-280.
+        blur=False: the caller drew the random blur already (the BYOL step hands the online and the target network the same pixels)."""
         if training and FLAGS.train_mode == 'pretrain':
             if FLAGS.fine_tune_after_block > -1:
                 raise ValueError('Does not support layer freezing during pretraining,'
@@ -287,7 +323,7 @@ class Model(Layer):
         # activations to fp16's range (a freshly initialised network's moving averages do not normalise at all): the split-fp16 forward is
         # for training-mode BatchNorm only, an inference forward runs its fp32 products as six bf16 terms instead (same accuracy class).
         ops.select_f32_matmul(inference=not training)
-        if FLAGS.use_blur and training and FLAGS.train_mode == 'pretrain':
+        if blur and FLAGS.use_blur and training and FLAGS.train_mode == 'pretrain':
             # batch_random_blur on the device (tf2/model.py:255-258), fused over the k views
             inputs = data_util.batch_random_blur_tensor(inputs, FLAGS.image_size, FLAGS.image_size)
         num_transforms = inputs.shape[3] // 3
@@ -326,6 +362,14 @@ class Model(Layer):
         out = ops.cast(hiddens, torch.float32) if hiddens.dtype != torch.float32 else hiddens.clone()
         self.release()
         return out
+
+    def predict(self, projection_head_outputs, training=True):
+        """BYOL: the predictor on the online projection output, float32 [2b, D] -> float32 [2b, D]."""
+        return self.prediction_head(projection_head_outputs, training)
+
+    def backward_predictor(self, dq):
+        """Gradient wrt the predictor's output -> d_proj for Model.backward (the predictor's weight gradients are written)."""
+        return self.prediction_head.backward(dq)
 
     def backward_supervised(self, d_sup):
         """Backward of the linear-eval head alone (its input is stop_gradient'ed, tf2/model.py:276-277)."""
@@ -403,6 +447,11 @@ class Model(Layer):
         if self.supervised_head is not None:
             sel = FLAGS.ft_proj_selector if FLAGS.proj_head_mode != 'none' else 0
             self.supervised_head.linear_layer.build(feats[sel])
+        if self.prediction_head is not None:
+            l0, l1 = self.prediction_head.linear_layers
+            l0.build(feats[-1])
+            l0.bn_relu.build(l0.npad)
+            l1.build(l0.npad)
 
     def release(self):
         super().release()
@@ -478,6 +527,126 @@ class Teacher:
             _, logits = self.model(features, training=False)
         self.model.release()
         return logits
+
+
+def byol_tau(step, total_steps, tau_base):
+    """Decay of the target network's moving average at optimizer step `step` of `total_steps` (Grill et al. 2020, section 3.3):
+    1 - (1 - tau_base) * (cos(pi * step / total_steps) + 1) / 2, in double.  tau_0 = tau_base, tau_K = 1."""
+    return 1.0 - (1.0 - float(tau_base)) * (math.cos(math.pi * float(step) / float(total_steps)) + 1.0) / 2.0
+
+
+def target_flag_values():
+    """The flag values the BYOL target network is built and called under: a plain pretraining encoder and projection head of the
+    online architecture -- no supervised head, no predictor, no DropBlock site."""
+    return dict(train_mode='pretrain', contrastive_loss='ntxent', lineareval_while_pretraining=False, fine_tune_after_block=-1,
+                dropblock_keep_probs='')
+
+
+class _WithTarget:
+    """What a BYOL checkpoint holds: every variable of the online model under its own name (the optimizer's slots hang on these very
+    objects) and every target variable under the prefix `target/`."""
+
+    def __init__(self, model, target):
+        self.model, self.target = model, target
+        self.supervised_head = model.supervised_head
+        self._target_variables = [Variable(TargetNetwork.PREFIX + v.name, v.value, False) for v in target.model.variables]
+
+    @property
+    def variables(self):
+        return self.model.variables + self._target_variables
+
+
+class TargetNetwork:
+    """The momentum target network of BYOL: a second encoder and projection head (no supervised head, no predictor), built under
+    `target_flag_values()` and RT.fresh_names() -- its variables carry the online names, the online model's names and initial values
+    are those of a run without a target.  The whole model is `trainable = False`: nothing of it reaches trainable_variables, the flat
+    gradient buffer, the optimizer's table or add_weight_decay.
+
+    It is not frozen through fine_tune_after_block (Model.__call__ refuses that flag in pretraining): the layer switch alone makes
+    every block release what it kept, and `stem_trainable = False` drops the stem's pooling tap ids.
+
+    A call is a TRAINING-mode forward (batch statistics, SyncBN over the replicas, the target's own moving statistics move) on pixels
+    the caller has blurred already; it returns the float32 [2b, D] projection output and keeps no activation.
+
+    update(step) moves every trainable variable of the online encoder and projection head into its target namesake,
+    t + (1 - tau_step) * (o - t), in one launch, and marks the target's compute copies stale: RT.optimizer_stepped() leaves frozen
+    layers' copies alone, and these masters change every step."""
+
+    PREFIX = 'target/'
+
+    def __init__(self, online_model, total_steps, image_size=None):
+        if online_model.prediction_head is None:
+            raise ValueError('TargetNetwork: the online model has no predictor (it was built without --contrastive_loss=byol)')
+        self.online = online_model
+        self.total_steps = max(int(total_steps), 1)
+        self.flag_values = target_flag_values()
+        size = image_size or FLAGS.image_size
+        zeros = None
+        if online_model.resnet_model.stem_conv.kernel is None:
+            # variables exist only after the first forward pass (lazy build); inference mode: no statistic moves
+            zeros = torch.zeros(2, size, size, 3, device=RT.device)
+            online_model(zeros, training=False)
+            online_model.release()
+        if online_model.prediction_head.linear_layers[0].kernel is None:
+            # after the encoder, the projection head and the supervised head: their initial values are those of an ntxent run
+            online_model.prediction_head(torch.zeros(2, projection_width(), device=RT.device), training=False)
+            online_model.prediction_head.release()
+        with FLAGS.override(**self.flag_values), RT.fresh_names():
+            self.model = Model(0)
+            self.model.trainable = False
+            self.model.resnet_model.stem_trainable = False
+            self.model(zeros if zeros is not None else torch.zeros(2, size, size, 3, device=RT.device), training=False)
+            self.model.release()
+        online = {v.name: v for v in online_model.resnet_model.variables + online_model._projection_head.variables}
+        self._pairs = []                      # (target variable, online variable) by name, every variable of the target
+        for v in self.model.variables:
+            o = online.get(v.name)
+            if o is None or o.shape != v.shape:
+                raise ValueError('TargetNetwork: target variable %s has no online namesake of its shape' % v.name)
+            self._pairs.append((v, o))
+        trained = {id(v) for v in online_model.resnet_model.trainable_variables + online_model._projection_head.trainable_variables}
+        self._ema_pairs = [(t, o) for t, o in self._pairs if id(o) in trained]
+        self._tables = ops.EmaTables()
+        self.copy_from_online()
+
+    def copy_from_online(self):
+        """Every target variable (moving statistics included) becomes a bitwise copy of its online namesake."""
+        for t, o in self._pairs:
+            t.value.copy_(o.value)
+        self._invalidate()
+
+    def _invalidate(self):
+        for l in _all_layers(self.model):
+            if '_version' in l.__dict__:
+                l._frozen_key = None
+                l._dtype = None
+
+    @property
+    def variables(self):
+        return self.model.variables
+
+    def checkpointable(self):
+        """The object run.main hands the checkpoint: online variables + `target/`-prefixed target variables."""
+        return _WithTarget(self.online, self)
+
+    def tau(self, step):
+        return byol_tau(step, self.total_steps, FLAGS.byol_tau_base)
+
+    def update(self, step):
+        """After optimizer.apply_gradients of step `step` (optimizer.iterations before its increment).  tau is formed on the host in
+        double; 1 - tau is cast to float32 once."""
+        import numpy as np
+        omt = float(np.float32(1.0 - self.tau(step)))
+        self._tables.run([t.value for t, _ in self._ema_pairs], [o.value for _, o in self._ema_pairs], omt)
+        self._invalidate()
+        return omt
+
+    def __call__(self, features):
+        """features [b, H, W, 6] (blurred by the caller) -> float32 [2b, D] projection output of the target network."""
+        with FLAGS.override(**self.flag_values):
+            proj, _ = self.model(features, training=True, blur=False)
+        self.model.release()
+        return proj
 
 
 def _all_layers(layer):

@@ -16,6 +16,9 @@ positive) on the kernels of csrc/supcon.hip.
 
 `add_barlow_twins_loss` is the Barlow Twins loss of Zbontar et al. 2021 (redundancy reduction on the cross-correlation of the two views'
 batch-standardised hiddens; no negatives) in its Gram form on the kernels of csrc/barlow.hip.
+
+`add_byol_loss` is the BYOL loss of Grill et al. 2020 (squared distance of the l2-normalised online prediction of one view to the
+l2-normalised projection a momentum target network gives the other view; no negatives, no collective) on the kernels of csrc/byol.hip.
 """
 import torch
 
@@ -455,6 +458,36 @@ def add_barlow_twins_loss(hidden, lambda_weight=0.0051, loss_scaling=1.0, eps=1e
     N = n * R
     v1 = zhat_all[rank * n:(rank + 1) * n]
     loss.normalized = zhat_all if R == 1 else torch.cat([v1, zhat_all[N + rank * n:N + (rank + 1) * n]], 0)
+    return loss
+
+
+def add_byol_loss(online, target, strategy=None, overlap=None):
+    """BYOL loss (Grill et al. 2020, Bootstrap Your Own Latent, eq. 2) on the kernels of csrc/byol.hip:
+      loss = (1 / b) sum_{r < 2b} |l2n(online_r) - l2n(target_{(r + b) mod 2b})|^2,
+    the prediction of each view against the target projection of the other one, both directions -- the sum of the two per-view means,
+    as add_contrastive_loss forms NT-Xent.  l2n is tf.math.l2_normalize (epsilon 1e-12); always applied.  The squared difference is
+    summed in double: 2 - 2 cos is never formed, so a nearly converged pair keeps its digits.
+
+    Args:
+      online: float32 device tensor [2b, D] = the online predictor's output, [view-a rows; view-b rows]; D a multiple of 64 in [64, 8192].
+      target: float32 device tensor [2b, D] = the target network's projection output of the same batch.  It gets no gradient.
+      strategy: replica context or None.  The loss needs NO collective: a replica's value is the mean over its own rows, the mean over
+        the replicas is the loss, and `backward` is called with 1 / R (SyncBN is the only cross-replica coupling).
+      overlap: optional zero-argument callable, run after the forward launch.
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * dloss/donline, [2b, D]), the device scalar
+      .cosine (mean cosine of the paired rows) and .value.
+    """
+    online, target = online.contiguous(), target.contiguous()
+    out, row_stats = ops.byol_fwd(online, target)
+    if overlap is not None:
+        overlap()
+
+    def backward(grad_scale=1.0):
+        return ops.byol_bwd(online, target, row_stats, grad_scale)
+
+    loss = _Loss(out[0:1], backward)
+    loss.cosine = out[1:2]
     return loss
 
 

@@ -487,6 +487,89 @@ def bt_apply(g_local, zhat_all, rstd, colsums, rank):
     return dh
 
 
+# ---------------------------------------------------------------- BYOL (csrc/byol.hip)
+BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
+
+
+def byol_dim_ok(D):
+    return BYOL_MIN_DIM <= D <= BYOL_MAX_DIM and D % BYOL_DIM_STEP == 0
+
+
+def _byol_check(q, t):
+    if q.dtype != torch.float32 or t.dtype != torch.float32 or q.dim() != 2 or tuple(q.shape) != tuple(t.shape):
+        raise ValueError('byol: need float32 q and t of one shape [2b, D] (got %s %s, %s %s)'
+                         % (tuple(q.shape), q.dtype, tuple(t.shape), t.dtype))
+    rows, D = q.shape
+    if rows < 2 or rows % 2:
+        raise ValueError('byol: q and t hold both views, [2b, D] with b >= 1 (got %d rows)' % rows)
+    if not byol_dim_ok(D):
+        raise ValueError('the BYOL loss supports widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM, D))
+    return rows // 2, D
+
+
+def byol_fwd(q, t):
+    """q [2b, D] (online predictor output), t [2b, D] (target projection) -> (out = [loss, cosine] device fp32, row_stats [2b, 4] float64
+    for byol_bwd).  Row r of q pairs with row (r + b) mod 2b of t (include/simclr_hip.h)."""
+    b, D = _byol_check(q, t)
+    out = step_scalars(2, q.device)
+    buf = torch.empty(2 * b * 6, device=q.device, dtype=torch.float64)
+    row_stats, row_out = buf[:2 * b * 4], buf[2 * b * 4:]
+    _launch('byol_fwd', 8.0 * 2 * b * D, 8.0 * 2 * b * D,
+            lambda: lib().byol_fwd(_p(q), _p(t), b, D, _p(out), _p(row_stats), _p(row_out), _s()))
+    return out, row_stats.view(2 * b, 4)
+
+
+def byol_bwd(q, t, row_stats, grad_scale):
+    """dq [2b, D] = (grad_scale / b) * d(sum_r l_r) / dq, the eps branch of the normalisation included; t gets no gradient."""
+    b, D = _byol_check(q, t)
+    if row_stats.dtype != torch.float64 or row_stats.numel() != 2 * b * 4:
+        raise ValueError('byol_bwd: row_stats is the float64 [2b, 4] block byol_fwd returned (got %s %s)' % (tuple(row_stats.shape), row_stats.dtype))
+    dq = torch.empty_like(q)
+    _launch('byol_bwd', 10.0 * 2 * b * D, 12.0 * 2 * b * D,
+            lambda: lib().byol_bwd(_p(q), _p(t), b, D, _p(row_stats), float(grad_scale), _p(dq), _s()))
+    return dq
+
+
+class EmaTables:
+    """Descriptor and chunk tables of simclr_ema_multi_tensor over (target, online) fp32 tensor pairs, in the layout of
+    lars_optimizer.LARSOptimizer._build: built once, rebuilt when a pointer changes.
+    run(targets, onlines, one_minus_tau): targets[k] <- targets[k] + one_minus_tau * (onlines[k] - targets[k]) in one launch."""
+
+    def __init__(self):
+        self._key = None
+
+    def build(self, targets, onlines):
+        chunk = lib().lars_chunk_elems()
+        T = len(targets)
+        table = torch.zeros(3 * T, dtype=torch.int64)
+        chunks = []
+        for k, (t, o) in enumerate(zip(targets, onlines)):
+            if t.dtype != torch.float32 or o.dtype != torch.float32 or t.numel() != o.numel():
+                raise ValueError('ema: tensor %d: need two float32 tensors of one size (got %s %s, %s %s)'
+                                 % (k, tuple(t.shape), t.dtype, tuple(o.shape), o.dtype))
+            assert t.is_cuda and o.is_cuda and t.is_contiguous() and o.is_contiguous(), 'need contiguous device tensors'
+            table[0 * T + k] = t.data_ptr()
+            table[1 * T + k] = o.data_ptr()
+            table[2 * T + k] = t.numel()
+            for off in range(0, t.numel(), chunk):
+                chunks.append((k, off))
+        dev = targets[0].device
+        self.table = table.to(dev)
+        self.chunks = torch.tensor(chunks, dtype=torch.int64).view(-1).to(dev)
+        self.num = (T, len(chunks))
+        self.elems = int(sum(t.numel() for t in targets))
+        self._key = tuple((t.data_ptr(), o.data_ptr()) for t, o in zip(targets, onlines))
+
+    def run(self, targets, onlines, one_minus_tau):
+        key = tuple((t.data_ptr(), o.data_ptr()) for t, o in zip(targets, onlines))
+        if key != self._key:
+            self.build(targets, onlines)
+        T, nchunks = self.num
+        _launch('ema_multi_tensor', 3.0 * self.elems, 12.0 * self.elems,
+                lambda: lib().ema_multi_tensor(_p(self.table), T, _p(self.chunks), nchunks, float(one_minus_tau), _s()))
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

@@ -17,7 +17,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from . import metrics, ops
+from . import data_util, metrics, ops
 from . import model as model_lib
 from . import objective as obj_lib
 from .comm import Strategy, collectives_on, num_replicas
@@ -42,16 +42,31 @@ def barlow_loss_on():
 
 def barlow_loss_width():
     """Width of the block the Barlow Twins loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none."""
-    if FLAGS.proj_head_mode == 'none':
-        return (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
-    return FLAGS.proj_out_dim
+    return model_lib.projection_width()
+
+
+# --contrastive_loss=byol replaces NT-Xent in the pretraining step by BYOL on a momentum target network; train_mode=finetune ignores it.
+# One definition: the model reads the same switch to decide whether it carries a predictor.
+byol_loss_on = model_lib.byol_on
 
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() tell the other two)."""
-    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow'):
-        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' (got %r)" % FLAGS.contrastive_loss)
+    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() tell the others)."""
+    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow', 'byol'):
+        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' (got %r)" % FLAGS.contrastive_loss)
+    if byol_loss_on() and FLAGS.mode != 'eval':
+        if not 0.0 <= FLAGS.byol_tau_base <= 1.0:           # (NaN fails both comparisons)
+            raise ValueError('--byol_tau_base must lie in [0, 1] (got %r)' % (FLAGS.byol_tau_base,))
+        if not ops.byol_dim_ok(FLAGS.byol_pred_hidden_dim):
+            raise ValueError('--byol_pred_hidden_dim must be a multiple of %d in [%d, %d] (got %r)'
+                             % (ops.BYOL_DIM_STEP, ops.BYOL_MIN_DIM, ops.BYOL_MAX_DIM, FLAGS.byol_pred_hidden_dim))
+        width = barlow_loss_width()
+        if not ops.byol_dim_ok(width):
+            raise ValueError('--contrastive_loss=byol needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
+                             'proj_head_mode=%r, proj_out_dim=%d): the BYOL kernels and the predictor take those widths only'
+                             % (ops.BYOL_DIM_STEP, ops.BYOL_MIN_DIM, ops.BYOL_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if barlow_loss_on() and FLAGS.mode != 'eval':
         if FLAGS.bt_lambda < 0:
             raise ValueError('--bt_lambda must be >= 0 (got %r)' % (FLAGS.bt_lambda,))
@@ -93,6 +108,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_positives']
     elif FLAGS.train_mode == 'pretrain' and barlow_loss_on():
         names += ['train/contrast_loss', 'train/bt_on_diag', 'train/bt_off_diag']     # no logits to score: the two raw sums instead
+    elif FLAGS.train_mode == 'pretrain' and byol_loss_on():
+        names += ['train/contrast_loss', 'train/byol_cosine']         # no logits to score: the mean cosine of the paired rows instead
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -202,8 +219,11 @@ def check_knn_flags(num_train_examples=None):
     return bank
 
 
-def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None):
+def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
+    target: model.TargetNetwork (or a stand-in with its __call__ / update), required by --contrastive_loss=byol.  The step is then:
+    blur once, target forward (training mode, nothing kept), online forward on the same pixels, predictor, add_byol_loss, the usual
+    backward entering through the predictor, optimizer, target.update(step).
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -220,6 +240,12 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
     generalized = check_contrastive_loss_flags()
     supcon = supcon_loss_on() and not generalized
     barlow = barlow_loss_on() and not generalized
+    byol = byol_loss_on() and not generalized
+    if byol and target is None:
+        raise ValueError('--contrastive_loss=byol needs a target network: make_single_step(..., target=model.TargetNetwork(model, steps))')
+    if target is not None and not byol:
+        raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
+                         % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
 
     def single_step(features, labels):
@@ -232,7 +258,14 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
             # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
             # training arithmetic again, for the rest of the step
             teacher_logits = teacher(features)
-        projection_head_outputs, supervised_head_outputs = model(features, training=True)   # :577-578
+        if byol:
+            # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
+            if FLAGS.use_blur:
+                features = data_util.batch_random_blur_tensor(features, FLAGS.image_size, FLAGS.image_size)
+            target_outputs = target(features)          # released before the online forward: the two activation sets never coexist
+            projection_head_outputs, supervised_head_outputs = model(features, training=True, blur=False)
+        else:
+            projection_head_outputs, supervised_head_outputs = model(features, training=True)   # :577-578
         R = num_replicas(strategy)
         con_loss = sup_loss = None
         sup_box = {}
@@ -264,6 +297,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 logits_con = None
                 con_loss = obj_lib.add_barlow_twins_loss(
                     outputs, lambda_weight=FLAGS.bt_lambda, loss_scaling=FLAGS.bt_loss_scaling, strategy=strategy, overlap=supervised_part)
+            elif byol:
+                logits_con = None
+                con_loss = obj_lib.add_byol_loss(model.predict(outputs), target_outputs, strategy=strategy, overlap=supervised_part)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -297,10 +333,16 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
         else:
             model.backward_supervised(d_sup)
             d_proj = con_loss.backward_finish() if con_loss is not None else None
+            if byol:
+                d_proj = model.backward_predictor(d_proj)
             model.backward(d_proj, None, on_stage=sync.on_stage)
         join_wgrad_stream()
         sync.wait()
+        if byol:
+            step_index = int(getattr(optimizer, 'iterations', 0))      # before the increment: a restored run continues the tau schedule
         optimizer.apply_gradients([(v.grad, v) for v in state['apply']])                   # :622
+        if byol:
+            target.update(step_index)
         RT.optimizer_stepped()
         ops.end_step()
         if strategy is not None:
@@ -333,6 +375,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/bt_on_diag'] = con_loss.on_diag.reshape(-1)[:1]
             vals['train/bt_off_diag'] = con_loss.off_diag.reshape(-1)[:1]
+        elif con_loss is not None and byol:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/byol_cosine'] = con_loss.cosine.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -362,6 +407,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None)
                 con_loss.acc, con_loss.positives = at['train/contrast_acc'], at['train/contrast_positives']
             elif barlow and 'train/bt_on_diag' in at and 'train/bt_off_diag' in at:
                 con_loss.on_diag, con_loss.off_diag = at['train/bt_on_diag'], at['train/bt_off_diag']
+            elif byol:
+                if 'train/byol_cosine' in at:
+                    con_loss.cosine = at['train/byol_cosine']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:
@@ -598,7 +646,9 @@ def main(argv):
 
     learning_rate = model_lib.WarmUpAndCosineDecay(FLAGS.learning_rate, num_train_examples)
     optimizer = model_lib.build_optimizer(learning_rate)
-    step_fn = make_single_step(model, optimizer, strategy, teacher=teacher)
+    # BYOL: the target network is built after the online model (whose variables it makes exist first) as a bitwise copy of it
+    target = model_lib.TargetNetwork(model, train_steps) if byol_loss_on() else None
+    step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
     if builder is None:
@@ -613,8 +663,12 @@ def main(argv):
         # restore BEFORE step 0 as tf2/run.py:520-521 does: the latest checkpoint of model_dir (weights, BN moving
         # statistics, LARS slots, step) or, failing that, the weights of --checkpoint (slots stay zero, step 0).
         model(torch.zeros(2, FLAGS.image_size, FLAGS.image_size, 3, device=RT.device), training=False)
-        manager, status = try_restore_from_checkpoint(model, optimizer, FLAGS.model_dir, FLAGS.checkpoint,
+        manager, status = try_restore_from_checkpoint(target.checkpointable() if target is not None else model, optimizer,
+                                                      FLAGS.model_dir, FLAGS.checkpoint,
                                                       FLAGS.keep_checkpoint_max, FLAGS.zero_init_logits_layer)
+        if target is not None and status is not None and (
+                not manager.latest_checkpoint or any(n.startswith(target.PREFIX) for n in status.missing_in_checkpoint)):
+            target.copy_from_online()        # --checkpoint (or a file without target entries): the copy is made after the restore
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -375,6 +375,48 @@ def main():
                      row['ntxent_bwd_tfs'], row['bt_over_ntxent_fwd'], row['bt_over_ntxent_bwd']), flush=True)
             res.append(row)
             del h, zl, za, ws, bws, zhat, rstd, g, cs
+    if 'byol' in what:
+        # BYOL (csrc/byol.hip).  The moving average of the target network over ResNet-50's variable list (the list of the 'lars' entry
+        # below) in GB/s of 12 bytes per element (target read + write, online read), beside simclr_lars_multi_tensor on the same list in
+        # the same run -- LARS moves at least 20 bytes per element (w, g, v read, w, v written) plus its norm pass.  Then the loss
+        # kernels in GB/s of the bytes each must move: forward q and t once (8 B / element), backward q, t and dq (12 B / element).
+        from simclr_amd.lars_optimizer import LARSOptimizer, Variable
+        sizes = []
+        for (H, Cin, Cout, k, s, cnt) in R50:
+            sizes += [(k * k * Cin * Cout,)] * cnt + [(Cout,), (Cout,)] * cnt
+        sizes += [(7 * 7 * 3 * 64,), (2048 * 2048,), (2048 * 2048,), (2048 * 128,), (2048 * 1000,), (1000,)]
+        vs = []
+        for i, shp in enumerate(sizes):
+            v = Variable('conv2d_%d/kernel:0' % i if shp[0] > 4096 else 'batch_normalization_%d/gamma:0' % i,
+                         torch.randn(shp, device=dev) * 0.05)
+            v.grad = torch.randn(shp, device=dev) * 1e-3
+            vs.append(v)
+        targets = [torch.randn(shp, device=dev) * 0.05 for shp in sizes]
+        onlines = [v.value for v in vs]
+        nel = sum(s[0] for s in sizes)
+        tables = ops.EmaTables()
+        t_ema = timeit(lambda: tables.run(targets, onlines, 0.004), args.iters)
+        opt = LARSOptimizer(0.1, weight_decay=1e-6, exclude_from_weight_decay=['batch_normalization', 'bias', 'head_supervised'])
+        gv = [(v.grad, v) for v in vs]
+        t_lars = timeit(lambda: opt.apply_gradients(gv), args.iters)
+        row = dict(layer='byol ema', tensors=len(vs), elems=nel, ema_us=t_ema, ema_gbs=12.0 * nel / t_ema / 1e3, lars_us=t_lars,
+                   lars_gbs_of_20_bytes=20.0 * nel / t_lars / 1e3, ema_over_lars=t_ema / t_lars)
+        print('byol ema %d tensors %.1f M elems: %.0f us (%.0f GB/s of 12 B/elem) | lars %.0f us (%.0f GB/s of 20 B/elem) | ema / lars %.2f'
+              % (len(vs), nel / 1e6, t_ema, row['ema_gbs'], t_lars, row['lars_gbs_of_20_bytes'], row['ema_over_lars']), flush=True)
+        res.append(row)
+        del vs, targets, onlines, gv, opt
+        for (rows, D) in [(1024, 256), (1024, 4096), (8192, 256)]:
+            q = torch.randn(rows, D, device=dev)
+            t = torch.randn(rows, D, device=dev)
+            _, rs = ops.byol_fwd(q, t)
+            t_f = timeit(lambda: ops.byol_fwd(q, t), args.iters)
+            t_b = timeit(lambda: ops.byol_bwd(q, t, rs, 1.0), args.iters)
+            row = dict(layer='byol loss rows%d D%d' % (rows, D), fwd_us=t_f, fwd_gbs=8.0 * rows * D / t_f / 1e3, bwd_us=t_b,
+                       bwd_gbs=12.0 * rows * D / t_b / 1e3)
+            print('byol loss 2b=%d D=%d: fwd %.1f us (%.0f GB/s of 8 B/elem, two launches) bwd %.1f us (%.0f GB/s of 12 B/elem)'
+                  % (rows, D, t_f, row['fwd_gbs'], t_b, row['bwd_gbs']), flush=True)
+            res.append(row)
+            del q, t, rs
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
