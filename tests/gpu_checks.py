@@ -3097,3 +3097,164 @@ def check_stem_pool_lattice(V, H, W, C, dtype, ksz=3, stride=2, seed=0):
     res += [_bitwise('unfused bn_bwd_reduce sums ' + tag, pu.double().sum(0), want_sums), _bitwise('unfused bn_bwd_apply ' + tag, dxu, want_dx),
             _bitwise('fused dx == unfused dx ' + tag, dxf, dxu)]
     return res
+
+
+# ------------------------------------------------------------------ augmentation and blur kernels stage by stage
+# (tests/test_gpu_augment.py).  Cases, float64 references, the comparator and the tolerances (4 x the float32 emulation's own error, measured
+# on the CPU) come from tests/augment_reference.py; stages are isolated through the parameter table alone.
+def _aug_canvas(case, tag=''):
+    """ops.augment_views on a case, the output in a guarded, NaN-filled buffer.  Returns (output as numpy, guard result)."""
+    p = case['params']
+    out, chk = _guarded((p.shape[0], case['H'], case['W'], 3 * p.shape[1]), torch.float32)
+    out.fill_(float('nan'))
+    ops.augment_views(torch.from_numpy(case['src']).to(DEV), torch.from_numpy(p).to(DEV), case['H'], case['W'], out=out)
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), _guards(case['name'] + tag, chk)
+
+
+def _identity_results(case, got, guard, tag=''):
+    from tests import augment_reference as ar
+    return [_bitwise(case['name'] + tag + ' bitwise the source (mirrored where flip=1) at channel 3v', got, ar.identity_expected(case)), guard]
+
+
+def check_augment_identity(H, W, views):
+    """Identity crop with and without flip, float32 and uint8 sources: bitwise the source."""
+    from tests import augment_reference as ar
+    res = []
+    for kind in ('u8', 'f32'):
+        case = ar.identity_case(H, W, views, kind)
+        res += _identity_results(case, *_aug_canvas(case))
+        if kind == 'u8':
+            res += _identity_results(case, *_aug_ragged(case), tag=' ragged')
+    return res
+
+
+def check_augment_colour(H, W):
+    """The colour stage alone (identity crop on the palette): all 24 orders at every factor set, both source types."""
+    from tests import augment_reference as ar
+    tol = ar.stage_tolerance('colour')
+    res = []
+    for case in ar.colour_cases(H, W):
+        got, guard = _aug_canvas(case)
+        res += ar.compare(got, case, tol) + [guard]
+    return res
+
+
+def check_augment_exact_colour():
+    """Brightness and contrast in {0.5, 1.5} on k/64 pixels with a dyadic mean: tolerance zero against the float64 oracle."""
+    from tests import augment_reference as ar
+    res = []
+    for case in ar.exact_colour_cases():
+        assert np.array_equal(ar.emulate(case, np.float32).astype(np.float64), ar.oracle(case))
+        got, guard = _aug_canvas(case)
+        res += [_bitwise(case['name'] + ' bitwise the float64 oracle', got, ar.oracle(case)), guard]
+    return res
+
+
+def check_augment_resize(H, W, kind):
+    """The resize stage alone (jitter and grayscale off) and the eval centre crop through preprocess_for_eval_batch."""
+    from simclr_amd import data_util as du
+    from tests import augment_reference as ar
+    tol = ar.stage_tolerance('resize')
+    case = ar.resize_case(H, W, kind)
+    got, guard = _aug_canvas(case)
+    res = ar.compare(got, case, tol) + [guard]
+    ev = ar.eval_case(H, W, kind)
+    got = du.preprocess_for_eval_batch(torch.from_numpy(ev['src']).to(DEV), H, W, sizes=ev['sizes'])
+    torch.cuda.synchronize()
+    res += ar.compare(got.cpu().numpy(), ev, tol)
+    if (H, W) == (24, 40):
+        for axis in ('rows', 'cols'):
+            amb = ar.ambiguous_case(axis, kind)
+            got, guard = _aug_canvas(amb)
+            res += ar.compare(got, amb, tol) + [guard]
+            plain = np.abs(got - ar.oracle(amb)).max() <= tol
+            print('  %s: the kernel takes the %s index at the ambiguous coordinate' % (amb['name'], 'uncontracted' if plain else 'contracted'))
+    return res
+
+
+_FILLER = 1 << 16
+
+
+def _aug_ragged(case, params=None, table_dev=None, tag=''):
+    """ops.augment_views_ragged on a uint8 case.  The packed bytes are a slice in the middle of a larger device buffer with 64 KiB of 255
+    on either side: a read that leaves the records returns filler, never leaves the allocation."""
+    from tests import augment_reference as ar
+    packed, table = ar.pack(case)
+    big = torch.full((packed.size + 2 * _FILLER,), 255, dtype=torch.uint8, device=DEV)
+    big[_FILLER:_FILLER + packed.size] = torch.from_numpy(packed).to(DEV)
+    p = case['params'] if params is None else params
+    out, chk = _guarded((p.shape[0], case['H'], case['W'], 3 * p.shape[1]), torch.float32)
+    out.fill_(float('nan'))
+    ops.augment_views_ragged(big[_FILLER:_FILLER + packed.size], table, torch.from_numpy(p).to(DEV), case['H'], case['W'], out=out,
+                             table_dev=None if table_dev is None else torch.from_numpy(table_dev(table)).to(DEV))
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), _guards(case['name'] + ' ragged' + tag, chk)
+
+
+def check_augment_ragged(H, W):
+    """The resize cases from packed records: the comparator, and bitwise the canvas path (also through two_view_batch_ragged)."""
+    from simclr_amd import data_util as du
+    from tests import augment_reference as ar
+    tol = ar.stage_tolerance('resize')
+    res = []
+    for case in (ar.resize_case(H, W, 'u8'), ar.eval_case(H, W, 'u8')):
+        got, guard = _aug_ragged(case)
+        canvas, _ = _aug_canvas(case)
+        res += ar.compare(got, case, tol, ' ragged') + [guard, _bitwise(case['name'] + ' ragged == canvas', got, canvas)]
+    case = ar.resize_case(H, W, 'u8')
+    packed, table = ar.pack(case)
+    a = du.two_view_batch_ragged(torch.from_numpy(packed).to(DEV), table, H, W, params=case['params'])
+    b = du.two_view_batch(torch.from_numpy(case['src']).to(DEV), H, W, sizes=case['sizes'], params=case['params'])
+    torch.cuda.synchronize()
+    res.append(_entry(case['name'] + ' torch.equal(two_view_batch_ragged, two_view_batch)', 0.0 if torch.equal(a, b) else 1.0, 0.0))
+    res += ar.compare(a.cpu().numpy(), case, tol, ' two_view_batch_ragged')
+    # the colour stage behind the ragged front end: all 24 orders once
+    col = ar.colour_case(16, 17, 'mixed', 'u8')
+    got, guard = _aug_ragged(col)
+    res += ar.compare(got, col, ar.stage_tolerance('colour'), ' ragged') + [guard]
+    return res
+
+
+def check_augment_ragged_clamps(H, W):
+    """What aug_crop_resize_flip_ragged promises beyond the host check: an overhanging crop box is clamped into its image, a record that
+    does not fit the buffer yields zeros and leaves the other images alone."""
+    from tests import augment_reference as ar
+    tol = ar.stage_tolerance('resize')
+    case = ar.clamp_case(H, W)
+    got, guard = _aug_ragged(case)
+    res = ar.compare(got, case, tol, ' (oracle on the clamped box)') + [guard]
+    # the same records with their clamped boxes: the kernel computes the very same thing
+    same, _ = _aug_ragged(case, params=case['ref_params'])
+    res.append(_bitwise(case['name'] + ' overhanging box == clamped box', got, same))
+    b = case['params'].shape[0]
+    for bad, what in ((b - 1, 'offset + 3 bytes'), (1, 'one more row'), (0, 'negative offset')):
+        def table_dev(t, bad=bad, what=what):
+            t = t.copy()
+            if what == 'offset + 3 bytes':
+                t[bad, 0] += 3                                              # the last record now ends 3 bytes past packed_bytes
+            elif what == 'one more row':
+                t[bad, 1] += int(t[:, 1].max()) * 40                        # 3 * h * w beyond what is left behind the offset
+            else:
+                t[bad, 0] = -3
+            return t
+        out, g2 = _aug_ragged(case, table_dev=table_dev, tag=' ' + what)
+        keep = [i for i in range(b) if i != bad]
+        res += [_bitwise('%s record %d (%s) does not fit: zeros' % (case['name'], bad, what), out[bad], np.zeros_like(out[bad])),
+                _bitwise('%s record %d (%s) does not fit: the other images unchanged' % (case['name'], bad, what), out[keep], got[keep]), g2]
+    return res
+
+
+def check_blur_cases(H, W, height):
+    """blur1d through data_util.batch_random_blur_tensor: non-square maps, a filter wider than the short side, 1 / 2 / 3 views, selectors
+    none / all / mixed, sigma 0.1 and 2.0, inputs in [-0.1, 1.1]; every element against oracle/blur.py."""
+    from simclr_amd import data_util as du
+    from tests import augment_reference as ar
+    tol = ar.blur_tolerance()
+    res = []
+    for case in ar.blur_cases(H, W, height):
+        y = du.batch_random_blur_tensor(torch.from_numpy(case['x']).to(DEV), case['height'], W, sigmas=list(case['sigmas']),
+                                        selectors=torch.from_numpy(case['sel']))
+        torch.cuda.synchronize()
+        res += ar.blur_compare(y.cpu().numpy(), case, tol)
+    return res

@@ -114,6 +114,19 @@ def main():
             run(gc.check_avgpool2, 2, H, 192, s, dt, W=W)
     for nslot, C in [(1, 8), (33, 40), (129, 64), (160, 40), (768, 2048)]:
         run(gc.check_bn_slot_kernels, nslot, C)
+    # augmentation and blur kernels stage by stage (tests/test_gpu_augment.py)
+    for views in (1, 2, 3):
+        run(gc.check_augment_identity, 15, 17, views)
+    for (H, W) in [(15, 17), (16, 16), (16, 17), (24, 40)]:
+        run(gc.check_augment_colour, H, W)
+    run(gc.check_augment_exact_colour)
+    for (H, W) in [(16, 32), (32, 16), (24, 40), (40, 24)]:
+        for kind in ('u8', 'f32'):
+            run(gc.check_augment_resize, H, W, kind)
+    run(gc.check_augment_ragged, 40, 24)
+    run(gc.check_augment_ragged_clamps, 24, 40)
+    for (H, W, hh) in [(40, 3, 40), (3, 40, 3), (3, 40, 40), (45, 20, 45), (7, 9, 7)]:
+        run(gc.check_blur_cases, H, W, hh)
     nfail = sum(1 for r in results if not r['ok'])
     print('TOTAL %d checks, %d failed' % (len(results), nfail), flush=True)
     os.makedirs('gpurun_out', exist_ok=True)
