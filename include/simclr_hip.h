@@ -585,6 +585,31 @@ int simclr_byol_fwd(const float* q, const float* t, int b, int D, float* out, do
 int simclr_byol_bwd(const float* q, const float* t, int b, int D, const double* row_stats, float grad_scale, float* dq,
                     simclr_stream_t stream);
 
+/* ---- MoCo v2 on a queue of momentum keys (csrc/moco.hip): He et al. 2020, Momentum Contrast; Chen et al. 2020, Improved Baselines ----
+ * q [two_n, D] = the l2-normalised online projections, [view-a rows; view-b rows]; t [two_n, D] = the l2-normalised momentum keys of
+ * the same rows; queue [K, D] = keys of earlier steps; all fp32, 16-byte aligned, D in {64, 128, 256}.  The pairing is formed inside:
+ * row r's positive key is t_p, p = (r + two_n / 2) mod two_n (BYOL's pairing; pass t as the target network returned it).  The
+ * negatives of a row are the K queue rows and nothing else.  With n = two_n / 2:
+ *   s_r+ = q_r . t_p / T,  s_rj = q_r . queue_j / T,  l_r = logsumexp([s_r+, s_r0 .. s_r,K-1]) - s_r+
+ *   out[0] = (1 / n) sum_r l_r (the sum of the two per-view means, the convention of NT-Xent here),
+ *   out[1] = share of the rows with q_r . t_p >= max_j q_r . queue_j (equality is a hit).
+ * Exact-fp32 MFMA sweep over 64-row queue tiles, online log-sum-exp on the rounded logit, key splits merged in a fixed order, the
+ * [two_n, K] matrix never written, no atomics: two calls are bitwise equal.  The negatives' sum stays apart from the positive term
+ * until the row finalize, which forms l_r in double (log1p of the negatives' sum when the positive is the maximum): logsumexp - s+ is
+ * never formed in fp32.  row_stats: device float [two_n, 2] = {logsumexp over the K + 1 logits in the base-2 domain, 1 - P_r+ formed as
+ * the negatives' share of the softmax sum}, kept for simclr_moco_bwd.  workspace: simclr_moco_workspace_bytes(two_n, K, D) bytes, shared
+ * by both calls (0 for a refused shape).  simclr_moco_key_splits: the number of key splits of the forward sweep (0 for a refused shape).
+ * Refused (1 returned, nothing launched): null / misaligned pointers, another D, two_n < 2 or odd, K < 1, temperature <= 0 or NaN. */
+size_t simclr_moco_workspace_bytes(int two_n, int K, int D);
+int simclr_moco_key_splits(int two_n, int K);
+int simclr_moco_fwd(const float* q, const float* t, const float* queue, int two_n, int K, int D, float temperature, float* out,
+                    float* row_stats, void* workspace, simclr_stream_t stream);
+/* dq [two_n, D] fp32 = grad_scale * d out[0] / dq = (grad_scale / (n T)) (sum_j P_rj queue_j - (1 - P_r+) t_p), P the softmax over the
+ * K + 1 logits, from the row_stats of simclr_moco_fwd on the same arguments.  One query-side sweep that recomputes S; t and the queue
+ * get no gradient.  Refusals as simclr_moco_fwd. */
+int simclr_moco_bwd(const float* q, const float* t, const float* queue, int two_n, int K, int D, float temperature,
+                    const float* row_stats, float grad_scale, float* dq, void* workspace, simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

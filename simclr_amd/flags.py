@@ -104,7 +104,9 @@ _DEFS = [
                                         "projection width 64, 128 or 256) or 'barlow' (add_barlow_twins_loss: Barlow Twins, no negatives; loss width "
                                         '= proj_out_dim, or the encoder width with proj_head_mode=none, a multiple of 64 in [64, 8192]; --hidden_norm and '
                                         "--temperature are ignored with it) or 'byol' (add_byol_loss: BYOL on a momentum target network with a predictor "
-                                        'on the online side; loss width as for barlow; always l2-normalised, --hidden_norm and --temperature are ignored).  '
+                                        'on the online side; loss width as for barlow; always l2-normalised, --hidden_norm and --temperature are ignored) '
+                                        "or 'mocov2' (add_moco_loss: MoCo v2, InfoNCE against a queue of momentum keys; loss width 64, 128 or 256; always "
+                                        'l2-normalised, --hidden_norm is ignored, --temperature is honoured: 0.2 is the usual choice).  '
                                         'Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
@@ -118,6 +120,10 @@ _DEFS = [
     ('byol_tau_base', 0.996, float, 'MI355X build: base decay of the target network\'s moving average; step k of K uses '
                                     'tau_k = 1 - (1 - byol_tau_base) * (cos(pi k / K) + 1) / 2.  In [0, 1].'),
     ('byol_pred_hidden_dim', 4096, int, 'MI355X build: hidden width of the BYOL predictor (dense + BN + ReLU, dense): a multiple of 64 in [64, 8192].'),
+    # MoCo v2 (He et al. 2020; Chen et al. 2020) in place of NT-Xent for pretraining: a momentum target network and a queue of its keys
+    ('moco_queue_size', 65536, int, 'MI355X build: rows K of the MoCo key queue: a multiple of 2 x train_batch_size, at least that and at most 1048576.'),
+    ('moco_momentum', 0.999, float, 'MI355X build: constant decay m of the MoCo target network\'s moving average, t <- t + (1 - m) (o - t).  In [0, 1].'),
+    ('moco_queue_seed', 0, int, 'MI355X build: seed of the random unit rows the MoCo queue starts from (the same on every replica).'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),

@@ -236,6 +236,12 @@ def byol_on():
     return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'byol' and FLAGS.train_mode == 'pretrain'
 
 
+def moco_on():
+    """--contrastive_loss=mocov2 in a pretraining run: the step needs a TargetNetwork with a MocoQueue; the online model is the ntxent
+    model (no predictor)."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'mocov2' and FLAGS.train_mode == 'pretrain'
+
+
 def projection_width():
     """Width of the block the pretraining loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none.  The one
     statement of that rule: the start-up checks of run.check_contrastive_loss_flags and the predictor's output layer both call it."""
@@ -542,14 +548,73 @@ def target_flag_values():
                 dropblock_keep_probs='')
 
 
+def moco_queue_ptr(step, rows_per_step, K):
+    """Row of the queue the keys of optimizer step `step` (optimizer.iterations before its increment) are written at.  No pointer is
+    stored: a resumed run continues by construction.  K is a multiple of rows_per_step, so a step's rows never wrap."""
+    return (int(step) * int(rows_per_step)) % int(K)
+
+
+def moco_queue_init(K, D, seed):
+    """The initial queue of MoCo: K random unit rows -- numpy.random.default_rng([seed]).standard_normal((K, D)), l2-normalised in
+    float64 and cast to float32 once.  A function of (K, D, seed) alone: identical on every replica."""
+    import numpy as np
+    x = np.random.default_rng([int(seed)]).standard_normal((int(K), int(D)))
+    return (x / np.sqrt(np.maximum((x * x).sum(axis=1, keepdims=True), 1e-12))).astype(np.float32)
+
+
+class MocoQueue:
+    """The ring buffer of momentum keys of MoCo (He et al. 2020): a device fp32 [K, D] tensor of l2-normalised rows, exposed as ONE
+    non-trainable Variable `moco/queue` (checkpointed with the target network; no optimizer slot, no weight decay, no gradient).
+    enqueue(keys_all, step) overwrites the rows [ptr, ptr + 2N), ptr = moco_queue_ptr(step, 2N, K), with the gathered keys of the
+    step in the NT-Xent gather layout (every replica's view-a rows, then every replica's view-b rows): one device-to-device slice copy
+    on the step's stream."""
+
+    NAME = 'moco/queue'
+
+    def __init__(self, K, D, seed=0, device=None):
+        K, D = int(K), int(D)
+        if K < 1 or D < 1:
+            raise ValueError('MocoQueue: need K >= 1 rows of width D >= 1 (got K = %d, D = %d)' % (K, D))
+        self.K, self.D, self.seed = K, D, int(seed)
+        self.variable = Variable(self.NAME, torch.empty(K, D, device=device or RT.device, dtype=torch.float32), False)
+        self.reset()
+
+    def reset(self):
+        """Back to the seeded random unit rows."""
+        self.variable.value.copy_(torch.from_numpy(moco_queue_init(self.K, self.D, self.seed)))
+
+    @property
+    def value(self):
+        return self.variable.value
+
+    @property
+    def variables(self):
+        return [self.variable]
+
+    def ptr(self, step, rows):
+        return moco_queue_ptr(step, rows, self.K)
+
+    def enqueue(self, keys_all, step):
+        rows = keys_all.shape[0]
+        if keys_all.dim() != 2 or keys_all.shape[1] != self.D or keys_all.dtype != torch.float32:
+            raise ValueError('MocoQueue.enqueue: need float32 keys [2N, %d] (got %s %s)' % (self.D, tuple(keys_all.shape), keys_all.dtype))
+        if rows < 1 or self.K % rows:
+            raise ValueError('MocoQueue.enqueue: the queue size %d is not a multiple of the %d rows of a step' % (self.K, rows))
+        ptr = self.ptr(step, rows)
+        self.variable.value[ptr:ptr + rows].copy_(keys_all)
+        return ptr
+
+
 class _WithTarget:
-    """What a BYOL checkpoint holds: every variable of the online model under its own name (the optimizer's slots hang on these very
-    objects) and every target variable under the prefix `target/`."""
+    """What a BYOL / MoCo checkpoint holds: every variable of the online model under its own name (the optimizer's slots hang on these
+    very objects), every target variable under the prefix `target/` and, with a queue attached, `moco/queue`."""
 
     def __init__(self, model, target):
         self.model, self.target = model, target
         self.supervised_head = model.supervised_head
         self._target_variables = [Variable(TargetNetwork.PREFIX + v.name, v.value, False) for v in target.model.variables]
+        if target.queue is not None:
+            self._target_variables += target.queue.variables
 
     @property
     def variables(self):
@@ -570,13 +635,23 @@ class TargetNetwork:
 
     update(step) moves every trainable variable of the online encoder and projection head into its target namesake,
     t + (1 - tau_step) * (o - t), in one launch, and marks the target's compute copies stale: RT.optimizer_stepped() leaves frozen
-    layers' copies alone, and these masters change every step."""
+    layers' copies alone, and these masters change every step.
+
+    --contrastive_loss=mocov2 (MoCo v2) uses the same network: the online model then has no predictor, the decay is the constant
+    --moco_momentum instead of BYOL's cosine schedule, and `queue` (a MocoQueue) is checkpointed with it."""
 
     PREFIX = 'target/'
 
-    def __init__(self, online_model, total_steps, image_size=None):
-        if online_model.prediction_head is None:
+    def __init__(self, online_model, total_steps, image_size=None, queue=None):
+        self.moco = moco_on()
+        if online_model.prediction_head is None and not self.moco:
             raise ValueError('TargetNetwork: the online model has no predictor (it was built without --contrastive_loss=byol)')
+        self.queue = queue                    # model.MocoQueue (mocov2) or None: listed by checkpointable()
+        # mocov2: the constant --moco_momentum m; 1 - m is formed in double and cast to float32 once
+        self._moco_omt = None
+        if self.moco:
+            import numpy as np
+            self._moco_omt = float(np.float32(1.0 - float(FLAGS.moco_momentum)))
         self.online = online_model
         self.total_steps = max(int(total_steps), 1)
         self.flag_values = target_flag_values()
@@ -587,7 +662,7 @@ class TargetNetwork:
             zeros = torch.zeros(2, size, size, 3, device=RT.device)
             online_model(zeros, training=False)
             online_model.release()
-        if online_model.prediction_head.linear_layers[0].kernel is None:
+        if online_model.prediction_head is not None and online_model.prediction_head.linear_layers[0].kernel is None:
             # after the encoder, the projection head and the supervised head: their initial values are those of an ntxent run
             online_model.prediction_head(torch.zeros(2, projection_width(), device=RT.device), training=False)
             online_model.prediction_head.release()
@@ -626,7 +701,8 @@ class TargetNetwork:
         return self.model.variables
 
     def checkpointable(self):
-        """The object run.main hands the checkpoint: online variables + `target/`-prefixed target variables."""
+        """The object run.main hands the checkpoint: online variables + `target/`-prefixed target variables (+ `moco/queue` when a
+        queue is attached)."""
         return _WithTarget(self.online, self)
 
     def tau(self, step):
@@ -634,9 +710,10 @@ class TargetNetwork:
 
     def update(self, step):
         """After optimizer.apply_gradients of step `step` (optimizer.iterations before its increment).  tau is formed on the host in
-        double; 1 - tau is cast to float32 once."""
+        double; 1 - tau is cast to float32 once.  The decay is chosen by the loss: BYOL's cosine schedule, or the constant
+        --moco_momentum of mocov2."""
         import numpy as np
-        omt = float(np.float32(1.0 - self.tau(step)))
+        omt = self._moco_omt if self.moco else float(np.float32(1.0 - self.tau(step)))
         self._tables.run([t.value for t, _ in self._ema_pairs], [o.value for _, o in self._ema_pairs], omt)
         self._invalidate()
         return omt

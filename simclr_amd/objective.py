@@ -19,6 +19,9 @@ batch-standardised hiddens; no negatives) in its Gram form on the kernels of csr
 
 `add_byol_loss` is the BYOL loss of Grill et al. 2020 (squared distance of the l2-normalised online prediction of one view to the
 l2-normalised projection a momentum target network gives the other view; no negatives, no collective) on the kernels of csrc/byol.hip.
+
+`add_moco_loss` is the MoCo v2 loss of He et al. 2020 / Chen et al. 2020 (InfoNCE of each online row against the momentum key of its
+other view and a queue of keys of earlier steps; no collective) on the kernels of csrc/moco.hip.
 """
 import torch
 
@@ -488,6 +491,47 @@ def add_byol_loss(online, target, strategy=None, overlap=None):
 
     loss = _Loss(out[0:1], backward)
     loss.cosine = out[1:2]
+    return loss
+
+
+def add_moco_loss(online, target, queue, temperature=1.0, strategy=None, overlap=None, keys=None):
+    """MoCo v2 loss (He et al. 2020; Chen et al. 2020) on the kernels of csrc/moco.hip: InfoNCE of every online row against its one
+    positive momentum key and a queue of keys of earlier steps,
+      s_r+ = l2n(online_r) . l2n(target_{(r + b) mod 2b}) / T,   s_rj = l2n(online_r) . queue_j / T,
+      loss = (1 / b) sum_{r < 2b} [logsumexp([s_r+, s_r0 .. s_r,K-1]) - s_r+],
+    the sum of the two per-view means, as add_contrastive_loss forms NT-Xent.  The negatives are the queue rows alone: the other rows
+    of the batch are not.  l2n is tf.math.l2_normalize (epsilon 1e-12); always applied.  The [2b, K] logits are never written.
+
+    Args:
+      online: float32 device tensor [2b, D] = the online projection output, [view-a rows; view-b rows]; D in {64, 128, 256}.
+      target: float32 device tensor [2b, D] = the target network's projection output of the same batch.  It gets no gradient.
+      queue: float32 device tensor [K, D], the (normalised) keys of earlier steps.  It gets no gradient and is READ AGAIN by the
+        backward, which recomputes the logits: the caller enqueues this step's keys only after `backward`.
+      temperature: T.
+      strategy: replica context or None.  The loss needs NO collective: a replica's value is the mean over its own rows, the mean over
+        the replicas is the loss, and `backward` is called with 1 / R.
+      overlap: optional zero-argument callable, run after the forward launches.
+      keys: l2n(target), when the caller formed it already (the step does, to start the gather of the keys before the online forward).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * dloss/donline, [2b, D]), the device scalars
+      .value and .acc (share of rows whose positive scores at least as high as their best negative), and .keys = l2n(target), the
+      [2b, D] rows the step enqueues.
+    """
+    online, target = online.contiguous(), target.contiguous()
+    ops._moco_check(online, target, queue, temperature)
+    z, inv = ops.l2norm_fwd(online)
+    if keys is None:
+        keys, _ = ops.l2norm_fwd(target)
+    out, row_stats, ws = ops.moco_fwd(z, keys, queue, temperature)
+    if overlap is not None:
+        overlap()
+
+    def backward(grad_scale=1.0):
+        return ops.l2norm_bwd(z, inv, ops.moco_bwd(z, keys, queue, temperature, row_stats, grad_scale, ws))
+
+    loss = _Loss(out[0:1], backward)
+    loss.acc = out[1:2]
+    loss.keys = keys
     return loss
 
 

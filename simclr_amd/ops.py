@@ -570,6 +570,81 @@ class EmaTables:
                 lambda: lib().ema_multi_tensor(_p(self.table), T, _p(self.chunks), nchunks, float(one_minus_tau), _s()))
 
 
+# ---------------------------------------------------------------- MoCo v2 (csrc/moco.hip)
+MOCO_DIMS = (64, 128, 256)          # loss widths the MoCo kernels are instantiated for
+MOCO_MAX_QUEUE = 1048576            # largest --moco_queue_size
+
+
+def _moco_check_dim(D):
+    if D not in MOCO_DIMS:
+        raise ValueError('the MoCo loss supports widths %s (got %d)' % ('/'.join(map(str, MOCO_DIMS)), D))
+
+
+def _moco_check(q, t, queue, temperature):
+    if q.dtype != torch.float32 or t.dtype != torch.float32 or q.dim() != 2 or tuple(q.shape) != tuple(t.shape):
+        raise ValueError('moco: need float32 q and t of one shape [2b, D] (got %s %s, %s %s)'
+                         % (tuple(q.shape), q.dtype, tuple(t.shape), t.dtype))
+    rows, D = q.shape
+    if rows < 2 or rows % 2:
+        raise ValueError('moco: q and t hold both views, [2b, D] with b >= 1 (got %d rows)' % rows)
+    _moco_check_dim(D)
+    if queue.dtype != torch.float32 or queue.dim() != 2 or queue.shape[0] < 1 or queue.shape[1] != D:
+        raise ValueError('moco: the queue is a float32 [K, %d] block with K >= 1 (got %s %s)' % (D, tuple(queue.shape), queue.dtype))
+    if not float(temperature) > 0.0:            # (NaN fails the comparison)
+        raise ValueError('moco: temperature must be > 0 (got %r)' % (temperature,))
+    return rows, queue.shape[0], D
+
+
+def moco_key_splits(two_n, K):
+    """Number of key splits the forward sweep of moco_fwd uses for two_n query rows against a queue of K rows."""
+    splits = lib().moco_key_splits(int(two_n), int(K))
+    if splits < 1:
+        raise ValueError('moco: need an even two_n >= 2 and K >= 1 (got two_n = %d, K = %d)' % (two_n, K))
+    return splits
+
+
+def moco_workspace(two_n, K, D, device):
+    _moco_check_dim(D)
+    nbytes = lib().moco_workspace_bytes(two_n, K, D)
+    if nbytes == 0:
+        raise ValueError('moco: need an even two_n >= 2 and K >= 1 (got two_n = %d, K = %d)' % (two_n, K))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def _moco_check_ws(ws, two_n, K, D):
+    if ws is None or ws.numel() * ws.element_size() < lib().moco_workspace_bytes(two_n, K, D):
+        raise ValueError('moco: the workspace is smaller than moco_workspace(%d, %d, %d)' % (two_n, K, D))
+
+
+def moco_fwd(q, t, queue, temperature, ws=None):
+    """q [2b, D] (normalised online projections), t [2b, D] (normalised momentum keys of the same rows, as the target network returned
+    them: row r of q pairs with row (r + b) mod 2b of t inside the kernel), queue [K, D] -> (out = [loss, contrast_acc] device fp32,
+    row_stats [2b, 2] for moco_bwd, the workspace both calls share)."""
+    two_n, K, D = _moco_check(q, t, queue, temperature)
+    if ws is None:
+        ws = moco_workspace(two_n, K, D, q.device)
+    _moco_check_ws(ws, two_n, K, D)
+    out = step_scalars(2, q.device)
+    row_stats = torch.empty(two_n, 2, device=q.device, dtype=torch.float32)
+    _launch('moco_fwd', 2.0 * two_n * K * D, 4.0 * (2 * two_n + K) * D,
+            lambda: lib().moco_fwd(_p(q), _p(t), _p(queue), two_n, K, D, float(temperature), _p(out), _p(row_stats), _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def moco_bwd(q, t, queue, temperature, row_stats, grad_scale, ws):
+    """dq [2b, D] = grad_scale * dloss / dq from moco_fwd's row_stats and workspace on the same arguments; t and the queue get no
+    gradient."""
+    two_n, K, D = _moco_check(q, t, queue, temperature)
+    if row_stats.dtype != torch.float32 or tuple(row_stats.shape) != (two_n, 2):
+        raise ValueError('moco_bwd: row_stats is the float32 [2b, 2] block moco_fwd returned (got %s %s)' % (tuple(row_stats.shape), row_stats.dtype))
+    _moco_check_ws(ws, two_n, K, D)
+    dq = torch.empty_like(q)
+    _launch('moco_bwd', 4.0 * two_n * K * D, 4.0 * (3 * two_n + K) * D,
+            lambda: lib().moco_bwd(_p(q), _p(t), _p(queue), two_n, K, D, float(temperature), _p(row_stats), float(grad_scale), _p(dq),
+                                   _p(ws), _s()))
+    return dq
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

@@ -48,13 +48,31 @@ def barlow_loss_width():
 # --contrastive_loss=byol replaces NT-Xent in the pretraining step by BYOL on a momentum target network; train_mode=finetune ignores it.
 # One definition: the model reads the same switch to decide whether it carries a predictor.
 byol_loss_on = model_lib.byol_on
+# --contrastive_loss=mocov2 replaces NT-Xent in the pretraining step by MoCo v2: InfoNCE against a queue of the target network's keys.
+moco_loss_on = model_lib.moco_on
 
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() tell the others)."""
-    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow', 'byol'):
-        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' (got %r)" % FLAGS.contrastive_loss)
+    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() tell the others)."""
+    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
+        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r)"
+                         % FLAGS.contrastive_loss)
+    if moco_loss_on() and FLAGS.mode != 'eval':
+        rows = 2 * FLAGS.train_batch_size               # the global 2N rows a step enqueues
+        K = FLAGS.moco_queue_size
+        if rows < 2 or K < rows or K % rows != 0 or K > ops.MOCO_MAX_QUEUE:
+            raise ValueError('--moco_queue_size must be a multiple of 2 x train_batch_size = %d, at least that and at most %d (got %r): '
+                             'the ring never wraps inside a step' % (rows, ops.MOCO_MAX_QUEUE, K))
+        if not 0.0 <= FLAGS.moco_momentum <= 1.0:          # (NaN fails both comparisons)
+            raise ValueError('--moco_momentum must lie in [0, 1] (got %r)' % (FLAGS.moco_momentum,))
+        if not FLAGS.temperature > 0:
+            raise ValueError('--contrastive_loss=mocov2 needs --temperature > 0 (got %r)' % (FLAGS.temperature,))
+        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.MOCO_DIMS:
+            raise ValueError('--contrastive_loss=mocov2 needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
+                             'the MoCo kernels are instantiated for those widths only'
+                             % ('/'.join(map(str, ops.MOCO_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if byol_loss_on() and FLAGS.mode != 'eval':
         if not 0.0 <= FLAGS.byol_tau_base <= 1.0:           # (NaN fails both comparisons)
             raise ValueError('--byol_tau_base must lie in [0, 1] (got %r)' % (FLAGS.byol_tau_base,))
@@ -110,6 +128,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/bt_on_diag', 'train/bt_off_diag']     # no logits to score: the two raw sums instead
     elif FLAGS.train_mode == 'pretrain' and byol_loss_on():
         names += ['train/contrast_loss', 'train/byol_cosine']         # no logits to score: the mean cosine of the paired rows instead
+    elif FLAGS.train_mode == 'pretrain' and moco_loss_on():
+        names += ['train/contrast_loss', 'train/contrast_acc']        # positive against the best queue row; no entropy
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -224,6 +244,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     target: model.TargetNetwork (or a stand-in with its __call__ / update), required by --contrastive_loss=byol.  The step is then:
     blur once, target forward (training mode, nothing kept), online forward on the same pixels, predictor, add_byol_loss, the usual
     backward entering through the predictor, optimizer, target.update(step).
+    --contrastive_loss=mocov2 needs a target with a model.MocoQueue attached (target.queue).  The step is: blur once, target forward
+    and release, normalise the keys and start their asynchronous all-gather (nothing in the loss waits for it), online forward,
+    add_moco_loss against the queue, backward, optimizer, target.update(step), then wait for the gather and queue.enqueue.
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -241,9 +264,13 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     supcon = supcon_loss_on() and not generalized
     barlow = barlow_loss_on() and not generalized
     byol = byol_loss_on() and not generalized
+    moco = moco_loss_on() and not generalized
     if byol and target is None:
         raise ValueError('--contrastive_loss=byol needs a target network: make_single_step(..., target=model.TargetNetwork(model, steps))')
-    if target is not None and not byol:
+    if moco and (target is None or getattr(target, 'queue', None) is None):
+        raise ValueError('--contrastive_loss=mocov2 needs a target network with a key queue: make_single_step(..., '
+                         'target=model.TargetNetwork(model, steps, queue=model.MocoQueue(K, D, seed)))')
+    if target is not None and not (byol or moco):
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
@@ -258,11 +285,16 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
             # training arithmetic again, for the rest of the step
             teacher_logits = teacher(features)
-        if byol:
+        if byol or moco:
             # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
             if FLAGS.use_blur:
                 features = data_util.batch_random_blur_tensor(features, FLAGS.image_size, FLAGS.image_size)
             target_outputs = target(features)          # released before the online forward: the two activation sets never coexist
+            if moco:
+                # the keys of this step, and their gather for the enqueue at the END of the step: in flight during the online forward,
+                # the loss and the whole backward -- the loss reads the local keys and the queue as it stands
+                moco_keys, _ = ops.l2norm_fwd(target_outputs.contiguous())
+                moco_gather = obj_lib.gather_hidden(moco_keys, strategy, async_op=True)
             projection_head_outputs, supervised_head_outputs = model(features, training=True, blur=False)
         else:
             projection_head_outputs, supervised_head_outputs = model(features, training=True)   # :577-578
@@ -300,6 +332,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             elif byol:
                 logits_con = None
                 con_loss = obj_lib.add_byol_loss(model.predict(outputs), target_outputs, strategy=strategy, overlap=supervised_part)
+            elif moco:
+                logits_con = None
+                con_loss = obj_lib.add_moco_loss(outputs, target_outputs, target.queue.value, temperature=FLAGS.temperature,
+                                                 strategy=strategy, overlap=supervised_part, keys=moco_keys)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -338,11 +374,16 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             model.backward(d_proj, None, on_stage=sync.on_stage)
         join_wgrad_stream()
         sync.wait()
-        if byol:
-            step_index = int(getattr(optimizer, 'iterations', 0))      # before the increment: a restored run continues the tau schedule
+        if byol or moco:
+            # before the increment: a restored run continues the tau schedule / the queue's write position
+            step_index = int(getattr(optimizer, 'iterations', 0))
         optimizer.apply_gradients([(v.grad, v) for v in state['apply']])                   # :622
-        if byol:
+        if byol or moco:
             target.update(step_index)
+        if moco:
+            # The enqueue comes AFTER the backward: the backward recomputes the logits from the queue, and a queue that already held
+            # this step's keys would silently differentiate another loss (every query would find its own positive among the negatives).
+            target.queue.enqueue(moco_gather(), step_index)
         RT.optimizer_stepped()
         ops.end_step()
         if strategy is not None:
@@ -378,6 +419,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         elif con_loss is not None and byol:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/byol_cosine'] = con_loss.cosine.reshape(-1)[:1]
+        elif con_loss is not None and moco:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -410,6 +454,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             elif byol:
                 if 'train/byol_cosine' in at:
                     con_loss.cosine = at['train/byol_cosine']
+            elif moco:
+                if 'train/contrast_acc' in at:
+                    con_loss.acc = at['train/contrast_acc']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:
@@ -648,6 +695,10 @@ def main(argv):
     optimizer = model_lib.build_optimizer(learning_rate)
     # BYOL: the target network is built after the online model (whose variables it makes exist first) as a bitwise copy of it
     target = model_lib.TargetNetwork(model, train_steps) if byol_loss_on() else None
+    if moco_loss_on():
+        # MoCo v2: the same target network under a constant momentum, and the queue of its keys (seeded: the same on every replica)
+        target = model_lib.TargetNetwork(model, train_steps,
+                                         queue=model_lib.MocoQueue(FLAGS.moco_queue_size, FLAGS.proj_out_dim, FLAGS.moco_queue_seed))
     step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
@@ -669,6 +720,9 @@ def main(argv):
         if target is not None and status is not None and (
                 not manager.latest_checkpoint or any(n.startswith(target.PREFIX) for n in status.missing_in_checkpoint)):
             target.copy_from_online()        # --checkpoint (or a file without target entries): the copy is made after the restore
+        if target is not None and target.queue is not None and status is not None and (
+                not manager.latest_checkpoint or target.queue.NAME in status.missing_in_checkpoint):
+            target.queue.reset()             # likewise the seeded queue (a weights-only restore may have filled it from the file)
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)

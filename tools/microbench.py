@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -417,6 +417,61 @@ def main():
                   % (rows, D, t_f, row['fwd_gbs'], t_b, row['bwd_gbs']), flush=True)
             res.append(row)
             del q, t, rs
+    if 'moco' in what:
+        # MoCo v2 (csrc/moco.hip): the one-sided sweep of 2n query rows against a queue of K keys, beside the supervised contrastive and the
+        # decoupled sweeps at (n, N, D) = (512, 4096, 128) -- the same 1024 x 8192 logits -- and NT-Xent at (512, 512, 128) (what the step
+        # trades for it), all in the same run.  Matrix FLOPs of moco: forward S = 2 (2n) K D, backward S again + P Q = 4 (2n) K D.
+        n, N, D = 512, 4096, 128
+        zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+        za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+        za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+        labels = torch.randint(0, 100, (N,), device=dev, dtype=torch.int32)
+        gws = ops.gcl_lse_workspace(n, N, D, dev)
+        _, grs, _ = ops.gcl_lse_fwd(zl, za, 0.1, ws=gws)
+        sws = ops.supcon_workspace(n, N, D, dev)
+        _, srs, _ = ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)
+        ff, fb = 8.0 * n * N * D, 24.0 * n * N * D
+        ref = dict(layer='moco reference sweeps n%d N%d D%d' % (n, N, D), fwd_flops=ff, bwd_flops=fb,
+                   supcon_fwd_us=timeit(lambda: ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws), args.iters),
+                   supcon_bwd_us=timeit(lambda: ops.supcon_bwd(zl, za, labels, 0, 0.1, srs, 1.0, sws), args.iters),
+                   gcl_lse_fwd_us=timeit(lambda: ops.gcl_lse_fwd(zl, za, 0.1, ws=gws), args.iters),
+                   gcl_lse_bwd_us=timeit(lambda: ops.gcl_lse_bwd(zl, za, 0.1, grs, 1.0, gws, skip_self=True), args.iters))
+        zs = za[:2 * n].contiguous()
+        zs[:n] = zl[:n]; zs[n:] = zl[n:]
+        nws = ops.ntxent_workspace(n, n, D, dev)
+        nout, nrs, _ = ops.ntxent_fwd(zl, zs, 0, 0.1, nws)
+        ref['ntxent_n512_N512_fwd_us'] = timeit(lambda: ops.ntxent_fwd(zl, zs, 0, 0.1, nws), args.iters)
+        ref['ntxent_n512_N512_bwd_us'] = timeit(lambda: ops.ntxent_bwd(zl, zs, 0, 0.1, nrs, 1.0, nout, nws), args.iters)
+        for k in ('supcon', 'gcl_lse'):
+            ref[k + '_fwd_tfs'] = ff / ref[k + '_fwd_us'] / 1e6
+            ref[k + '_bwd_tfs'] = fb / ref[k + '_bwd_us'] / 1e6
+        print('moco reference sweeps n=%d N=%d D=%d: ' % (n, N, D) + ' | '.join(
+            '%s fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s)' % (k, ref[k + '_fwd_us'], ref[k + '_fwd_tfs'], ref[k + '_bwd_us'], ref[k + '_bwd_tfs'])
+            for k in ('supcon', 'gcl_lse')) + ' | ntxent n=512 N=512 fwd %.0f us bwd %.0f us' % (
+                ref['ntxent_n512_N512_fwd_us'], ref['ntxent_n512_N512_bwd_us']), flush=True)
+        res.append(ref)
+        del za, gws, sws, nws
+        for (two_n, K, D) in [(1024, 8192, 128), (1024, 65536, 128), (1024, 65536, 256)]:
+            q = torch.nn.functional.normalize(torch.randn(two_n, D, device=dev), dim=1)
+            t = torch.nn.functional.normalize(q.roll(two_n // 2, 0) + 0.5 * torch.randn(two_n, D, device=dev), dim=1)
+            queue = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            mws = ops.moco_workspace(two_n, K, D, dev)
+            _, mrs, _ = ops.moco_fwd(q, t, queue, 0.2, ws=mws)
+            ff, fb = 2.0 * two_n * K * D, 4.0 * two_n * K * D
+            row = dict(layer='moco 2n%d K%d D%d' % (two_n, K, D), fwd_flops=ff, bwd_flops=fb, key_splits=ops.moco_key_splits(two_n, K),
+                       moco_fwd_us=timeit(lambda: ops.moco_fwd(q, t, queue, 0.2, ws=mws), args.iters),
+                       moco_bwd_us=timeit(lambda: ops.moco_bwd(q, t, queue, 0.2, mrs, 1.0, mws), args.iters))
+            row['moco_fwd_tfs'] = ff / row['moco_fwd_us'] / 1e6
+            row['moco_bwd_tfs'] = fb / row['moco_bwd_us'] / 1e6
+            if (two_n, K, D) == (1024, 8192, 128):
+                row['moco_over_supcon_fwd'] = row['moco_fwd_us'] / ref['supcon_fwd_us']
+                row['moco_over_supcon_bwd'] = row['moco_bwd_us'] / ref['supcon_bwd_us']
+            print('moco 2n=%d K=%d D=%d: fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s)' % (
+                two_n, K, D, row['moco_fwd_us'], row['moco_fwd_tfs'], row['moco_bwd_us'], row['moco_bwd_tfs'])
+                + (' | moco / supcon fwd %.2f bwd %.2f' % (row['moco_over_supcon_fwd'], row['moco_over_supcon_bwd'])
+                   if 'moco_over_supcon_fwd' in row else ''), flush=True)
+            res.append(row)
+            del q, t, queue, mws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
