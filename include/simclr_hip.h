@@ -610,6 +610,49 @@ int simclr_moco_fwd(const float* q, const float* t, const float* queue, int two_
 int simclr_moco_bwd(const float* q, const float* t, const float* queue, int two_n, int K, int D, float temperature,
                     const float* row_stats, float grad_scale, float* dq, void* workspace, simclr_stream_t stream);
 
+/* ---- DINO self-distillation (csrc/dino.hip): Caron et al. 2021, Emerging Properties in Self-Supervised Vision Transformers ----
+ * q [two_n, D] = the l2-normalised online projections, [view-a rows; view-b rows]; k [two_n, D] = the l2-normalised target projections
+ * of the same rows; ws / wt [K, D] = the row-normalised prototypes of the online / the target network; center [K]; all fp32, the
+ * matrices 16-byte aligned, D in {64, 128, 256}, K >= 2 (a ragged last tile is fine), two_n even.  The pairing is formed inside:
+ * p(r) = (r + two_n / 2) mod two_n.  With s_rj = q_r . ws_j / Ts, t_rj = (k_r . wt_j - center_j) / Tt, Ps / Pt their row softmaxes:
+ *   l_r = logsumexp_j(s_r) - sum_j Pt[p(r), j] s_rj,   out[0] = (1 / two_n) sum_r l_r (the mean over the two cross-view terms),
+ *   out[1] = (1 / two_n) sum_r H(Pt[r]), the mean teacher entropy in nats,
+ *   u [two_n, D] = sum_j Pt[r, j] ws_j (the positive term of row r is q_r . u_p(r) / Ts; kept for simclr_dino_bwd_q).
+ * Two-pass form: a statistics sweep of both sides (one launch), the merge of their key splits, the teacher expectation sweep (wt and
+ * ws tiles side by side in LDS), the row finalize in double, a one-workgroup reduce.  Exact-fp32 MFMA sweeps over 64-row tiles, online
+ * statistics on the rounded logit, splits merged in a fixed order, no [two_n, K] matrix ever written, no atomics: two calls are
+ * bitwise equal.  The statistics keep the non-maximum mass apart (log1p) and the entropy is log(sum) - sum e^(t-m)(t-m) / sum with
+ * every term <= 0.  row_stats: device float [two_n, 2] = {logsumexp of s_r, logsumexp of t_r} in the base-2 domain, kept for the two
+ * backward calls.  workspace: simclr_dino_workspace_bytes(two_n, K, D) bytes, shared by the three calls (0 for a refused shape).
+ * simclr_dino_key_splits: key splits of the statistics sweeps; simclr_dino_row_splits: row splits of the key-side sweep (0 for a
+ * refused shape).  Refused (1 returned, nothing launched): null / misaligned pointers, another D, two_n < 2 or odd, K < 2, a
+ * temperature <= 0 or NaN. */
+size_t simclr_dino_workspace_bytes(int two_n, int K, int D);
+int simclr_dino_key_splits(int two_n, int K);
+int simclr_dino_row_splits(int two_n, int K);
+int simclr_dino_fwd(const float* q, const float* k, const float* ws, const float* wt, const float* center, int two_n, int K, int D,
+                    float student_temp, float teacher_temp, float* out, float* row_stats, float* u, void* workspace,
+                    simclr_stream_t stream);
+/* dq [two_n, D] = grad_scale * d out[0] / dq = (grad_scale / (two_n Ts)) (sum_j Ps[r, j] ws_j - u_p(r)) from the row_stats and u of
+ * simclr_dino_fwd on the same arguments: one query-side sweep that recomputes s. */
+int simclr_dino_bwd_q(const float* q, const float* ws, const float* u, int two_n, int K, int D, float student_temp,
+                      const float* row_stats, float grad_scale, float* dq, void* workspace, simclr_stream_t stream);
+/* dws [K, D] = grad_scale * d out[0] / dws = (grad_scale / (two_n Ts)) sum_r (Ps[r, j] - Pt[p(r), j]) q_r: the key-side sweep.  A
+ * workgroup owns 64 prototypes and streams 64-row tiles of q and of the paired rows k_p(r); it recomputes BOTH logits, so center and
+ * wt must still be the ones simclr_dino_fwd read.  Row splits are merged in a fixed order.  k, wt and center get no gradient. */
+int simclr_dino_bwd_w(const float* q, const float* k, const float* ws, const float* wt, const float* center, int two_n, int K, int D,
+                      float student_temp, float teacher_temp, const float* row_stats, float grad_scale, float* dws, void* workspace,
+                      simclr_stream_t stream);
+/* kbar [D] (device double) = scale * sum_r k[r][d] over the rows of k [rows, D] fp32, accumulated in double in a fixed order: with
+ * scale = 1 / (global rows) and a SUM all-reduce over the replicas it is the global mean of the normalised target projections, the
+ * one vector the DINO centre needs.  Refused: null / misaligned pointers, another D, rows < 1. */
+int simclr_dino_key_mean(const float* k, int rows, int D, double scale, double* kbar, simclr_stream_t stream);
+/* center_j <- center_j + (1 - momentum) (wt_j . kbar - center_j), kbar = device double [D], the mean of the l2-normalised target
+ * projections over all rows of the global batch.  The dot product accumulates in double and is rounded to fp32 once; the blend's three
+ * fp32 roundings are separate, (1 - momentum) is formed in double and cast once.  Refused: null / misaligned pointers, another D,
+ * K < 2, a momentum outside [0, 1] or NaN. */
+int simclr_dino_center(const float* wt, const double* kbar, float* center, int K, int D, float momentum, simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

@@ -106,7 +106,9 @@ _DEFS = [
                                         "--temperature are ignored with it) or 'byol' (add_byol_loss: BYOL on a momentum target network with a predictor "
                                         'on the online side; loss width as for barlow; always l2-normalised, --hidden_norm and --temperature are ignored) '
                                         "or 'mocov2' (add_moco_loss: MoCo v2, InfoNCE against a queue of momentum keys; loss width 64, 128 or 256; always "
-                                        'l2-normalised, --hidden_norm is ignored, --temperature is honoured: 0.2 is the usual choice).  '
+                                        'l2-normalised, --hidden_norm is ignored, --temperature is honoured: 0.2 is the usual choice) '
+                                        "or 'dino' (add_dino_loss: DINO self-distillation onto --dino_out_dim prototypes, a momentum target network and "
+                                        'a centre; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and --temperature are ignored).  '
                                         'Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
@@ -124,6 +126,16 @@ _DEFS = [
     ('moco_queue_size', 65536, int, 'MI355X build: rows K of the MoCo key queue: a multiple of 2 x train_batch_size, at least that and at most 1048576.'),
     ('moco_momentum', 0.999, float, 'MI355X build: constant decay m of the MoCo target network\'s moving average, t <- t + (1 - m) (o - t).  In [0, 1].'),
     ('moco_queue_seed', 0, int, 'MI355X build: seed of the random unit rows the MoCo queue starts from (the same on every replica).'),
+    # DINO (Caron et al. 2021) in place of NT-Xent for pretraining: a momentum target network, a trained prototype layer and a centre
+    ('dino_out_dim', 65536, int, 'MI355X build: number K of DINO prototypes (the width of the two softmaxes): 2 .. 1048576.'),
+    ('dino_student_temp', 0.1, float, 'MI355X build: temperature of the DINO student softmax.  > 0.'),
+    ('dino_teacher_temp', 0.04, float, 'MI355X build: final temperature of the DINO teacher softmax.  > 0.'),
+    ('dino_warmup_teacher_temp', 0.04, float, 'MI355X build: teacher temperature at step 0; it moves linearly to --dino_teacher_temp over '
+                                              '--dino_warmup_teacher_temp_epochs.  > 0.'),
+    ('dino_warmup_teacher_temp_epochs', 0, int, 'MI355X build: epochs of the teacher temperature warm-up.  >= 0.'),
+    ('dino_center_momentum', 0.9, float, 'MI355X build: decay m of the DINO centre, c <- m c + (1 - m) (batch mean of the teacher logits).  In [0, 1].'),
+    ('dino_momentum', 0.996, float, 'MI355X build: base decay of the DINO target network; it follows the cosine schedule of BYOL to 1.  In [0, 1].'),
+    ('dino_freeze_last_layer_epochs', 1, int, 'MI355X build: epochs during which the DINO prototypes take no update at all.  >= 0.'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),

@@ -242,6 +242,66 @@ def moco_on():
     return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'mocov2' and FLAGS.train_mode == 'pretrain'
 
 
+def dino_on():
+    """--contrastive_loss=dino in a pretraining run: the model carries a PrototypeHead and the step needs a TargetNetwork with a
+    DinoCenter; no predictor."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'dino' and FLAGS.train_mode == 'pretrain'
+
+
+def dino_teacher_temp(step, steps_per_epoch):
+    """Teacher temperature of DINO at optimizer step `step`: linear from --dino_warmup_teacher_temp to --dino_teacher_temp over
+    --dino_warmup_teacher_temp_epochs * steps_per_epoch steps, then constant.  Formed in double, cast to float32 once."""
+    import numpy as np
+    final, warm = float(FLAGS.dino_teacher_temp), float(FLAGS.dino_warmup_teacher_temp)
+    n = int(FLAGS.dino_warmup_teacher_temp_epochs) * int(steps_per_epoch)
+    if n <= 0 or int(step) >= n:
+        return float(np.float32(final))
+    return float(np.float32(warm + (final - warm) * (float(int(step)) / float(n))))
+
+
+def dino_last_layer_frozen(step, steps_per_epoch):
+    """True while the prototypes take no update: step < --dino_freeze_last_layer_epochs * steps_per_epoch."""
+    return int(step) < int(FLAGS.dino_freeze_last_layer_epochs) * int(steps_per_epoch)
+
+
+class PrototypeHead(Layer):
+    """The prototype layer of DINO (Caron et al. 2021): ONE variable [K, D] whose rows, l2-normalised every step, score the
+    l2-normalised projection output -- the paper's weight-normalised last layer with norm_last_layer=True (gain fixed at 1).  The
+    variable is initialised as a LinearLayer kernel of that shape (RandomNormal(stddev=.01)) and is trained, weight-decayed and
+    LARS-adapted by the name rules that cover the projection head's kernels.
+
+    A call returns the normalised rows [K, D] (tf.math.l2_normalize, epsilon 1e-12) and keeps them for `backward(dws)`, which writes
+    the gradient of the raw variable into its gradient slot.  The [2b, K] logits are never formed here: the loss kernels sweep them."""
+
+    def __init__(self, num_prototypes, **kwargs):
+        self.num_prototypes = int(num_prototypes)
+        with scope('prototype_head'):
+            self._path = RT.path('kernel:0')
+        self.kernel = None
+        self.saved = None
+
+    def build(self, width):
+        RT.seed += 1
+        g = torch.Generator().manual_seed(RT.seed)
+        w = torch.randn(self.num_prototypes, int(width), generator=g) * 0.01          # as LinearLayer.build
+        self.kernel = Variable(self._path, w.to(RT.device))
+
+    def __call__(self, width=None):
+        if self.kernel is None:
+            self.build(projection_width() if width is None else width)
+        w, inv = ops.l2norm_fwd(self.kernel.value)
+        self.saved = (w, inv)
+        return w
+
+    def backward(self, dws):
+        """dws: gradient wrt the normalised rows [K, D] -> written into the variable's gradient slot (and returned)."""
+        w, inv = self.saved
+        self.saved = None
+        g = self.kernel.ensure_grad()
+        g.copy_(ops.l2norm_bwd(w, inv, dws))
+        return g
+
+
 def projection_width():
     """Width of the block the pretraining loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none.  The one
     statement of that rule: the start-up checks of run.check_contrastive_loss_flags and the predictor's output layer both call it."""
@@ -312,6 +372,8 @@ class Model(Layer):
                 self.supervised_head = SupervisedHead(num_classes)
             # BYOL: constructed last, so every other layer keeps the name (and, built after them, the initial value) of an ntxent run
             self.prediction_head = PredictionHead() if byol_on() else None
+            # DINO: constructed (and, by TargetNetwork, built) LAST for the same reason
+            self.prototype_head = PrototypeHead(FLAGS.dino_out_dim) if dino_on() else None
         self._flat_grads = None
 
     def __call__(self, inputs, training, blur=True):
@@ -458,6 +520,8 @@ class Model(Layer):
             l0.build(feats[-1])
             l0.bn_relu.build(l0.npad)
             l1.build(l0.npad)
+        if self.prototype_head is not None:
+            self.prototype_head.build(feats[-1])
 
     def release(self):
         super().release()
@@ -544,8 +608,8 @@ def byol_tau(step, total_steps, tau_base):
 def target_flag_values():
     """The flag values the BYOL target network is built and called under: a plain pretraining encoder and projection head of the
     online architecture -- no supervised head, no predictor, no DropBlock site."""
-    return dict(train_mode='pretrain', contrastive_loss='ntxent', lineareval_while_pretraining=False, fine_tune_after_block=-1,
-                dropblock_keep_probs='')
+    return dict(train_mode='pretrain', contrastive_loss='dino' if dino_on() else 'ntxent', lineareval_while_pretraining=False,
+                fine_tune_after_block=-1, dropblock_keep_probs='')
 
 
 def moco_queue_ptr(step, rows_per_step, K):
@@ -605,6 +669,37 @@ class MocoQueue:
         return ptr
 
 
+class DinoCenter:
+    """The centre of the DINO teacher (Caron et al. 2021, eq. 4): a device fp32 [K] vector, zeros at the start, exposed as ONE
+    non-trainable Variable `dino/center` (checkpointed with the target network; no optimizer slot, no weight decay, no gradient) and
+    identical on every replica: update() reads the GLOBAL mean of the normalised target projections.
+    update(wt, kbar, momentum): c <- c + (1 - m) (wt . kbar - c) in one launch (ops.dino_center), with wt the normalised target
+    prototypes THE FORWARD USED -- the caller runs it after the backward (which recomputes the teacher softmax from the centre)."""
+
+    NAME = 'dino/center'
+
+    def __init__(self, K, device=None):
+        K = int(K)
+        if K < 2:
+            raise ValueError('DinoCenter: need K >= 2 prototypes (got %d)' % K)
+        self.K = K
+        self.variable = Variable(self.NAME, torch.zeros(K, device=device or RT.device, dtype=torch.float32), False)
+
+    def reset(self):
+        self.variable.value.zero_()
+
+    @property
+    def value(self):
+        return self.variable.value
+
+    @property
+    def variables(self):
+        return [self.variable]
+
+    def update(self, wt, kbar, momentum):
+        return ops.dino_center(wt, kbar, self.variable.value, momentum)
+
+
 class _WithTarget:
     """What a BYOL / MoCo checkpoint holds: every variable of the online model under its own name (the optimizer's slots hang on these
     very objects), every target variable under the prefix `target/` and, with a queue attached, `moco/queue`."""
@@ -615,6 +710,8 @@ class _WithTarget:
         self._target_variables = [Variable(TargetNetwork.PREFIX + v.name, v.value, False) for v in target.model.variables]
         if target.queue is not None:
             self._target_variables += target.queue.variables
+        if getattr(target, 'center', None) is not None:
+            self._target_variables += target.center.variables
 
     @property
     def variables(self):
@@ -642,11 +739,19 @@ class TargetNetwork:
 
     PREFIX = 'target/'
 
-    def __init__(self, online_model, total_steps, image_size=None, queue=None):
+    def __init__(self, online_model, total_steps, image_size=None, queue=None, center=None, steps_per_epoch=None):
         self.moco = moco_on()
-        if online_model.prediction_head is None and not self.moco:
+        self.dino = dino_on()
+        if online_model.prediction_head is None and not (self.moco or self.dino):
             raise ValueError('TargetNetwork: the online model has no predictor (it was built without --contrastive_loss=byol)')
+        if self.dino and getattr(online_model, 'prototype_head', None) is None:
+            raise ValueError('TargetNetwork: the online model has no prototype head (it was built without --contrastive_loss=dino)')
+        if self.dino and (steps_per_epoch is None or int(steps_per_epoch) < 1):
+            raise ValueError('TargetNetwork: --contrastive_loss=dino needs steps_per_epoch >= 1 (the teacher temperature and the '
+                             'freeze of the prototypes count epochs)')
         self.queue = queue                    # model.MocoQueue (mocov2) or None: listed by checkpointable()
+        self.center = center                  # model.DinoCenter (dino) or None: listed by checkpointable()
+        self.steps_per_epoch = None if steps_per_epoch is None else int(steps_per_epoch)
         # mocov2: the constant --moco_momentum m; 1 - m is formed in double and cast to float32 once
         self._moco_omt = None
         if self.moco:
@@ -666,20 +771,25 @@ class TargetNetwork:
             # after the encoder, the projection head and the supervised head: their initial values are those of an ntxent run
             online_model.prediction_head(torch.zeros(2, projection_width(), device=RT.device), training=False)
             online_model.prediction_head.release()
+        if self.dino and online_model.prototype_head.kernel is None:
+            online_model.prototype_head.build(projection_width())       # last: every other initial value is that of an ntxent run
         with FLAGS.override(**self.flag_values), RT.fresh_names():
             self.model = Model(0)
             self.model.trainable = False
             self.model.resnet_model.stem_trainable = False
             self.model(zeros if zeros is not None else torch.zeros(2, size, size, 3, device=RT.device), training=False)
             self.model.release()
-        online = {v.name: v for v in online_model.resnet_model.variables + online_model._projection_head.variables}
+            if self.dino:
+                self.model.prototype_head.build(projection_width())
+        heads = [online_model._projection_head] + ([online_model.prototype_head] if self.dino else [])
+        online = {v.name: v for v in online_model.resnet_model.variables + [v for h in heads for v in h.variables]}
         self._pairs = []                      # (target variable, online variable) by name, every variable of the target
         for v in self.model.variables:
             o = online.get(v.name)
             if o is None or o.shape != v.shape:
                 raise ValueError('TargetNetwork: target variable %s has no online namesake of its shape' % v.name)
             self._pairs.append((v, o))
-        trained = {id(v) for v in online_model.resnet_model.trainable_variables + online_model._projection_head.trainable_variables}
+        trained = {id(v) for v in online_model.resnet_model.trainable_variables + [v for h in heads for v in h.trainable_variables]}
         self._ema_pairs = [(t, o) for t, o in self._pairs if id(o) in trained]
         self._tables = ops.EmaTables()
         self.copy_from_online()
@@ -706,7 +816,14 @@ class TargetNetwork:
         return _WithTarget(self.online, self)
 
     def tau(self, step):
-        return byol_tau(step, self.total_steps, FLAGS.byol_tau_base)
+        """BYOL's cosine schedule to 1, from --byol_tau_base or (dino) from --dino_momentum."""
+        return byol_tau(step, self.total_steps, FLAGS.dino_momentum if self.dino else FLAGS.byol_tau_base)
+
+    def prototypes(self):
+        """dino: the row-normalised prototypes of the target network, float32 [K, D]; nothing is kept."""
+        w = self.model.prototype_head()
+        self.model.prototype_head.saved = None
+        return w
 
     def update(self, step):
         """After optimizer.apply_gradients of step `step` (optimizer.iterations before its increment).  tau is formed on the host in

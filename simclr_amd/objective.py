@@ -22,6 +22,9 @@ l2-normalised projection a momentum target network gives the other view; no nega
 
 `add_moco_loss` is the MoCo v2 loss of He et al. 2020 / Chen et al. 2020 (InfoNCE of each online row against the momentum key of its
 other view and a queue of keys of earlier steps; no collective) on the kernels of csrc/moco.hip.
+
+`add_dino_loss` is the DINO loss of Caron et al. 2021 (cross-entropy of the student's softmax over K trained prototypes against the
+centred, sharpened softmax the momentum teacher gives the other view; no collective) on the kernels of csrc/dino.hip.
 """
 import torch
 
@@ -532,6 +535,66 @@ def add_moco_loss(online, target, queue, temperature=1.0, strategy=None, overlap
     loss = _Loss(out[0:1], backward)
     loss.acc = out[1:2]
     loss.keys = keys
+    return loss
+
+
+def add_dino_loss(online, target, prototypes, target_prototypes, center, student_temp=0.1, teacher_temp=0.04, strategy=None,
+                  overlap=None, keys=None, update_prototypes=True):
+    """DINO loss (Caron et al. 2021) on the kernels of csrc/dino.hip: with q = l2n(online), k = l2n(target), ws / wt the row-normalised
+    prototypes of the online / the target network, c the centre and p(r) = (r + b) mod 2b,
+      s_rj = q_r . ws_j / Ts,   t_rj = (k_r . wt_j - c_j) / Tt,   Ps = softmax_j(s_r),   Pt = softmax_j(t_r),
+      loss = (1 / 2b) sum_{r < 2b} [logsumexp_j(s_r) - sum_j Pt[p(r), j] s_rj],
+    the paper's MEAN over the two cross-view terms (the official code divides by n_loss_terms).  This differs on purpose from the
+    (1 / b) sum -- the sum of the two per-view means -- of add_byol_loss and add_moco_loss.  l2n is tf.math.l2_normalize (epsilon
+    1e-12); always applied.  None of the four [2b, K] matrices is written.
+
+    Args:
+      online: float32 device tensor [2b, D] = the online projection output, [view-a rows; view-b rows]; D in {64, 128, 256}.
+      target: float32 device tensor [2b, D] = the target network's projection output of the same batch.  It gets no gradient.
+      prototypes: the online model.PrototypeHead.  It is called here (its rows are normalised) and its `backward` receives the
+        gradient of the normalised rows: grad_scale * the prototype gradient lands in the variable's gradient slot, where the
+        model's backward collects parameter gradients.
+      target_prototypes: float32 device tensor [K, D], the target network's row-normalised prototypes (TargetNetwork.prototypes()),
+        or a PrototypeHead, which is called.  No gradient.
+      center: float32 device tensor [K].  No gradient.  The backward READS IT AGAIN (it recomputes the teacher softmax), and the
+        target prototypes too: the caller moves the centre and the target only after `backward`.
+      student_temp, teacher_temp: Ts, Tt.
+      strategy: replica context or None.  The loss needs NO collective of its own: a replica's value is the mean over its own rows,
+        the mean over the replicas is the loss, `backward` is called with 1 / R, a rank's prototype gradient is the share of its own
+        rows and the usual gradient synchronisation sums the shares.
+      overlap: optional zero-argument callable, run after the forward launches.
+      keys: l2n(target), when the caller formed it already (the step does, to start the all-reduce of its mean before the online forward).
+      update_prototypes: False while the prototypes are frozen: the key-side sweep is skipped and no gradient is written.
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * dloss/donline, [2b, D]), the device scalars
+      .value and .entropy (mean entropy of the teacher rows in nats: log K = uniform, 0 = one-hot collapse), .keys = l2n(target) and
+      .target_prototypes = the [K, D] rows the forward used (what the centre update reads).
+    """
+    online, target = online.contiguous(), target.contiguous()
+    ws = prototypes()
+    wt = target_prototypes if torch.is_tensor(target_prototypes) else target_prototypes()
+    if not torch.is_tensor(target_prototypes):
+        target_prototypes.saved = None
+    z, inv = ops.l2norm_fwd(online)
+    if keys is None:
+        keys, _ = ops.l2norm_fwd(target)
+    ops._dino_check(z, keys, ws, wt, center, student_temp, teacher_temp)
+    out, row_stats, u, wsp = ops.dino_fwd(z, keys, ws, wt, center, student_temp, teacher_temp)
+    if overlap is not None:
+        overlap()
+
+    def backward(grad_scale=1.0):
+        dq = ops.l2norm_bwd(z, inv, ops.dino_bwd_q(z, ws, u, student_temp, row_stats, grad_scale, wsp))
+        if update_prototypes:
+            prototypes.backward(ops.dino_bwd_w(z, keys, ws, wt, center, student_temp, teacher_temp, row_stats, grad_scale, wsp))
+        else:
+            prototypes.saved = None
+        return dq
+
+    loss = _Loss(out[0:1], backward)
+    loss.entropy = out[1:2]
+    loss.keys = keys
+    loss.target_prototypes = wt
     return loss
 
 

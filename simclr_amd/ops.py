@@ -645,6 +645,165 @@ def moco_bwd(q, t, queue, temperature, row_stats, grad_scale, ws):
     return dq
 
 
+# ---------------------------------------------------------------- DINO self-distillation (csrc/dino.hip)
+DINO_DIMS = (64, 128, 256)          # loss widths the DINO kernels are instantiated for
+DINO_MAX_OUT_DIM = 1048576          # largest --dino_out_dim
+
+
+def _dino_check_dim(D):
+    if D not in DINO_DIMS:
+        raise ValueError('the DINO loss supports widths %s (got %d)' % ('/'.join(map(str, DINO_DIMS)), D))
+
+
+def _dino_check_temp(name, value):
+    if not 0.0 < float(value) < float('inf'):            # (NaN fails the comparison)
+        raise ValueError('dino: %s must be > 0 and finite (got %r)' % (name, value))
+
+
+def _dino_check(q, k, ws, wt, center, student_temp, teacher_temp):
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 2 or tuple(q.shape) != tuple(k.shape):
+        raise ValueError('dino: need float32 q and k of one shape [2b, D] (got %s %s, %s %s)'
+                         % (tuple(q.shape), q.dtype, tuple(k.shape), k.dtype))
+    rows, D = q.shape
+    if rows < 2 or rows % 2:
+        raise ValueError('dino: q and k hold both views, [2b, D] with b >= 1 (got %d rows)' % rows)
+    _dino_check_dim(D)
+    if (ws.dtype != torch.float32 or wt.dtype != torch.float32 or ws.dim() != 2 or tuple(ws.shape) != tuple(wt.shape)
+            or ws.shape[0] < 2 or ws.shape[1] != D):
+        raise ValueError('dino: the prototypes are two float32 [K, %d] blocks with K >= 2 (got %s %s, %s %s)'
+                         % (D, tuple(ws.shape), ws.dtype, tuple(wt.shape), wt.dtype))
+    K = ws.shape[0]
+    if center.dtype != torch.float32 or tuple(center.shape) != (K,):
+        raise ValueError('dino: the centre is a float32 [%d] vector (got %s %s)' % (K, tuple(center.shape), center.dtype))
+    for t in (q, k, ws, wt, center):
+        if not t.is_contiguous():
+            raise ValueError('dino: every argument is contiguous')
+    _dino_check_temp('the student temperature', student_temp)
+    _dino_check_temp('the teacher temperature', teacher_temp)
+    return rows, K, D
+
+
+def dino_key_splits(two_n, K):
+    """Number of key splits the statistics sweeps of dino_fwd use for two_n rows against K prototypes."""
+    splits = lib().dino_key_splits(int(two_n), int(K))
+    if splits < 1:
+        raise ValueError('dino: need an even two_n >= 2 and K >= 2 (got two_n = %d, K = %d)' % (two_n, K))
+    return splits
+
+
+def dino_row_splits(two_n, K):
+    """Number of row splits the key-side sweep of dino_bwd_w uses for two_n rows against K prototypes."""
+    splits = lib().dino_row_splits(int(two_n), int(K))
+    if splits < 1:
+        raise ValueError('dino: need an even two_n >= 2 and K >= 2 (got two_n = %d, K = %d)' % (two_n, K))
+    return splits
+
+
+def dino_workspace(two_n, K, D, device):
+    _dino_check_dim(D)
+    nbytes = lib().dino_workspace_bytes(two_n, K, D)
+    if nbytes == 0:
+        raise ValueError('dino: need an even two_n >= 2 and K >= 2 (got two_n = %d, K = %d)' % (two_n, K))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def _dino_check_ws(ws, two_n, K, D):
+    if ws is None or ws.numel() * ws.element_size() < lib().dino_workspace_bytes(two_n, K, D):
+        raise ValueError('dino: the workspace is smaller than dino_workspace(%d, %d, %d)' % (two_n, K, D))
+
+
+def _dino_check_stats(name, row_stats, two_n):
+    if row_stats.dtype != torch.float32 or tuple(row_stats.shape) != (two_n, 2):
+        raise ValueError('%s: row_stats is the float32 [2b, 2] block dino_fwd returned (got %s %s)'
+                         % (name, tuple(row_stats.shape), row_stats.dtype))
+
+
+def dino_fwd(q, k, ws, wt, center, student_temp, teacher_temp, workspace=None):
+    """q [2b, D] (normalised online projections), k [2b, D] (normalised target projections of the same rows: row r of q pairs with
+    row (r + b) mod 2b of k inside the kernels), ws / wt [K, D] (row-normalised online / target prototypes), center [K] ->
+    (out = [loss, teacher entropy] device fp32, row_stats [2b, 2], u [2b, D] = Pt . ws, the workspace the three calls share)."""
+    two_n, K, D = _dino_check(q, k, ws, wt, center, student_temp, teacher_temp)
+    if workspace is None:
+        workspace = dino_workspace(two_n, K, D, q.device)
+    _dino_check_ws(workspace, two_n, K, D)
+    out = step_scalars(2, q.device)
+    row_stats = torch.empty(two_n, 2, device=q.device, dtype=torch.float32)
+    u = torch.empty_like(q)
+    _launch('dino_fwd', 8.0 * two_n * K * D, 4.0 * (3 * two_n + 3 * K) * D,
+            lambda: lib().dino_fwd(_p(q), _p(k), _p(ws), _p(wt), _p(center), two_n, K, D, float(student_temp), float(teacher_temp),
+                                   _p(out), _p(row_stats), _p(u), _p(workspace), _s()))
+    return out, row_stats, u, workspace
+
+
+def dino_bwd_q(q, ws, u, student_temp, row_stats, grad_scale, workspace):
+    """dq [2b, D] = grad_scale * dloss / dq from dino_fwd's row_stats, u and workspace on the same arguments."""
+    if (q.dtype != torch.float32 or q.dim() != 2 or q.shape[0] < 2 or q.shape[0] % 2 or u.dtype != torch.float32
+            or tuple(u.shape) != tuple(q.shape) or not q.is_contiguous() or not u.is_contiguous()):
+        raise ValueError('dino_bwd_q: need contiguous float32 q and u of one shape [2b, D] (got %s %s, %s %s)'
+                         % (tuple(q.shape), q.dtype, tuple(u.shape), u.dtype))
+    two_n, D = q.shape
+    _dino_check_dim(D)
+    if ws.dtype != torch.float32 or ws.dim() != 2 or ws.shape[0] < 2 or ws.shape[1] != D or not ws.is_contiguous():
+        raise ValueError('dino_bwd_q: the prototypes are a contiguous float32 [K, %d] block with K >= 2 (got %s %s)'
+                         % (D, tuple(ws.shape), ws.dtype))
+    K = ws.shape[0]
+    _dino_check_temp('the student temperature', student_temp)
+    _dino_check_stats('dino_bwd_q', row_stats, two_n)
+    _dino_check_ws(workspace, two_n, K, D)
+    dq = torch.empty_like(q)
+    _launch('dino_bwd_q', 4.0 * two_n * K * D, 4.0 * (3 * two_n + K) * D,
+            lambda: lib().dino_bwd_q(_p(q), _p(ws), _p(u), two_n, K, D, float(student_temp), _p(row_stats), float(grad_scale), _p(dq),
+                                     _p(workspace), _s()))
+    return dq
+
+
+def dino_bwd_w(q, k, ws, wt, center, student_temp, teacher_temp, row_stats, grad_scale, workspace):
+    """dws [K, D] = grad_scale * dloss / dws: the key-side sweep.  It recomputes both logits: wt and center are still the ones dino_fwd
+    read."""
+    two_n, K, D = _dino_check(q, k, ws, wt, center, student_temp, teacher_temp)
+    _dino_check_stats('dino_bwd_w', row_stats, two_n)
+    _dino_check_ws(workspace, two_n, K, D)
+    dws = torch.empty_like(ws)
+    _launch('dino_bwd_w', 6.0 * two_n * K * D, 4.0 * (2 * two_n + 3 * K) * D,
+            lambda: lib().dino_bwd_w(_p(q), _p(k), _p(ws), _p(wt), _p(center), two_n, K, D, float(student_temp), float(teacher_temp),
+                                     _p(row_stats), float(grad_scale), _p(dws), _p(workspace), _s()))
+    return dws
+
+
+def dino_key_mean(k, global_rows):
+    """k [2b, D] float32 -> float64 device [D] = (sum of this replica's rows) / global_rows, accumulated in double in a fixed order; summed
+    over the replicas it is the global mean the centre update reads."""
+    if k.dtype != torch.float32 or k.dim() != 2 or k.shape[0] < 1 or not k.is_contiguous():
+        raise ValueError('dino_key_mean: need a contiguous float32 [rows, D] block (got %s %s)' % (tuple(k.shape), k.dtype))
+    rows, D = k.shape
+    _dino_check_dim(D)
+    if int(global_rows) < rows:
+        raise ValueError('dino_key_mean: the global batch has at least the %d local rows (got %r)' % (rows, global_rows))
+    kbar = torch.empty(D, device=k.device, dtype=torch.float64)
+    _launch('dino_key_mean', 1.0 * rows * D, 4.0 * rows * D,
+            lambda: lib().dino_key_mean(_p(k), rows, D, 1.0 / float(int(global_rows)), _p(kbar), _s()))
+    return kbar
+
+
+def dino_center(wt, kbar, center, momentum):
+    """In place: center <- center + (1 - momentum) (wt . kbar - center); kbar = float64 device [D], the global mean of the normalised
+    target projections."""
+    if wt.dtype != torch.float32 or wt.dim() != 2 or wt.shape[0] < 2 or not wt.is_contiguous():
+        raise ValueError('dino_center: the prototypes are a contiguous float32 [K, D] block with K >= 2 (got %s %s)'
+                         % (tuple(wt.shape), wt.dtype))
+    K, D = wt.shape
+    _dino_check_dim(D)
+    if kbar.dtype != torch.float64 or tuple(kbar.shape) != (D,) or not kbar.is_contiguous():
+        raise ValueError('dino_center: kbar is a float64 [%d] vector (got %s %s)' % (D, tuple(kbar.shape), kbar.dtype))
+    if center.dtype != torch.float32 or tuple(center.shape) != (K,) or not center.is_contiguous():
+        raise ValueError('dino_center: the centre is a float32 [%d] vector (got %s %s)' % (K, tuple(center.shape), center.dtype))
+    if not 0.0 <= float(momentum) <= 1.0:            # (NaN fails both comparisons)
+        raise ValueError('dino_center: the momentum must lie in [0, 1] (got %r)' % (momentum,))
+    _launch('dino_center', 2.0 * K * D, 4.0 * K * D,
+            lambda: lib().dino_center(_p(wt), _p(kbar), _p(center), K, D, float(momentum), _s()))
+    return center
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

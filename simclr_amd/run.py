@@ -50,14 +50,34 @@ def barlow_loss_width():
 byol_loss_on = model_lib.byol_on
 # --contrastive_loss=mocov2 replaces NT-Xent in the pretraining step by MoCo v2: InfoNCE against a queue of the target network's keys.
 moco_loss_on = model_lib.moco_on
+# --contrastive_loss=dino replaces NT-Xent in the pretraining step by DINO: self-distillation onto trained prototypes.
+dino_loss_on = model_lib.dino_on
 
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() tell the others)."""
-    if FLAGS.contrastive_loss not in ('ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
-        raise ValueError("--contrastive_loss must be 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r)"
+    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on()
+    tell the others)."""
+    if FLAGS.contrastive_loss not in ('dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
+        raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r)"
                          % FLAGS.contrastive_loss)
+    if dino_loss_on() and FLAGS.mode != 'eval':
+        if not 2 <= FLAGS.dino_out_dim <= ops.DINO_MAX_OUT_DIM:
+            raise ValueError('--dino_out_dim must lie in [2, %d] (got %r)' % (ops.DINO_MAX_OUT_DIM, FLAGS.dino_out_dim))
+        for name in ('dino_student_temp', 'dino_teacher_temp', 'dino_warmup_teacher_temp'):
+            if not 0.0 < getattr(FLAGS, name) < float('inf'):          # (NaN fails the comparison)
+                raise ValueError('--%s must be > 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
+        for name in ('dino_center_momentum', 'dino_momentum'):
+            if not 0.0 <= getattr(FLAGS, name) <= 1.0:                 # (NaN fails both comparisons)
+                raise ValueError('--%s must lie in [0, 1] (got %r)' % (name, getattr(FLAGS, name)))
+        for name in ('dino_warmup_teacher_temp_epochs', 'dino_freeze_last_layer_epochs'):
+            if getattr(FLAGS, name) < 0:
+                raise ValueError('--%s must be >= 0 (got %r)' % (name, getattr(FLAGS, name)))
+        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.DINO_DIMS:
+            raise ValueError('--contrastive_loss=dino needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
+                             'the DINO kernels are instantiated for those widths only'
+                             % ('/'.join(map(str, ops.DINO_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if moco_loss_on() and FLAGS.mode != 'eval':
         rows = 2 * FLAGS.train_batch_size               # the global 2N rows a step enqueues
         K = FLAGS.moco_queue_size
@@ -130,6 +150,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/byol_cosine']         # no logits to score: the mean cosine of the paired rows instead
     elif FLAGS.train_mode == 'pretrain' and moco_loss_on():
         names += ['train/contrast_loss', 'train/contrast_acc']        # positive against the best queue row; no entropy
+    elif FLAGS.train_mode == 'pretrain' and dino_loss_on():
+        names += ['train/contrast_loss', 'train/dino_teacher_entropy']   # log K = uniform teacher, 0 = one-hot collapse
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -239,6 +261,23 @@ def check_knn_flags(num_train_examples=None):
     return bank
 
 
+def all_reduce_stats_async(tensor, strategy):
+    """SUM of a small statistics tensor over the replicas on the route the SyncBN sums and the Barlow Twins column sums use, started
+    now; returns a zero-argument function that waits for it and returns the tensor.  One replica: nothing to do."""
+    if not collectives_on(strategy):
+        return lambda: tensor
+    if strategy.peer_stats is not None and strategy.peer_stats.usable(tensor):
+        strategy.all_reduce_sum(tensor)            # the peer-mapped exchange is stream-ordered: the host does not wait
+        return lambda: tensor
+    strategy.stat_collectives += 1
+    work = dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=strategy.stat_group, async_op=True)
+
+    def wait():
+        work.wait()
+        return tensor
+    return wait
+
+
 def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
     target: model.TargetNetwork (or a stand-in with its __call__ / update), required by --contrastive_loss=byol.  The step is then:
@@ -247,6 +286,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     --contrastive_loss=mocov2 needs a target with a model.MocoQueue attached (target.queue).  The step is: blur once, target forward
     and release, normalise the keys and start their asynchronous all-gather (nothing in the loss waits for it), online forward,
     add_moco_loss against the queue, backward, optimizer, target.update(step), then wait for the gather and queue.enqueue.
+    --contrastive_loss=dino needs a target with a model.DinoCenter attached (target.center) and its steps_per_epoch.  The step is: blur
+    once, target forward and release, normalise the keys and start the asynchronous all-reduce of their mean, online forward, normalise
+    both prototype tables, add_dino_loss, backward (loss kernels, the normalisations, the heads, the encoder), gradient synchronisation,
+    optimizer (without the prototypes while they are frozen), target.update(step), THEN wait for the mean and move the centre.
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -265,12 +308,16 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     barlow = barlow_loss_on() and not generalized
     byol = byol_loss_on() and not generalized
     moco = moco_loss_on() and not generalized
+    dino = dino_loss_on() and not generalized
     if byol and target is None:
         raise ValueError('--contrastive_loss=byol needs a target network: make_single_step(..., target=model.TargetNetwork(model, steps))')
     if moco and (target is None or getattr(target, 'queue', None) is None):
         raise ValueError('--contrastive_loss=mocov2 needs a target network with a key queue: make_single_step(..., '
                          'target=model.TargetNetwork(model, steps, queue=model.MocoQueue(K, D, seed)))')
-    if target is not None and not (byol or moco):
+    if dino and (target is None or getattr(target, 'center', None) is None or not getattr(target, 'steps_per_epoch', None)):
+        raise ValueError('--contrastive_loss=dino needs a target network with a centre: make_single_step(..., '
+                         'target=model.TargetNetwork(model, steps, center=model.DinoCenter(K), steps_per_epoch=n))')
+    if target is not None and not (byol or moco or dino):
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
@@ -285,7 +332,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
             # training arithmetic again, for the rest of the step
             teacher_logits = teacher(features)
-        if byol or moco:
+        if byol or moco or dino:
             # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
             if FLAGS.use_blur:
                 features = data_util.batch_random_blur_tensor(features, FLAGS.image_size, FLAGS.image_size)
@@ -295,6 +342,12 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 # the loss and the whole backward -- the loss reads the local keys and the queue as it stands
                 moco_keys, _ = ops.l2norm_fwd(target_outputs.contiguous())
                 moco_gather = obj_lib.gather_hidden(moco_keys, strategy, async_op=True)
+            if dino:
+                # the mean of this step's keys over the GLOBAL batch -- the one vector the centre update at the END of the step needs:
+                # formed in double in a fixed order, its all-reduce in flight during the online forward, the loss and the backward
+                dino_keys, _ = ops.l2norm_fwd(target_outputs.contiguous())
+                dino_kbar = ops.dino_key_mean(dino_keys, dino_keys.shape[0] * num_replicas(strategy))
+                dino_kbar_wait = all_reduce_stats_async(dino_kbar, strategy)
             projection_head_outputs, supervised_head_outputs = model(features, training=True, blur=False)
         else:
             projection_head_outputs, supervised_head_outputs = model(features, training=True)   # :577-578
@@ -336,6 +389,15 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 logits_con = None
                 con_loss = obj_lib.add_moco_loss(outputs, target_outputs, target.queue.value, temperature=FLAGS.temperature,
                                                  strategy=strategy, overlap=supervised_part, keys=moco_keys)
+            elif dino:
+                logits_con = None
+                # both derive from optimizer.iterations (before its increment): a restored run continues them
+                dino_step = int(getattr(optimizer, 'iterations', 0))
+                dino_frozen = model_lib.dino_last_layer_frozen(dino_step, target.steps_per_epoch)
+                con_loss = obj_lib.add_dino_loss(
+                    outputs, target_outputs, model.prototype_head, target.prototypes(), target.center.value,
+                    student_temp=FLAGS.dino_student_temp, teacher_temp=model_lib.dino_teacher_temp(dino_step, target.steps_per_epoch),
+                    strategy=strategy, overlap=supervised_part, keys=dino_keys, update_prototypes=not dino_frozen)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -374,16 +436,26 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             model.backward(d_proj, None, on_stage=sync.on_stage)
         join_wgrad_stream()
         sync.wait()
-        if byol or moco:
+        if byol or moco or dino:
             # before the increment: a restored run continues the tau schedule / the queue's write position
             step_index = int(getattr(optimizer, 'iterations', 0))
-        optimizer.apply_gradients([(v.grad, v) for v in state['apply']])                   # :622
-        if byol or moco:
+        if dino and dino_frozen:
+            # the frozen prototypes take no update at all -- no gradient, no weight decay, no momentum: the pair is dropped, as
+            # apply_gradients drops a variable without a gradient.  Online and target copies stay bitwise what they are.
+            frozen_id = id(model.prototype_head.kernel)
+            optimizer.apply_gradients([(v.grad, v) for v in state['apply'] if id(v) != frozen_id])
+        else:
+            optimizer.apply_gradients([(v.grad, v) for v in state['apply']])               # :622
+        if byol or moco or dino:
             target.update(step_index)
         if moco:
             # The enqueue comes AFTER the backward: the backward recomputes the logits from the queue, and a queue that already held
             # this step's keys would silently differentiate another loss (every query would find its own positive among the negatives).
             target.queue.enqueue(moco_gather(), step_index)
+        if dino:
+            # The centre moves AFTER the backward, which recomputes the teacher softmax from it (moved earlier, the step would
+            # differentiate another loss in silence), and it reads the target prototypes the FORWARD used, not the ones update() left.
+            target.center.update(con_loss.target_prototypes, dino_kbar_wait(), FLAGS.dino_center_momentum)
         RT.optimizer_stepped()
         ops.end_step()
         if strategy is not None:
@@ -422,6 +494,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         elif con_loss is not None and moco:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
+        elif con_loss is not None and dino:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/dino_teacher_entropy'] = con_loss.entropy.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -457,6 +532,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             elif moco:
                 if 'train/contrast_acc' in at:
                     con_loss.acc = at['train/contrast_acc']
+            elif dino:
+                if 'train/dino_teacher_entropy' in at:
+                    con_loss.entropy = at['train/dino_teacher_entropy']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:
@@ -699,6 +777,10 @@ def main(argv):
         # MoCo v2: the same target network under a constant momentum, and the queue of its keys (seeded: the same on every replica)
         target = model_lib.TargetNetwork(model, train_steps,
                                          queue=model_lib.MocoQueue(FLAGS.moco_queue_size, FLAGS.proj_out_dim, FLAGS.moco_queue_seed))
+    if dino_loss_on():
+        # DINO: the same target network under BYOL's cosine schedule from --dino_momentum, prototypes included, and the teacher's centre
+        target = model_lib.TargetNetwork(model, train_steps, center=model_lib.DinoCenter(FLAGS.dino_out_dim),
+                                         steps_per_epoch=max(epoch_steps, 1))
     step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
@@ -723,6 +805,9 @@ def main(argv):
         if target is not None and target.queue is not None and status is not None and (
                 not manager.latest_checkpoint or target.queue.NAME in status.missing_in_checkpoint):
             target.queue.reset()             # likewise the seeded queue (a weights-only restore may have filled it from the file)
+        if target is not None and target.center is not None and status is not None and (
+                not manager.latest_checkpoint or target.center.NAME in status.missing_in_checkpoint):
+            target.center.reset()            # likewise the zero centre
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -472,6 +472,42 @@ def main():
                    if 'moco_over_supcon_fwd' in row else ''), flush=True)
             res.append(row)
             del q, t, queue, mws
+    if 'dino' in what:
+        # DINO (csrc/dino.hip): the two statistics sweeps, the teacher expectation sweep and the finalize (forward), the query-side and
+        # the key-side sweep (backward), beside moco fwd / bwd at the same (2n, K, D) in the same run.  Matrix FLOPs: forward S_t + S_s +
+        # S_t again + Pt ws = 8 (2n) K D against moco's 2; backward (S_s + Ps ws) + (S_s + S_t + (Ps - Pt)^T q) = 4 + 6 = 10 against 4.
+        for (two_n, K, D) in [(1024, 8192, 128), (1024, 65536, 128), (1024, 65536, 256)]:
+            q = torch.nn.functional.normalize(torch.randn(two_n, D, device=dev), dim=1)
+            k = torch.nn.functional.normalize(q.roll(two_n // 2, 0) + 0.5 * torch.randn(two_n, D, device=dev), dim=1)
+            wsn = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            wtn = torch.nn.functional.normalize(wsn + 0.1 * torch.randn(K, D, device=dev), dim=1)
+            cen = 0.05 * torch.randn(K, device=dev)
+            dws = ops.dino_workspace(two_n, K, D, dev)
+            _, drs, du, _ = ops.dino_fwd(q, k, wsn, wtn, cen, 0.1, 0.04, workspace=dws)
+            mws = ops.moco_workspace(two_n, K, D, dev)
+            _, mrs, _ = ops.moco_fwd(q, k, wsn, 0.2, ws=mws)
+            unit = 2.0 * two_n * K * D
+            row = dict(layer='dino 2n%d K%d D%d' % (two_n, K, D), fwd_flops=4 * unit, bwd_q_flops=2 * unit, bwd_w_flops=3 * unit,
+                       key_splits=ops.dino_key_splits(two_n, K), row_splits=ops.dino_row_splits(two_n, K),
+                       dino_fwd_us=timeit(lambda: ops.dino_fwd(q, k, wsn, wtn, cen, 0.1, 0.04, workspace=dws), args.iters),
+                       dino_bwd_q_us=timeit(lambda: ops.dino_bwd_q(q, wsn, du, 0.1, drs, 1.0, dws), args.iters),
+                       dino_bwd_w_us=timeit(lambda: ops.dino_bwd_w(q, k, wsn, wtn, cen, 0.1, 0.04, drs, 1.0, dws), args.iters),
+                       moco_fwd_us=timeit(lambda: ops.moco_fwd(q, k, wsn, 0.2, ws=mws), args.iters),
+                       moco_bwd_us=timeit(lambda: ops.moco_bwd(q, k, wsn, 0.2, mrs, 1.0, mws), args.iters))
+            row['dino_bwd_us'] = row['dino_bwd_q_us'] + row['dino_bwd_w_us']
+            row['dino_fwd_tfs'] = 4 * unit / row['dino_fwd_us'] / 1e6
+            row['dino_bwd_tfs'] = 5 * unit / row['dino_bwd_us'] / 1e6
+            row['moco_fwd_tfs'] = unit / row['moco_fwd_us'] / 1e6
+            row['moco_bwd_tfs'] = 2 * unit / row['moco_bwd_us'] / 1e6
+            row['dino_over_moco_fwd'] = row['dino_fwd_us'] / row['moco_fwd_us']       # expected from the matrix work: about 4
+            row['dino_over_moco_bwd'] = row['dino_bwd_us'] / row['moco_bwd_us']       # expected: about 2.5
+            print('dino 2n=%d K=%d D=%d: fwd %.0f us (%.1f TF/s) bwd_q %.0f us bwd_w %.0f us (bwd %.1f TF/s) | moco fwd %.0f us '
+                  '(%.1f TF/s) bwd %.0f us (%.1f TF/s) | dino / moco fwd %.2f bwd %.2f' % (
+                      two_n, K, D, row['dino_fwd_us'], row['dino_fwd_tfs'], row['dino_bwd_q_us'], row['dino_bwd_w_us'], row['dino_bwd_tfs'],
+                      row['moco_fwd_us'], row['moco_fwd_tfs'], row['moco_bwd_us'], row['moco_bwd_tfs'], row['dino_over_moco_fwd'],
+                      row['dino_over_moco_bwd']), flush=True)
+            res.append(row)
+            del q, k, wsn, wtn, cen, dws, mws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
