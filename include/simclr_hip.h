@@ -653,6 +653,44 @@ int simclr_dino_key_mean(const float* k, int rows, int D, double scale, double* 
  * K < 2, a momentum outside [0, 1] or NaN. */
 int simclr_dino_center(const float* wt, const double* kbar, float* center, int K, int D, float momentum, simclr_stream_t stream);
 
+/* ---- SwAV (csrc/swav.hip): Caron et al. 2020, Unsupervised Learning of Visual Features by Contrasting Cluster Assignments ----
+ * q [two_n, D] = the l2-normalised online projections, [view-a rows; view-b rows]; w [K, D] = the row-normalised prototypes; z_all
+ * [rows_all, D] = the gathered global batch, view-major (rows < rows_all / 2 are view a); alpha [2, K] = the per-view column potentials
+ * in nats; all fp32, the matrices 16-byte aligned, D in {64, 128, 256}, K in [2, 1048576] (a ragged last tile is fine), row counts even.
+ * simclr_swav_sinkhorn: the Sinkhorn-Knopp assignment of the official distributed_sinkhorn, per view on the global batch, as scaling
+ * potentials.  With L_gj = z_g . w_j / epsilon, beta = 0 at the start, N = rows_all / 2 and it = 1 .. iters:
+ *   alpha[v][j] = -ln K - logsumexp_{g in view v}(L_gj + beta_g);   for it < iters: beta_g = -ln N - logsumexp_j(L_gj + alpha[v(g)][j]).
+ * The code of row g is softmax_j(L_gj + alpha[v(g)][j]); no [rows_all, K] matrix is written.  The column sweep fixes 64 prototypes and
+ * streams 64-row tiles (a tile may straddle the view boundary: every element counts for its own row's view), the row sweep fixes 64
+ * rows and streams prototype tiles; splits are merged in a fixed order and finalized in double; no atomics: two calls are bitwise equal.
+ * iters in [1, 16].  workspace: simclr_swav_workspace_bytes(rows, K, D) bytes serve the Sinkhorn on `rows` rows as well as the three
+ * loss calls on `rows` rows (0 for a refused shape).  simclr_swav_key_splits / simclr_swav_row_splits: key splits of the query-side
+ * statistics sweeps / row splits of the key-side sweeps (the Sinkhorn's column sweep and simclr_swav_bwd_w) at that shape.
+ * simclr_swav_fwd: with p(r) = (r + two_n / 2) mod two_n, v(r) = the view of row r, s_rj = q_r . w_j / temperature,
+ * t_rj = q_r . w_j / epsilon + alpha[v(r)][j], Ps / Pt their row softmaxes (Pt is the code):
+ *   l_r = logsumexp_j(s_r) - sum_j Pt[p(r), j] s_rj,   out[0] = (1 / two_n) sum_r l_r,   out[1] = (1 / two_n) sum_r H(Pt[r]) in nats,
+ *   u [two_n, D] = sum_j Pt[r, j] w_j (kept for simclr_swav_bwd_q),  row_stats [two_n, 2] = {logsumexp of s_r, of t_r}, base 2.
+ * One statistics sweep pushes both statistics from one dot product; then the code expectation sweep, the row finalize in double and a
+ * one-workgroup reduce.  The non-maximum mass stays apart (log1p) and the entropy is formed from two non-negative terms.
+ * Refused (1 returned, nothing launched): null / misaligned pointers, another D, a row count < 2 or odd, K outside [2, 1048576], a
+ * temperature or epsilon <= 0 or NaN, iters outside [1, 16]. */
+size_t simclr_swav_workspace_bytes(int rows, int K, int D);
+int simclr_swav_key_splits(int rows, int K);
+int simclr_swav_row_splits(int rows, int K);
+int simclr_swav_sinkhorn(const float* z_all, const float* w, int rows_all, int K, int D, float epsilon, int iters, float* alpha,
+                         void* workspace, simclr_stream_t stream);
+int simclr_swav_fwd(const float* q, const float* w, const float* alpha, int two_n, int K, int D, float temperature, float epsilon,
+                    float* out, float* row_stats, float* u, void* workspace, simclr_stream_t stream);
+/* dq [two_n, D] = grad_scale * d out[0] / dq = (grad_scale / (two_n T)) (sum_j Ps[r, j] w_j - u_p(r)) from the row_stats and u of
+ * simclr_swav_fwd on the same arguments.  The codes are stop-gradient: alpha gets none. */
+int simclr_swav_bwd_q(const float* q, const float* w, const float* u, int two_n, int K, int D, float temperature,
+                      const float* row_stats, float grad_scale, float* dq, void* workspace, simclr_stream_t stream);
+/* dw [K, D] = grad_scale * d out[0] / dw = (grad_scale / (two_n T)) sum_r (Ps[r, j] - Pt[p(r), j]) q_r: the key-side sweep.  A
+ * workgroup owns 64 prototypes and streams 64-row tiles of q and of the paired rows q_p(r); alpha is read for the view of the PAIRED
+ * row.  Row splits are merged in a fixed order. */
+int simclr_swav_bwd_w(const float* q, const float* w, const float* alpha, int two_n, int K, int D, float temperature, float epsilon,
+                      const float* row_stats, float grad_scale, float* dw, void* workspace, simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

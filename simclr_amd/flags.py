@@ -108,7 +108,10 @@ _DEFS = [
                                         "or 'mocov2' (add_moco_loss: MoCo v2, InfoNCE against a queue of momentum keys; loss width 64, 128 or 256; always "
                                         'l2-normalised, --hidden_norm is ignored, --temperature is honoured: 0.2 is the usual choice) '
                                         "or 'dino' (add_dino_loss: DINO self-distillation onto --dino_out_dim prototypes, a momentum target network and "
-                                        'a centre; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and --temperature are ignored).  '
+                                        'a centre; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and --temperature are ignored) '
+                                        "or 'swav' (add_swav_loss: SwAV, swapped prediction of Sinkhorn-Knopp codes on --swav_num_prototypes "
+                                        'prototypes; no target network; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and '
+                                        '--temperature are ignored).  '
                                         'Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
@@ -136,6 +139,12 @@ _DEFS = [
     ('dino_center_momentum', 0.9, float, 'MI355X build: decay m of the DINO centre, c <- m c + (1 - m) (batch mean of the teacher logits).  In [0, 1].'),
     ('dino_momentum', 0.996, float, 'MI355X build: base decay of the DINO target network; it follows the cosine schedule of BYOL to 1.  In [0, 1].'),
     ('dino_freeze_last_layer_epochs', 1, int, 'MI355X build: epochs during which the DINO prototypes take no update at all.  >= 0.'),
+    # SwAV (Caron et al. 2020) in place of NT-Xent for pretraining: a trained prototype layer and Sinkhorn-Knopp codes, no target network
+    ('swav_num_prototypes', 3000, int, 'MI355X build: number K of SwAV prototypes: 2 .. 1048576.'),
+    ('swav_epsilon', 0.05, float, 'MI355X build: entropy regularisation of the SwAV Sinkhorn-Knopp assignment (the temperature of the codes).  > 0.'),
+    ('swav_temperature', 0.1, float, 'MI355X build: temperature of the SwAV student softmax.  > 0.'),
+    ('swav_sinkhorn_iterations', 3, int, 'MI355X build: Sinkhorn-Knopp iterations of the SwAV codes: 1 .. 16.'),
+    ('swav_freeze_prototypes_epochs', 1, int, 'MI355X build: epochs during which the SwAV prototypes take no update at all.  >= 0.'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),

@@ -264,6 +264,16 @@ def dino_last_layer_frozen(step, steps_per_epoch):
     return int(step) < int(FLAGS.dino_freeze_last_layer_epochs) * int(steps_per_epoch)
 
 
+def swav_on():
+    """--contrastive_loss=swav in a pretraining run: the model carries a PrototypeHead; no target network, no predictor."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'swav' and FLAGS.train_mode == 'pretrain'
+
+
+def swav_prototypes_frozen(step, steps_per_epoch):
+    """True while the SwAV prototypes take no update: step < --swav_freeze_prototypes_epochs * steps_per_epoch."""
+    return int(step) < int(FLAGS.swav_freeze_prototypes_epochs) * int(steps_per_epoch)
+
+
 class PrototypeHead(Layer):
     """The prototype layer of DINO (Caron et al. 2021): ONE variable [K, D] whose rows, l2-normalised every step, score the
     l2-normalised projection output -- the paper's weight-normalised last layer with norm_last_layer=True (gain fixed at 1).  The
@@ -374,6 +384,9 @@ class Model(Layer):
             self.prediction_head = PredictionHead() if byol_on() else None
             # DINO: constructed (and, by TargetNetwork, built) LAST for the same reason
             self.prototype_head = PrototypeHead(FLAGS.dino_out_dim) if dino_on() else None
+            # SwAV: the same layer under the same name, built last too (at its first call, or by build_variables)
+            if swav_on():
+                self.prototype_head = PrototypeHead(FLAGS.swav_num_prototypes)
         self._flat_grads = None
 
     def __call__(self, inputs, training, blur=True):

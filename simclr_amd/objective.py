@@ -25,6 +25,10 @@ other view and a queue of keys of earlier steps; no collective) on the kernels o
 
 `add_dino_loss` is the DINO loss of Caron et al. 2021 (cross-entropy of the student's softmax over K trained prototypes against the
 centred, sharpened softmax the momentum teacher gives the other view; no collective) on the kernels of csrc/dino.hip.
+
+`add_swav_loss` is the SwAV loss of Caron et al. 2020 (cross-entropy of the student's softmax over K trained prototypes against the
+Sinkhorn-Knopp code of the other view, the codes equipartitioned over the GLOBAL batch per view; one all-gather of the normalised block,
+nothing in the backward) on the kernels of csrc/swav.hip.
 """
 import torch
 
@@ -595,6 +599,60 @@ def add_dino_loss(online, target, prototypes, target_prototypes, center, student
     loss.entropy = out[1:2]
     loss.keys = keys
     loss.target_prototypes = wt
+    return loss
+
+
+def add_swav_loss(online, prototypes, temperature=0.1, epsilon=0.05, sinkhorn_iterations=3, strategy=None, overlap=None,
+                  update_prototypes=True):
+    """SwAV loss (Caron et al. 2020) on the kernels of csrc/swav.hip: with q = l2n(online), w the row-normalised prototypes,
+    p(r) = (r + b) mod 2b, v(r) the view of row r and alpha [2, K] the per-view column potentials of the Sinkhorn-Knopp assignment,
+      s_rj = q_r . w_j / T,   t_rj = q_r . w_j / eps + alpha[v(r)][j],   Ps = softmax_j(s_r),   Pt = softmax_j(t_r)  (the CODE of row r),
+      loss = (1 / 2b) sum_{r < 2b} [logsumexp_j(s_r) - sum_j Pt[p(r), j] s_rj],
+    the paper's mean over the two swapped terms (add_dino_loss's convention, not the (1 / b) sum of add_byol_loss / add_moco_loss).
+    The codes are STOP-GRADIENT: alpha and Pt are constants of the backward.  l2n is tf.math.l2_normalize (epsilon 1e-12); always
+    applied.  No [2b, K] or [2N, K] matrix is written.
+
+    The Sinkhorn is GLOBAL and PER VIEW, as the official distributed_sinkhorn: the normalised block is all-gathered (detached: the
+    backward has no reduce-scatter) and every replica runs the same iteration on the same gathered block in the one fixed order, so alpha
+    is bitwise identical on every rank and no further collective is needed (the Barlow Twins idiom).  With a global batch smaller than K
+    the iteration stays well defined: every prototype still receives N / K of a view's mass, the codes are simply spread over more
+    prototypes than there are rows (the official code uses a feature queue there; not built).
+
+    Args:
+      online: float32 device tensor [2b, D] = the online projection output, [view-a rows; view-b rows]; D in {64, 128, 256}.
+      prototypes: the model.PrototypeHead.  It is called here (its rows are normalised) and its `backward` receives the gradient of the
+        normalised rows: grad_scale * the prototype gradient lands in the variable's gradient slot.
+      temperature, epsilon, sinkhorn_iterations: T, eps and I (1 .. 16).
+      strategy: replica context or None.  A replica's value is the mean over its own rows, the mean over the replicas is the loss,
+        `backward` is called with 1 / R, a rank's prototype gradient is the share of its own rows and the usual gradient synchronisation
+        sums the shares.
+      overlap: optional zero-argument callable, run after the forward launches.
+      update_prototypes: False while the prototypes are frozen: the key-side sweep is skipped and no gradient is written.
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * dloss/donline, [2b, D]), the device scalars
+      .value and .entropy (mean entropy of the codes in nats: log K = uniform, 0 = one-hot) and .alpha [2, K].
+    """
+    online = online.contiguous()
+    w = prototypes()
+    z, inv = ops.l2norm_fwd(online)
+    ops._swav_check('add_swav_loss', z, w)
+    z_all = gather_hidden(z.detach(), strategy)
+    alpha = ops.swav_sinkhorn(z_all, w, epsilon, sinkhorn_iterations)
+    out, row_stats, u, wsp = ops.swav_fwd(z, w, alpha, temperature, epsilon)
+    if overlap is not None:
+        overlap()
+
+    def backward(grad_scale=1.0):
+        dq = ops.l2norm_bwd(z, inv, ops.swav_bwd_q(z, w, u, temperature, row_stats, grad_scale, wsp))
+        if update_prototypes:
+            prototypes.backward(ops.swav_bwd_w(z, w, alpha, temperature, epsilon, row_stats, grad_scale, wsp))
+        else:
+            prototypes.saved = None
+        return dq
+
+    loss = _Loss(out[0:1], backward)
+    loss.entropy = out[1:2]
+    loss.alpha = alpha
     return loss
 
 

@@ -804,6 +804,141 @@ def dino_center(wt, kbar, center, momentum):
     return center
 
 
+# ---------------------------------------------------------------- SwAV: Sinkhorn codes on prototypes (csrc/swav.hip)
+SWAV_DIMS = (64, 128, 256)          # loss widths the SwAV kernels are instantiated for
+SWAV_MAX_PROTOTYPES = 1048576       # largest --swav_num_prototypes
+SWAV_MAX_ITERS = 16                 # largest --swav_sinkhorn_iterations
+
+
+def _swav_check_dim(D):
+    if D not in SWAV_DIMS:
+        raise ValueError('the SwAV loss supports widths %s (got %d)' % ('/'.join(map(str, SWAV_DIMS)), D))
+
+
+def _swav_check_pos(name, value):
+    if not 0.0 < float(value) < float('inf'):            # (NaN fails the comparison)
+        raise ValueError('swav: %s must be > 0 and finite (got %r)' % (name, value))
+
+
+def _swav_check(name, x, w, alpha=None):
+    """x [rows, D] (rows even), w [K, D], alpha [2, K] or None -> (rows, K, D)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 2 or x.shape[0] % 2 or not x.is_contiguous():
+        raise ValueError('%s: need a contiguous float32 block of both views, [2b, D] with b >= 1 (got %s %s)'
+                         % (name, tuple(x.shape), x.dtype))
+    rows, D = x.shape
+    _swav_check_dim(D)
+    if (w.dtype != torch.float32 or w.dim() != 2 or not 2 <= w.shape[0] <= SWAV_MAX_PROTOTYPES or w.shape[1] != D
+            or not w.is_contiguous()):
+        raise ValueError('%s: the prototypes are a contiguous float32 [K, %d] block with K in [2, %d] (got %s %s)'
+                         % (name, D, SWAV_MAX_PROTOTYPES, tuple(w.shape), w.dtype))
+    K = w.shape[0]
+    if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (2, K) or not alpha.is_contiguous()):
+        raise ValueError('%s: alpha is the contiguous float32 [2, %d] block swav_sinkhorn returned (got %s %s)'
+                         % (name, K, tuple(alpha.shape), alpha.dtype))
+    return rows, K, D
+
+
+def swav_key_splits(rows, K):
+    """Number of key splits the query-side statistics sweeps (swav_fwd, the Sinkhorn's row sweep) use for `rows` rows and K prototypes."""
+    splits = lib().swav_key_splits(int(rows), int(K))
+    if splits < 1:
+        raise ValueError('swav: need an even row count >= 2 and K in [2, %d] (got rows = %d, K = %d)' % (SWAV_MAX_PROTOTYPES, rows, K))
+    return splits
+
+
+def swav_row_splits(rows, K):
+    """Number of row splits the key-side sweeps (the Sinkhorn's column sweep, swav_bwd_w) use for `rows` rows and K prototypes."""
+    splits = lib().swav_row_splits(int(rows), int(K))
+    if splits < 1:
+        raise ValueError('swav: need an even row count >= 2 and K in [2, %d] (got rows = %d, K = %d)' % (SWAV_MAX_PROTOTYPES, rows, K))
+    return splits
+
+
+def swav_workspace(rows, K, D, device):
+    """Workspace for swav_sinkhorn on `rows` rows, or for swav_fwd / swav_bwd_q / swav_bwd_w on `rows` rows."""
+    _swav_check_dim(D)
+    nbytes = lib().swav_workspace_bytes(rows, K, D)
+    if nbytes == 0:
+        raise ValueError('swav: need an even row count >= 2 and K in [2, %d] (got rows = %d, K = %d)' % (SWAV_MAX_PROTOTYPES, rows, K))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def _swav_check_ws(ws, rows, K, D):
+    if ws is None or ws.numel() * ws.element_size() < lib().swav_workspace_bytes(rows, K, D):
+        raise ValueError('swav: the workspace is smaller than swav_workspace(%d, %d, %d)' % (rows, K, D))
+
+
+def _swav_check_stats(name, row_stats, two_n):
+    if row_stats.dtype != torch.float32 or tuple(row_stats.shape) != (two_n, 2):
+        raise ValueError('%s: row_stats is the float32 [2b, 2] block swav_fwd returned (got %s %s)'
+                         % (name, tuple(row_stats.shape), row_stats.dtype))
+
+
+def swav_sinkhorn(z_all, w, epsilon=0.05, iters=3, workspace=None):
+    """z_all [2N, D] (the gathered normalised batch, view-major), w [K, D] (row-normalised prototypes) -> alpha [2, K] float32, the
+    per-view column potentials in nats after `iters` Sinkhorn-Knopp iterations: the code of row g is
+    softmax_j(z_g . w_j / epsilon + alpha[view(g)][j])."""
+    rows, K, D = _swav_check('swav_sinkhorn', z_all, w)
+    _swav_check_pos('epsilon', epsilon)
+    if int(iters) != iters or not 1 <= int(iters) <= SWAV_MAX_ITERS:
+        raise ValueError('swav_sinkhorn: the iterations lie in [1, %d] (got %r)' % (SWAV_MAX_ITERS, iters))
+    if workspace is None:
+        workspace = swav_workspace(rows, K, D, z_all.device)
+    _swav_check_ws(workspace, rows, K, D)
+    alpha = torch.empty(2, K, device=z_all.device, dtype=torch.float32)
+    _launch('swav_sinkhorn', (2 * int(iters) - 1) * 2.0 * rows * K * D, 4.0 * (2 * int(iters) - 1) * (rows + K) * D,
+            lambda: lib().swav_sinkhorn(_p(z_all), _p(w), rows, K, D, float(epsilon), int(iters), _p(alpha), _p(workspace), _s()))
+    return alpha
+
+
+def swav_fwd(q, w, alpha, temperature, epsilon, workspace=None):
+    """q [2b, D] (normalised online projections), w [K, D], alpha [2, K] -> (out = [loss, code entropy] device fp32, row_stats [2b, 2],
+    u [2b, D] = Pt . w, the workspace the three calls share)."""
+    two_n, K, D = _swav_check('swav_fwd', q, w, alpha)
+    _swav_check_pos('the temperature', temperature)
+    _swav_check_pos('epsilon', epsilon)
+    if workspace is None:
+        workspace = swav_workspace(two_n, K, D, q.device)
+    _swav_check_ws(workspace, two_n, K, D)
+    out = step_scalars(2, q.device)
+    row_stats = torch.empty(two_n, 2, device=q.device, dtype=torch.float32)
+    u = torch.empty_like(q)
+    _launch('swav_fwd', 6.0 * two_n * K * D, 4.0 * (3 * two_n + 2 * K) * D,
+            lambda: lib().swav_fwd(_p(q), _p(w), _p(alpha), two_n, K, D, float(temperature), float(epsilon), _p(out), _p(row_stats),
+                                   _p(u), _p(workspace), _s()))
+    return out, row_stats, u, workspace
+
+
+def swav_bwd_q(q, w, u, temperature, row_stats, grad_scale, workspace):
+    """dq [2b, D] = grad_scale * dloss / dq from swav_fwd's row_stats, u and workspace on the same arguments."""
+    two_n, K, D = _swav_check('swav_bwd_q', q, w)
+    if u.dtype != torch.float32 or tuple(u.shape) != tuple(q.shape) or not u.is_contiguous():
+        raise ValueError('swav_bwd_q: u is the contiguous float32 %s block swav_fwd returned (got %s %s)'
+                         % (tuple(q.shape), tuple(u.shape), u.dtype))
+    _swav_check_pos('the temperature', temperature)
+    _swav_check_stats('swav_bwd_q', row_stats, two_n)
+    _swav_check_ws(workspace, two_n, K, D)
+    dq = torch.empty_like(q)
+    _launch('swav_bwd_q', 4.0 * two_n * K * D, 4.0 * (3 * two_n + K) * D,
+            lambda: lib().swav_bwd_q(_p(q), _p(w), _p(u), two_n, K, D, float(temperature), _p(row_stats), float(grad_scale), _p(dq),
+                                     _p(workspace), _s()))
+    return dq
+
+
+def swav_bwd_w(q, w, alpha, temperature, epsilon, row_stats, grad_scale, workspace):
+    """dw [K, D] = grad_scale * dloss / dw: the key-side sweep.  It recomputes both logits from the alpha swav_fwd read."""
+    two_n, K, D = _swav_check('swav_bwd_w', q, w, alpha)
+    _swav_check_pos('the temperature', temperature)
+    _swav_check_pos('epsilon', epsilon)
+    _swav_check_stats('swav_bwd_w', row_stats, two_n)
+    _swav_check_ws(workspace, two_n, K, D)
+    dw = torch.empty_like(w)
+    _launch('swav_bwd_w', 6.0 * two_n * K * D, 4.0 * (2 * two_n + 2 * K) * D,
+            lambda: lib().swav_bwd_w(_p(q), _p(w), _p(alpha), two_n, K, D, float(temperature), float(epsilon), _p(row_stats),
+                                     float(grad_scale), _p(dw), _p(workspace), _s()))
+    return dw
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

@@ -52,15 +52,32 @@ byol_loss_on = model_lib.byol_on
 moco_loss_on = model_lib.moco_on
 # --contrastive_loss=dino replaces NT-Xent in the pretraining step by DINO: self-distillation onto trained prototypes.
 dino_loss_on = model_lib.dino_on
+# --contrastive_loss=swav replaces NT-Xent in the pretraining step by SwAV: swapped prediction of Sinkhorn-Knopp codes on prototypes.
+swav_loss_on = model_lib.swav_on
 
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on()
-    tell the others)."""
-    if FLAGS.contrastive_loss not in ('dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
-        raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r)"
-                         % FLAGS.contrastive_loss)
+    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on() /
+    swav_loss_on() tell the others)."""
+    if FLAGS.contrastive_loss not in ('swav', 'dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
+        raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r), "
+                         "or 'swav'" % FLAGS.contrastive_loss)
+    if swav_loss_on() and FLAGS.mode != 'eval':
+        if not 2 <= FLAGS.swav_num_prototypes <= ops.SWAV_MAX_PROTOTYPES:
+            raise ValueError('--swav_num_prototypes must lie in [2, %d] (got %r)' % (ops.SWAV_MAX_PROTOTYPES, FLAGS.swav_num_prototypes))
+        for name in ('swav_epsilon', 'swav_temperature'):
+            if not 0.0 < getattr(FLAGS, name) < float('inf'):          # (NaN fails the comparison)
+                raise ValueError('--%s must be > 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
+        if not 1 <= FLAGS.swav_sinkhorn_iterations <= ops.SWAV_MAX_ITERS:
+            raise ValueError('--swav_sinkhorn_iterations must lie in [1, %d] (got %r)' % (ops.SWAV_MAX_ITERS, FLAGS.swav_sinkhorn_iterations))
+        if FLAGS.swav_freeze_prototypes_epochs < 0:
+            raise ValueError('--swav_freeze_prototypes_epochs must be >= 0 (got %r)' % FLAGS.swav_freeze_prototypes_epochs)
+        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.SWAV_DIMS:
+            raise ValueError('--contrastive_loss=swav needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
+                             'the SwAV kernels are instantiated for those widths only'
+                             % ('/'.join(map(str, ops.SWAV_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        return False
     if dino_loss_on() and FLAGS.mode != 'eval':
         if not 2 <= FLAGS.dino_out_dim <= ops.DINO_MAX_OUT_DIM:
             raise ValueError('--dino_out_dim must lie in [2, %d] (got %r)' % (ops.DINO_MAX_OUT_DIM, FLAGS.dino_out_dim))
@@ -152,6 +169,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/contrast_acc']        # positive against the best queue row; no entropy
     elif FLAGS.train_mode == 'pretrain' and dino_loss_on():
         names += ['train/contrast_loss', 'train/dino_teacher_entropy']   # log K = uniform teacher, 0 = one-hot collapse
+    elif FLAGS.train_mode == 'pretrain' and swav_loss_on():
+        names += ['train/contrast_loss', 'train/swav_code_entropy']      # log K = uniform codes, 0 = one-hot codes
     elif FLAGS.train_mode == 'pretrain':
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
@@ -278,7 +297,7 @@ def all_reduce_stats_async(tensor, strategy):
     return wait
 
 
-def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None):
+def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None, steps_per_epoch=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
     target: model.TargetNetwork (or a stand-in with its __call__ / update), required by --contrastive_loss=byol.  The step is then:
     blur once, target forward (training mode, nothing kept), online forward on the same pixels, predictor, add_byol_loss, the usual
@@ -290,6 +309,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     once, target forward and release, normalise the keys and start the asynchronous all-reduce of their mean, online forward, normalise
     both prototype tables, add_dino_loss, backward (loss kernels, the normalisations, the heads, the encoder), gradient synchronisation,
     optimizer (without the prototypes while they are frozen), target.update(step), THEN wait for the mean and move the centre.
+    --contrastive_loss=swav needs no target (passing one is refused) and steps_per_epoch >= 1, which the freeze of the prototypes counts.
+    The step is the NT-Xent step with add_swav_loss in place of the loss: online forward, normalise the rows and the prototypes, gather
+    the normalised block, the Sinkhorn on it, the loss on the local rows, backward, gradient synchronisation, optimizer (without the
+    prototypes while they are frozen).
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -309,6 +332,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     byol = byol_loss_on() and not generalized
     moco = moco_loss_on() and not generalized
     dino = dino_loss_on() and not generalized
+    swav = swav_loss_on() and not generalized
+    if swav and (steps_per_epoch is None or int(steps_per_epoch) < 1):
+        raise ValueError('--contrastive_loss=swav needs steps_per_epoch >= 1 (the freeze of the prototypes counts epochs): '
+                         'make_single_step(..., steps_per_epoch=n)')
     if byol and target is None:
         raise ValueError('--contrastive_loss=byol needs a target network: make_single_step(..., target=model.TargetNetwork(model, steps))')
     if moco and (target is None or getattr(target, 'queue', None) is None):
@@ -398,6 +425,14 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                     outputs, target_outputs, model.prototype_head, target.prototypes(), target.center.value,
                     student_temp=FLAGS.dino_student_temp, teacher_temp=model_lib.dino_teacher_temp(dino_step, target.steps_per_epoch),
                     strategy=strategy, overlap=supervised_part, keys=dino_keys, update_prototypes=not dino_frozen)
+            elif swav:
+                logits_con = None
+                # derives from optimizer.iterations (before its increment): a restored run continues it
+                swav_frozen = model_lib.swav_prototypes_frozen(int(getattr(optimizer, 'iterations', 0)), steps_per_epoch)
+                con_loss = obj_lib.add_swav_loss(
+                    outputs, model.prototype_head, temperature=FLAGS.swav_temperature, epsilon=FLAGS.swav_epsilon,
+                    sinkhorn_iterations=FLAGS.swav_sinkhorn_iterations, strategy=strategy, overlap=supervised_part,
+                    update_prototypes=not swav_frozen)
             else:
                 con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
                     outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
@@ -439,7 +474,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         if byol or moco or dino:
             # before the increment: a restored run continues the tau schedule / the queue's write position
             step_index = int(getattr(optimizer, 'iterations', 0))
-        if dino and dino_frozen:
+        if (dino and dino_frozen) or (swav and swav_frozen):
             # the frozen prototypes take no update at all -- no gradient, no weight decay, no momentum: the pair is dropped, as
             # apply_gradients drops a variable without a gradient.  Online and target copies stay bitwise what they are.
             frozen_id = id(model.prototype_head.kernel)
@@ -497,6 +532,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         elif con_loss is not None and dino:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/dino_teacher_entropy'] = con_loss.entropy.reshape(-1)[:1]
+        elif con_loss is not None and swav:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/swav_code_entropy'] = con_loss.entropy.reshape(-1)[:1]
         elif con_loss is not None:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
@@ -535,6 +573,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             elif dino:
                 if 'train/dino_teacher_entropy' in at:
                     con_loss.entropy = at['train/dino_teacher_entropy']
+            elif swav:
+                if 'train/swav_code_entropy' in at:
+                    con_loss.entropy = at['train/swav_code_entropy']
             elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
                 logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
         if sup_loss is not None and sup_names[0] in at:
@@ -781,7 +822,9 @@ def main(argv):
         # DINO: the same target network under BYOL's cosine schedule from --dino_momentum, prototypes included, and the teacher's centre
         target = model_lib.TargetNetwork(model, train_steps, center=model_lib.DinoCenter(FLAGS.dino_out_dim),
                                          steps_per_epoch=max(epoch_steps, 1))
-    step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target)
+    # SwAV: no target network; the freeze of the prototypes counts epochs
+    step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target,
+                               steps_per_epoch=max(epoch_steps, 1) if swav_loss_on() else None)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
     if builder is None:
@@ -796,6 +839,8 @@ def main(argv):
         # restore BEFORE step 0 as tf2/run.py:520-521 does: the latest checkpoint of model_dir (weights, BN moving
         # statistics, LARS slots, step) or, failing that, the weights of --checkpoint (slots stay zero, step 0).
         model(torch.zeros(2, FLAGS.image_size, FLAGS.image_size, 3, device=RT.device), training=False)
+        if swav_loss_on() and model.prototype_head.kernel is None:
+            model.prototype_head.build(model_lib.projection_width())    # last: every other initial value is that of an ntxent run
         manager, status = try_restore_from_checkpoint(target.checkpointable() if target is not None else model, optimizer,
                                                       FLAGS.model_dir, FLAGS.checkpoint,
                                                       FLAGS.keep_checkpoint_max, FLAGS.zero_init_logits_layer)

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,swav,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -508,6 +508,62 @@ def main():
                       row['dino_over_moco_bwd']), flush=True)
             res.append(row)
             del q, k, wsn, wtn, cen, dws, mws
+    if 'swav' in what:
+        # SwAV (csrc/swav.hip): the Sinkhorn (I = 3: three column sweeps, two row sweeps), the forward (one statistics sweep for both
+        # scales + the code expectation sweep), the query-side and the key-side sweep, beside dino fwd / bwd at the same (2b, K, D) in the
+        # same run.  Matrix FLOPs in units of 2 (2b) K D: swav fwd 1 + 2 = 3 against dino's 4 (expected ratio 6 / 8), bwd 2 + 3 = 5
+        # against 5 (about equal), Sinkhorn (2 I - 1) on rows_all rows.
+        iters_s = 3
+        for (two_n, K, D) in [(1024, 3000, 128), (1024, 65536, 128), (1024, 65536, 256)]:
+            q = torch.nn.functional.normalize(torch.randn(two_n, D, device=dev), dim=1)
+            k = torch.nn.functional.normalize(q.roll(two_n // 2, 0) + 0.5 * torch.randn(two_n, D, device=dev), dim=1)
+            wsn = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            cen = 0.05 * torch.randn(K, device=dev)
+            sws = ops.swav_workspace(two_n, K, D, dev)
+            alpha = ops.swav_sinkhorn(q, wsn, 0.05, iters_s, workspace=sws)
+            lws = ops.swav_workspace(two_n, K, D, dev)
+            _, srs, su, _ = ops.swav_fwd(q, wsn, alpha, 0.1, 0.05, workspace=lws)
+            dws = ops.dino_workspace(two_n, K, D, dev)
+            _, drs, du, _ = ops.dino_fwd(q, k, wsn, wsn, cen, 0.1, 0.04, workspace=dws)
+            unit = 2.0 * two_n * K * D
+            row = dict(layer='swav 2b%d K%d D%d' % (two_n, K, D), sinkhorn_iterations=iters_s, fwd_flops=3 * unit, bwd_q_flops=2 * unit,
+                       bwd_w_flops=3 * unit, sinkhorn_flops=(2 * iters_s - 1) * unit,
+                       key_splits=ops.swav_key_splits(two_n, K), row_splits=ops.swav_row_splits(two_n, K),
+                       swav_sinkhorn_us=timeit(lambda: ops.swav_sinkhorn(q, wsn, 0.05, iters_s, workspace=sws), args.iters),
+                       swav_fwd_us=timeit(lambda: ops.swav_fwd(q, wsn, alpha, 0.1, 0.05, workspace=lws), args.iters),
+                       swav_bwd_q_us=timeit(lambda: ops.swav_bwd_q(q, wsn, su, 0.1, srs, 1.0, lws), args.iters),
+                       swav_bwd_w_us=timeit(lambda: ops.swav_bwd_w(q, wsn, alpha, 0.1, 0.05, srs, 1.0, lws), args.iters),
+                       dino_fwd_us=timeit(lambda: ops.dino_fwd(q, k, wsn, wsn, cen, 0.1, 0.04, workspace=dws), args.iters),
+                       dino_bwd_q_us=timeit(lambda: ops.dino_bwd_q(q, wsn, du, 0.1, drs, 1.0, dws), args.iters),
+                       dino_bwd_w_us=timeit(lambda: ops.dino_bwd_w(q, k, wsn, wsn, cen, 0.1, 0.04, drs, 1.0, dws), args.iters))
+            row['swav_bwd_us'] = row['swav_bwd_q_us'] + row['swav_bwd_w_us']
+            row['dino_bwd_us'] = row['dino_bwd_q_us'] + row['dino_bwd_w_us']
+            row['swav_sinkhorn_tfs'] = row['sinkhorn_flops'] / row['swav_sinkhorn_us'] / 1e6
+            row['swav_fwd_tfs'] = 3 * unit / row['swav_fwd_us'] / 1e6
+            row['swav_bwd_tfs'] = 5 * unit / row['swav_bwd_us'] / 1e6
+            row['swav_over_dino_fwd'] = row['swav_fwd_us'] / row['dino_fwd_us']       # expected from the matrix work: about 6 / 8
+            row['swav_over_dino_bwd'] = row['swav_bwd_us'] / row['dino_bwd_us']       # expected: about 1
+            print('swav 2b=%d K=%d D=%d: sinkhorn %.0f us (%.1f TF/s) fwd %.0f us (%.1f TF/s) bwd_q %.0f us bwd_w %.0f us (bwd %.1f TF/s) '
+                  '| dino fwd %.0f us bwd %.0f us | swav / dino fwd %.2f bwd %.2f' % (
+                      two_n, K, D, row['swav_sinkhorn_us'], row['swav_sinkhorn_tfs'], row['swav_fwd_us'], row['swav_fwd_tfs'],
+                      row['swav_bwd_q_us'], row['swav_bwd_w_us'], row['swav_bwd_tfs'], row['dino_fwd_us'], row['dino_bwd_us'],
+                      row['swav_over_dino_fwd'], row['swav_over_dino_bwd']), flush=True)
+            res.append(row)
+            del q, k, wsn, cen, sws, lws, dws
+        # the Sinkhorn on a gathered batch: rows_all = 8192 (estimate: (2 I - 1) * 2 * rows_all * K * D = 31 GFLOP at K = 3000, D = 128)
+        for (rows_all, K, D) in [(8192, 3000, 128), (8192, 65536, 128)]:
+            z = torch.nn.functional.normalize(torch.randn(rows_all, D, device=dev), dim=1)
+            wsn = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            sws = ops.swav_workspace(rows_all, K, D, dev)
+            flops = (2 * iters_s - 1) * 2.0 * rows_all * K * D
+            t = timeit(lambda: ops.swav_sinkhorn(z, wsn, 0.05, iters_s, workspace=sws), args.iters)
+            row = dict(layer='swav_sinkhorn rows%d K%d D%d' % (rows_all, K, D), sinkhorn_iterations=iters_s, sinkhorn_flops=flops,
+                       key_splits=ops.swav_key_splits(rows_all, K), row_splits=ops.swav_row_splits(rows_all, K), swav_sinkhorn_us=t,
+                       swav_sinkhorn_tfs=flops / t / 1e6)
+            print('swav sinkhorn rows_all=%d K=%d D=%d I=%d: %.0f us (%.1f TF/s)' % (rows_all, K, D, iters_s, t, row['swav_sinkhorn_tfs']),
+                  flush=True)
+            res.append(row)
+            del z, wsn, sws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
