@@ -691,6 +691,35 @@ int simclr_swav_bwd_q(const float* q, const float* w, const float* u, int two_n,
 int simclr_swav_bwd_w(const float* q, const float* w, const float* alpha, int two_n, int K, int D, float temperature, float epsilon,
                       const float* row_stats, float grad_scale, float* dw, void* workspace, simclr_stream_t stream);
 
+/* ---- SwAV multi-crop (csrc/swav_multicrop.hip): Caron et al. 2020 section 4, the official loss with crops_for_assign = [0, 1] ----
+ * x [L b, D] = the l2-normalised LOCAL rows, view-major (row v b + i = local view v of image i); z [2b, D], u [2b, D], alpha [2, K] and
+ * global_row_stats [2b, 2] = the global rows handed to simclr_swav_fwd, and what it read / returned for them; w [K, D] as there.  All
+ * fp32, the matrices 16-byte aligned, D in {64, 128, 256}, K in [2, 1048576], L in [1, 8], b >= 1 (L b may be odd and ragged).
+ * With s_rj = x_r . w_j / temperature, Ps its row softmax, i = r mod b and c = 1 / (2 (L + 1) b):
+ *   simclr_swav_local_fwd:   out[0] = c sum_r (2 logsumexp_j(s_r) - x_r . (u_i + u_{b+i}) / temperature),
+ *                            row_stats [L b] = logsumexp_j(s_r), base 2.  A statistics sweep, a row finalize in double, a reduce.
+ *   simclr_swav_local_bwd_x: dx [L b, D] = grad_scale (c / temperature) (2 sum_j Ps[r, j] w_j - u_i - u_{b+i}).
+ *   simclr_swav_local_bwd_w: dw [K, D] = grad_scale (c / temperature) (sum_r 2 Ps[r, j] x_r - sum_{g < 2b} Pt[g, j] m_{g mod b}),
+ *                            m_i = sum_v x_{v b + i} (views added in the order 0, 1, ...), Pt[g] = the code of global row g
+ *                            recomputed from z, alpha of the row's own view and the lse_t of global_row_stats: two key-side sweeps
+ *                            (64 prototypes per workgroup), the second streaming z for the logits and m as the multiplier tile.
+ * The codes are stop-gradient and the local rows take no part in the Sinkhorn.  Splits are merged in a fixed order, no atomics: two
+ * calls are bitwise equal.  workspace: simclr_swav_local_workspace_bytes(b, L, K, D) bytes serve the three calls (0 for a refused
+ * shape).  simclr_swav_local_key_splits: key splits of the statistics sweep; _row_splits / _code_row_splits: row splits of the student
+ * / code key-side sweep.  Refused (1 returned, nothing launched): null / misaligned pointers, another D, K outside [2, 1048576], L
+ * outside [1, 8], b < 1, a temperature or epsilon <= 0 or NaN. */
+size_t simclr_swav_local_workspace_bytes(int b, int L, int K, int D);
+int simclr_swav_local_key_splits(int b, int L, int K);
+int simclr_swav_local_row_splits(int b, int L, int K);
+int simclr_swav_local_code_row_splits(int b, int L, int K);
+int simclr_swav_local_fwd(const float* x, const float* w, const float* u, int b, int L, int K, int D, float temperature, float* out,
+                          float* row_stats, void* workspace, simclr_stream_t stream);
+int simclr_swav_local_bwd_x(const float* x, const float* w, const float* u, int b, int L, int K, int D, float temperature,
+                            const float* row_stats, float grad_scale, float* dx, void* workspace, simclr_stream_t stream);
+int simclr_swav_local_bwd_w(const float* x, const float* z, const float* w, const float* alpha, int b, int L, int K, int D,
+                            float temperature, float epsilon, const float* row_stats, const float* global_row_stats, float grad_scale,
+                            float* dw, void* workspace, simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

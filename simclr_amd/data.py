@@ -166,7 +166,7 @@ def _align(x, a=16):
     return (x + a - 1) // a * a
 
 
-HostBatch = collections.namedtuple('HostBatch', 'step indices labels weights table params nbytes')
+HostBatch = collections.namedtuple('HostBatch', 'step indices labels weights table params nbytes local_params', defaults=(None,))
 
 
 class DatasetIterator:
@@ -175,7 +175,7 @@ class DatasetIterator:
 
     def __init__(self, split, num_classes, global_batch, is_training, replica=0, num_replicas=1, device=None,
                  start_step=0, image_size=None, train_mode=None, color_jitter_strength=None, data_seed=None,
-                 input_threads=None, prefetch_batches=None):
+                 input_threads=None, prefetch_batches=None, local_crops=None):
         self.split, self.num_classes = split, num_classes
         self.n = split.index.shape[0]
         self.B, self.R, self.r = int(global_batch), int(num_replicas), int(replica)
@@ -191,6 +191,12 @@ class DatasetIterator:
         self.strength = float(s) if self.pretrain else 0.
         self.test_crop = self.size > 32
         self.views = 2 if self.pretrain else 1
+        # SwAV multi-crop: L local views per image at their own size, area range and generator (pretraining with --contrastive_loss=swav)
+        if local_crops is None:
+            local_crops = FLAGS.swav_local_crops if (self.pretrain and FLAGS.contrastive_loss == 'swav') else 0
+        self.local_crops = int(local_crops) if self.pretrain else 0
+        self.local_size = int(FLAGS.swav_local_crop_size)
+        self.local_scale = (float(FLAGS.swav_local_crop_min_scale), float(FLAGS.swav_local_crop_max_scale))
         self.seed = int(FLAGS.data_seed if data_seed is None else data_seed)
         self.threads = max(1, int(FLAGS.input_threads if input_threads is None else input_threads))
         self.depth = max(1, int(FLAGS.prefetch_batches if prefetch_batches is None else prefetch_batches))
@@ -201,7 +207,9 @@ class DatasetIterator:
         self._o_lab = _align(24 * self.b)
         self._o_w = self._o_lab + _align(8 * self.b)
         self._o_par = self._o_w + _align(4 * self.b)
-        self._o_img = self._o_par + _align(4 * 16 * self.views * self.b)
+        # (the local parameters have a section of their own behind the global ones: empty without local crops)
+        self._o_lpar = self._o_par + _align(4 * 16 * self.views * self.b)
+        self._o_img = self._o_lpar + _align(4 * 16 * self.local_crops * self.b)
         self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix='simclr-input')
         self._slots = [dict(host=None, dev=None, copied=None, consumed=None) for _ in range(self.depth + 1)]
         self._free = collections.deque(range(len(self._slots)))
@@ -224,6 +232,16 @@ class DatasetIterator:
             hw = self.split.index[idx, 1:3]
             params = data_util.eval_params(hw[:, 0], hw[:, 1], self.size, self.size, crop=self.test_crop)
         return idx, w, params
+
+    def local_plan(self, step, idx=None):
+        """The parameters [b, L, 16] of the L local views of batch `step`, from a generator of their own -- a function of (data_seed,
+        step, replica, 1): the global views of a run with local crops are bitwise those of a run without."""
+        if idx is None:
+            idx = train_indices(self.n, self.seed, step, self.B, self.r, self.R)
+        rng = np.random.default_rng([self.seed, int(step), self.r, 1])
+        hw = self.split.index[idx, 1:3]
+        return data_util.draw_local_params(self.b, hw[:, 0], hw[:, 1], self.local_size, self.local_crops, self.local_scale[0],
+                                           self.local_scale[1], self.strength, rng=rng)
 
     def _host_buffer(self, slot, nbytes):
         buf = slot['host']
@@ -250,10 +268,14 @@ class DatasetIterator:
         buf[self._o_lab:self._o_lab + 8 * self.b].view(np.int64)[:] = rows[:, 3]
         buf[self._o_w:self._o_w + 4 * self.b].view(np.float32)[:] = w
         buf[self._o_par:self._o_par + params.size * 4].view(np.float32)[:] = params.reshape(-1)
+        local_params = None
+        if self.local_crops:
+            local_params = self.local_plan(step, idx)
+            buf[self._o_lpar:self._o_lpar + local_params.size * 4].view(np.float32)[:] = local_params.reshape(-1)
         images, dst = self.split.images, buf[self._o_img:]
         for o, src, sz in zip(offs, rows[:, 0], sizes):
             dst[o:o + sz] = images[src:src + sz]
-        return HostBatch(step, idx, rows[:, 3].copy(), w, table, params, nbytes)
+        return HostBatch(step, idx, rows[:, 3].copy(), w, table, params, nbytes, local_params)
 
     def _submit_ahead(self):
         while self._free and self._next_submit < self.step + self.depth + 1 and \
@@ -304,6 +326,11 @@ class DatasetIterator:
         params = d[self._o_par:self._o_par + 64 * self.views * b].view(torch.float32).view(b, self.views, 16)
         packed = d[self._o_img:hb.nbytes]
         features = ops.augment_views_ragged(packed, hb.table, params, self.size, self.size, table_dev=table_dev)
+        if self.local_crops:
+            # one more launch at the local size on the same packed records
+            lparams = d[self._o_lpar:self._o_lpar + 64 * self.local_crops * b].view(torch.float32).view(b, self.local_crops, 16)
+            features = (features, ops.augment_views_ragged(packed, hb.table, lparams, self.local_size, self.local_size,
+                                                           table_dev=table_dev))
         lab = {'labels': torch.nn.functional.one_hot(labels, self.num_classes).float()}
         if not self.is_training:
             lab['mask'] = d[self._o_w:self._o_w + 4 * b].view(torch.float32).clone()

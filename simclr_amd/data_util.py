@@ -96,11 +96,14 @@ def _lrint(x):
     return np.rint(x).astype(np.int64)
 
 
-def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100):
+def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100, area_range=(0.08, 1.0), min_object_covered=0.1):
     """tf.image.sample_distorted_bounding_box as crop_and_resize calls it (tf2/data_util.py:298-320: whole-image box,
     min_object_covered 0.1, aspect ratio in [3/4, 4/3] * out_w/out_h, area in [0.08, 1], 100 attempts, then the whole
     image), vectorised over the images; the per-attempt arithmetic follows TensorFlow's GenerateRandomCrop
-    (float32 areas, lrintf roundings).  heights / widths: int arrays [m].  Returns int64 [m, 4] = (y, x, h, w)."""
+    (float32 areas, lrintf roundings).  heights / widths: int arrays [m].  Returns int64 [m, 4] = (y, x, h, w).
+    area_range / min_object_covered: the sampler's two other arguments (the defaults are the reference's call).  The cover test
+    rejects every box below min_object_covered of the image, so an area range that starts lower is silently truncated unless the
+    cover is lowered with it: the local crops of SwAV's multi-crop pass their minimum scale as the cover."""
     Hh = np.asarray(heights, dtype=np.int64)
     Ww = np.asarray(widths, dtype=np.int64)
     m = Hh.shape[0]
@@ -109,8 +112,8 @@ def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100):
     lo, hi = f32(3. / 4 * ar0), f32(4. / 3. * ar0)
     box = np.stack([np.zeros(m, np.int64), np.zeros(m, np.int64), Hh, Ww], 1)
     todo = np.ones(m, bool)
-    min_area = f32(0.08) * Ww.astype(f32) * Hh.astype(f32)
-    max_area = f32(1.0) * Ww.astype(f32) * Hh.astype(f32)
+    min_area = f32(area_range[0]) * Ww.astype(f32) * Hh.astype(f32)
+    max_area = f32(area_range[1]) * Ww.astype(f32) * Hh.astype(f32)
     for _ in range(max_attempts):
         if not todo.any():
             break
@@ -133,7 +136,7 @@ def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100):
         ok = ~((area < min_area) | (area > max_area) | (w > Ww) | (h > Hh) | (w <= 0) | (h <= 0))
         y = np.floor(rng.random(m) * np.maximum(Hh - h, 1)).astype(np.int64) * (h < Hh)
         x = np.floor(rng.random(m) * np.maximum(Ww - w, 1)).astype(np.int64) * (w < Ww)
-        ok &= (w * h) / (Ww * Hh).astype(np.float64) >= 0.1            # min_object_covered of the whole-image box
+        ok &= (w * h) / (Ww * Hh).astype(np.float64) >= min_object_covered    # of the whole-image box
         take = todo & ok
         box[take] = np.stack([y, x, h, w], 1)[take]
         todo &= ~ok
@@ -141,15 +144,17 @@ def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100):
 
 
 def draw_train_params(b, heights, widths, height, width, color_jitter_strength=1.0, crop=True, flip=True, views=2,
-                      rng=None):
+                      rng=None, area_range=(0.08, 1.0), min_object_covered=0.1):
     """Random draws of preprocess_for_train (tf2/data_util.py:443-475) for `views` views of each of `b` images.
-    heights / widths: per-image source sizes (int or arrays).  Returns float32 [b, views, 16] laid out as PARAM_FIELDS."""
+    heights / widths: per-image source sizes (int or arrays).  Returns float32 [b, views, 16] laid out as PARAM_FIELDS.
+    area_range / min_object_covered: sample_crop_boxes's; draw_local_params sets them for SwAV's local views."""
     rng = _rng() if rng is None else rng
     m = b * views
     Hh = np.repeat(np.broadcast_to(np.asarray(heights, np.int64), (b,)), views)
     Ww = np.repeat(np.broadcast_to(np.asarray(widths, np.int64), (b,)), views)
     p = np.zeros((m, len(PARAM_FIELDS)), np.float32)
-    p[:, 0:4] = sample_crop_boxes(rng, Hh, Ww, height, width) if crop else np.stack([0 * Hh, 0 * Ww, Hh, Ww], 1)
+    p[:, 0:4] = (sample_crop_boxes(rng, Hh, Ww, height, width, area_range=area_range, min_object_covered=min_object_covered)
+                 if crop else np.stack([0 * Hh, 0 * Ww, Hh, Ww], 1))
     if flip:
         p[:, 4] = rng.random(m) < 0.5                                              # :463
     s = float(color_jitter_strength)
@@ -163,6 +168,15 @@ def draw_train_params(b, heights, widths, height, width, color_jitter_strength=1
         p[:, 13] = rng.uniform(-hh, hh, m)
         p[:, 14] = rng.random(m) < 0.2
     return p.reshape(b, views, len(PARAM_FIELDS))
+
+
+def draw_local_params(b, heights, widths, size, views, min_scale, max_scale, color_jitter_strength=1.0, rng=None):
+    """draw_train_params for the `views` LOCAL views of SwAV's multi-crop (Caron et al. 2020, section 4): square crops of `size`
+    pixels whose area is a [min_scale, max_scale] share of the image, the same flip and colour jitter as the global views.  The
+    cover is the minimum scale: left at the sampler's 0.1, a [0.05, 0.14] range would silently become [0.1, 0.14].
+    Returns float32 [b, views, 16]."""
+    return draw_train_params(b, heights, widths, size, size, color_jitter_strength, views=views, rng=rng,
+                             area_range=(float(min_scale), float(max_scale)), min_object_covered=float(min_scale))
 
 
 def _sizes(images, sizes):

@@ -145,6 +145,11 @@ _DEFS = [
     ('swav_temperature', 0.1, float, 'MI355X build: temperature of the SwAV student softmax.  > 0.'),
     ('swav_sinkhorn_iterations', 3, int, 'MI355X build: Sinkhorn-Knopp iterations of the SwAV codes: 1 .. 16.'),
     ('swav_freeze_prototypes_epochs', 1, int, 'MI355X build: epochs during which the SwAV prototypes take no update at all.  >= 0.'),
+    # SwAV multi-crop (Caron et al. 2020, section 4): L low-resolution views through a second encoder pass, against both global codes
+    ('swav_local_crops', 0, int, 'MI355X build: number L of local (low-resolution) views of SwAV multi-crop: 0 (off) .. 8.'),
+    ('swav_local_crop_size', 96, int, 'MI355X build: side of the local views in pixels: at most image_size, a multiple of the stem stride.'),
+    ('swav_local_crop_min_scale', 0.05, float, 'MI355X build: smallest area share of a local crop; also its min_object_covered.'),
+    ('swav_local_crop_max_scale', 0.14, float, 'MI355X build: largest area share of a local crop: 0 < min < max <= 1.'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),

@@ -389,10 +389,11 @@ class Model(Layer):
                 self.prototype_head = PrototypeHead(FLAGS.swav_num_prototypes)
         self._flat_grads = None
 
-    def __call__(self, inputs, training, blur=True):
+    def __call__(self, inputs, training, blur=True, supervised=True):
         """inputs: float32 [b, H, W, 3k] in [0,1].  Returns (projection_head_outputs float32
         [k*b, proj_out_dim], supervised_head_outputs SupLogits) like tf2/model.py:241-280.
-        blur=False: the caller drew the random blur already (the BYOL step hands the online and the target network the same pixels)."""
+        blur=False: the caller drew the random blur already (the BYOL step hands the online and the target network the same pixels).
+        supervised=False (pretraining): the linear-eval head does not run (the second, local-view pass of SwAV multi-crop)."""
         if training and FLAGS.train_mode == 'pretrain':
             if FLAGS.fine_tune_after_block > -1:
                 raise ValueError('Does not support layer freezing during pretraining,'
@@ -425,7 +426,7 @@ class Model(Layer):
         self._proj_dtype = proj.dtype
         proj32 = ops.cast(proj, torch.float32) if proj.dtype != torch.float32 else proj
         sup_out = None
-        if FLAGS.train_mode == 'pretrain' and FLAGS.lineareval_while_pretraining:
+        if FLAGS.train_mode == 'pretrain' and FLAGS.lineareval_while_pretraining and supervised:
             sup_out = self.supervised_head(sup_in, training)                       # stop_gradient, :276-278
         return proj32, sup_out
 

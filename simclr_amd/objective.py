@@ -28,7 +28,8 @@ centred, sharpened softmax the momentum teacher gives the other view; no collect
 
 `add_swav_loss` is the SwAV loss of Caron et al. 2020 (cross-entropy of the student's softmax over K trained prototypes against the
 Sinkhorn-Knopp code of the other view, the codes equipartitioned over the GLOBAL batch per view; one all-gather of the normalised block,
-nothing in the backward) on the kernels of csrc/swav.hip.
+nothing in the backward) on the kernels of csrc/swav.hip.  `add_swav_local_loss` is its multi-crop share: the local views of the same
+images against the codes of both global views (csrc/swav_multicrop.hip; no collective).
 """
 import torch
 
@@ -653,7 +654,52 @@ def add_swav_loss(online, prototypes, temperature=0.1, epsilon=0.05, sinkhorn_it
     loss = _Loss(out[0:1], backward)
     loss.entropy = out[1:2]
     loss.alpha = alpha
+    # what add_swav_local_loss reads for the local views of the same images
+    loss.z, loss.u, loss.row_stats, loss.epsilon = z, u, row_stats, epsilon
     return loss
+
+
+def add_swav_local_loss(local_online, global_loss, prototypes, temperature=0.1, strategy=None, update_prototypes=True):
+    """The multi-crop share of the SwAV loss (Caron et al. 2020, section 4; the official loss with crops_for_assign = [0, 1]) on the
+    kernels of csrc/swav_multicrop.hip: every LOCAL view's softmax over the prototypes against the codes of BOTH global views of its
+    image.  With x = l2n(local_online) [L b, D] view-major (row v b + i = local view v of image i), V = 2 + L and u_g = sum_j Pt[g, j] w_j
+    the code expectation add_swav_loss kept for global row g,
+      value = 1 / (2 (V - 1) b) sum_r [2 logsumexp_j(s_r) - x_r . (u_i + u_{b+i}) / T],   s_rj = x_r . w_j / T,  i = r mod b.
+    The total loss of the step is global_loss.value / (V - 1) + value.  The codes are the global views' alone and stop-gradient: the
+    local rows take no part in the Sinkhorn, so nothing is gathered here and no collective runs.
+
+    Args:
+      local_online: float32 device tensor [L b, D] = the online projection output of the L local views, view-major.
+      global_loss: the handle add_swav_loss returned for the two global views of the same b images (its z, u, row_stats, alpha, epsilon).
+      prototypes: the model.PrototypeHead.  It is called here again (the variable has not moved since add_swav_loss: the normalised
+        rows are bitwise the same) and its `backward` receives the gradient of the normalised rows, student and code term together.
+      temperature: T, the one add_swav_loss was given.
+      strategy: replica context or None; unused beyond the signature's symmetry: a replica's value is the share of its own rows.
+      update_prototypes: False while the prototypes are frozen: both key-side sweeps are skipped and no gradient is written.
+    Returns:
+      A loss scalar with .value and .backward(grad_scale) (-> grad_scale * dvalue/dlocal_online, [L b, D]).
+    """
+    x_raw = local_online.contiguous()
+    zg, u = global_loss.z, global_loss.u
+    b = zg.shape[0] // 2
+    if x_raw.dim() != 2 or x_raw.shape[0] < b or x_raw.shape[0] % b:
+        raise ValueError('add_swav_local_loss: the local block holds L views of the %d images of the global loss, [L * %d, D] (got %s)'
+                         % (b, b, tuple(x_raw.shape)))
+    L = x_raw.shape[0] // b
+    w = prototypes()
+    x, inv = ops.l2norm_fwd(x_raw)
+    out, row_stats, wsp = ops.swav_local_fwd(x, w, u, L, temperature)
+
+    def backward(grad_scale=1.0):
+        dx = ops.l2norm_bwd(x, inv, ops.swav_local_bwd_x(x, w, u, L, temperature, row_stats, grad_scale, wsp))
+        if update_prototypes:
+            prototypes.backward(ops.swav_local_bwd_w(x, zg, w, global_loss.alpha, L, temperature, global_loss.epsilon, row_stats,
+                                                     global_loss.row_stats, grad_scale, wsp))
+        else:
+            prototypes.saved = None
+        return dx
+
+    return _Loss(out[0:1], backward)
 
 
 def add_supervised_loss(labels, logits):

@@ -939,6 +939,120 @@ def swav_bwd_w(q, w, alpha, temperature, epsilon, row_stats, grad_scale, workspa
     return dw
 
 
+# ---------------------------------------------------------------- SwAV multi-crop: local rows against both global codes (csrc/swav_multicrop.hip)
+SWAV_MAX_LOCAL_CROPS = 8            # largest --swav_local_crops
+
+
+def _swav_local_check(name, x, w, u, L):
+    """x [L b, D] (view-major local rows), w [K, D], u [2b, D] (swav_fwd's, of the globals) -> (b, L, K, D)."""
+    if int(L) != L or not 1 <= int(L) <= SWAV_MAX_LOCAL_CROPS:
+        raise ValueError('%s: the number of local views lies in [1, %d] (got %r)' % (name, SWAV_MAX_LOCAL_CROPS, L))
+    L = int(L)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < L or x.shape[0] % L or not x.is_contiguous():
+        raise ValueError('%s: need a contiguous float32 block of the %d local views, [%d b, D] with b >= 1 (got %s %s)'
+                         % (name, L, L, tuple(x.shape), x.dtype))
+    b, D = x.shape[0] // L, x.shape[1]
+    _swav_check_dim(D)
+    if (w.dtype != torch.float32 or w.dim() != 2 or not 2 <= w.shape[0] <= SWAV_MAX_PROTOTYPES or w.shape[1] != D
+            or not w.is_contiguous()):
+        raise ValueError('%s: the prototypes are a contiguous float32 [K, %d] block with K in [2, %d] (got %s %s)'
+                         % (name, D, SWAV_MAX_PROTOTYPES, tuple(w.shape), w.dtype))
+    if u.dtype != torch.float32 or tuple(u.shape) != (2 * b, D) or not u.is_contiguous():
+        raise ValueError('%s: the global block is the contiguous float32 %s block of swav_fwd on the same images (got %s %s)'
+                         % (name, (2 * b, D), tuple(u.shape), u.dtype))
+    return b, L, w.shape[0], D
+
+
+def _swav_local_shape_error(b, L, K):
+    return ValueError('swav_local: need b >= 1, L in [1, %d] and K in [2, %d] (got b = %d, L = %d, K = %d)'
+                      % (SWAV_MAX_LOCAL_CROPS, SWAV_MAX_PROTOTYPES, b, L, K))
+
+
+def swav_local_key_splits(b, L, K):
+    """Number of key splits of swav_local_fwd's statistics sweep for L views of b images and K prototypes."""
+    splits = lib().swav_local_key_splits(int(b), int(L), int(K))
+    if splits < 1:
+        raise _swav_local_shape_error(b, L, K)
+    return splits
+
+
+def swav_local_row_splits(b, L, K):
+    """(row splits of swav_local_bwd_w's student sweep over the L b local rows, of its code sweep over the 2b global rows)."""
+    splits = lib().swav_local_row_splits(int(b), int(L), int(K)), lib().swav_local_code_row_splits(int(b), int(L), int(K))
+    if min(splits) < 1:
+        raise _swav_local_shape_error(b, L, K)
+    return splits
+
+
+def swav_local_workspace(b, L, K, D, device):
+    """Workspace for swav_local_fwd / swav_local_bwd_x / swav_local_bwd_w on L views of b images."""
+    _swav_check_dim(D)
+    nbytes = lib().swav_local_workspace_bytes(int(b), int(L), int(K), D)
+    if nbytes == 0:
+        raise _swav_local_shape_error(b, L, K)
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def _swav_local_check_ws(ws, b, L, K, D):
+    if ws is None or ws.numel() * ws.element_size() < lib().swav_local_workspace_bytes(b, L, K, D):
+        raise ValueError('swav_local: the workspace is smaller than swav_local_workspace(%d, %d, %d, %d)' % (b, L, K, D))
+
+
+def _swav_local_check_stats(name, row_stats, rows):
+    if row_stats.dtype != torch.float32 or tuple(row_stats.shape) != (rows,) or not row_stats.is_contiguous():
+        raise ValueError('%s: row_stats is the float32 [L b] block swav_local_fwd returned (got %s %s)'
+                         % (name, tuple(row_stats.shape), row_stats.dtype))
+
+
+def swav_local_fwd(x, w, u, L, temperature, workspace=None):
+    """x [L b, D] (normalised local rows, view-major), w [K, D], u [2b, D] (swav_fwd's code expectations of the two global views of the
+    same images) -> (out = [the local share of the loss, divided by 2 (L + 1) b] device fp32, row_stats [L b], the workspace the three
+    calls share)."""
+    b, L, K, D = _swav_local_check('swav_local_fwd', x, w, u, L)
+    _swav_check_pos('the temperature', temperature)
+    if workspace is None:
+        workspace = swav_local_workspace(b, L, K, D, x.device)
+    _swav_local_check_ws(workspace, b, L, K, D)
+    out = step_scalars(1, x.device)
+    row_stats = torch.empty(L * b, device=x.device, dtype=torch.float32)
+    _launch('swav_local_fwd', 2.0 * L * b * K * D, 4.0 * (2 * L * b + 2 * b + K) * D,
+            lambda: lib().swav_local_fwd(_p(x), _p(w), _p(u), b, L, K, D, float(temperature), _p(out), _p(row_stats), _p(workspace),
+                                         _s()))
+    return out, row_stats, workspace
+
+
+def swav_local_bwd_x(x, w, u, L, temperature, row_stats, grad_scale, workspace):
+    """dx [L b, D] = grad_scale * d out / dx from swav_local_fwd's row_stats and workspace on the same arguments."""
+    b, L, K, D = _swav_local_check('swav_local_bwd_x', x, w, u, L)
+    _swav_check_pos('the temperature', temperature)
+    _swav_local_check_stats('swav_local_bwd_x', row_stats, L * b)
+    _swav_local_check_ws(workspace, b, L, K, D)
+    dx = torch.empty_like(x)
+    _launch('swav_local_bwd_x', 4.0 * L * b * K * D, 4.0 * (2 * L * b + 2 * b + K) * D,
+            lambda: lib().swav_local_bwd_x(_p(x), _p(w), _p(u), b, L, K, D, float(temperature), _p(row_stats), float(grad_scale),
+                                           _p(dx), _p(workspace), _s()))
+    return dx
+
+
+def swav_local_bwd_w(x, z, w, alpha, L, temperature, epsilon, row_stats, global_row_stats, grad_scale, workspace):
+    """dw [K, D] = grad_scale * d out / dw: the student term over the local rows and the code term over the global rows z [2b, D], whose
+    codes are recomputed from alpha [2, K] and the lse_t of swav_fwd's row_stats [2b, 2]."""
+    b, L, K, D = _swav_local_check('swav_local_bwd_w', x, w, z, L)
+    _swav_check('swav_local_bwd_w', z, w, alpha)
+    _swav_check_pos('the temperature', temperature)
+    _swav_check_pos('epsilon', epsilon)
+    _swav_local_check_stats('swav_local_bwd_w', row_stats, L * b)
+    _swav_check_stats('swav_local_bwd_w', global_row_stats, 2 * b)
+    if not global_row_stats.is_contiguous():
+        raise ValueError('swav_local_bwd_w: the row_stats of swav_fwd must be contiguous')
+    _swav_local_check_ws(workspace, b, L, K, D)
+    dw = torch.empty_like(w)
+    _launch('swav_local_bwd_w', 4.0 * (L * b + 2 * b) * K * D, 4.0 * (L * b + 5 * b + 2 * K) * D,
+            lambda: lib().swav_local_bwd_w(_p(x), _p(z), _p(w), _p(alpha), b, L, K, D, float(temperature), float(epsilon),
+                                           _p(row_stats), _p(global_row_stats), float(grad_scale), _p(dw), _p(workspace), _s()))
+    return dw
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

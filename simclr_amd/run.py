@@ -56,10 +56,43 @@ dino_loss_on = model_lib.dino_on
 swav_loss_on = model_lib.swav_on
 
 
+def swav_local_crops():
+    """L of SwAV multi-crop in a pretraining run (0: off); train_mode=finetune and --mode=eval ignore the flags."""
+    if FLAGS.train_mode != 'pretrain' or FLAGS.mode == 'eval':
+        return 0
+    return int(getattr(FLAGS, 'swav_local_crops', 0))
+
+
+def check_swav_local_flags():
+    """Raise before any device work when the multi-crop flags name something the step does not cover.  Returns L."""
+    L = swav_local_crops()
+    if not 0 <= L <= ops.SWAV_MAX_LOCAL_CROPS:
+        raise ValueError('--swav_local_crops must lie in [0, %d] (got %r)' % (ops.SWAV_MAX_LOCAL_CROPS, FLAGS.swav_local_crops))
+    if L == 0:
+        return 0
+    if FLAGS.contrastive_loss != 'swav':
+        raise ValueError('--swav_local_crops belongs to --contrastive_loss=swav (got %r): multi-crop is built for SwAV only'
+                         % FLAGS.contrastive_loss)
+    size = FLAGS.swav_local_crop_size
+    stride = 1 if FLAGS.image_size <= 32 else 2           # the stem's: resnet.Resnet.stem_kernel_stride
+    if not 1 <= size <= FLAGS.image_size or size % stride:
+        raise ValueError('--swav_local_crop_size must lie in [1, image_size = %d] and be a multiple of the stem stride %d (got %r)'
+                         % (FLAGS.image_size, stride, size))
+    lo, hi = FLAGS.swav_local_crop_min_scale, FLAGS.swav_local_crop_max_scale
+    if not 0.0 < lo < hi <= 1.0:                          # (NaN fails the comparison)
+        raise ValueError('the local crop scales need 0 < --swav_local_crop_min_scale < --swav_local_crop_max_scale <= 1 (got %r, %r)'
+                         % (lo, hi))
+    if any(p is not None for p in (check_dropblock_flags()[0] or [])):
+        raise ValueError('--swav_local_crops with an active DropBlock is refused: the noise of a site is a function of (seed, step, '
+                         'replica, site) and would repeat in the second encoder pass')
+    return L
+
+
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
     Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on() /
     swav_loss_on() tell the others)."""
+    check_swav_local_flags()
     if FLAGS.contrastive_loss not in ('swav', 'dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
         raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r), "
                          "or 'swav'" % FLAGS.contrastive_loss)
@@ -313,6 +346,12 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     The step is the NT-Xent step with add_swav_loss in place of the loss: online forward, normalise the rows and the prototypes, gather
     the normalised block, the Sinkhorn on it, the loss on the local rows, backward, gradient synchronisation, optimizer (without the
     prototypes while they are frozen).
+    --swav_local_crops=L > 0 (multi-crop): features = (globals [b, H, W, 6], locals [b, h, h, 3L]).  The layers keep the activations of
+    ONE pending forward, so the step has two passes: pass A is the swav step on the global views up to model.backward with
+    grad_scale 1 / (R (V - 1)), V = 2 + L (the supervised head trains here only); the flat gradient buffer is saved and zeroed; pass B
+    blurs the local views at their own size, forwards them in training mode (BatchNorm on statistics of its own), add_swav_local_loss
+    against pass A's codes, backward without the supervised head; the saved buffer is added back, the gradients are all-reduced ONCE
+    (after the add: the sum is linear, one reduction is cheaper than two), then one optimizer step.
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -348,8 +387,15 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
+    local_crops = swav_local_crops() if swav else 0
 
     def single_step(features, labels):
+        local_features = None
+        if local_crops:
+            features, local_features = features
+            if local_features.dim() != 4 or local_features.shape[3] != 3 * local_crops or local_features.shape[0] != features.shape[0]:
+                raise ValueError('--swav_local_crops=%d: the step reads (globals [b, H, W, 6], locals [b, h, h, %d]) (got locals %s)'
+                                 % (local_crops, 3 * local_crops, tuple(local_features.shape)))
         ops.begin_step(features.device)
         if dropblock:
             # the noise of a DropBlock site is a function of (dropblock_seed, global step, replica, site): the restored step continues it
@@ -457,8 +503,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         model._wd_grad_scale = 1.0 / R
         # NT-Xent backward launches the reduce-scatter of the key-side gradient (transpose of collective A); the
         # supervised head's backward (independent: stop_gradient, tf2/model.py:276-277) runs while it is in flight
+        # multi-crop: the global views carry 1 / (V - 1) of the loss, and the one gradient all-reduce comes after pass B
+        share = 1.0 / (1 + local_crops)
+        on_stage = sync.on_stage if not local_crops else None
         if con_loss is not None:
-            con_loss.backward_start(1.0 / R)
+            con_loss.backward_start(share / R)
         d_sup = sup_loss.backward() if sup_loss is not None else None
         if FLAGS.train_mode == 'finetune':
             # no stop_gradient: supervised head -> projection head below ft_proj_selector -> trainable encoder layers
@@ -468,8 +517,32 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             d_proj = con_loss.backward_finish() if con_loss is not None else None
             if byol:
                 d_proj = model.backward_predictor(d_proj)
-            model.backward(d_proj, None, on_stage=sync.on_stage)
+            model.backward(d_proj, None, on_stage=on_stage)
         join_wgrad_stream()
+        if local_crops:
+            # ---- pass B: the local views through the encoder a second time, against the codes of pass A ----
+            # Every weight-gradient launch OVERWRITES its slot (the flat buffer is never cleared between steps), so pass A's gradients
+            # are set aside; the buffer is zeroed because pass B writes no supervised-head (and no frozen-prototype) slot
+            saved_grads = model._flat_grads.clone()
+            model._flat_grads.zero_()
+            if FLAGS.use_blur:
+                # Model.__call__ blurs at FLAGS.image_size: the local views are blurred here, at their own size
+                local_features = data_util.batch_random_blur_tensor(local_features, local_features.shape[1], local_features.shape[2])
+            local_outputs, _ = model(local_features, training=True, blur=False, supervised=False)
+            global_loss = con_loss
+            local_loss = obj_lib.add_swav_local_loss(local_outputs, global_loss, model.prototype_head,
+                                                     temperature=FLAGS.swav_temperature, strategy=strategy,
+                                                     update_prototypes=not swav_frozen)
+            model.backward(local_loss.backward(1.0 / R), None, on_stage=None)
+            join_wgrad_stream()
+            ops.axpy_f32(1.0, saved_grads, model._flat_grads)
+            # train/contrast_loss is the total: global / (V - 1) + local
+            total_con = torch.empty(1, device=features.device, dtype=torch.float32)
+            ops.accumulate_scalars([global_loss.value.reshape(-1)[:1], local_loss.value.reshape(-1)[:1]], scales=[share, 1.0],
+                                   total=total_con, total_mask=3)
+            con_loss = obj_lib._Loss(total_con, None)
+            con_loss.entropy, con_loss.alpha = global_loss.entropy, global_loss.alpha
+            con_loss.global_loss, con_loss.local_loss = global_loss, local_loss
         sync.wait()
         if byol or moco or dino:
             # before the increment: a restored run continues the tau schedule / the queue's write position
@@ -591,13 +664,18 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     return single_step
 
 
-def synthetic_batches(batch, image_size, num_classes, device, seed=0, pool=2, views=2):
+def synthetic_batches(batch, image_size, num_classes, device, seed=0, pool=2, views=2, local_crops=0, local_size=None):
     """i.i.d. U[0,1) two-view batches [b, H, W, 6] + one-hot labels; views=1: the single-view
-    [b, H, W, 3] batches of train_mode=finetune (tf2/data.py:52-58)."""
+    [b, H, W, 3] batches of train_mode=finetune (tf2/data.py:52-58).  local_crops = L > 0 (SwAV multi-crop): features =
+    (globals [b, H, W, 6], locals [b, h, h, 3L]); the local tensors are drawn AFTER every global tensor and label from the same
+    seeded generator, so the globals and labels are those of a run without local crops."""
     g = torch.Generator(device='cpu').manual_seed(seed)
     feats = [torch.rand(batch, image_size, image_size, 3 * views, generator=g).to(device) for _ in range(pool)]
     labs = [torch.nn.functional.one_hot(torch.randint(0, num_classes, (batch,), generator=g), num_classes)
             .float().to(device) for _ in range(pool)]
+    if local_crops:
+        locs = [torch.rand(batch, local_size, local_size, 3 * local_crops, generator=g).to(device) for _ in range(pool)]
+        feats = list(zip(feats, locs))
     i = 0
     while True:
         yield feats[i % pool], {'labels': labs[i % pool]}
@@ -829,7 +907,8 @@ def main(argv):
     data = None
     if builder is None:
         data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep,
-                                 views=1 if FLAGS.train_mode == 'finetune' else 2)
+                                 views=1 if FLAGS.train_mode == 'finetune' else 2,
+                                 local_crops=swav_local_crops() if swav_loss_on() else 0, local_size=FLAGS.swav_local_crop_size)
     manager = None
     summary_writer = metrics.JsonlSummaryWriter(FLAGS.model_dir) if (FLAGS.model_dir and rank0) else None   # :526
     log_every = FLAGS.checkpoint_steps or 10

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,swav,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,swav,swav_multicrop,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -564,6 +564,42 @@ def main():
                   flush=True)
             res.append(row)
             del z, wsn, sws
+    if 'swav_multicrop' in what:
+        # SwAV multi-crop (csrc/swav_multicrop.hip): the three local-view calls at L views of b images, beside swav fwd / bwd on the 2b
+        # global rows of the same images in the same run.  Matrix FLOPs: local_fwd 2 (L b) K D (one statistics sweep) against swav_fwd's
+        # 6 (2b) K D (expected time ratio L / 6 at equal rates), local_bwd_x 4 (L b) K D, local_bwd_w 4 (L b + 2b) K D.
+        for (b, L, K, D) in [(512, 6, 3000, 128), (512, 6, 65536, 128)]:
+            q = torch.nn.functional.normalize(torch.randn(2 * b, D, device=dev), dim=1)
+            x = torch.nn.functional.normalize(q[:b].repeat(L, 1) + 0.7 * torch.randn(L * b, D, device=dev) / D ** 0.5, dim=1)
+            wsn = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            sws = ops.swav_workspace(2 * b, K, D, dev)
+            alpha = ops.swav_sinkhorn(q, wsn, 0.05, 3, workspace=sws)
+            lws = ops.swav_workspace(2 * b, K, D, dev)
+            _, srs, su, _ = ops.swav_fwd(q, wsn, alpha, 0.1, 0.05, workspace=lws)
+            mws = ops.swav_local_workspace(b, L, K, D, dev)
+            _, mrs, _ = ops.swav_local_fwd(x, wsn, su, L, 0.1, workspace=mws)
+            unit = 2.0 * K * D
+            row = dict(layer='swav_multicrop b%d L%d K%d D%d' % (b, L, K, D), local_fwd_flops=unit * L * b, swav_fwd_flops=3 * unit * 2 * b,
+                       local_bwd_x_flops=2 * unit * L * b, local_bwd_w_flops=2 * unit * (L * b + 2 * b),
+                       key_splits=ops.swav_local_key_splits(b, L, K), row_splits=list(ops.swav_local_row_splits(b, L, K)),
+                       local_fwd_us=timeit(lambda: ops.swav_local_fwd(x, wsn, su, L, 0.1, workspace=mws), args.iters),
+                       local_bwd_x_us=timeit(lambda: ops.swav_local_bwd_x(x, wsn, su, L, 0.1, mrs, 1.0, mws), args.iters),
+                       local_bwd_w_us=timeit(lambda: ops.swav_local_bwd_w(x, q, wsn, alpha, L, 0.1, 0.05, mrs, srs, 1.0, mws), args.iters),
+                       swav_fwd_us=timeit(lambda: ops.swav_fwd(q, wsn, alpha, 0.1, 0.05, workspace=lws), args.iters),
+                       swav_bwd_q_us=timeit(lambda: ops.swav_bwd_q(q, wsn, su, 0.1, srs, 1.0, lws), args.iters),
+                       swav_bwd_w_us=timeit(lambda: ops.swav_bwd_w(q, wsn, alpha, 0.1, 0.05, srs, 1.0, lws), args.iters))
+            row['local_fwd_tfs'] = row['local_fwd_flops'] / row['local_fwd_us'] / 1e6
+            row['local_bwd_x_tfs'] = row['local_bwd_x_flops'] / row['local_bwd_x_us'] / 1e6
+            row['local_bwd_w_tfs'] = row['local_bwd_w_flops'] / row['local_bwd_w_us'] / 1e6
+            row['local_over_swav_fwd'] = row['local_fwd_us'] / row['swav_fwd_us']
+            row['local_over_swav_fwd_expected'] = row['local_fwd_flops'] / row['swav_fwd_flops']          # L / 6
+            print('swav_multicrop b=%d L=%d K=%d D=%d: local fwd %.0f us (%.1f TF/s) bwd_x %.0f us (%.1f TF/s) bwd_w %.0f us (%.1f TF/s) | '
+                  'swav fwd %.0f us bwd_q %.0f us bwd_w %.0f us | local / swav fwd %.2f (matrix work: %.2f)' % (
+                      b, L, K, D, row['local_fwd_us'], row['local_fwd_tfs'], row['local_bwd_x_us'], row['local_bwd_x_tfs'],
+                      row['local_bwd_w_us'], row['local_bwd_w_tfs'], row['swav_fwd_us'], row['swav_bwd_q_us'], row['swav_bwd_w_us'],
+                      row['local_over_swav_fwd'], row['local_over_swav_fwd_expected']), flush=True)
+            res.append(row)
+            del q, x, wsn, sws, lws, mws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
