@@ -191,6 +191,48 @@ int simclr_bt_bwd(const float* zhat_all, int n, int N, int D, int rank, float la
 int simclr_bt_apply(const float* g_local, const float* zhat_all, const float* rstd, const double* colsums, int n, int N, int D, int rank,
                     float* dh, simclr_stream_t stream);
 
+/* ---- VICReg loss (Bardes, Ponce, LeCun 2022, VICReg: Variance-Invariance-Covariance Regularization for Self-Supervised Learning),
+ * csrc/vicreg.hip ----
+ * The Gram form: per view v of the gathered block, xc = h - colmean(h) over the GLOBAL batch, var_i = sum_a xc_ai^2 / (N - 1)
+ * (unbiased), std_i = sqrt(var_i + eps), Cov = xc^T xc / (N - 1) ([D, D], never formed), G = xc xc^T ([N, N]),
+ *   inv  = (1 / (N D)) sum_{a, i} (h1_ai - h2_ai)^2,
+ *   var  = (1 / 2) sum_v (1 / D) sum_i max(0, gamma - std_vi),
+ *   cov  = sum_v (1 / D) sum_{i != j} Cov_v,ij^2 = sum_v (1 / D) ((1 / (N-1)^2) sum_{a, b} G_v,ab^2 - sum_i var_vi^2),
+ *   L    = sim_coeff * inv + std_coeff * var + cov_coeff * cov.
+ * Layout as simclr_bt_fwd: h_all / xc_all [2N, D] = every replica's view-1 rows, then every replica's view-2 rows, N = R*n; this
+ * replica's rows are rank*n .. rank*n + n - 1 of each view.  D a multiple of 64 in [64, 8192], n >= 1, N >= 2.  Exact fp32-input MFMA,
+ * one view per workgroup; where both views' tiles give fewer than 256 workgroups the k range (D) is split into S parts at multiples
+ * of 32 whose partial tiles a merge launch adds in the fixed order ((p0 + p1) + p2) + ... in fp32.  Column statistics, loss sums and the
+ * subtraction in double in a fixed order, no atomics: bitwise run-to-run deterministic, and everything computed from the gathered block
+ * alone is identical on every replica.  The workspace holds one fwd/bwd pair. */
+size_t simclr_vicreg_workspace_bytes(int n, int N, int D);      /* 0 for a shape the kernels refuse */
+/* Where simclr_vicreg_fwd keeps the (merged) Gram blocks of the local rows in the workspace: fp32 [2, rows, pitch] from that byte
+ * offset, block v row a column b = xc_v[rank*n + a] . xc_v[b]; rows >= n and pitch >= N are padded to the tile with zeros.  0 for a
+ * refused shape. */
+size_t simclr_vicreg_gram_offset_bytes(int n, int N, int D);
+size_t simclr_vicreg_gram_rows(int n, int N, int D);
+size_t simclr_vicreg_gram_pitch(int n, int N, int D);
+/* S, the number of k parts of the Gram launch (1: no split, no merge launch), and the workgroups of that launch = 2 views x tiles x S.
+ * 0 for a refused shape. */
+int simclr_vicreg_k_splits(int n, int N, int D);
+int simclr_vicreg_fwd_workgroups(int n, int N, int D);
+/* xc = fl32(h - mu) per view and column over the N rows (mean in double); stats [2 views, 2, D] doubles = {var, std}: var from the
+ * squares of the ROUNDED xc it stores, summed in double, / (N - 1); std = sqrt(var + eps).  N < 2 is refused. */
+int simclr_vicreg_center(const float* h_all, int N, int D, float eps, float* xc_all, double* stats, simclr_stream_t stream);
+/* out[0] = this replica's loss value sim_coeff * inv + std_coeff * var + cov_coeff * cov, out[1] = inv over its own rows (1 / (n D)),
+ * out[2] = var (global), out[3] = cov with R / (N-1)^2 * sum_{a local, b} G_ab^2 in place of the full sum, reported as computed (never
+ * clamped at zero).  The mean over the replicas is L. */
+int simclr_vicreg_fwd(const float* h_all, const float* xc_all, const double* stats, int n, int N, int D, int rank, float sim_coeff,
+                      float std_coeff, float cov_coeff, float gamma, float* out, void* workspace, simclr_stream_t stream);
+/* dh_local [2n, D] = grad_scale * R * dL/dh of the local rows of both views, one launch from the Gram blocks simclr_vicreg_fwd left in
+ * the workspace.  With x, o the raw rows of this view and of the other one:
+ *   dL/dh_a = cov_coeff * (4 / ((N-1)^2 D) * sum_b G_ab xc_b - 4 / ((N-1) D) * var o xc_a)
+ *           - std_coeff * (1 / (2 D)) * [std < gamma] o xc_a / ((N-1) std) + sim_coeff * (2 / (N D)) * (x_a - o_a).
+ * The centring has no backward (the column sums of the xc-gradient vanish) and no collective follows. */
+int simclr_vicreg_bwd(const float* h_all, const float* xc_all, const double* stats, int n, int N, int D, int rank, float sim_coeff,
+                      float std_coeff, float cov_coeff, float gamma, float grad_scale, void* workspace, float* dh_local,
+                      simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

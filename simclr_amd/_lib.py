@@ -93,7 +93,8 @@ class _Lib:
                           'simclr_prep_chunk_elems', 'simclr_get_f32_matmul', 'simclr_conv2d_last_split_parts', 'simclr_conv2d_last_presplit',
                           'simclr_stem_wgrad_ps_supported', 'simclr_knn_slab_rows', 'simclr_moco_key_splits',
                           'simclr_dino_key_splits', 'simclr_dino_row_splits', 'simclr_swav_key_splits', 'simclr_swav_row_splits',
-                          'simclr_swav_local_key_splits', 'simclr_swav_local_row_splits', 'simclr_swav_local_code_row_splits'}
+                          'simclr_swav_local_key_splits', 'simclr_swav_local_row_splits', 'simclr_swav_local_code_row_splits',
+                          'simclr_vicreg_k_splits', 'simclr_vicreg_fwd_workgroups'}
 
     def last_error(self):
         return self._dll.simclr_last_error().decode()

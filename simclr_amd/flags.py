@@ -111,7 +111,9 @@ _DEFS = [
                                         'a centre; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and --temperature are ignored) '
                                         "or 'swav' (add_swav_loss: SwAV, swapped prediction of Sinkhorn-Knopp codes on --swav_num_prototypes "
                                         'prototypes; no target network; loss width 64, 128 or 256; always l2-normalised, --hidden_norm and '
-                                        '--temperature are ignored).  '
+                                        '--temperature are ignored) '
+                                        "or 'vicreg' (add_vicreg_loss: VICReg, invariance + variance hinge + covariance, no negatives; loss "
+                                        'width as for barlow, the official expander is 8192 wide; --hidden_norm and --temperature are ignored).  '
                                         'Ignored by --train_mode=finetune.'),
     ('gcl_dist', 'logsumexp', str, "MI355X build: distribution-matching term of the generalized loss: 'logsumexp' (decoupled NT-Xent), 'normal' or "
                                    "'uniform' (sliced Wasserstein distance to that prior; global batch <= 4096)."),
@@ -121,6 +123,10 @@ _DEFS = [
     # Barlow Twins (Zbontar et al. 2021) in place of NT-Xent for pretraining
     ('bt_lambda', 0.0051, float, 'MI355X build: weight of the off-diagonal (redundancy-reduction) term of the Barlow Twins loss (lambda_weight).'),
     ('bt_loss_scaling', 1.0, float, 'MI355X build: factor on the whole Barlow Twins loss (loss_scaling).'),
+    # VICReg (Bardes, Ponce, LeCun 2022) in place of NT-Xent for pretraining
+    ('vicreg_sim_coeff', 25.0, float, 'MI355X build: weight of the invariance term of the VICReg loss (sim_coeff).  >= 0.'),
+    ('vicreg_std_coeff', 25.0, float, 'MI355X build: weight of the variance (hinge on the standard deviation) term of the VICReg loss (std_coeff).  >= 0.'),
+    ('vicreg_cov_coeff', 1.0, float, 'MI355X build: weight of the covariance term of the VICReg loss (cov_coeff).  >= 0.'),
     # BYOL (Grill et al. 2020) in place of NT-Xent for pretraining: a momentum target network and a predictor on the online side
     ('byol_tau_base', 0.996, float, 'MI355X build: base decay of the target network\'s moving average; step k of K uses '
                                     'tau_k = 1 - (1 - byol_tau_base) * (cos(pi k / K) + 1) / 2.  In [0, 1].'),

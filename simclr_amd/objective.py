@@ -17,6 +17,9 @@ positive) on the kernels of csrc/supcon.hip.
 `add_barlow_twins_loss` is the Barlow Twins loss of Zbontar et al. 2021 (redundancy reduction on the cross-correlation of the two views'
 batch-standardised hiddens; no negatives) in its Gram form on the kernels of csrc/barlow.hip.
 
+`add_vicreg_loss` is the VICReg loss of Bardes, Ponce, LeCun 2022 (invariance + a hinge on every dimension's standard deviation + the
+squared off-diagonal covariance, per view over the global batch; no negatives) in its Gram form on the split-k kernels of csrc/vicreg.hip.
+
 `add_byol_loss` is the BYOL loss of Grill et al. 2020 (squared distance of the l2-normalised online prediction of one view to the
 l2-normalised projection a momentum target network gives the other view; no negatives, no collective) on the kernels of csrc/byol.hip.
 
@@ -469,6 +472,68 @@ def add_barlow_twins_loss(hidden, lambda_weight=0.0051, loss_scaling=1.0, eps=1e
     N = n * R
     v1 = zhat_all[rank * n:(rank + 1) * n]
     loss.normalized = zhat_all if R == 1 else torch.cat([v1, zhat_all[N + rank * n:N + (rank + 1) * n]], 0)
+    return loss
+
+
+def add_vicreg_loss(hidden, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, eps=1e-4, gamma=1.0, strategy=None, overlap=None):
+    """VICReg loss (Bardes, Ponce, LeCun 2022) on the Gram-form kernels of csrc/vicreg.hip:
+      loss = sim_coeff * inv + std_coeff * var + cov_coeff * cov,
+      inv = mean (h1 - h2)^2,  var = (1/2) sum_v mean_i max(0, gamma - sqrt(Var_i(h_v) + eps)),  cov = sum_v (1/D) sum_{i != j} Cov(h_v)_ij^2,
+    variance (unbiased) and covariance over the GLOBAL batch.  No negatives, no temperature and no l2 normalisation.  Cov [D, D] is
+    never formed: sum_ij Cov_ij^2 = sum_ab (xc_a.xc_b)^2 / (N-1)^2 on the centred rows xc, and a replica sums its own rows a of that
+    against all columns b.
+
+    Args:
+      hidden: float32 device tensor [2n, D] = [view-a rows; view-b rows], D a multiple of 64 in [64, 8192]; the global batch N >= 2.
+      sim_coeff, std_coeff, cov_coeff: weights of the invariance, variance and covariance terms (finite, >= 0).
+      eps: added to the variance under the root.  gamma: target of the standard deviation.
+      strategy, overlap: as add_contrastive_loss (the raw hidden block is gathered asynchronously; overlap() runs meanwhile).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> grad_scale * R * dL/dhidden of the local rows, [2n, D]: with
+      grad_scale = 1 / R and the summed gradient synchronisation a run optimises L itself; backward_start launches, backward_finish
+      returns, and there is no collective between them), the device scalars .invariance, .variance and .covariance (the raw terms,
+      before the coefficients) and .centered (xc of the local rows).  The value is this replica's share -- inv over its own rows, the
+      global var, cov with R / (N-1)^2 * sum_{a local, b} G_ab^2 in place of the full sum: the mean over the replicas is the loss, as
+      for add_contrastive_loss.
+    """
+    assert hidden.dtype == torch.float32 and hidden.dim() == 2
+    hidden = hidden.contiguous()
+    n, D = hidden.shape[0] // 2, hidden.shape[1]
+    ops._vicreg_check_dim(D)
+    if n < 1 or hidden.shape[0] != 2 * n:
+        raise ValueError('add_vicreg_loss: hidden holds both views, [2n, D] with n >= 1 (got %d rows)' % hidden.shape[0])
+    if not all(ops.vicreg_coeff_ok(c) for c in (sim_coeff, std_coeff, cov_coeff)):
+        raise ValueError('add_vicreg_loss: sim_coeff, std_coeff and cov_coeff must be finite and >= 0 (got %r, %r, %r)'
+                         % (sim_coeff, std_coeff, cov_coeff))
+    if not float(eps) >= 0.0:
+        raise ValueError('add_vicreg_loss: eps must be >= 0 (got %r)' % (eps,))
+    R, rank = num_replicas(strategy), replica_id(strategy)
+    if n * R < 2:
+        raise ValueError('add_vicreg_loss: the unbiased variance needs a global batch of at least 2 (got %d)' % (n * R))
+    pending = gather_hidden(hidden, strategy, async_op=True)
+    if overlap is not None:
+        overlap()
+    h_all = pending()
+    # every replica centres the whole gathered block in one fixed order: xc_all and the statistics are bitwise the same everywhere
+    xc_all, stats = ops.vicreg_center(h_all, eps)
+    out, ws = ops.vicreg_fwd(h_all, xc_all, stats, n, rank, sim_coeff, std_coeff, cov_coeff, gamma)
+    state = {}
+
+    def backward_start(grad_scale=1.0):
+        state['dh'] = ops.vicreg_bwd(h_all, xc_all, stats, n, rank, sim_coeff, std_coeff, cov_coeff, gamma, grad_scale, ws)
+
+    def backward_finish():
+        return state.pop('dh')
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.invariance, loss.variance, loss.covariance = out[1:2], out[2:3], out[3:4]
+    N = n * R
+    v1 = xc_all[rank * n:(rank + 1) * n]
+    loss.centered = xc_all if R == 1 else torch.cat([v1, xc_all[N + rank * n:N + (rank + 1) * n]], 0)
     return loss
 
 

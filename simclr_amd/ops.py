@@ -487,6 +487,104 @@ def bt_apply(g_local, zhat_all, rstd, colsums, rank):
     return dh
 
 
+# ---------------------------------------------------------------- VICReg loss (csrc/vicreg.hip)
+VICREG_DIM_STEP, VICREG_MIN_DIM, VICREG_MAX_DIM = 64, 64, 8192   # hidden widths the VICReg kernels take: multiples of 64 in [64, 8192]
+VICREG_EPS, VICREG_GAMMA = 1e-4, 1.0
+
+
+def vicreg_dim_ok(D):
+    return VICREG_MIN_DIM <= D <= VICREG_MAX_DIM and D % VICREG_DIM_STEP == 0
+
+
+def _vicreg_check_dim(D):
+    if not vicreg_dim_ok(D):
+        raise ValueError('the VICReg loss supports hidden widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (VICREG_DIM_STEP, VICREG_MIN_DIM, VICREG_MAX_DIM, D))
+
+
+def vicreg_coeff_ok(c):
+    """A coefficient of the VICReg loss: finite and >= 0 (NaN fails the comparison)."""
+    return 0.0 <= float(c) < float('inf')
+
+
+def _vicreg_check(h_all, xc_all, stats, n, rank, coeffs):
+    if h_all.dtype != torch.float32 or h_all.dim() != 2:
+        raise ValueError('vicreg: need a float32 [2N, D] block (got %s %s)' % (tuple(h_all.shape), h_all.dtype))
+    D = h_all.shape[1]
+    _vicreg_check_dim(D)
+    N = h_all.shape[0] // 2
+    n, rank = int(n), int(rank)
+    if n < 1 or N < 2 or N < n or N % n != 0 or h_all.shape[0] != 2 * N:
+        raise ValueError('vicreg: need h_all [2N, D] with N = R*n, n >= 1 and N >= 2 (got %d rows for n = %d)' % (h_all.shape[0], n))
+    if not 0 <= rank < N // n:
+        raise ValueError('vicreg: rank %d is not one of the R = %d replicas' % (rank, N // n))
+    if xc_all.dtype != torch.float32 or xc_all.shape != h_all.shape or stats.dtype != torch.float64 or tuple(stats.shape) != (2, 2, D):
+        raise ValueError('vicreg: need xc_all like h_all and float64 stats [2, 2, D] (got %s %s, %s %s)'
+                         % (tuple(xc_all.shape), xc_all.dtype, tuple(stats.shape), stats.dtype))
+    if not all(vicreg_coeff_ok(c) for c in coeffs):
+        raise ValueError('vicreg: sim_coeff, std_coeff and cov_coeff must be finite and >= 0 (got %r)' % (tuple(coeffs),))
+    return n, N, D, rank
+
+
+def vicreg_workspace(n, N, D, device):
+    _vicreg_check_dim(D)
+    nbytes = lib().vicreg_workspace_bytes(n, N, D)
+    if nbytes == 0:
+        raise ValueError('vicreg: need N = R*n with n >= 1 and N >= 2 (got n = %d, N = %d)' % (n, N))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def vicreg_k_splits(n, N, D):
+    """S, the number of k parts of vicreg_fwd's Gram launch at this shape (0 for a refused shape)."""
+    return int(lib().vicreg_k_splits(int(n), int(N), int(D)))
+
+
+def vicreg_center(h_all, eps=VICREG_EPS):
+    """h_all [2N, D] = [view-1 rows; view-2 rows] of the global batch -> (xc_all [2N, D], stats [2, 2, D] float64 = {var, std} per view):
+    every column of each view centred over its N rows; var is the unbiased variance of the stored xc, std = sqrt(var + eps)."""
+    if h_all.dtype != torch.float32 or h_all.dim() != 2 or h_all.shape[0] < 4 or h_all.shape[0] % 2:
+        raise ValueError('vicreg_center: need a float32 [2N, D] block with N >= 2 (got %s %s)' % (tuple(h_all.shape), h_all.dtype))
+    N, D = h_all.shape[0] // 2, h_all.shape[1]
+    _vicreg_check_dim(D)
+    if not float(eps) >= 0.0:
+        raise ValueError('vicreg_center: eps must be >= 0 (got %r)' % (eps,))
+    xc = torch.empty_like(h_all)
+    stats = torch.empty(2, 2, D, device=h_all.device, dtype=torch.float64)
+    _launch('vicreg_center', 8.0 * N * D, 16.0 * N * D,
+            lambda: lib().vicreg_center(_p(h_all), N, D, float(eps), _p(xc), _p(stats), _s()), impl_bytes=24.0 * N * D)
+    return xc, stats
+
+
+def vicreg_fwd(h_all, xc_all, stats, n, rank, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, gamma=VICREG_GAMMA, ws=None):
+    """VICReg forward on the centred global block.  Returns out = [loss, inv, var, cov] (device; the per-replica values of
+    include/simclr_hip.h) and the workspace, which keeps the Gram blocks for vicreg_bwd."""
+    n, N, D, rank = _vicreg_check(h_all, xc_all, stats, n, rank, (sim_coeff, std_coeff, cov_coeff))
+    if ws is None:
+        ws = vicreg_workspace(n, N, D, h_all.device)
+    out = step_scalars(4, h_all.device)
+    _launch('vicreg_fwd', 4.0 * n * N * D, 4.0 * (2 * N * D + 2 * n * N + 2 * n * D),
+            lambda: lib().vicreg_fwd(_p(h_all), _p(xc_all), _p(stats), n, N, D, rank, float(sim_coeff), float(std_coeff), float(cov_coeff),
+                                     float(gamma), _p(out), _p(ws), _s()))
+    return out, ws
+
+
+def vicreg_gram_blocks(ws, n, N, D):
+    """The [2, n, N] fp32 view of the Gram blocks vicreg_fwd left in `ws`: block v, row a, column b = xc_v[rank*n + a] . xc_v[b]."""
+    off, rows, pitch = lib().vicreg_gram_offset_bytes(n, N, D), lib().vicreg_gram_rows(n, N, D), lib().vicreg_gram_pitch(n, N, D)
+    assert rows > 0 and off % 8 == 0, 'vicreg_gram_blocks: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return ws[off // 8:].view(torch.float32)[:2 * rows * pitch].view(2, rows, pitch)[:, :n, :N]
+
+
+def vicreg_bwd(h_all, xc_all, stats, n, rank, sim_coeff, std_coeff, cov_coeff, gamma, grad_scale, ws):
+    """Returns dh_local [2n, D] = grad_scale * R * dL/dh of the local rows of both views: one launch, nothing to reduce."""
+    n, N, D, rank = _vicreg_check(h_all, xc_all, stats, n, rank, (sim_coeff, std_coeff, cov_coeff))
+    dh = torch.empty(2 * n, D, device=h_all.device, dtype=torch.float32)
+    _launch('vicreg_bwd', 4.0 * n * N * D, 4.0 * (2 * N * D + 2 * n * N + 6 * n * D),
+            lambda: lib().vicreg_bwd(_p(h_all), _p(xc_all), _p(stats), n, N, D, rank, float(sim_coeff), float(std_coeff), float(cov_coeff),
+                                     float(gamma), float(grad_scale), _p(ws), _p(dh), _s()))
+    return dh
+
+
 # ---------------------------------------------------------------- BYOL (csrc/byol.hip)
 BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
 

@@ -45,6 +45,11 @@ def barlow_loss_width():
     return model_lib.projection_width()
 
 
+def vicreg_loss_on():
+    """--contrastive_loss=vicreg replaces NT-Xent in the pretraining step by the VICReg loss; train_mode=finetune ignores it."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'vicreg' and FLAGS.train_mode == 'pretrain'
+
+
 # --contrastive_loss=byol replaces NT-Xent in the pretraining step by BYOL on a momentum target network; train_mode=finetune ignores it.
 # One definition: the model reads the same switch to decide whether it carries a predictor.
 byol_loss_on = model_lib.byol_on
@@ -91,11 +96,11 @@ def check_swav_local_flags():
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
     Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on() /
-    swav_loss_on() tell the others)."""
+    swav_loss_on() / vicreg_loss_on() tell the others)."""
     check_swav_local_flags()
-    if FLAGS.contrastive_loss not in ('swav', 'dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2'):
+    if FLAGS.contrastive_loss not in ('swav', 'dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2', 'vicreg'):
         raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r), "
-                         "or 'swav'" % FLAGS.contrastive_loss)
+                         "or 'swav' or 'vicreg'" % FLAGS.contrastive_loss)
     if swav_loss_on() and FLAGS.mode != 'eval':
         if not 2 <= FLAGS.swav_num_prototypes <= ops.SWAV_MAX_PROTOTYPES:
             raise ValueError('--swav_num_prototypes must lie in [2, %d] (got %r)' % (ops.SWAV_MAX_PROTOTYPES, FLAGS.swav_num_prototypes))
@@ -155,6 +160,19 @@ def check_contrastive_loss_flags():
                              'proj_head_mode=%r, proj_out_dim=%d): the BYOL kernels and the predictor take those widths only'
                              % (ops.BYOL_DIM_STEP, ops.BYOL_MIN_DIM, ops.BYOL_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
         return False
+    if vicreg_loss_on() and FLAGS.mode != 'eval':
+        for name in ('vicreg_sim_coeff', 'vicreg_std_coeff', 'vicreg_cov_coeff'):
+            if not ops.vicreg_coeff_ok(getattr(FLAGS, name)):          # (NaN fails the comparison)
+                raise ValueError('--%s must be >= 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
+        width = barlow_loss_width()
+        if not ops.vicreg_dim_ok(width):
+            raise ValueError('--contrastive_loss=vicreg needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
+                             'proj_head_mode=%r, proj_out_dim=%d): the VICReg kernels take those widths only'
+                             % (ops.VICREG_DIM_STEP, ops.VICREG_MIN_DIM, ops.VICREG_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        if FLAGS.train_batch_size < 2:
+            raise ValueError('--contrastive_loss=vicreg needs --train_batch_size >= 2 (got %r): the variance over the global batch is '
+                             'the unbiased one' % (FLAGS.train_batch_size,))
+        return False
     if barlow_loss_on() and FLAGS.mode != 'eval':
         if FLAGS.bt_lambda < 0:
             raise ValueError('--bt_lambda must be >= 0 (got %r)' % (FLAGS.bt_lambda,))
@@ -196,6 +214,8 @@ def build_metrics():
         names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_positives']
     elif FLAGS.train_mode == 'pretrain' and barlow_loss_on():
         names += ['train/contrast_loss', 'train/bt_on_diag', 'train/bt_off_diag']     # no logits to score: the two raw sums instead
+    elif FLAGS.train_mode == 'pretrain' and vicreg_loss_on():
+        names += ['train/contrast_loss', 'train/vicreg_inv', 'train/vicreg_var', 'train/vicreg_cov']   # the three raw terms
     elif FLAGS.train_mode == 'pretrain' and byol_loss_on():
         names += ['train/contrast_loss', 'train/byol_cosine']         # no logits to score: the mean cosine of the paired rows instead
     elif FLAGS.train_mode == 'pretrain' and moco_loss_on():
@@ -368,6 +388,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     generalized = check_contrastive_loss_flags()
     supcon = supcon_loss_on() and not generalized
     barlow = barlow_loss_on() and not generalized
+    vicreg = vicreg_loss_on() and not generalized
     byol = byol_loss_on() and not generalized
     moco = moco_loss_on() and not generalized
     dino = dino_loss_on() and not generalized
@@ -455,6 +476,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 logits_con = None
                 con_loss = obj_lib.add_barlow_twins_loss(
                     outputs, lambda_weight=FLAGS.bt_lambda, loss_scaling=FLAGS.bt_loss_scaling, strategy=strategy, overlap=supervised_part)
+            elif vicreg:
+                logits_con = None
+                con_loss = obj_lib.add_vicreg_loss(
+                    outputs, sim_coeff=FLAGS.vicreg_sim_coeff, std_coeff=FLAGS.vicreg_std_coeff, cov_coeff=FLAGS.vicreg_cov_coeff,
+                    strategy=strategy, overlap=supervised_part)
             elif byol:
                 logits_con = None
                 con_loss = obj_lib.add_byol_loss(model.predict(outputs), target_outputs, strategy=strategy, overlap=supervised_part)
@@ -596,6 +622,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/bt_on_diag'] = con_loss.on_diag.reshape(-1)[:1]
             vals['train/bt_off_diag'] = con_loss.off_diag.reshape(-1)[:1]
+        elif con_loss is not None and vicreg:
+            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
+            vals['train/vicreg_inv'] = con_loss.invariance.reshape(-1)[:1]
+            vals['train/vicreg_var'] = con_loss.variance.reshape(-1)[:1]
+            vals['train/vicreg_cov'] = con_loss.covariance.reshape(-1)[:1]
         elif con_loss is not None and byol:
             vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
             vals['train/byol_cosine'] = con_loss.cosine.reshape(-1)[:1]
@@ -637,6 +668,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 con_loss.acc, con_loss.positives = at['train/contrast_acc'], at['train/contrast_positives']
             elif barlow and 'train/bt_on_diag' in at and 'train/bt_off_diag' in at:
                 con_loss.on_diag, con_loss.off_diag = at['train/bt_on_diag'], at['train/bt_off_diag']
+            elif vicreg and 'train/vicreg_inv' in at and 'train/vicreg_var' in at and 'train/vicreg_cov' in at:
+                con_loss.invariance, con_loss.variance, con_loss.covariance = at['train/vicreg_inv'], at['train/vicreg_var'], at['train/vicreg_cov']
             elif byol:
                 if 'train/byol_cosine' in at:
                     con_loss.cosine = at['train/byol_cosine']

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,byol,moco,dino,swav,swav_multicrop,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -375,6 +375,54 @@ def main():
                      row['ntxent_bwd_tfs'], row['bt_over_ntxent_fwd'], row['bt_over_ntxent_bwd']), flush=True)
             res.append(row)
             del h, zl, za, ws, bws, zhat, rstd, g, cs
+    if 'vicreg' in what:
+        # VICReg loss (csrc/vicreg.hip) beside the Barlow Twins launches at the same (n, N, D) in the same run: both forwards form two
+        # [n, N] Gram blocks over D (4nND matrix FLOPs), both backwards two [n, N] x [N, D] products (4nND).  VICReg's forward carries one
+        # view per workgroup and splits the k range where the grid is small (S parts, then a merge launch); its backward is one launch,
+        # Barlow's is bt_bwd + bt_apply around an all-reduce.  Median of --iters launches, and their spread (max - min).
+        def spread(fn):
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.iters):
+                a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
+                a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) * 1e3)
+            ts.sort()
+            return ts[len(ts) // 2], ts[-1] - ts[0]
+        from simclr_amd._lib import lib
+        for (n, N, D) in [(512, 512, 128), (512, 4096, 2048), (512, 512, 8192), (256, 2048, 8192)]:
+            h = torch.randn(2 * N, D, device=dev) + 1.0
+            bws = ops.bt_workspace(n, N, D, dev)
+            zhat, rstd = ops.bt_standardize(h)
+            ops.bt_fwd(zhat, n, 0, 0.0051, ws=bws)
+            g, cs = ops.bt_bwd(zhat, n, 0, 0.0051, 1.0, 1.0, bws)
+            vws = ops.vicreg_workspace(n, N, D, dev)
+            xc, st = ops.vicreg_center(h)
+            ops.vicreg_fwd(h, xc, st, n, 0, ws=vws)
+            row = dict(layer='vicreg n%d N%d D%d' % (n, N, D), flops=4.0 * n * N * D, k_splits=ops.vicreg_k_splits(n, N, D),
+                       vicreg_fwd_workgroups=int(lib().vicreg_fwd_workgroups(n, N, D)), vicreg_workspace_bytes=vws.numel() * 8,
+                       bt_workspace_bytes=bws.numel() * 8, iters=args.iters)
+            for name, fn in (('vicreg_center', lambda: ops.vicreg_center(h)), ('vicreg_fwd', lambda: ops.vicreg_fwd(h, xc, st, n, 0, ws=vws)),
+                             ('vicreg_bwd', lambda: ops.vicreg_bwd(h, xc, st, n, 0, 25.0, 25.0, 1.0, 1.0, 1.0, vws)),
+                             ('bt_standardize', lambda: ops.bt_standardize(h)), ('bt_fwd', lambda: ops.bt_fwd(zhat, n, 0, 0.0051, ws=bws)),
+                             ('bt_bwd', lambda: ops.bt_bwd(zhat, n, 0, 0.0051, 1.0, 1.0, bws)),
+                             ('bt_apply', lambda: ops.bt_apply(g, zhat, rstd, cs, 0))):
+                row[name + '_us'], row[name + '_spread_us'] = spread(fn)
+            for name in ('vicreg_fwd', 'vicreg_bwd', 'bt_fwd', 'bt_bwd'):
+                row[name + '_tfs'] = row['flops'] / row[name + '_us'] / 1e6
+            row['vicreg_over_bt_fwd'] = row['vicreg_fwd_us'] / row['bt_fwd_us']
+            row['vicreg_total_us'] = row['vicreg_center_us'] + row['vicreg_fwd_us'] + row['vicreg_bwd_us']
+            row['bt_total_us'] = row['bt_standardize_us'] + row['bt_fwd_us'] + row['bt_bwd_us'] + row['bt_apply_us']
+            print('vicreg n=%d N=%d D=%d S=%d (%d workgroups): centre %.0f us fwd %.0f us (%.1f TF/s) bwd %.0f us (%.1f TF/s) | barlow standardize '
+                  '%.0f us fwd %.0f us (%.1f TF/s, spread %.0f us) bwd %.0f us (%.1f TF/s) apply %.0f us | vicreg / barlow fwd %.2f'
+                  % (n, N, D, row['k_splits'], row['vicreg_fwd_workgroups'], row['vicreg_center_us'], row['vicreg_fwd_us'], row['vicreg_fwd_tfs'],
+                     row['vicreg_bwd_us'], row['vicreg_bwd_tfs'], row['bt_standardize_us'], row['bt_fwd_us'], row['bt_fwd_tfs'],
+                     row['bt_fwd_spread_us'], row['bt_bwd_us'], row['bt_bwd_tfs'], row['bt_apply_us'], row['vicreg_over_bt_fwd']), flush=True)
+            res.append(row)
+            del h, bws, zhat, rstd, g, cs, vws, xc, st
     if 'byol' in what:
         # BYOL (csrc/byol.hip).  The moving average of the target network over ResNet-50's variable list (the list of the 'lars' entry
         # below) in GB/s of 12 bytes per element (target read + write, online read), beside simclr_lars_multi_tensor on the same list in
