@@ -231,21 +231,28 @@ class ProjectionHead(Layer):  # tf2/model.py:157-213
         return d
 
 
+def pretrain_loss():
+    """Name of the active pretraining loss (--contrastive_loss), or None outside a pretraining run: train_mode=finetune has no
+    contrastive loss and ignores the flag.  The one statement of that switch: the model reads it to decide which heads it carries,
+    run.py to pick the row of pretrain_losses.LOSSES."""
+    return getattr(FLAGS, 'contrastive_loss', 'ntxent') if FLAGS.train_mode == 'pretrain' else None
+
+
 def byol_on():
     """--contrastive_loss=byol in a pretraining run: the online model carries a predictor and the step needs a TargetNetwork."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'byol' and FLAGS.train_mode == 'pretrain'
+    return pretrain_loss() == 'byol'
 
 
 def moco_on():
     """--contrastive_loss=mocov2 in a pretraining run: the step needs a TargetNetwork with a MocoQueue; the online model is the ntxent
     model (no predictor)."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'mocov2' and FLAGS.train_mode == 'pretrain'
+    return pretrain_loss() == 'mocov2'
 
 
 def dino_on():
     """--contrastive_loss=dino in a pretraining run: the model carries a PrototypeHead and the step needs a TargetNetwork with a
     DinoCenter; no predictor."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'dino' and FLAGS.train_mode == 'pretrain'
+    return pretrain_loss() == 'dino'
 
 
 def dino_teacher_temp(step, steps_per_epoch):
@@ -266,7 +273,7 @@ def dino_last_layer_frozen(step, steps_per_epoch):
 
 def swav_on():
     """--contrastive_loss=swav in a pretraining run: the model carries a PrototypeHead; no target network, no predictor."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'swav' and FLAGS.train_mode == 'pretrain'
+    return pretrain_loss() == 'swav'
 
 
 def swav_prototypes_frozen(step, steps_per_epoch):

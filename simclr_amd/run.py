@@ -13,6 +13,7 @@ import json
 import logging
 import sys
 import time
+import types
 
 import torch
 import torch.distributed as dist
@@ -20,45 +21,23 @@ import torch.distributed as dist
 from . import data_util, metrics, ops
 from . import model as model_lib
 from . import objective as obj_lib
+from . import pretrain_losses as loss_lib
 from .comm import Strategy, collectives_on, num_replicas
 from .flags import FLAGS, check_dropblock_flags
 from .resnet import RT, join_wgrad_stream, set_dropblock_step
 
 
-def generalized_loss_on():
-    """--contrastive_loss=generalized replaces NT-Xent in the pretraining step; train_mode=finetune has no contrastive loss and ignores it."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'generalized' and FLAGS.train_mode == 'pretrain'
+# One predicate (model.pretrain_loss) and one table (pretrain_losses.LOSSES) say which loss a pretraining run trains; the names below
+# are that predicate spelt per loss.  train_mode=finetune has no contrastive loss and ignores --contrastive_loss.
+def _loss_on(name):
+    return lambda: model_lib.pretrain_loss() == name
 
 
-def supcon_loss_on():
-    """--contrastive_loss=supcon replaces NT-Xent in the pretraining step by the supervised contrastive loss; train_mode=finetune ignores it."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'supcon' and FLAGS.train_mode == 'pretrain'
-
-
-def barlow_loss_on():
-    """--contrastive_loss=barlow replaces NT-Xent in the pretraining step by the Barlow Twins loss; train_mode=finetune ignores it."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'barlow' and FLAGS.train_mode == 'pretrain'
-
-
-def barlow_loss_width():
-    """Width of the block the Barlow Twins loss reads: proj_out_dim, or the encoder's pooled output for proj_head_mode=none."""
-    return model_lib.projection_width()
-
-
-def vicreg_loss_on():
-    """--contrastive_loss=vicreg replaces NT-Xent in the pretraining step by the VICReg loss; train_mode=finetune ignores it."""
-    return getattr(FLAGS, 'contrastive_loss', 'ntxent') == 'vicreg' and FLAGS.train_mode == 'pretrain'
-
-
-# --contrastive_loss=byol replaces NT-Xent in the pretraining step by BYOL on a momentum target network; train_mode=finetune ignores it.
-# One definition: the model reads the same switch to decide whether it carries a predictor.
-byol_loss_on = model_lib.byol_on
-# --contrastive_loss=mocov2 replaces NT-Xent in the pretraining step by MoCo v2: InfoNCE against a queue of the target network's keys.
-moco_loss_on = model_lib.moco_on
-# --contrastive_loss=dino replaces NT-Xent in the pretraining step by DINO: self-distillation onto trained prototypes.
-dino_loss_on = model_lib.dino_on
-# --contrastive_loss=swav replaces NT-Xent in the pretraining step by SwAV: swapped prediction of Sinkhorn-Knopp codes on prototypes.
-swav_loss_on = model_lib.swav_on
+generalized_loss_on, supcon_loss_on = _loss_on('generalized'), _loss_on('supcon')
+barlow_loss_on, vicreg_loss_on = _loss_on('barlow'), _loss_on('vicreg')
+# the model reads the same switches to decide which heads it carries
+byol_loss_on, moco_loss_on, dino_loss_on, swav_loss_on = model_lib.byol_on, model_lib.moco_on, model_lib.dino_on, model_lib.swav_on
+barlow_loss_width = model_lib.projection_width      # the width of the block every pretraining loss reads, under its first name
 
 
 def swav_local_crops():
@@ -94,145 +73,32 @@ def check_swav_local_flags():
 
 
 def check_contrastive_loss_flags():
-    """Raise before any device work when the pretraining loss flags name something the kernels do not cover.
-    Returns True for the generalized loss only (supcon_loss_on() / barlow_loss_on() / byol_loss_on() / moco_loss_on() / dino_loss_on() /
-    swav_loss_on() / vicreg_loss_on() tell the others)."""
+    """Raise before any device work when the pretraining loss flags name something the kernels do not cover: the multi-crop flags,
+    the loss name, then the check of that loss's row of pretrain_losses.LOSSES (a pretraining run outside --mode=eval only).
+    Returns True for the generalized loss in such a run, False otherwise (model.pretrain_loss() tells the others)."""
     check_swav_local_flags()
-    if FLAGS.contrastive_loss not in ('swav', 'dino', 'ntxent', 'generalized', 'supcon', 'barlow', 'byol', 'mocov2', 'vicreg'):
+    if FLAGS.contrastive_loss not in loss_lib.LOSSES:
         raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r), "
                          "or 'swav' or 'vicreg'" % FLAGS.contrastive_loss)
-    if swav_loss_on() and FLAGS.mode != 'eval':
-        if not 2 <= FLAGS.swav_num_prototypes <= ops.SWAV_MAX_PROTOTYPES:
-            raise ValueError('--swav_num_prototypes must lie in [2, %d] (got %r)' % (ops.SWAV_MAX_PROTOTYPES, FLAGS.swav_num_prototypes))
-        for name in ('swav_epsilon', 'swav_temperature'):
-            if not 0.0 < getattr(FLAGS, name) < float('inf'):          # (NaN fails the comparison)
-                raise ValueError('--%s must be > 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
-        if not 1 <= FLAGS.swav_sinkhorn_iterations <= ops.SWAV_MAX_ITERS:
-            raise ValueError('--swav_sinkhorn_iterations must lie in [1, %d] (got %r)' % (ops.SWAV_MAX_ITERS, FLAGS.swav_sinkhorn_iterations))
-        if FLAGS.swav_freeze_prototypes_epochs < 0:
-            raise ValueError('--swav_freeze_prototypes_epochs must be >= 0 (got %r)' % FLAGS.swav_freeze_prototypes_epochs)
-        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.SWAV_DIMS:
-            raise ValueError('--contrastive_loss=swav needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
-                             'the SwAV kernels are instantiated for those widths only'
-                             % ('/'.join(map(str, ops.SWAV_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+    spec = loss_lib.active()
+    if spec is None or FLAGS.mode == 'eval':
         return False
-    if dino_loss_on() and FLAGS.mode != 'eval':
-        if not 2 <= FLAGS.dino_out_dim <= ops.DINO_MAX_OUT_DIM:
-            raise ValueError('--dino_out_dim must lie in [2, %d] (got %r)' % (ops.DINO_MAX_OUT_DIM, FLAGS.dino_out_dim))
-        for name in ('dino_student_temp', 'dino_teacher_temp', 'dino_warmup_teacher_temp'):
-            if not 0.0 < getattr(FLAGS, name) < float('inf'):          # (NaN fails the comparison)
-                raise ValueError('--%s must be > 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
-        for name in ('dino_center_momentum', 'dino_momentum'):
-            if not 0.0 <= getattr(FLAGS, name) <= 1.0:                 # (NaN fails both comparisons)
-                raise ValueError('--%s must lie in [0, 1] (got %r)' % (name, getattr(FLAGS, name)))
-        for name in ('dino_warmup_teacher_temp_epochs', 'dino_freeze_last_layer_epochs'):
-            if getattr(FLAGS, name) < 0:
-                raise ValueError('--%s must be >= 0 (got %r)' % (name, getattr(FLAGS, name)))
-        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.DINO_DIMS:
-            raise ValueError('--contrastive_loss=dino needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
-                             'the DINO kernels are instantiated for those widths only'
-                             % ('/'.join(map(str, ops.DINO_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        return False
-    if moco_loss_on() and FLAGS.mode != 'eval':
-        rows = 2 * FLAGS.train_batch_size               # the global 2N rows a step enqueues
-        K = FLAGS.moco_queue_size
-        if rows < 2 or K < rows or K % rows != 0 or K > ops.MOCO_MAX_QUEUE:
-            raise ValueError('--moco_queue_size must be a multiple of 2 x train_batch_size = %d, at least that and at most %d (got %r): '
-                             'the ring never wraps inside a step' % (rows, ops.MOCO_MAX_QUEUE, K))
-        if not 0.0 <= FLAGS.moco_momentum <= 1.0:          # (NaN fails both comparisons)
-            raise ValueError('--moco_momentum must lie in [0, 1] (got %r)' % (FLAGS.moco_momentum,))
-        if not FLAGS.temperature > 0:
-            raise ValueError('--contrastive_loss=mocov2 needs --temperature > 0 (got %r)' % (FLAGS.temperature,))
-        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.MOCO_DIMS:
-            raise ValueError('--contrastive_loss=mocov2 needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
-                             'the MoCo kernels are instantiated for those widths only'
-                             % ('/'.join(map(str, ops.MOCO_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        return False
-    if byol_loss_on() and FLAGS.mode != 'eval':
-        if not 0.0 <= FLAGS.byol_tau_base <= 1.0:           # (NaN fails both comparisons)
-            raise ValueError('--byol_tau_base must lie in [0, 1] (got %r)' % (FLAGS.byol_tau_base,))
-        if not ops.byol_dim_ok(FLAGS.byol_pred_hidden_dim):
-            raise ValueError('--byol_pred_hidden_dim must be a multiple of %d in [%d, %d] (got %r)'
-                             % (ops.BYOL_DIM_STEP, ops.BYOL_MIN_DIM, ops.BYOL_MAX_DIM, FLAGS.byol_pred_hidden_dim))
-        width = barlow_loss_width()
-        if not ops.byol_dim_ok(width):
-            raise ValueError('--contrastive_loss=byol needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
-                             'proj_head_mode=%r, proj_out_dim=%d): the BYOL kernels and the predictor take those widths only'
-                             % (ops.BYOL_DIM_STEP, ops.BYOL_MIN_DIM, ops.BYOL_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        return False
-    if vicreg_loss_on() and FLAGS.mode != 'eval':
-        for name in ('vicreg_sim_coeff', 'vicreg_std_coeff', 'vicreg_cov_coeff'):
-            if not ops.vicreg_coeff_ok(getattr(FLAGS, name)):          # (NaN fails the comparison)
-                raise ValueError('--%s must be >= 0 and finite (got %r)' % (name, getattr(FLAGS, name)))
-        width = barlow_loss_width()
-        if not ops.vicreg_dim_ok(width):
-            raise ValueError('--contrastive_loss=vicreg needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
-                             'proj_head_mode=%r, proj_out_dim=%d): the VICReg kernels take those widths only'
-                             % (ops.VICREG_DIM_STEP, ops.VICREG_MIN_DIM, ops.VICREG_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        if FLAGS.train_batch_size < 2:
-            raise ValueError('--contrastive_loss=vicreg needs --train_batch_size >= 2 (got %r): the variance over the global batch is '
-                             'the unbiased one' % (FLAGS.train_batch_size,))
-        return False
-    if barlow_loss_on() and FLAGS.mode != 'eval':
-        if FLAGS.bt_lambda < 0:
-            raise ValueError('--bt_lambda must be >= 0 (got %r)' % (FLAGS.bt_lambda,))
-        if not FLAGS.bt_loss_scaling > 0:
-            raise ValueError('--bt_loss_scaling must be > 0 (got %r)' % (FLAGS.bt_loss_scaling,))
-        width = barlow_loss_width()
-        if not ops.bt_dim_ok(width):
-            raise ValueError('--contrastive_loss=barlow needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
-                             'proj_head_mode=%r, proj_out_dim=%d): the Barlow Twins kernels take those widths only'
-                             % (ops.BT_DIM_STEP, ops.BT_MIN_DIM, ops.BT_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        return False
-    if supcon_loss_on() and FLAGS.mode != 'eval':
-        if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.SUPCON_DIMS:
-            raise ValueError('--contrastive_loss=supcon needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
-                             'the supervised contrastive kernels are instantiated for those widths only'
-                             % ('/'.join(map(str, ops.SUPCON_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-        return False
-    if not generalized_loss_on() or FLAGS.mode == 'eval':
-        return False
-    if FLAGS.gcl_dist not in obj_lib.GCL_DISTS:
-        raise ValueError('Unknown prior {}'.format(FLAGS.gcl_dist))
-    if FLAGS.proj_head_mode == 'none' or FLAGS.proj_out_dim not in ops.GCL_DIMS:
-        raise ValueError('--contrastive_loss=generalized needs a projection head of width %s (got proj_head_mode=%r, proj_out_dim=%d): '
-                         'the generalized-loss kernels are instantiated for those widths only'
-                         % ('/'.join(map(str, ops.GCL_DIMS)), FLAGS.proj_head_mode, FLAGS.proj_out_dim))
-    if FLAGS.gcl_dist != 'logsumexp' and 2 * FLAGS.train_batch_size > ops.SWD_MAX_ROWS:
-        raise ValueError('--gcl_dist=%s sorts the 2 x train_batch_size global rows of every projected dimension in LDS: '
-                         'train_batch_size <= %d (got %d)' % (FLAGS.gcl_dist, ops.SWD_MAX_ROWS // 2, FLAGS.train_batch_size))
-    return True
+    if spec.check is not None:
+        spec.check()
+    return spec is loss_lib.LOSSES['generalized']
 
 
 def build_metrics():
-    """The metric set of tf2/run.py:534-549."""
-    m = {}
+    """The metric set of tf2/run.py:534-549; the pretraining names are those of the loss's row of pretrain_losses.LOSSES."""
     names = ['train/weight_decay', 'train/total_loss']
-    if FLAGS.train_mode == 'pretrain' and generalized_loss_on():
-        names += ['train/contrast_loss', 'train/align_loss', 'train/dist_loss']   # the generalized loss has no logits to score
-    elif FLAGS.train_mode == 'pretrain' and supcon_loss_on():
-        names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_positives']
-    elif FLAGS.train_mode == 'pretrain' and barlow_loss_on():
-        names += ['train/contrast_loss', 'train/bt_on_diag', 'train/bt_off_diag']     # no logits to score: the two raw sums instead
-    elif FLAGS.train_mode == 'pretrain' and vicreg_loss_on():
-        names += ['train/contrast_loss', 'train/vicreg_inv', 'train/vicreg_var', 'train/vicreg_cov']   # the three raw terms
-    elif FLAGS.train_mode == 'pretrain' and byol_loss_on():
-        names += ['train/contrast_loss', 'train/byol_cosine']         # no logits to score: the mean cosine of the paired rows instead
-    elif FLAGS.train_mode == 'pretrain' and moco_loss_on():
-        names += ['train/contrast_loss', 'train/contrast_acc']        # positive against the best queue row; no entropy
-    elif FLAGS.train_mode == 'pretrain' and dino_loss_on():
-        names += ['train/contrast_loss', 'train/dino_teacher_entropy']   # log K = uniform teacher, 0 = one-hot collapse
-    elif FLAGS.train_mode == 'pretrain' and swav_loss_on():
-        names += ['train/contrast_loss', 'train/swav_code_entropy']      # log K = uniform codes, 0 = one-hot codes
-    elif FLAGS.train_mode == 'pretrain':
-        names += ['train/contrast_loss', 'train/contrast_acc', 'train/contrast_entropy']
+    spec = loss_lib.active()
+    if spec is not None:
+        names += [n for n, _ in spec.metrics + spec.logits_metrics]
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
         names += ['train/distill_loss', 'train/distill_agreement']       # distillation: the teacher replaces the labels
     elif FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
         names += ['train/supervised_loss', 'train/supervised_acc']
-    for n in names:
-        m[n] = metrics.Mean(n)
-    return m
+    return {n: metrics.Mean(n) for n in names}
 
 
 class GradSync:
@@ -352,6 +218,9 @@ def all_reduce_stats_async(tensor, strategy):
 
 def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None, steps_per_epoch=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
+    A pretraining step trains the row of pretrain_losses.LOSSES that model.pretrain_loss() names: the row's `call` makes the loss, its
+    (metric name, attribute) pairs are logged and re-pointed by one loop each; the phases that differ between losses (below) are
+    explicit code in the step, keyed on what the loss uses: a target, a queue, a centre, prototypes that can be frozen.
     target: model.TargetNetwork (or a stand-in with its __call__ / update), required by --contrastive_loss=byol.  The step is then:
     blur once, target forward (training mode, nothing kept), online forward on the same pixels, predictor, add_byol_loss, the usual
     backward entering through the predictor, optimizer, target.update(step).
@@ -385,32 +254,24 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         m = build_metrics()
     state = {'sync': None}
     RT.strategy = strategy
-    generalized = check_contrastive_loss_flags()
-    supcon = supcon_loss_on() and not generalized
-    barlow = barlow_loss_on() and not generalized
-    vicreg = vicreg_loss_on() and not generalized
-    byol = byol_loss_on() and not generalized
-    moco = moco_loss_on() and not generalized
-    dino = dino_loss_on() and not generalized
-    swav = swav_loss_on() and not generalized
-    if swav and (steps_per_epoch is None or int(steps_per_epoch) < 1):
+    check_contrastive_loss_flags()
+    name = model_lib.pretrain_loss()          # None: fine-tuning, no contrastive loss
+    spec = loss_lib.active()
+    if name == 'swav' and (steps_per_epoch is None or int(steps_per_epoch) < 1):
         raise ValueError('--contrastive_loss=swav needs steps_per_epoch >= 1 (the freeze of the prototypes counts epochs): '
                          'make_single_step(..., steps_per_epoch=n)')
-    if byol and target is None:
-        raise ValueError('--contrastive_loss=byol needs a target network: make_single_step(..., target=model.TargetNetwork(model, steps))')
-    if moco and (target is None or getattr(target, 'queue', None) is None):
-        raise ValueError('--contrastive_loss=mocov2 needs a target network with a key queue: make_single_step(..., '
-                         'target=model.TargetNetwork(model, steps, queue=model.MocoQueue(K, D, seed)))')
-    if dino and (target is None or getattr(target, 'center', None) is None or not getattr(target, 'steps_per_epoch', None)):
-        raise ValueError('--contrastive_loss=dino needs a target network with a centre: make_single_step(..., '
-                         'target=model.TargetNetwork(model, steps, center=model.DinoCenter(K), steps_per_epoch=n))')
-    if target is not None and not (byol or moco or dino):
+    if spec is not None and spec.check_target is not None:
+        spec.check_target(target)
+    elif target is not None:
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
-    local_crops = swav_local_crops() if swav else 0
+    local_crops = swav_local_crops() if name == 'swav' else 0
 
     def single_step(features, labels):
+        # optimizer.iterations is a host int that apply_gradients increments: every "before the increment" read of the step is this
+        # value, and a restored run continues what derives from it (DropBlock noise, SWD draws, temperatures, freezes, tau, queue row)
+        step = int(getattr(optimizer, 'iterations', 0))
         local_features = None
         if local_crops:
             features, local_features = features
@@ -420,27 +281,29 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         ops.begin_step(features.device)
         if dropblock:
             # the noise of a DropBlock site is a function of (dropblock_seed, global step, replica, site): the restored step continues it
-            set_dropblock_step(getattr(optimizer, 'iterations', 0))
+            set_dropblock_step(step)
         teacher_logits = None
         if teacher is not None:
             # the frozen teacher's inference forward (it selects its own arithmetic); the student's forward below selects the
             # training arithmetic again, for the rest of the step
             teacher_logits = teacher(features)
-        if byol or moco or dino:
+        c = types.SimpleNamespace(model=model, target=target, strategy=strategy, steps_per_epoch=steps_per_epoch, step=step,
+                                  labels=labels, target_outputs=None, keys=None, frozen=False, logits_con=None)
+        if target is not None:
             # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
             if FLAGS.use_blur:
                 features = data_util.batch_random_blur_tensor(features, FLAGS.image_size, FLAGS.image_size)
-            target_outputs = target(features)          # released before the online forward: the two activation sets never coexist
-            if moco:
+            c.target_outputs = target(features)        # released before the online forward: the two activation sets never coexist
+            if name == 'mocov2':
                 # the keys of this step, and their gather for the enqueue at the END of the step: in flight during the online forward,
                 # the loss and the whole backward -- the loss reads the local keys and the queue as it stands
-                moco_keys, _ = ops.l2norm_fwd(target_outputs.contiguous())
-                moco_gather = obj_lib.gather_hidden(moco_keys, strategy, async_op=True)
-            if dino:
+                c.keys, _ = ops.l2norm_fwd(c.target_outputs.contiguous())
+                moco_gather = obj_lib.gather_hidden(c.keys, strategy, async_op=True)
+            if name == 'dino':
                 # the mean of this step's keys over the GLOBAL batch -- the one vector the centre update at the END of the step needs:
                 # formed in double in a fixed order, its all-reduce in flight during the online forward, the loss and the backward
-                dino_keys, _ = ops.l2norm_fwd(target_outputs.contiguous())
-                dino_kbar = ops.dino_key_mean(dino_keys, dino_keys.shape[0] * num_replicas(strategy))
+                c.keys, _ = ops.l2norm_fwd(c.target_outputs.contiguous())
+                dino_kbar = ops.dino_key_mean(c.keys, c.keys.shape[0] * num_replicas(strategy))
                 dino_kbar_wait = all_reduce_stats_async(dino_kbar, strategy)
             projection_head_outputs, supervised_head_outputs = model(features, training=True, blur=False)
         else:
@@ -457,58 +320,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 # pretraining: labels are reused for both views (tf2/run.py:599-600: l = concat([l, l], 0)); finetune: one view
                 sup_box['loss'] = obj_lib.add_supervised_loss(labels=l, logits=supervised_head_outputs)   # :601
         if projection_head_outputs is not None:
-            outputs = projection_head_outputs
             # collective A (all-gather of the hidden block) is in flight while the supervised loss is computed
-            if generalized:
-                # the draws of the SWD priors are a function of (gcl_seed, global step): the restored step continues them
-                obj_lib.set_gcl_step(getattr(optimizer, 'iterations', 0))
-                logits_con = None
-                con_loss = obj_lib.generalized_loss_of_block(
-                    outputs, lambda_weight=FLAGS.gcl_lambda, temperature=FLAGS.temperature, dist=FLAGS.gcl_dist,
-                    hidden_norm=FLAGS.hidden_norm, loss_scaling=FLAGS.gcl_loss_scaling, strategy=strategy, overlap=supervised_part)
-            elif supcon:
-                # the labels define the positives, whether or not the supervised head trains on them too
-                logits_con = None
-                con_loss = obj_lib.add_supcon_loss(
-                    outputs, labels['labels'] if isinstance(labels, dict) else labels, hidden_norm=FLAGS.hidden_norm,
-                    temperature=FLAGS.temperature, strategy=strategy, overlap=supervised_part)
-            elif barlow:
-                logits_con = None
-                con_loss = obj_lib.add_barlow_twins_loss(
-                    outputs, lambda_weight=FLAGS.bt_lambda, loss_scaling=FLAGS.bt_loss_scaling, strategy=strategy, overlap=supervised_part)
-            elif vicreg:
-                logits_con = None
-                con_loss = obj_lib.add_vicreg_loss(
-                    outputs, sim_coeff=FLAGS.vicreg_sim_coeff, std_coeff=FLAGS.vicreg_std_coeff, cov_coeff=FLAGS.vicreg_cov_coeff,
-                    strategy=strategy, overlap=supervised_part)
-            elif byol:
-                logits_con = None
-                con_loss = obj_lib.add_byol_loss(model.predict(outputs), target_outputs, strategy=strategy, overlap=supervised_part)
-            elif moco:
-                logits_con = None
-                con_loss = obj_lib.add_moco_loss(outputs, target_outputs, target.queue.value, temperature=FLAGS.temperature,
-                                                 strategy=strategy, overlap=supervised_part, keys=moco_keys)
-            elif dino:
-                logits_con = None
-                # both derive from optimizer.iterations (before its increment): a restored run continues them
-                dino_step = int(getattr(optimizer, 'iterations', 0))
-                dino_frozen = model_lib.dino_last_layer_frozen(dino_step, target.steps_per_epoch)
-                con_loss = obj_lib.add_dino_loss(
-                    outputs, target_outputs, model.prototype_head, target.prototypes(), target.center.value,
-                    student_temp=FLAGS.dino_student_temp, teacher_temp=model_lib.dino_teacher_temp(dino_step, target.steps_per_epoch),
-                    strategy=strategy, overlap=supervised_part, keys=dino_keys, update_prototypes=not dino_frozen)
-            elif swav:
-                logits_con = None
-                # derives from optimizer.iterations (before its increment): a restored run continues it
-                swav_frozen = model_lib.swav_prototypes_frozen(int(getattr(optimizer, 'iterations', 0)), steps_per_epoch)
-                con_loss = obj_lib.add_swav_loss(
-                    outputs, model.prototype_head, temperature=FLAGS.swav_temperature, epsilon=FLAGS.swav_epsilon,
-                    sinkhorn_iterations=FLAGS.swav_sinkhorn_iterations, strategy=strategy, overlap=supervised_part,
-                    update_prototypes=not swav_frozen)
-            else:
-                con_loss, logits_con, labels_con = obj_lib.add_contrastive_loss(            # :582-586
-                    outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=strategy,
-                    overlap=supervised_part)
+            c.outputs, c.overlap = projection_head_outputs, supervised_part
+            if spec.frozen is not None:
+                c.frozen = spec.frozen(c)
+            con_loss = spec.call(c)
         else:
             supervised_part()
         sup_loss = sup_box.get('loss')
@@ -541,7 +357,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         else:
             model.backward_supervised(d_sup)
             d_proj = con_loss.backward_finish() if con_loss is not None else None
-            if byol:
+            if name == 'byol':
                 d_proj = model.backward_predictor(d_proj)
             model.backward(d_proj, None, on_stage=on_stage)
         join_wgrad_stream()
@@ -558,7 +374,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             global_loss = con_loss
             local_loss = obj_lib.add_swav_local_loss(local_outputs, global_loss, model.prototype_head,
                                                      temperature=FLAGS.swav_temperature, strategy=strategy,
-                                                     update_prototypes=not swav_frozen)
+                                                     update_prototypes=not c.frozen)
             model.backward(local_loss.backward(1.0 / R), None, on_stage=None)
             join_wgrad_stream()
             ops.axpy_f32(1.0, saved_grads, model._flat_grads)
@@ -570,23 +386,20 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             con_loss.entropy, con_loss.alpha = global_loss.entropy, global_loss.alpha
             con_loss.global_loss, con_loss.local_loss = global_loss, local_loss
         sync.wait()
-        if byol or moco or dino:
-            # before the increment: a restored run continues the tau schedule / the queue's write position
-            step_index = int(getattr(optimizer, 'iterations', 0))
-        if (dino and dino_frozen) or (swav and swav_frozen):
+        if c.frozen:
             # the frozen prototypes take no update at all -- no gradient, no weight decay, no momentum: the pair is dropped, as
             # apply_gradients drops a variable without a gradient.  Online and target copies stay bitwise what they are.
             frozen_id = id(model.prototype_head.kernel)
             optimizer.apply_gradients([(v.grad, v) for v in state['apply'] if id(v) != frozen_id])
         else:
             optimizer.apply_gradients([(v.grad, v) for v in state['apply']])               # :622
-        if byol or moco or dino:
-            target.update(step_index)
-        if moco:
+        if target is not None:
+            target.update(step)
+        if name == 'mocov2':
             # The enqueue comes AFTER the backward: the backward recomputes the logits from the queue, and a queue that already held
             # this step's keys would silently differentiate another loss (every query would find its own positive among the negatives).
-            target.queue.enqueue(moco_gather(), step_index)
-        if dino:
+            target.queue.enqueue(moco_gather(), step)
+        if name == 'dino':
             # The centre moves AFTER the backward, which recomputes the teacher softmax from it (moved earlier, the step would
             # differentiate another loss in silence), and it reads the target prototypes the FORWARD used, not the ones update() left.
             target.center.update(con_loss.target_prototypes, dino_kbar_wait(), FLAGS.dino_center_momentum)
@@ -601,8 +414,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         if state.get('bank') is None or state['bank'].device != features.device:
             state['bank'] = torch.zeros(16, device=features.device, dtype=torch.float32)
             state['zero'] = torch.zeros(1, device=features.device, dtype=torch.float32)
-            for i, name in enumerate(sorted(m)):
-                m[name].attach(state['bank'], i)
+            for i, nm in enumerate(sorted(m)):
+                m[nm].attach(state['bank'], i)
         order = sorted(m)
         wd_t = weight_decay.reshape(-1)[:1] if torch.is_tensor(weight_decay) else state['zero']
         total = torch.empty(1, device=features.device, dtype=torch.float32)
@@ -610,39 +423,13 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 ([sup_loss.value.reshape(-1)[:1]] if sup_loss is not None else [])
         ops.accumulate_scalars(terms, total=total, total_mask=(1 << len(terms)) - 1)
         vals = {'train/weight_decay': wd_t, 'train/total_loss': total}
-        if con_loss is not None and generalized:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/align_loss'] = con_loss.align.reshape(-1)[:1]
-            vals['train/dist_loss'] = con_loss.dist_match.reshape(-1)[:1]
-        elif con_loss is not None and supcon:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
-            vals['train/contrast_positives'] = con_loss.positives.reshape(-1)[:1]
-        elif con_loss is not None and barlow:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/bt_on_diag'] = con_loss.on_diag.reshape(-1)[:1]
-            vals['train/bt_off_diag'] = con_loss.off_diag.reshape(-1)[:1]
-        elif con_loss is not None and vicreg:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/vicreg_inv'] = con_loss.invariance.reshape(-1)[:1]
-            vals['train/vicreg_var'] = con_loss.variance.reshape(-1)[:1]
-            vals['train/vicreg_cov'] = con_loss.covariance.reshape(-1)[:1]
-        elif con_loss is not None and byol:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/byol_cosine'] = con_loss.cosine.reshape(-1)[:1]
-        elif con_loss is not None and moco:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/contrast_acc'] = con_loss.acc.reshape(-1)[:1]
-        elif con_loss is not None and dino:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/dino_teacher_entropy'] = con_loss.entropy.reshape(-1)[:1]
-        elif con_loss is not None and swav:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/swav_code_entropy'] = con_loss.entropy.reshape(-1)[:1]
-        elif con_loss is not None:
-            vals['train/contrast_loss'] = con_loss.value.reshape(-1)[:1]
-            vals['train/contrast_acc'] = logits_con.contrast_acc.reshape(-1)[:1]
-            vals['train/contrast_entropy'] = logits_con.contrast_entropy.reshape(-1)[:1]
+        # the (metric name, attribute) pairs of the loss's row of pretrain_losses.LOSSES, read from the loss handle and (NT-Xent) the logits
+        pairs = spec.metrics if con_loss is not None else ()
+        logits_pairs = spec.logits_metrics if c.logits_con is not None else ()
+        for nm, attr in pairs:
+            vals[nm] = getattr(con_loss, attr).reshape(-1)[:1]
+        for nm, attr in logits_pairs:
+            vals[nm] = getattr(c.logits_con, attr).reshape(-1)[:1]
         sup_names = ('train/distill_loss', 'train/distill_agreement') if teacher is not None else \
                     ('train/supervised_loss', 'train/supervised_acc')
         if sup_loss is not None:
@@ -660,38 +447,20 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         for nm in names:
             m[nm].bump()
         at = {nm: keep[i:i + 1] for i, nm in enumerate(order) if nm in vals}
-        if con_loss is not None and 'train/contrast_loss' in at:
-            con_loss.value = at['train/contrast_loss']
-            if generalized and 'train/align_loss' in at and 'train/dist_loss' in at:
-                con_loss.align, con_loss.dist_match = at['train/align_loss'], at['train/dist_loss']
-            elif supcon and 'train/contrast_acc' in at and 'train/contrast_positives' in at:
-                con_loss.acc, con_loss.positives = at['train/contrast_acc'], at['train/contrast_positives']
-            elif barlow and 'train/bt_on_diag' in at and 'train/bt_off_diag' in at:
-                con_loss.on_diag, con_loss.off_diag = at['train/bt_on_diag'], at['train/bt_off_diag']
-            elif vicreg and 'train/vicreg_inv' in at and 'train/vicreg_var' in at and 'train/vicreg_cov' in at:
-                con_loss.invariance, con_loss.variance, con_loss.covariance = at['train/vicreg_inv'], at['train/vicreg_var'], at['train/vicreg_cov']
-            elif byol:
-                if 'train/byol_cosine' in at:
-                    con_loss.cosine = at['train/byol_cosine']
-            elif moco:
-                if 'train/contrast_acc' in at:
-                    con_loss.acc = at['train/contrast_acc']
-            elif dino:
-                if 'train/dino_teacher_entropy' in at:
-                    con_loss.entropy = at['train/dino_teacher_entropy']
-            elif swav:
-                if 'train/swav_code_entropy' in at:
-                    con_loss.entropy = at['train/swav_code_entropy']
-            elif 'train/contrast_acc' in at and 'train/contrast_entropy' in at:
-                logits_con.keep(at['train/contrast_acc'], at['train/contrast_entropy'])
+        # Per name: a caller who passes an `all_metrics` without some name of the row still has every handle whose name it did pass
+        # re-pointed (the handles of the names it left out keep reading the arena, as they must: nothing copied them).
+        for nm, attr in pairs:
+            if nm in at:
+                setattr(con_loss, attr, at[nm])
+        if logits_pairs and all(nm in at for nm, _ in logits_pairs):
+            c.logits_con.keep(*(at[nm] for nm, _ in logits_pairs))                # LazyLogits.keep(acc, entropy): both or neither
         if sup_loss is not None and sup_names[0] in at:
             sup_loss.value = at[sup_names[0]]
             if sup_names[1] in at:
                 sup_loss.acc = at[sup_names[1]]
         if torch.is_tensor(weight_decay) and 'train/weight_decay' in at:
             weight_decay = at['train/weight_decay']
-        return dict(con_loss=con_loss, sup_loss=sup_loss, weight_decay=weight_decay, total_loss=total,
-                    logits_con=logits_con if con_loss is not None else None)
+        return dict(con_loss=con_loss, sup_loss=sup_loss, weight_decay=weight_decay, total_loss=total, logits_con=c.logits_con)
 
     single_step.metrics = m
     return single_step
@@ -923,17 +692,10 @@ def main(argv):
 
     learning_rate = model_lib.WarmUpAndCosineDecay(FLAGS.learning_rate, num_train_examples)
     optimizer = model_lib.build_optimizer(learning_rate)
-    # BYOL: the target network is built after the online model (whose variables it makes exist first) as a bitwise copy of it
-    target = model_lib.TargetNetwork(model, train_steps) if byol_loss_on() else None
-    if moco_loss_on():
-        # MoCo v2: the same target network under a constant momentum, and the queue of its keys (seeded: the same on every replica)
-        target = model_lib.TargetNetwork(model, train_steps,
-                                         queue=model_lib.MocoQueue(FLAGS.moco_queue_size, FLAGS.proj_out_dim, FLAGS.moco_queue_seed))
-    if dino_loss_on():
-        # DINO: the same target network under BYOL's cosine schedule from --dino_momentum, prototypes included, and the teacher's centre
-        target = model_lib.TargetNetwork(model, train_steps, center=model_lib.DinoCenter(FLAGS.dino_out_dim),
-                                         steps_per_epoch=max(epoch_steps, 1))
-    # SwAV: no target network; the freeze of the prototypes counts epochs
+    # a loss with a momentum target network builds it after the online model (whose variables it makes exist first); SwAV has none,
+    # and the freeze of its prototypes counts epochs
+    spec = loss_lib.active()
+    target = spec.make_target(model, train_steps, epoch_steps) if spec is not None and spec.make_target is not None else None
     step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target,
                                steps_per_epoch=max(epoch_steps, 1) if swav_loss_on() else None)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
@@ -956,15 +718,16 @@ def main(argv):
         manager, status = try_restore_from_checkpoint(target.checkpointable() if target is not None else model, optimizer,
                                                       FLAGS.model_dir, FLAGS.checkpoint,
                                                       FLAGS.keep_checkpoint_max, FLAGS.zero_init_logits_layer)
-        if target is not None and status is not None and (
-                not manager.latest_checkpoint or any(n.startswith(target.PREFIX) for n in status.missing_in_checkpoint)):
-            target.copy_from_online()        # --checkpoint (or a file without target entries): the copy is made after the restore
-        if target is not None and target.queue is not None and status is not None and (
-                not manager.latest_checkpoint or target.queue.NAME in status.missing_in_checkpoint):
-            target.queue.reset()             # likewise the seeded queue (a weights-only restore may have filled it from the file)
-        if target is not None and target.center is not None and status is not None and (
-                not manager.latest_checkpoint or target.center.NAME in status.missing_in_checkpoint):
-            target.center.reset()            # likewise the zero centre
+        if target is not None and status is not None:
+            # --checkpoint, or a file without these entries: the copy of the online model is made after the restore; likewise the
+            # seeded queue (a weights-only restore may have filled it from the file) and the zero centre.  In this order.
+            missing = status.missing_in_checkpoint
+            for part, absent, reset in (
+                    (target, lambda: any(n.startswith(target.PREFIX) for n in missing), target.copy_from_online),
+                    (target.queue, lambda: target.queue.NAME in missing, lambda: target.queue.reset()),
+                    (target.center, lambda: target.center.NAME in missing, lambda: target.center.reset())):
+                if part is not None and (not manager.latest_checkpoint or absent()):
+                    reset()
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)
