@@ -762,6 +762,31 @@ int simclr_swav_local_bwd_w(const float* x, const float* z, const float* w, cons
                             float temperature, float epsilon, const float* row_stats, const float* global_row_stats, float grad_scale,
                             float* dw, void* workspace, simclr_stream_t stream);
 
+/* ---- DINO multi-crop (csrc/dino_multicrop.hip): Caron et al. 2021, the official loss with ncrops = 2 + L ----
+ * The L local views of the b images against the teacher rows of BOTH global views.  x [L b, D] = the l2-normalised local rows,
+ * view-major; k [2b, D], ws / wt [K, D], center [K], u [2b, D] and global_row_stats [2b, 2] = what simclr_dino_fwd read / returned
+ * for the two global views of the same images.  A logit is linear in the prototype, sum_j Pt[g, j] s_rj = x_r . u_g / Ts, so the
+ * value and the query-side backward of the local term are simclr_swav_local_fwd / simclr_swav_local_bwd_x on (x, ws, u, L, Ts) as
+ * they stand; their row_stats [L b] (logsumexp_j of x_r . ws_j / Ts, base 2) is local_row_stats here.  The key-side backward is
+ * this family: with c = 1 / (2 (L + 1) b), Ps the student softmax of the local rows and Pt[g] = softmax_j((k_g . wt_j - center_j)
+ * / Tt) the teacher row of global row g ITSELF (normalised by global_row_stats[2 g + 1], not by the paired row's entry that
+ * simclr_dino_bwd_w reads),
+ *   simclr_dino_local_bwd_w: dws [K, D] = grad_scale (c / Ts) (2 sum_r Ps[r, j] x_r - sum_{g < 2b} Pt[g, j] m_{g mod b}),
+ *                            m_i = sum_v x_{v b + i} (views added in the order 0, 1, ...): the build of m, two key-side sweeps
+ *                            (64 prototypes per workgroup; the second holds wt and center_j and streams k beside the wrapped m
+ *                            tile), a combine.  center, wt and k must still be the ones simclr_dino_fwd read.
+ * All fp32, the matrices 16-byte aligned, D in {64, 128, 256}, K in [2, 1048576], L in [1, 8], b >= 1.  Row splits are merged in a
+ * fixed order, no atomics: two calls are bitwise equal.  workspace: simclr_dino_local_workspace_bytes(b, L, K, D) bytes, this
+ * family's own (0 for a refused shape).  simclr_dino_local_row_splits / _teacher_row_splits: row splits of the student sweep over the
+ * L b local rows / of the teacher sweep over the 2b global rows.  Refused (1 returned, nothing launched): null / misaligned
+ * pointers, another D, K outside [2, 1048576], L outside [1, 8], b < 1, a temperature <= 0 or NaN. */
+size_t simclr_dino_local_workspace_bytes(int b, int L, int K, int D);
+int simclr_dino_local_row_splits(int b, int L, int K);
+int simclr_dino_local_teacher_row_splits(int b, int L, int K);
+int simclr_dino_local_bwd_w(const float* x, const float* k, const float* ws, const float* wt, const float* center, int b, int L, int K,
+                            int D, float student_temp, float teacher_temp, const float* local_row_stats,
+                            const float* global_row_stats, float grad_scale, float* dws, void* workspace, simclr_stream_t stream);
+
 /* ---- DropBlock (csrc/dropblock.hip): tf2/resnet.py:81-157, the four sites of a bottleneck block (:424-487) ----
  * A site's block pattern is a BIT tensor packed along C: unsigned char [V,H,W,C/8], bit j of a byte = channel 8*byte + j (C % 8 == 0,
  * so it is also the linear bit string of the NHWC elements), with its `count`: device uint64 [2] = {ones, size} of the pattern in the

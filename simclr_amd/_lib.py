@@ -94,6 +94,7 @@ class _Lib:
                           'simclr_stem_wgrad_ps_supported', 'simclr_knn_slab_rows', 'simclr_moco_key_splits',
                           'simclr_dino_key_splits', 'simclr_dino_row_splits', 'simclr_swav_key_splits', 'simclr_swav_row_splits',
                           'simclr_swav_local_key_splits', 'simclr_swav_local_row_splits', 'simclr_swav_local_code_row_splits',
+                          'simclr_dino_local_row_splits', 'simclr_dino_local_teacher_row_splits',
                           'simclr_vicreg_k_splits', 'simclr_vicreg_fwd_workgroups'}
 
     def last_error(self):

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import data_util, ops
-from .flags import FLAGS
+from .flags import FLAGS, local_crop_flags
 
 FORMAT = 'simclr-arrays-1'
 LAYOUT = ('<data_dir>/<dataset>/info.json {"format": "%s", "num_classes": K, "splits": {"train": N, ...}}, '
@@ -191,12 +191,14 @@ class DatasetIterator:
         self.strength = float(s) if self.pretrain else 0.
         self.test_crop = self.size > 32
         self.views = 2 if self.pretrain else 1
-        # SwAV multi-crop: L local views per image at their own size, area range and generator (pretraining with --contrastive_loss=swav)
+        # multi-crop: L local views per image at their own size, area range and generator (pretraining with --contrastive_loss=swav or
+        # dino, each under its own four flags: flags.local_crop_flags)
+        flag_crops, local_size, lo, hi = local_crop_flags()
         if local_crops is None:
-            local_crops = FLAGS.swav_local_crops if (self.pretrain and FLAGS.contrastive_loss == 'swav') else 0
+            local_crops = flag_crops if self.pretrain else 0
         self.local_crops = int(local_crops) if self.pretrain else 0
-        self.local_size = int(FLAGS.swav_local_crop_size)
-        self.local_scale = (float(FLAGS.swav_local_crop_min_scale), float(FLAGS.swav_local_crop_max_scale))
+        self.local_size = local_size
+        self.local_scale = (lo, hi)
         self.seed = int(FLAGS.data_seed if data_seed is None else data_seed)
         self.threads = max(1, int(FLAGS.input_threads if input_threads is None else input_threads))
         self.depth = max(1, int(FLAGS.prefetch_batches if prefetch_batches is None else prefetch_batches))

@@ -156,6 +156,11 @@ _DEFS = [
     ('swav_local_crop_size', 96, int, 'MI355X build: side of the local views in pixels: at most image_size, a multiple of the stem stride.'),
     ('swav_local_crop_min_scale', 0.05, float, 'MI355X build: smallest area share of a local crop; also its min_object_covered.'),
     ('swav_local_crop_max_scale', 0.14, float, 'MI355X build: largest area share of a local crop: 0 < min < max <= 1.'),
+    # DINO multi-crop (Caron et al. 2021): L low-resolution student views through a second encoder pass, against both global teacher views
+    ('dino_local_crops', 0, int, 'MI355X build: number L of local (low-resolution) views of DINO multi-crop: 0 (off) .. 8.'),
+    ('dino_local_crop_size', 96, int, 'MI355X build: side of the DINO local views in pixels: at most image_size, a multiple of the stem stride.'),
+    ('dino_local_crop_min_scale', 0.05, float, 'MI355X build: smallest area share of a DINO local crop; also its min_object_covered.'),
+    ('dino_local_crop_max_scale', 0.14, float, 'MI355X build: largest area share of a DINO local crop: 0 < min < max <= 1.'),
     # DropBlock in the bottleneck blocks (tf2/resnet.py:81-157; the reference has the arguments of resnet() and no flag for them)
     ('dropblock_keep_probs', '', str, "MI355X build: DropBlock keep probabilities of block groups 1..4, four comma-separated values; 'none' or '1' "
                                       "switches a group off (e.g. none,none,0.9,0.9).  Default empty: no DropBlock."),
@@ -169,6 +174,20 @@ _DEFS = [
     ('knn_bank_examples', 0, int, 'MI355X build: examples of --train_split in the k-NN bank: 0 = the whole split, n > 0 = the first n positions of '
                                   'epoch_permutation(data_seed, 0, N).  --dataset=synthetic: a bank of random images, at most 8 eval batches.'),
 ]
+
+
+LOCAL_CROP_LOSSES = ('swav', 'dino')      # the losses multi-crop is built for: each has its own four flags, <loss>_local_crop*
+
+
+def local_crop_flags(flags=None):
+    """(L, size, min_scale, max_scale) of the multi-crop flags of --contrastive_loss ('swav' or 'dino'), L = 0 for every other loss.
+    The flags only: run.local_crop_plan adds that fine-tuning and evaluation ignore them."""
+    flags = FLAGS if flags is None else flags
+    loss = getattr(flags, 'contrastive_loss', 'ntxent')
+    if loss not in LOCAL_CROP_LOSSES:
+        return 0, int(flags.swav_local_crop_size), float(flags.swav_local_crop_min_scale), float(flags.swav_local_crop_max_scale)
+    get = lambda name: getattr(flags, '%s_local_%s' % (loss, name))
+    return int(get('crops')), int(get('crop_size')), float(get('crop_min_scale')), float(get('crop_max_scale'))
 
 
 def parse_dropblock_keep_probs(text):

@@ -28,6 +28,8 @@ other view and a queue of keys of earlier steps; no collective) on the kernels o
 
 `add_dino_loss` is the DINO loss of Caron et al. 2021 (cross-entropy of the student's softmax over K trained prototypes against the
 centred, sharpened softmax the momentum teacher gives the other view; no collective) on the kernels of csrc/dino.hip.
+`add_dino_local_loss` is its multi-crop share: the local views of the same images against the teacher rows of both global views
+(csrc/dino_multicrop.hip for the key side, the loss-agnostic local sweeps of csrc/swav_multicrop.hip for the rest; no collective).
 
 `add_swav_loss` is the SwAV loss of Caron et al. 2020 (cross-entropy of the student's softmax over K trained prototypes against the
 Sinkhorn-Knopp code of the other view, the codes equipartitioned over the GLOBAL batch per view; one all-gather of the normalised block,
@@ -665,7 +667,62 @@ def add_dino_loss(online, target, prototypes, target_prototypes, center, student
     loss.entropy = out[1:2]
     loss.keys = keys
     loss.target_prototypes = wt
+    # what add_dino_local_loss reads for the local views of the same images
+    loss.z, loss.u, loss.row_stats, loss.center = z, u, row_stats, center
+    loss.student_temp, loss.teacher_temp = student_temp, teacher_temp
     return loss
+
+
+def add_dino_local_loss(local_online, global_loss, prototypes, strategy=None, update_prototypes=True):
+    """The multi-crop share of the DINO loss (Caron et al. 2021; the official loss with ncrops = 2 + L): every LOCAL view's student
+    softmax against the teacher rows of BOTH global views of its image.  With x = l2n(local_online) [L b, D] view-major (row v b + i =
+    local view v of image i), V = 2 + L and u_g = sum_j Pt[g, j] ws_j the teacher expectation add_dino_loss kept for global row g,
+      value = 1 / (2 (V - 1) b) sum_r [2 logsumexp_j(s_r) - x_r . (u_i + u_{b+i}) / Ts],   s_rj = x_r . ws_j / Ts,  i = r mod b.
+    The total loss of the step is global_loss.value / (V - 1) + value: every student view against every global teacher view other
+    than itself, over 2 (V - 1) terms.  The teacher sees the global views only and is stop-gradient; the centre and its key mean use
+    the global keys only.  No collective runs here.
+
+    The value and the query-side backward are the loss-agnostic ops.swav_local_fwd / swav_local_bwd_x on (x, ws, u, L, Ts); the
+    key-side backward is ops.dino_local_bwd_w (csrc/dino_multicrop.hip), which READS AGAIN the keys, the target prototypes and the
+    centre add_dino_loss read: the caller moves the centre and the target only after `backward`.
+
+    Args:
+      local_online: float32 device tensor [L b, D] = the online projection output of the L local views, view-major.
+      global_loss: the handle add_dino_loss returned for the two global views of the same b images (its keys, target_prototypes, u,
+        row_stats, center and temperatures).
+      prototypes: the online model.PrototypeHead.  It is called here again (the variable has not moved since add_dino_loss: the
+        normalised rows are bitwise the same) and its `backward` receives the gradient of the normalised rows, student and teacher
+        term together.
+      strategy: replica context or None; unused beyond the signature's symmetry: a replica's value is the share of its own rows.
+      update_prototypes: False while the prototypes are frozen: both key-side sweeps are skipped and no gradient is written.
+    Returns:
+      A loss scalar with .value and .backward(grad_scale) (-> grad_scale * dvalue/dlocal_online, [L b, D]).
+    """
+    x_raw = local_online.contiguous()
+    keys, u = global_loss.keys, global_loss.u
+    b = keys.shape[0] // 2
+    if x_raw.dim() != 2 or x_raw.shape[0] < b or x_raw.shape[0] % b:
+        raise ValueError('add_dino_local_loss: the local block holds L views of the %d images of the global loss, [L * %d, D] (got %s)'
+                         % (b, b, tuple(x_raw.shape)))
+    L = x_raw.shape[0] // b
+    if not 1 <= L <= ops.DINO_MAX_LOCAL_CROPS:
+        raise ValueError('add_dino_local_loss: the number of local views lies in [1, %d] (got %d)' % (ops.DINO_MAX_LOCAL_CROPS, L))
+    ts, tt = global_loss.student_temp, global_loss.teacher_temp
+    ws = prototypes()
+    x, inv = ops.l2norm_fwd(x_raw)
+    # row_stats [L b]: lse_s of the local rows in the base-2 domain, what dino_local_bwd_w's student sweep normalises with
+    out, row_stats, wsp = ops.swav_local_fwd(x, ws, u, L, ts)
+
+    def backward(grad_scale=1.0):
+        dx = ops.l2norm_bwd(x, inv, ops.swav_local_bwd_x(x, ws, u, L, ts, row_stats, grad_scale, wsp))
+        if update_prototypes:
+            prototypes.backward(ops.dino_local_bwd_w(x, keys, ws, global_loss.target_prototypes, global_loss.center, L, ts, tt,
+                                                     row_stats, global_loss.row_stats, grad_scale))
+        else:
+            prototypes.saved = None
+        return dx
+
+    return _Loss(out[0:1], backward)
 
 
 def add_swav_loss(online, prototypes, temperature=0.1, epsilon=0.05, sinkhorn_iterations=3, strategy=None, overlap=None,

@@ -1151,6 +1151,69 @@ def swav_local_bwd_w(x, z, w, alpha, L, temperature, epsilon, row_stats, global_
     return dw
 
 
+# ---------------------------------------------------------------- DINO multi-crop: local rows against both global teacher rows (csrc/dino_multicrop.hip)
+# The value and the query-side backward of the local term are swav_local_fwd / swav_local_bwd_x on (x, ws, u, L, Ts) as they stand
+# (sum_j Pt[g, j] s_rj = x_r . u_g / Ts); the key-side backward below is DINO's own.
+DINO_MAX_LOCAL_CROPS = 8            # largest --dino_local_crops
+
+
+def _dino_local_shape_error(b, L, K):
+    return ValueError('dino_local: need b >= 1, L in [1, %d] and K in [2, %d] (got b = %d, L = %d, K = %d)'
+                      % (DINO_MAX_LOCAL_CROPS, DINO_MAX_OUT_DIM, b, L, K))
+
+
+def dino_local_row_splits(b, L, K):
+    """(row splits of dino_local_bwd_w's student sweep over the L b local rows, of its teacher sweep over the 2b global rows)."""
+    splits = lib().dino_local_row_splits(int(b), int(L), int(K)), lib().dino_local_teacher_row_splits(int(b), int(L), int(K))
+    if min(splits) < 1:
+        raise _dino_local_shape_error(b, L, K)
+    return splits
+
+
+def dino_local_workspace(b, L, K, D, device):
+    """Workspace of dino_local_bwd_w on L views of b images (its own: swav_local_fwd / swav_local_bwd_x keep theirs)."""
+    _dino_check_dim(D)
+    nbytes = lib().dino_local_workspace_bytes(int(b), int(L), int(K), D)
+    if nbytes == 0:
+        raise _dino_local_shape_error(b, L, K)
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def dino_local_bwd_w(x, k, ws, wt, center, L, student_temp, teacher_temp, local_row_stats, global_row_stats, grad_scale,
+                     workspace=None):
+    """dws [K, D] = grad_scale * d(local value) / dws: the student term over the local rows x [L b, D] and the teacher term over the
+    global keys k [2b, D], whose teacher rows are recomputed from wt, center and the lse_t of dino_fwd's row_stats [2b, 2] -- each
+    row's OWN entry.  local_row_stats [L b] is what swav_local_fwd(x, ws, u, L, student_temp) returned: lse_s per local row, base 2."""
+    if int(L) != L or not 1 <= int(L) <= DINO_MAX_LOCAL_CROPS:
+        raise ValueError('dino_local_bwd_w: the number of local views lies in [1, %d] (got %r)' % (DINO_MAX_LOCAL_CROPS, L))
+    L = int(L)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < L or x.shape[0] % L or not x.is_contiguous():
+        raise ValueError('dino_local_bwd_w: need a contiguous float32 block of the %d local views, [%d b, D] with b >= 1 (got %s %s)'
+                         % (L, L, tuple(x.shape), x.dtype))
+    b, D = x.shape[0] // L, x.shape[1]
+    _dino_check_dim(D)
+    if k.dtype != torch.float32 or tuple(k.shape) != (2 * b, D) or not k.is_contiguous():
+        raise ValueError('dino_local_bwd_w: the global block is the contiguous float32 %s block of keys dino_fwd read for the same '
+                         'images (got %s %s)' % ((2 * b, D), tuple(k.shape), k.dtype))
+    _, K, _ = _dino_check(k, k, ws, wt, center, student_temp, teacher_temp)
+    if K > DINO_MAX_OUT_DIM:
+        raise _dino_local_shape_error(b, L, K)
+    _swav_local_check_stats('dino_local_bwd_w', local_row_stats, L * b)
+    _dino_check_stats('dino_local_bwd_w', global_row_stats, 2 * b)
+    if not global_row_stats.is_contiguous():
+        raise ValueError('dino_local_bwd_w: the row_stats of dino_fwd must be contiguous')
+    if workspace is None:
+        workspace = dino_local_workspace(b, L, K, D, x.device)
+    if workspace.numel() * workspace.element_size() < lib().dino_local_workspace_bytes(b, L, K, D):
+        raise ValueError('dino_local: the workspace is smaller than dino_local_workspace(%d, %d, %d, %d)' % (b, L, K, D))
+    dws = torch.empty_like(ws)
+    _launch('dino_local_bwd_w', 4.0 * (L * b + 2 * b) * K * D, 4.0 * (L * b + 3 * b + 3 * K) * D,
+            lambda: lib().dino_local_bwd_w(_p(x), _p(k), _p(ws), _p(wt), _p(center), b, L, K, D, float(student_temp),
+                                           float(teacher_temp), _p(local_row_stats), _p(global_row_stats), float(grad_scale), _p(dws),
+                                           _p(workspace), _s()))
+    return dws
+
+
 # ---------------------------------------------------------------- weighted k-NN evaluation (csrc/knn.hip)
 KNN_SLAB = 4096                     # bank rows one workgroup of the top-k kernel reduces to k candidates (simclr_knn_slab_rows)
 KNN_MAX_K = 256                     # a query's candidate list is sorted in LDS

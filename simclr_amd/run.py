@@ -23,7 +23,7 @@ from . import model as model_lib
 from . import objective as obj_lib
 from . import pretrain_losses as loss_lib
 from .comm import Strategy, collectives_on, num_replicas
-from .flags import FLAGS, check_dropblock_flags
+from .flags import FLAGS, check_dropblock_flags, local_crop_flags
 from .resnet import RT, join_wgrad_stream, set_dropblock_step
 
 
@@ -72,11 +72,53 @@ def check_swav_local_flags():
     return L
 
 
+def dino_local_crops():
+    """L of DINO multi-crop in a pretraining run (0: off); train_mode=finetune and --mode=eval ignore the flags."""
+    if FLAGS.train_mode != 'pretrain' or FLAGS.mode == 'eval':
+        return 0
+    return int(getattr(FLAGS, 'dino_local_crops', 0))
+
+
+def check_dino_local_flags():
+    """check_swav_local_flags for the --dino_local_crop* flags.  Returns L."""
+    L = dino_local_crops()
+    if not 0 <= L <= ops.DINO_MAX_LOCAL_CROPS:
+        raise ValueError('--dino_local_crops must lie in [0, %d] (got %r)' % (ops.DINO_MAX_LOCAL_CROPS, FLAGS.dino_local_crops))
+    if L == 0:
+        return 0
+    if FLAGS.contrastive_loss != 'dino':
+        raise ValueError('--dino_local_crops belongs to --contrastive_loss=dino (got %r); SwAV has --swav_local_crops, no other loss '
+                         'has multi-crop' % FLAGS.contrastive_loss)
+    size = FLAGS.dino_local_crop_size
+    stride = 1 if FLAGS.image_size <= 32 else 2           # the stem's: resnet.Resnet.stem_kernel_stride
+    if not 1 <= size <= FLAGS.image_size or size % stride:
+        raise ValueError('--dino_local_crop_size must lie in [1, image_size = %d] and be a multiple of the stem stride %d (got %r)'
+                         % (FLAGS.image_size, stride, size))
+    lo, hi = FLAGS.dino_local_crop_min_scale, FLAGS.dino_local_crop_max_scale
+    if not 0.0 < lo < hi <= 1.0:                          # (NaN fails the comparison)
+        raise ValueError('the local crop scales need 0 < --dino_local_crop_min_scale < --dino_local_crop_max_scale <= 1 (got %r, %r)'
+                         % (lo, hi))
+    if any(p is not None for p in (check_dropblock_flags()[0] or [])):
+        raise ValueError('--dino_local_crops with an active DropBlock is refused: the noise of a site is a function of (seed, step, '
+                         'replica, site) and would repeat in the second encoder pass')
+    return L
+
+
+def local_crop_plan():
+    """(L, size, min_scale, max_scale) of the active multi-crop: the --swav_local_crop* flags under --contrastive_loss=swav, the
+    --dino_local_crop* flags under dino, L = 0 under every other loss, in fine-tuning and in --mode=eval."""
+    L, size, lo, hi = local_crop_flags()
+    if FLAGS.train_mode != 'pretrain' or FLAGS.mode == 'eval':
+        L = 0
+    return L, size, lo, hi
+
+
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover: the multi-crop flags,
     the loss name, then the check of that loss's row of pretrain_losses.LOSSES (a pretraining run outside --mode=eval only).
     Returns True for the generalized loss in such a run, False otherwise (model.pretrain_loss() tells the others)."""
     check_swav_local_flags()
+    check_dino_local_flags()
     if FLAGS.contrastive_loss not in loss_lib.LOSSES:
         raise ValueError("--contrastive_loss must be 'dino' or 'ntxent' or 'generalized' or 'supcon' or 'barlow' or 'byol' or 'mocov2' (got %r), "
                          "or 'swav' or 'vicreg'" % FLAGS.contrastive_loss)
@@ -241,6 +283,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     blurs the local views at their own size, forwards them in training mode (BatchNorm on statistics of its own), add_swav_local_loss
     against pass A's codes, backward without the supervised head; the saved buffer is added back, the gradients are all-reduced ONCE
     (after the add: the sum is linear, one reduction is cheaper than two), then one optimizer step.
+    --dino_local_crops=L > 0: the same two passes under --contrastive_loss=dino, pass B's loss being add_dino_local_loss against pass
+    A's teacher rows.  The teacher sees the global views only: the target forward, the keys, their mean and the centre are pass A's.
+    target.update(step), the wait for the mean and the centre update stay after the optimizer step, that is after pass B, whose
+    backward reads the centre, the keys and the target prototypes again.  train/dino_teacher_entropy is pass A's.
     teacher: a callable features -> SupLogits (model.Teacher, or a stub).  The step is then the fine-tuning step with the supervised
     loss replaced by add_kd_loss(student logits, teacher(features), FLAGS.distill_temperature) -- the self-training step of
     tf2/colabs/distillation_self_training.ipynb:908-919; labels are not read."""
@@ -266,7 +312,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
-    local_crops = swav_local_crops() if name == 'swav' else 0
+    local_crops = local_crop_plan()[0]
 
     def single_step(features, labels):
         # optimizer.iterations is a host int that apply_gradients increments: every "before the increment" read of the step is this
@@ -276,8 +322,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         if local_crops:
             features, local_features = features
             if local_features.dim() != 4 or local_features.shape[3] != 3 * local_crops or local_features.shape[0] != features.shape[0]:
-                raise ValueError('--swav_local_crops=%d: the step reads (globals [b, H, W, 6], locals [b, h, h, %d]) (got locals %s)'
-                                 % (local_crops, 3 * local_crops, tuple(local_features.shape)))
+                raise ValueError('--%s_local_crops=%d: the step reads (globals [b, H, W, 6], locals [b, h, h, %d]) (got locals %s)'
+                                 % (name, local_crops, 3 * local_crops, tuple(local_features.shape)))
         ops.begin_step(features.device)
         if dropblock:
             # the noise of a DropBlock site is a function of (dropblock_seed, global step, replica, site): the restored step continues it
@@ -372,9 +418,15 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 local_features = data_util.batch_random_blur_tensor(local_features, local_features.shape[1], local_features.shape[2])
             local_outputs, _ = model(local_features, training=True, blur=False, supervised=False)
             global_loss = con_loss
-            local_loss = obj_lib.add_swav_local_loss(local_outputs, global_loss, model.prototype_head,
-                                                     temperature=FLAGS.swav_temperature, strategy=strategy,
-                                                     update_prototypes=not c.frozen)
+            if name == 'dino':
+                # the teacher rows are pass A's (the global keys, the target prototypes and the centre as they stand: all three move
+                # only after the optimizer step below); frozen last layer: pass B writes no prototype gradient either
+                local_loss = obj_lib.add_dino_local_loss(local_outputs, global_loss, model.prototype_head, strategy=strategy,
+                                                         update_prototypes=not c.frozen)
+            else:
+                local_loss = obj_lib.add_swav_local_loss(local_outputs, global_loss, model.prototype_head,
+                                                         temperature=FLAGS.swav_temperature, strategy=strategy,
+                                                         update_prototypes=not c.frozen)
             model.backward(local_loss.backward(1.0 / R), None, on_stage=None)
             join_wgrad_stream()
             ops.axpy_f32(1.0, saved_grads, model._flat_grads)
@@ -383,7 +435,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             ops.accumulate_scalars([global_loss.value.reshape(-1)[:1], local_loss.value.reshape(-1)[:1]], scales=[share, 1.0],
                                    total=total_con, total_mask=3)
             con_loss = obj_lib._Loss(total_con, None)
-            con_loss.entropy, con_loss.alpha = global_loss.entropy, global_loss.alpha
+            con_loss.entropy = global_loss.entropy                                 # pass A's: the teacher / the codes see the globals only
+            if name == 'dino':
+                con_loss.keys, con_loss.target_prototypes = global_loss.keys, global_loss.target_prototypes
+            else:
+                con_loss.alpha = global_loss.alpha
             con_loss.global_loss, con_loss.local_loss = global_loss, local_loss
         sync.wait()
         if c.frozen:
@@ -468,7 +524,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
 
 def synthetic_batches(batch, image_size, num_classes, device, seed=0, pool=2, views=2, local_crops=0, local_size=None):
     """i.i.d. U[0,1) two-view batches [b, H, W, 6] + one-hot labels; views=1: the single-view
-    [b, H, W, 3] batches of train_mode=finetune (tf2/data.py:52-58).  local_crops = L > 0 (SwAV multi-crop): features =
+    [b, H, W, 3] batches of train_mode=finetune (tf2/data.py:52-58).  local_crops = L > 0 (SwAV / DINO multi-crop): features =
     (globals [b, H, W, 6], locals [b, h, h, 3L]); the local tensors are drawn AFTER every global tensor and label from the same
     seeded generator, so the globals and labels are those of a run without local crops."""
     g = torch.Generator(device='cpu').manual_seed(seed)
@@ -703,7 +759,7 @@ def main(argv):
     if builder is None:
         data = synthetic_batches(per_replica, FLAGS.image_size, num_classes, RT.device, seed=rep,
                                  views=1 if FLAGS.train_mode == 'finetune' else 2,
-                                 local_crops=swav_local_crops() if swav_loss_on() else 0, local_size=FLAGS.swav_local_crop_size)
+                                 local_crops=local_crop_plan()[0], local_size=local_crop_plan()[1])
     manager = None
     summary_writer = metrics.JsonlSummaryWriter(FLAGS.model_dir) if (FLAGS.model_dir and rank0) else None   # :526
     log_every = FLAGS.checkpoint_steps or 10

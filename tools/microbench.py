@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -648,6 +648,45 @@ def main():
                       row['local_over_swav_fwd'], row['local_over_swav_fwd_expected']), flush=True)
             res.append(row)
             del q, x, wsn, sws, lws, mws
+    if 'dino_multicrop' in what:
+        # DINO multi-crop (csrc/dino_multicrop.hip): dino_local_bwd_w at L views of b images, beside swav_local_bwd_w at the same shape
+        # and dino_bwd_w on the 2b global rows, in the same run.  Each figure is the median of 5 timeit() calls with their min / max as
+        # the spread.  Matrix FLOPs: 4 (L b + 2 b) K D in both local key-side calls -- expected dino_local / swav_local about 1.
+        def med5(fn):
+            ts = sorted(timeit(fn, args.iters) for _ in range(5))
+            return dict(us=ts[2], min_us=ts[0], max_us=ts[4])
+        for (b, L, K, D) in [(512, 6, 8192, 128), (512, 6, 65536, 128), (512, 6, 65536, 256)]:
+            q = torch.nn.functional.normalize(torch.randn(2 * b, D, device=dev), dim=1)
+            k = torch.nn.functional.normalize(q + 0.5 * torch.randn(2 * b, D, device=dev) / D ** 0.5, dim=1)
+            x = torch.nn.functional.normalize(q[:b].repeat(L, 1) + 0.7 * torch.randn(L * b, D, device=dev) / D ** 0.5, dim=1)
+            wsn = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            wtn = torch.nn.functional.normalize(wsn + 0.1 * torch.randn(K, D, device=dev) / D ** 0.5, dim=1)
+            cen = 0.05 * torch.randn(K, device=dev)
+            dws = ops.dino_workspace(2 * b, K, D, dev)
+            _, drs, du, _ = ops.dino_fwd(q, k, wsn, wtn, cen, 0.1, 0.04, workspace=dws)
+            sws = ops.swav_workspace(2 * b, K, D, dev)
+            alpha = ops.swav_sinkhorn(q, wsn, 0.05, 3, workspace=sws)
+            _, srs, su, _ = ops.swav_fwd(q, wsn, alpha, 0.1, 0.05, workspace=sws)
+            mws = ops.swav_local_workspace(b, L, K, D, dev)
+            _, mrs, _ = ops.swav_local_fwd(x, wsn, du, L, 0.1, workspace=mws)
+            lws = ops.dino_local_workspace(b, L, K, D, dev)
+            flops = 4.0 * (L * b + 2 * b) * K * D
+            t_d = med5(lambda: ops.dino_local_bwd_w(x, k, wsn, wtn, cen, L, 0.1, 0.04, mrs, drs, 1.0, lws))
+            t_s = med5(lambda: ops.swav_local_bwd_w(x, q, wsn, alpha, L, 0.1, 0.05, mrs, srs, 1.0, mws))
+            t_g = med5(lambda: ops.dino_bwd_w(q, k, wsn, wtn, cen, 0.1, 0.04, drs, 1.0, dws))
+            t_f = med5(lambda: ops.swav_local_fwd(x, wsn, du, L, 0.1, workspace=mws))
+            t_x = med5(lambda: ops.swav_local_bwd_x(x, wsn, du, L, 0.1, mrs, 1.0, mws))
+            row = dict(layer='dino_multicrop b%d L%d K%d D%d' % (b, L, K, D), local_bwd_w_flops=flops,
+                       row_splits=list(ops.dino_local_row_splits(b, L, K)), dino_local_bwd_w=t_d, swav_local_bwd_w=t_s, dino_bwd_w=t_g,
+                       local_fwd=t_f, local_bwd_x=t_x, dino_local_bwd_w_tfs=flops / t_d['us'] / 1e6,
+                       dino_local_over_swav_local=t_d['us'] / t_s['us'], dino_local_over_swav_local_expected=1.0,
+                       local_loss_launches_us=t_f['us'] + t_x['us'] + t_d['us'])
+            print('dino_multicrop b=%d L=%d K=%d D=%d: dino_local_bwd_w %.0f us [%.0f, %.0f] (%.1f TF/s) | swav_local_bwd_w %.0f us [%.0f, %.0f] '
+                  '| dino_bwd_w %.0f us [%.0f, %.0f] | local fwd %.0f us bwd_x %.0f us | dino_local / swav_local %.3f (matrix work: 1)' % (
+                      b, L, K, D, t_d['us'], t_d['min_us'], t_d['max_us'], row['dino_local_bwd_w_tfs'], t_s['us'], t_s['min_us'], t_s['max_us'],
+                      t_g['us'], t_g['min_us'], t_g['max_us'], t_f['us'], t_x['us'], row['dino_local_over_swav_local']), flush=True)
+            res.append(row)
+            del q, k, x, wsn, wtn, cen, dws, sws, mws, lws
     if 'knn' in what:
         # weighted k-NN evaluation (csrc/knn.hip): the fused similarity GEMM + streaming top-k and the vote at one ImageNet eval batch
         # against a 10 % bank, the full bank and a projection-width bank, beside simclr_ntxent_wide_logits_ab at the same (Q, N, D) --
