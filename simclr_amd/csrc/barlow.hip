@@ -14,156 +14,25 @@
 // and only local rows get one, so no reduce-scatter follows; the standardisation backward needs the column sums of g and g o zhat
 // over the global batch, which the caller all-reduces between simclr_bt_bwd and simclr_bt_apply.
 //
-// Matrix products run on the exact fp32-input MFMA (v_mfma_f32_16x16x4_f32) in the LDS-tiled form of the wide NT-Xent kernels
-// (csrc/ntxent.hip): a workgroup of 4 waves (2 x 2) owns an E x E output tile, E = 32 W, operands are staged
+// Matrix products run on the exact fp32-input MFMA (v_mfma_f32_16x16x4_f32) as the staged-k Gram tile of csrc/gram_tile.h, which the
+// wide NT-Xent kernels share: a workgroup of 4 waves (2 x 2) owns an E x E output tile, E = 32 W, operands are staged
 // global -> registers -> LDS one k-chunk ahead, and loads past the logical extents read zeros.  Every sum over rows, columns or tiles
 // runs in a fixed order (the column statistics, the tile sums and the subtraction of sum c_i^2 in double): no atomics, results are
 // bitwise repeatable and, for everything computed from the gathered block alone, identical on every replica.
-#include "common.h"
+#include "gram_tile.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int kBtKc = 32;   // k per LDS stage
-
-template <int E> constexpr int bt_op_floats() { return E * (kBtKc + 4); }   // LDS floats per staged operand (RK pitch kBtKc+4, KR pitch E+4)
-
-// the float4s of one E x kBtKc operand chunk this thread moves: RK -> (row r, k..k+3) of X[r * ld + k], KR -> (k, rows r..r+3) of
-// X[k * ld + r]; zeros out of range
-template <int E, bool KR>
-__device__ __forceinline__ void bt_fetch(float4* pf, const float* __restrict__ X, int ld, int rlim, int klim, int r0, int k0, bool vec,
-                                         int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kBtKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    const int r = KR ? (idx % (E / 4)) * 4 : idx / (kBtKc / 4);
-    const int k = KR ? idx / (E / 4) : (idx % (kBtKc / 4)) * 4;
-    const int gr = r0 + r, gk = k0 + k;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (KR) {
-      if (gk < klim) {
-        const float* p = X + (size_t)gk * ld + gr;
-        if (vec && gr + 3 < rlim) v = *(const float4*)p;
-        else {
-          if (gr < rlim) v.x = p[0];
-          if (gr + 1 < rlim) v.y = p[1];
-          if (gr + 2 < rlim) v.z = p[2];
-          if (gr + 3 < rlim) v.w = p[3];
-        }
-      }
-    } else {
-      if (gr < rlim) {
-        const float* p = X + (size_t)gr * ld + gk;
-        if (vec && gk + 3 < klim) v = *(const float4*)p;
-        else {
-          if (gk < klim) v.x = p[0];
-          if (gk + 1 < klim) v.y = p[1];
-          if (gk + 2 < klim) v.z = p[2];
-          if (gk + 3 < klim) v.w = p[3];
-        }
-      }
-    }
-    pf[j] = v;
-  }
-}
-template <int E, bool KR>
-__device__ __forceinline__ void bt_store(float* s, const float4* pf, int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kBtKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    if (KR) *(float4*)(s + (idx / (E / 4)) * (E + 4) + (idx % (E / 4)) * 4) = pf[j];
-    else *(float4*)(s + (idx / (kBtKc / 4)) * (kBtKc + 4) + (idx % (kBtKc / 4)) * 4) = pf[j];
-  }
-}
-// MFMA operand of tile row rr for the 16-k group kq: component j = X(rr, 16 kq + 4 g + j) -- k-slot g of MFMA step j (both operands
-// use this k order).  The pitches (kBtKc+4, E+4 = 4 mod 32 dwords) keep both reads free of bank conflicts.
-template <int E, bool KR>
-__device__ __forceinline__ float4 bt_frag(const float* s, int rr, int kq, int g) {
-  if (KR) {
-    const float* p = s + (16 * kq + 4 * g) * (E + 4) + rr;
-    return make_float4(p[0], p[E + 4], p[2 * (E + 4)], p[3 * (E + 4)]);
-  }
-  return *(const float4*)(s + rr * (kBtKc + 4) + 16 * kq + 4 * g);
-}
-
-// acc[i][w][r] = sum_k A(m, k) B(c, k) for m = m0 + 16 W wm + 16 i + 4 g + r, c = n0 + 16 W wn + 16 w + fl (wm = wave & 1,
-// wn = wave >> 1): rows on the MFMA's A side, columns on the lane.  k runs 0 .. K-1 in a fixed order.  The first LDS store sits
-// behind a barrier, so the function may be called twice in a row on the same LDS.
-template <int W, bool A_KR, bool B_KR>
-__device__ __forceinline__ void bt_tile(float* lds, const float* __restrict__ A, int lda, int mlim, bool avec,
-                                        const float* __restrict__ B, int ldb, int nlim, bool bvec, int K, int m0, int n0,
-                                        f32x4 (&acc)[W][W]) {
-  constexpr int E = 32 * W;
-  float* sa = lds;
-  float* sb = lds + bt_op_floats<E>();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
-#pragma unroll
-  for (int i = 0; i < W; ++i)
-#pragma unroll
-    for (int w = 0; w < W; ++w) acc[i][w] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float4 pa[E * kBtKc / 1024], pb[E * kBtKc / 1024];
-  const int nst = (K + kBtKc - 1) / kBtKc;
-  if (nst > 0) {
-    bt_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, 0, avec, tid);
-    bt_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, 0, bvec, tid);
-  }
-  for (int st = 0; st < nst; ++st) {
-    __syncthreads();
-    bt_store<E, A_KR>(sa, pa, tid);
-    bt_store<E, B_KR>(sb, pb, tid);
-    __syncthreads();
-    if (st + 1 < nst) {
-      bt_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, (st + 1) * kBtKc, avec, tid);
-      bt_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, (st + 1) * kBtKc, bvec, tid);
-    }
-#pragma unroll
-    for (int kq = 0; kq < kBtKc / 16; ++kq) {
-      float4 a[W], b[W];
-#pragma unroll
-      for (int i = 0; i < W; ++i) a[i] = bt_frag<E, A_KR>(sa, 16 * W * wm + 16 * i + fl, kq, g);
-#pragma unroll
-      for (int w = 0; w < W; ++w) b[w] = bt_frag<E, B_KR>(sb, 16 * W * wn + 16 * w + fl, kq, g);
-#pragma unroll
-      for (int i = 0; i < W; ++i)
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b[w].x, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b[w].y, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b[w].z, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b[w].w, acc[i][w], 0, 0, 0);
-        }
-    }
-  }
-}
-
-// ---- column reductions: a workgroup owns 32 columns; thread (q = tid & 7, rg = tid >> 3) walks rows rg, rg + 32, ... of the column
-// quad 4q .. 4q+3 with 16-byte loads and sums in double; the 32 row groups of a column are then added in the order 0 .. 31.
-constexpr int kBtCols = 32;
-// v[4] of every thread -> res[32] (column totals); sh holds 32 x 32 doubles.  Ends with a barrier: res is readable by all threads.
-__device__ __forceinline__ void bt_col_reduce(const double (&v)[4], double* sh, double* res) {
-  const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  __syncthreads();     // sh / res may still be read from an earlier reduction
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sh[rg * kBtCols + 4 * q + k] = v[k];
-  __syncthreads();
-  if (tid < kBtCols) {
-    double s = 0.0;
-    for (int r = 0; r < 32; ++r) s += sh[r * kBtCols + tid];
-    res[tid] = s;
-  }
-  __syncthreads();
-}
-
 // Standardise: blockIdx.y = view, blockIdx.x = 32-column group.  Two passes for the statistics (mean, then centred squares), a third
 // writes zhat = (h - mu) * rstd.  N = 1 gives var = 0 and zhat = 0.
 __global__ __launch_bounds__(256) void bt_standardize(const float* __restrict__ h_all, int N, int D, double eps, float* __restrict__ zhat_all,
                                                       float* __restrict__ rstd) {
-  __shared__ double sh[32 * kBtCols];
-  __shared__ double res[kBtCols];
+  __shared__ double sh[32 * gram_tile::kCols];
+  __shared__ double res[gram_tile::kCols];
   const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  const int j0 = blockIdx.x * kBtCols + 4 * q;
+  const int j0 = blockIdx.x * gram_tile::kCols + 4 * q;
   const float* h = h_all + (size_t)blockIdx.y * N * D + j0;
   float* z = zhat_all + (size_t)blockIdx.y * N * D + j0;
   double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -171,7 +40,7 @@ __global__ __launch_bounds__(256) void bt_standardize(const float* __restrict__ 
     const float4 x = *(const float4*)(h + (size_t)a * D);
     v[0] += (double)x.x; v[1] += (double)x.y; v[2] += (double)x.z; v[3] += (double)x.w;
   }
-  bt_col_reduce(v, sh, res);
+  gram_tile::col_reduce(v, sh, res);
   double mu[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) { mu[k] = res[4 * q + k] / (double)N; v[k] = 0.0; }
@@ -180,7 +49,7 @@ __global__ __launch_bounds__(256) void bt_standardize(const float* __restrict__ 
     const double d0 = (double)x.x - mu[0], d1 = (double)x.y - mu[1], d2 = (double)x.z - mu[2], d3 = (double)x.w - mu[3];
     v[0] += d0 * d0; v[1] += d1 * d1; v[2] += d2 * d2; v[3] += d3 * d3;
   }
-  bt_col_reduce(v, sh, res);
+  gram_tile::col_reduce(v, sh, res);
   double rs[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) rs[k] = 1.0 / sqrt(res[4 * q + k] / (double)N + eps);
@@ -194,10 +63,10 @@ __global__ __launch_bounds__(256) void bt_standardize(const float* __restrict__ 
 
 // c[j] = (1 / N) sum_a zhat1[a, j] zhat2[a, j] over all N rows: blockIdx.x = 32-column group.
 __global__ __launch_bounds__(256) void bt_cdiag(const float* __restrict__ zhat_all, int N, int D, double* __restrict__ c) {
-  __shared__ double sh[32 * kBtCols];
-  __shared__ double res[kBtCols];
+  __shared__ double sh[32 * gram_tile::kCols];
+  __shared__ double res[gram_tile::kCols];
   const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  const int j0 = blockIdx.x * kBtCols + 4 * q;
+  const int j0 = blockIdx.x * gram_tile::kCols + 4 * q;
   const float* z1 = zhat_all + j0;
   const float* z2 = zhat_all + (size_t)N * D + j0;
   double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -206,8 +75,8 @@ __global__ __launch_bounds__(256) void bt_cdiag(const float* __restrict__ zhat_a
     v[0] += (double)x.x * (double)y.x; v[1] += (double)x.y * (double)y.y;
     v[2] += (double)x.z * (double)y.z; v[3] += (double)x.w * (double)y.w;
   }
-  bt_col_reduce(v, sh, res);
-  if (tid < kBtCols) c[blockIdx.x * kBtCols + tid] = res[tid] / (double)N;
+  gram_tile::col_reduce(v, sh, res);
+  if (tid < gram_tile::kCols) c[blockIdx.x * gram_tile::kCols + tid] = res[tid] / (double)N;
 }
 
 // Gram forward: blockIdx.x = tile of global columns b (MFMA rows: four consecutive b per lane -> 16-byte stores), blockIdx.y = tile
@@ -217,16 +86,16 @@ __global__ __launch_bounds__(256) void bt_cdiag(const float* __restrict__ zhat_a
 template <int W>
 __global__ __launch_bounds__(256) void bt_gram(const float* __restrict__ zhat_all, int n, int N, int D, int rank, int vec,
                                                float* __restrict__ gram, int ldg, int rows_pad, double* __restrict__ tilesum) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * bt_op_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   __shared__ double wsum[4];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
   f32x4 acc1[W][W], acc2[W][W];
-  bt_tile<W, false, false>(lds, zhat_all, D, N, vec, zhat_all + (size_t)rank * n * D, D, n, vec, D, m0, n0, acc1);
-  bt_tile<W, false, false>(lds, zhat_all + (size_t)N * D, D, N, vec, zhat_all + ((size_t)N + (size_t)rank * n) * D, D, n, vec, D, m0, n0,
-                           acc2);
+  gram_tile::tile<W, false, false>(lds, zhat_all, D, N, vec, zhat_all + (size_t)rank * n * D, D, n, vec, 0, D, m0, n0, acc1);
+  gram_tile::tile<W, false, false>(lds, zhat_all + (size_t)N * D, D, N, vec, zhat_all + ((size_t)N + (size_t)rank * n) * D, D, n, vec, 0, D,
+                                   m0, n0, acc2);
   double s = 0.0;
 #pragma unroll
   for (int w = 0; w < W; ++w) {
@@ -276,15 +145,15 @@ template <int W>
 __global__ __launch_bounds__(256) void bt_bwd_gemm(const float* __restrict__ zhat_all, const float* __restrict__ gram, int ldg, int rows_pad,
                                                    const double* __restrict__ c, int n, int N, int D, int rank, int vec, float alpha,
                                                    float beta, float lambda, float* __restrict__ g_local) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * bt_op_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int v = blockIdx.z;
   const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
   f32x4 acc[W][W];
-  bt_tile<W, true, false>(lds, zhat_all + (size_t)v * N * D, D, D, vec, gram + (size_t)(1 - v) * rows_pad * ldg, ldg, n, true, N, m0, n0,
-                          acc);
+  gram_tile::tile<W, true, false>(lds, zhat_all + (size_t)v * N * D, D, D, vec, gram + (size_t)(1 - v) * rows_pad * ldg, ldg, n, true, 0, N,
+                                  m0, n0, acc);
   const float* zo = zhat_all + ((size_t)(1 - v) * N + (size_t)rank * n) * D;
   float* out = g_local + (size_t)v * n * D;
 #pragma unroll
@@ -311,11 +180,11 @@ __global__ __launch_bounds__(256) void bt_bwd_gemm(const float* __restrict__ zha
 // colsums[v][0][j] = sum_{a local} g[v][a][j], colsums[v][1][j] = sum_{a local} g[v][a][j] zhat_v[rank n + a][j]
 __global__ __launch_bounds__(256) void bt_colsums(const float* __restrict__ g_local, const float* __restrict__ zhat_all, int n, int N, int D,
                                                   int rank, double* __restrict__ colsums) {
-  __shared__ double sh[32 * kBtCols];
-  __shared__ double res[kBtCols];
+  __shared__ double sh[32 * gram_tile::kCols];
+  __shared__ double res[gram_tile::kCols];
   const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
   const int v = blockIdx.y;
-  const int j0 = blockIdx.x * kBtCols + 4 * q;
+  const int j0 = blockIdx.x * gram_tile::kCols + 4 * q;
   const float* gp = g_local + (size_t)v * n * D + j0;
   const float* zp = zhat_all + ((size_t)v * N + (size_t)rank * n) * D + j0;
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
@@ -325,10 +194,10 @@ __global__ __launch_bounds__(256) void bt_colsums(const float* __restrict__ g_lo
     s2[0] += (double)x.x * (double)z.x; s2[1] += (double)x.y * (double)z.y;
     s2[2] += (double)x.z * (double)z.z; s2[3] += (double)x.w * (double)z.w;
   }
-  bt_col_reduce(s1, sh, res);
-  if (tid < kBtCols) colsums[((size_t)v * 2 + 0) * D + blockIdx.x * kBtCols + tid] = res[tid];
-  bt_col_reduce(s2, sh, res);
-  if (tid < kBtCols) colsums[((size_t)v * 2 + 1) * D + blockIdx.x * kBtCols + tid] = res[tid];
+  gram_tile::col_reduce(s1, sh, res);
+  if (tid < gram_tile::kCols) colsums[((size_t)v * 2 + 0) * D + blockIdx.x * gram_tile::kCols + tid] = res[tid];
+  gram_tile::col_reduce(s2, sh, res);
+  if (tid < gram_tile::kCols) colsums[((size_t)v * 2 + 1) * D + blockIdx.x * gram_tile::kCols + tid] = res[tid];
 }
 
 // Standardisation backward: dh[v][a][j] = (g - s1_j / N - zhat_v[rank n + a][j] * s2_j / N) * rstd[v][j]; one float4 per thread.
@@ -388,7 +257,7 @@ int simclr_bt_standardize(const float* h_all, int N, int D, float eps, float* zh
   SIMCLR_CHECK_ARG(eps >= 0.f, "bt_standardize: eps must be >= 0");
   SIMCLR_CHECK_ARG(h_all && zhat_all && rstd, "bt_standardize: null argument");
   SIMCLR_CHECK_ARG(bt_vec_ok(h_all) && bt_vec_ok(zhat_all) && bt_vec_ok(rstd), "bt_standardize: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(bt_standardize, dim3(D / kBtCols, 2), dim3(256), 0, stream, h_all, N, D, (double)eps, zhat_all, rstd);
+  hipLaunchKernelGGL(bt_standardize, dim3(D / gram_tile::kCols, 2), dim3(256), 0, stream, h_all, N, D, (double)eps, zhat_all, rstd);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -410,7 +279,7 @@ int simclr_bt_fwd(const float* zhat_all, int n, int N, int D, int rank, float la
   else
     hipLaunchKernelGGL(bt_gram<2>, grid, dim3(256), 0, stream, zhat_all, n, N, D, rank, 1, gram, p.ldg, p.rows_pad, tilesum);
   SIMCLR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bt_cdiag, dim3(D / kBtCols), dim3(256), 0, stream, zhat_all, N, D, c);
+  hipLaunchKernelGGL(bt_cdiag, dim3(D / gram_tile::kCols), dim3(256), 0, stream, zhat_all, N, D, c);
   SIMCLR_CHECK_LAUNCH();
   // R / N^2 = 1 / (n N)
   hipLaunchKernelGGL(bt_finish, dim3(1), dim3(256), 0, stream, c, D, tilesum, p.ntiles, 1.0 / ((double)n * (double)N), (double)lambda_weight,
@@ -442,7 +311,7 @@ int simclr_bt_bwd(const float* zhat_all, int n, int N, int D, int rank, float la
     hipLaunchKernelGGL(bt_bwd_gemm<2>, grid, dim3(256), 0, stream, zhat_all, gram, p.ldg, p.rows_pad, c, n, N, D, rank, 1, alpha, beta,
                        lambda_weight, g_local);
   SIMCLR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bt_colsums, dim3(D / kBtCols, 2), dim3(256), 0, stream, g_local, zhat_all, n, N, D, rank, colsums);
+  hipLaunchKernelGGL(bt_colsums, dim3(D / gram_tile::kCols, 2), dim3(256), 0, stream, g_local, zhat_all, n, N, D, rank, colsums);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -21,78 +21,14 @@
 //     H = log1p(r) - ln 2 * a / (1 + r) in double.  logsumexp - E[t] is never formed;
 //   * Ps - Pt is formed per element from the two rounded logits and the two saved log-sum-exps, never as 1 - ...
 //
-// MFMA mapping as in csrc/ntxent.hip: a = streamed-row fragment, b = fixed-row fragment, D[streamed = (lane >> 4) * 4 + reg][fixed = lane & 15].
-#include "common.h"
-#include <math.h>
+// MFMA mapping, tile stager (plain and PAIRED rows), S fragment and the (m, r, a) row statistics: csrc/sweep_tile.h.
+#include "sweep_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr double kLog2ed = 1.4426950408889634;
-constexpr double kLn2d = 0.6931471805599453;
-constexpr int kTile = 64;      // rows per LDS tile / fixed rows per workgroup
+using namespace sweep;
+
 constexpr int kPart = 4;       // floats per (side, split, row) statistics partial: {max, non-maximum mass, sum exp2(t - m)(t - m), -}
-
-// 64 x D tile, global -> LDS, 16-byte slots XOR-swizzled by the row; rows past the end read as zeros.  PAIRED: tile row i holds
-// source row p(row0 + i), p(r) = (r + n) mod 2n
-template <int D, bool PAIRED>
-__device__ __forceinline__ void load_tile(float* lds, const float* __restrict__ src, int row0, int nrows_total, int tid) {
-  constexpr int C = D / 4;
-  const int n = nrows_total >> 1;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int row = row0 + r;
-    if (row < nrows_total) {
-      const int srow = PAIRED ? (row < n ? row + n : row - n) : row;
-      v = *(const float4*)(src + (size_t)srow * D + c * 4);
-    }
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
-
-// S fragment: acc[r] = <tile row sub * 16 + 4 g + r, this lane's fixed row>
-template <int D>
-__device__ __forceinline__ f32x4 s_frag(const float* lds, int sub, int fl, int g, const float4* ff) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int trow = sub * 16 + fl;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.x, ff[s].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.y, ff[s].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.z, ff[s].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.w, ff[s].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// Row statistics in the base-2 domain: m = the maximum, r = sum over every element BUT one instance of the maximum of exp2(t - m),
-// a = sum over all of exp2(t - m) (t - m) (every term <= 0).  The softmax sum is 1 + r.
-__device__ __forceinline__ void mra_push(float& m, float& r, float& a, float t) {
-  if (m == -INFINITY) { m = t; return; }     // r = a = 0 already
-  if (t > m) {
-    const float dm = m - t, e = exp2f(dm), l = r + 1.f;
-    a = e * (a + l * dm);
-    r = l * e;
-    m = t;
-  } else {
-    const float x = t - m, p = exp2f(x);
-    a += p * x;
-    r += p;
-  }
-}
-__device__ __forceinline__ void mra_merge(float& m, float& r, float& a, float m2, float r2, float a2) {
-  if (m2 == -INFINITY) return;
-  if (m == -INFINITY) { m = m2; r = r2; a = a2; return; }
-  if (m2 > m) {
-    const float tm = m, tr = r, ta = a;
-    m = m2; r = r2; a = a2; m2 = tm; r2 = tr; a2 = ta;
-  }
-  const float dm = m2 - m, e = exp2f(dm), l2 = r2 + 1.f;   // the other side's maximum is one more non-maximum element here
-  r += l2 * e;
-  a += e * (a2 + l2 * dm);
-}
 
 // ---- statistics sweep: blockIdx.z = 0 the teacher (k rows against wt, centred), 1 the student (q rows against ws) ---------------------
 template <int D>
@@ -120,7 +56,7 @@ __global__ __launch_bounds__(256) void dino_stats_sweep(const float* __restrict_
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     if (tid < kTile) ldc[tid] = (teacher && kt * kTile + tid < K) ? center[kt * kTile + tid] : 0.f;
     __syncthreads();
 #pragma unroll
@@ -211,9 +147,9 @@ __global__ __launch_bounds__(256) void dino_prob_sweep(const float* __restrict__
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     if (TEACHER) {
-      load_tile<D, false>(ldv, v, kt * kTile, K, tid);
+      load_tile<D>(ldv, v, kt * kTile, K, tid);
       if (tid < kTile) ldc[tid] = (kt * kTile + tid < K) ? center[kt * kTile + tid] : 0.f;
     }
     __syncthreads();
@@ -357,8 +293,8 @@ __global__ __launch_bounds__(256) void dino_bwd_w_sweep(const float* __restrict_
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int rt = tile_begin; rt < tile_end; ++rt) {
     __syncthreads();
-    load_tile<D, false>(lds, q, rt * kTile, two_n, tid);
-    load_tile<D, true>(ldk, k, rt * kTile, two_n, tid);
+    load_tile<D>(lds, q, rt * kTile, two_n, tid);
+    load_tile<D, RowMap::kPaired>(ldk, k, rt * kTile, two_n, tid);
     if (tid < kTile) {
       const int row = rt * kTile + tid;
       const bool ok = row < two_n;
@@ -474,17 +410,7 @@ size_t off_gpart(const Plan& p) { return off_part(p) + 2 * (size_t)p.fks * p.row
 size_t off_wpart(const Plan& p, int D) { return off_gpart(p) + (size_t)p.bks * p.rows_pad * D; }
 size_t ws_words(const Plan& p, int D) { return off_wpart(p, D) + (size_t)p.rs * p.k_pad * D; }
 
-bool dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
 bool shape_ok(int two_n, int K) { return two_n >= 2 && two_n % 2 == 0 && two_n <= (1 << 22) && K >= 2 && K <= (1 << 22); }
-bool al16(const void* a) { return a && ((uintptr_t)a & 15) == 0; }
-bool al4(const void* a) { return a && ((uintptr_t)a & 3) == 0; }
-
-// more than 64 KB of dynamic LDS has to be asked for (csrc/knn.hip)
-template <typename F>
-bool raise_lds(F kernel, size_t lds) {
-  if (lds <= 65536 || simclr_dry_run()) return true;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-}
 
 }  // namespace
 

@@ -21,50 +21,16 @@
 // MFMA fragments and streams 64-row XOR-swizzled LDS tiles, the probabilities are exp2(rounded base-2 logit - saved lse), the row
 // splits are merged in a fixed order, no atomics: two calls are bitwise equal.
 //
-// MFMA mapping as in csrc/ntxent.hip: a = streamed-row fragment, b = fixed-row fragment, D[streamed = (lane >> 4) * 4 + reg][fixed = lane & 15].
-#include "common.h"
-#include <math.h>
+// MFMA mapping, tile stager (plain and WRAPPED rows) and S fragment: csrc/sweep_tile.h.  The prototypes are the fixed side.
+#include "sweep_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kTile = 64;      // rows per LDS tile / prototypes per workgroup
+using namespace sweep;
+
 constexpr int kMaxK = 1 << 20;
 constexpr int kMaxRows = 1 << 22;
 constexpr int kMaxL = 8;
-
-// 64 x D tile, global -> LDS, 16-byte slots XOR-swizzled by the row; rows past nrows read as zeros.  Tile row i holds source row
-// (row0 + i) mod period: period = nrows streams the rows themselves, period = b is m of the image of a global row
-template <int D>
-__device__ __forceinline__ void stage_tile(float* lds, const float* __restrict__ src, int row0, int nrows, int period, int tid) {
-  constexpr int C = D / 4;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int row = row0 + r;
-    if (row < nrows) {
-      const int srow = row < period ? row : row - period;        // nrows <= 2 * period
-      v = *(const float4*)(src + (size_t)srow * D + c * 4);
-    }
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
-
-// acc[r] = <tile row sub * 16 + 4 g + r, this lane's prototype>
-template <int D>
-__device__ __forceinline__ f32x4 dot_frag(const float* lds, int sub, int fl, int g, const float4* ff) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int trow = sub * 16 + fl;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.x, ff[s].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.y, ff[s].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.z, ff[s].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.w, ff[s].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 // m [b, D]: m_i = x_i + x_{b+i} + ... + x_{(L-1) b + i}, the views added in the order 0, 1, ...; one 16-byte chunk per thread
 __global__ __launch_bounds__(256) void dinol_build_m(const float* __restrict__ x, int b, int L, int D, float* __restrict__ m) {
@@ -110,8 +76,8 @@ __global__ __launch_bounds__(256) void dinol_bwd_w_sweep(const float* __restrict
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int rt = tile_begin; rt < tile_end; ++rt) {
     __syncthreads();
-    stage_tile<D>(lds, src, rt * kTile, rows, rows, tid);
-    if (TEACHER) stage_tile<D>(ldm, mult, rt * kTile, rows, b, tid);    // a tile may straddle the view boundary: per-row wrap
+    load_tile<D>(lds, src, rt * kTile, rows, tid);
+    if (TEACHER) load_tile<D, RowMap::kWrapped>(ldm, mult, rt * kTile, rows, tid);    // rows = 2b: row g reads m at g mod b
     if (tid < kTile) {
       const int row = rt * kTile + tid;
       lst[tid] = row < rows ? stats[TEACHER ? 2 * row + 1 : row] : 0.f;
@@ -119,7 +85,7 @@ __global__ __launch_bounds__(256) void dinol_bwd_w_sweep(const float* __restrict
     __syncthreads();
 #pragma unroll 1                           // a fragment set and an accumulator set live: keep the loop rolled as dino_bwd_w_sweep does
     for (int sub = 0; sub < 4; ++sub) {
-      const f32x4 as = dot_frag<D>(lds, sub, fl, g, ff);
+      const f32x4 as = s_frag<D>(lds, sub, fl, g, ff);
       const int row0 = rt * kTile + sub * 16 + g * 4;  // streamed row of as[0]
       const float4 l4 = *(const float4*)(lst + sub * 16 + 4 * g);
       const float ll[4] = {l4.x, l4.y, l4.z, l4.w};
@@ -194,18 +160,8 @@ size_t off_spart(const Plan& p, int D) { return (size_t)p.b_pad * D; }
 size_t off_tpart(const Plan& p, int D) { return off_spart(p, D) + (size_t)p.rs * p.k_pad * D; }
 size_t total_words(const Plan& p, int D) { return off_tpart(p, D) + (size_t)p.ts * p.k_pad * D; }
 
-bool dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
 bool shape_ok(int b, int L, int K) {
   return b >= 1 && L >= 1 && L <= kMaxL && (long long)b * L <= kMaxRows && 2LL * b <= kMaxRows && K >= 2 && K <= kMaxK;
-}
-bool pos_finite(float x) { return x > 0.f && x <= 3.0e38f; }          // (NaN fails the comparison)
-bool aligned(const void* a, uintptr_t n) { return a && ((uintptr_t)a & (n - 1)) == 0; }
-
-// more than 64 KB of dynamic LDS has to be asked for (csrc/knn.hip)
-template <typename F>
-bool raise_lds(F kernel, size_t lds) {
-  if (lds <= 65536 || simclr_dry_run()) return true;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
 }  // namespace
@@ -233,8 +189,8 @@ int simclr_dino_local_bwd_w(const float* x, const float* k, const float* ws, con
   SIMCLR_CHECK_ARG(dim_ok(D), "dino_local_bwd_w: D must be 64/128/256 (got %d)", D);
   SIMCLR_CHECK_ARG(shape_ok(b, L, K), "dino_local_bwd_w: need b >= 1, L in [1, 8] and K in [2, 1048576] (b=%d L=%d K=%d)", b, L, K);
   SIMCLR_CHECK_ARG(pos_finite(student_temp) && pos_finite(teacher_temp), "dino_local_bwd_w: the temperatures must be > 0 and finite");
-  SIMCLR_CHECK_ARG(aligned(x, 16) && aligned(k, 16) && aligned(ws, 16) && aligned(wt, 16) && aligned(dws, 16) && aligned(workspace, 16) &&
-                       aligned(center, 4) && aligned(local_row_stats, 4) && aligned(global_row_stats, 8),
+  SIMCLR_CHECK_ARG(al16(x) && al16(k) && al16(ws) && al16(wt) && al16(dws) && al16(workspace) && al4(center) && al4(local_row_stats) &&
+                       al8(global_row_stats),
                    "dino_local_bwd_w: null argument, or x / k / ws / wt / dws / workspace not 16-byte aligned");
   const Plan p = make_plan(b, L, K);
   float* wsp = (float*)workspace;

@@ -18,53 +18,15 @@
 //    the matched differences back in ROW order: the gradient of mean((Q_sorted - P_sorted)^2) wrt the projections.  Equal keys are
 //    ordered by row index (numpy.argsort(kind='stable')): the network compares (key, index) pairs.
 //
-// MFMA mapping as in csrc/ntxent.hip: a = streamed-row fragment, b = fixed-row fragment, D[streamed = (lane >> 4) * 4 + reg][fixed = lane & 15].
-#include "common.h"
-#include <math.h>
+// MFMA mapping, tile stager, S fragment and online (max, sum): csrc/sweep_tile.h.
+#include "sweep_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr double kLn2d = 0.6931471805599453;
-constexpr int kTile = 64;      // rows per LDS tile / fixed rows per workgroup
+using namespace sweep;
+
 constexpr int kSortThreads = 1024;
 constexpr int kSortMaxM = 8192;
-
-// 64 x D tile, global -> LDS, 16-byte slots XOR-swizzled by the row; rows past the end read as zeros
-template <int D>
-__device__ __forceinline__ void load_tile(float* lds, const float* __restrict__ src, int row0, int nrows_total, int tid) {
-  constexpr int C = D / 4;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row0 + r < nrows_total) v = *(const float4*)(src + (size_t)(row0 + r) * D + c * 4);
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
-
-// S fragment: acc[r] = <tile row sub * 16 + 4 g + r, this lane's fixed row>
-template <int D>
-__device__ __forceinline__ f32x4 s_frag(const float* lds, int sub, int fl, int g, const float4* ff) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int trow = sub * 16 + fl;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.x, ff[s].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.y, ff[s].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.z, ff[s].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.w, ff[s].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// online (max, sum) merge in the base-2 domain
-__device__ __forceinline__ void ml_merge(float& m, float& l, float m2, float l2) {
-  const float mn = fmaxf(m, m2);
-  const float a = (m == -INFINITY) ? 0.f : l * exp2f(m - mn);
-  const float b = (m2 == -INFINITY) ? 0.f : l2 * exp2f(m2 - mn);
-  m = mn; l = a + b;
-}
 
 // ---- forward: part[split][row] = {running max, sum of exp2} of the logits * log2(e) over the split's key columns -------------------
 template <int D>

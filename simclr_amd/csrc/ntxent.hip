@@ -20,14 +20,18 @@
 // so D[streamed=(lane>>4)*4+reg][fixed=lane&15]: every lane owns ONE fixed row and 4
 // streamed rows per 16x16 tile -> the online softmax is lane-local; only the final
 // merge over the 4 lane groups needs shuffles (xor 16, 32).
-#include "common.h"
+//
+// The un-pipelined tile stager, the S fragment and the online (max, sum) are csrc/sweep_tile.h's; the wide path's staged-k Gram tile
+// is csrc/gram_tile.h's.
+#include "gram_tile.h"
+#include "sweep_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
+using namespace sweep;
+
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr int kTile = 64;      // rows per LDS tile / fixed rows per workgroup
 constexpr int kPartStride = 8; // floats per (split,row) partial record
 
 __device__ __forceinline__ void row_cols(int q, int n, int N, int rank, int& mask_col, int& pos_col) {
@@ -57,17 +61,7 @@ __device__ __forceinline__ void tile_store(float* lds, const float4* pf, int tid
   }
 }
 
-// un-pipelined form (the backward sweeps): each 16-byte piece goes global -> LDS straight away
-template <int D>
-__device__ __forceinline__ void load_tile(float* lds, const float* __restrict__ src, int row0, int nrows_total, int tid) {
-  constexpr int C = D / 4;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row0 + r < nrows_total) v = *(const float4*)(src + (size_t)(row0 + r) * D + c * 4);
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
+// The backward sweeps use the un-pipelined sweep::load_tile: each 16-byte piece goes global -> LDS straight away.
 
 // ---- split-fp16 sweeps (round 6, opt-in: D argument carries SIMCLR_FMT_TERMS(13)) ------------------------------------------------
 // The sweeps are bound by the fp32-input matrix pipe (v_mfma_f32_16x16x4_f32: 1/16 of the 16-bit rate).  l2-normalised rows
@@ -138,13 +132,6 @@ __device__ __forceinline__ f32x4 s_frag_f16(const float* lds, int trow, int g, c
   return acc;
 }
 
-// online (max,sum) merge in the base-2 domain
-__device__ __forceinline__ void ml_merge(float& m, float& l, float m2, float l2) {
-  float mn = fmaxf(m, m2);
-  float a = (m == -INFINITY) ? 0.f : l * exp2f(m - mn);
-  float b = (m2 == -INFINITY) ? 0.f : l2 * exp2f(m2 - mn);
-  m = mn; l = a + b;
-}
 __device__ __forceinline__ void arg_merge(float& v, int& i, float v2, int i2) {
   if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
 }
@@ -197,6 +184,8 @@ __global__ __launch_bounds__(256) void ntxent_fwd_partial(
       if constexpr (F16) {
         acc = s_frag_f16<D>(lds, trow, g, ffh, ffl);
       } else {
+      // sweep::s_frag's loop, spelled out here and in ntxent_bwd_sweeps: the call form costs this kernel 32 bytes and changes that
+      // one's register counts
 #pragma unroll
       for (int s = 0; s < D / 16; ++s) {
         float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
@@ -613,127 +602,15 @@ size_t ws_floats(int n, int N, int D) {
 // ==============================================================================
 // Wide NT-Xent: any D (proj_out_dim > 256, proj_head_mode=none: the encoder's 512 ... 8192-wide pooled output).
 // The sweeps above keep a whole D-wide row per lane in registers and a 64 x D tile in LDS, which stops at D = 256.  Here every
-// product is an LDS-tiled GEMM with a k-loop in chunks of kWKc, on the same fp32-input MFMA (exact f32) and the same formulation:
+// product is the LDS-tiled, k-staged gram_tile::tile of csrc/gram_tile.h, on the same fp32-input MFMA (exact f32) and the same formulation:
 //   forward   S = Q K^T (keys = MFMA rows, queries = lane columns) -> per (query, 16*W-key strip) partial row statistics in the
 //             forward-sweep record format -> ntxent_finalize_rows / ntxent_reduce_out (fixed-order merges, shared with the sweeps);
 //   backward  S recomputed -> dS = (softmax - onehot) * grad_scale / (n T) written ONCE as a [rows_pad_q, rows_pad_k] fp32 array
 //             (plus the entropy partials) -> dz_local = dS K and dz_all = dS^T Q as two GEMMs, each output element one MFMA chain
 //             over the whole k range (no split-k, no atomics: bitwise run-to-run deterministic).
 // A workgroup (4 waves, 2 x 2) owns an E x E output tile, E = 32 W (W = 2: 64, W = 4: 128); a wave owns W x W 16x16 blocks.
-// Operands are staged global -> registers -> LDS one chunk ahead (the loads of chunk c+1 run under the MFMAs of chunk c), each in
-// its global orientation: RK = X[r * ld + k] (row r holds k contiguous), KR = X[k * ld + r].  Loads past the logical extents read
-// zeros, so D, n and N need no padding.
+// Loads past the logical extents read zeros, so D, n and N need no padding.
 // ==============================================================================
-constexpr int kWKc = 32;   // k per LDS stage
-
-template <int E> constexpr int wop_floats() { return E * (kWKc + 4); }   // LDS floats per staged operand (RK pitch kWKc+4, KR pitch E+4)
-
-// the float4s of one E x kWKc operand chunk this thread moves: RK -> (row r, k..k+3), KR -> (k, rows r..r+3); zeros out of range
-template <int E, bool KR>
-__device__ __forceinline__ void w_fetch(float4* pf, const float* __restrict__ X, int ld, int rlim, int klim, int r0, int k0, bool vec,
-                                        int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kWKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    const int r = KR ? (idx % (E / 4)) * 4 : idx / (kWKc / 4);
-    const int k = KR ? idx / (E / 4) : (idx % (kWKc / 4)) * 4;
-    const int gr = r0 + r, gk = k0 + k;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (KR) {
-      if (gk < klim) {
-        const float* p = X + (size_t)gk * ld + gr;
-        if (vec && gr + 3 < rlim) v = *(const float4*)p;
-        else {
-          if (gr < rlim) v.x = p[0];
-          if (gr + 1 < rlim) v.y = p[1];
-          if (gr + 2 < rlim) v.z = p[2];
-          if (gr + 3 < rlim) v.w = p[3];
-        }
-      }
-    } else {
-      if (gr < rlim) {
-        const float* p = X + (size_t)gr * ld + gk;
-        if (vec && gk + 3 < klim) v = *(const float4*)p;
-        else {
-          if (gk < klim) v.x = p[0];
-          if (gk + 1 < klim) v.y = p[1];
-          if (gk + 2 < klim) v.z = p[2];
-          if (gk + 3 < klim) v.w = p[3];
-        }
-      }
-    }
-    pf[j] = v;
-  }
-}
-template <int E, bool KR>
-__device__ __forceinline__ void w_store(float* s, const float4* pf, int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kWKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    if (KR) *(float4*)(s + (idx / (E / 4)) * (E + 4) + (idx % (E / 4)) * 4) = pf[j];
-    else *(float4*)(s + (idx / (kWKc / 4)) * (kWKc + 4) + (idx % (kWKc / 4)) * 4) = pf[j];
-  }
-}
-// MFMA operand of tile row rr for the 16-k group kq: component j = X(rr, 16 kq + 4 g + j) -- k-slot g of MFMA step j (both
-// operands use this k order).  The pitches (kWKc+4, E+4 = 4 mod 64 dwords) keep both reads free of bank conflicts.
-template <int E, bool KR>
-__device__ __forceinline__ float4 w_frag(const float* s, int rr, int kq, int g) {
-  if (KR) {
-    const float* p = s + (16 * kq + 4 * g) * (E + 4) + rr;
-    return make_float4(p[0], p[E + 4], p[2 * (E + 4)], p[3 * (E + 4)]);
-  }
-  return *(const float4*)(s + rr * (kWKc + 4) + 16 * kq + 4 * g);
-}
-
-// acc[i][w][r] = sum_k A(m, k) B(n, k) for m = m0 + 16 W wm + 16 i + 4 g + r, n = n0 + 16 W wn + 16 w + fl  (wm = wave & 1,
-// wn = wave >> 1): rows on the MFMA's A side, columns on the lane.  k runs 0 .. K-1 in a fixed order.
-template <int W, bool A_KR, bool B_KR>
-__device__ __forceinline__ void wide_tile(float* lds, const float* __restrict__ A, int lda, int mlim, bool avec,
-                                          const float* __restrict__ B, int ldb, int nlim, bool bvec, int K, int m0, int n0,
-                                          f32x4 (&acc)[W][W]) {
-  constexpr int E = 32 * W;
-  float* sa = lds;
-  float* sb = lds + wop_floats<E>();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
-#pragma unroll
-  for (int i = 0; i < W; ++i)
-#pragma unroll
-    for (int w = 0; w < W; ++w) acc[i][w] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float4 pa[E * kWKc / 1024], pb[E * kWKc / 1024];
-  const int nst = (K + kWKc - 1) / kWKc;
-  if (nst > 0) {
-    w_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, 0, avec, tid);
-    w_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, 0, bvec, tid);
-  }
-  for (int st = 0; st < nst; ++st) {
-    __syncthreads();
-    w_store<E, A_KR>(sa, pa, tid);
-    w_store<E, B_KR>(sb, pb, tid);
-    __syncthreads();
-    if (st + 1 < nst) {
-      w_fetch<E, A_KR>(pa, A, lda, mlim, K, m0, (st + 1) * kWKc, avec, tid);
-      w_fetch<E, B_KR>(pb, B, ldb, nlim, K, n0, (st + 1) * kWKc, bvec, tid);
-    }
-#pragma unroll
-    for (int kq = 0; kq < kWKc / 16; ++kq) {
-      float4 a[W], b[W];
-#pragma unroll
-      for (int i = 0; i < W; ++i) a[i] = w_frag<E, A_KR>(sa, 16 * W * wm + 16 * i + fl, kq, g);
-#pragma unroll
-      for (int w = 0; w < W; ++w) b[w] = w_frag<E, B_KR>(sb, 16 * W * wn + 16 * w + fl, kq, g);
-#pragma unroll
-      for (int i = 0; i < W; ++i)
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b[w].x, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b[w].y, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b[w].z, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b[w].w, acc[i][w], 0, 0, 0);
-        }
-    }
-  }
-}
 
 // Forward: S tile (blockIdx.x = key tile, blockIdx.y = query tile) -> part[split][q][8] as ntxent_fwd_partial writes it, one split
 // per (key tile, wave row): split = 2 * blockIdx.x + wm covers the 16 W keys of that wave row.
@@ -741,14 +618,14 @@ template <int W>
 __global__ __launch_bounds__(256) void ntxent_wide_fwd_partial(const float* __restrict__ zq, const float* __restrict__ zk, int n,
                                                                int N, int D, int rank, float scale2, int vec,
                                                                float* __restrict__ part, int rows_pad) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int two_n = 2 * n, two_N = 2 * N;
   const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
   f32x4 acc[W][W];
-  wide_tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, D, m0, n0, acc);
+  gram_tile::tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, 0, D, m0, n0, acc);
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     const int q = n0 + 16 * W * wn + 16 * w + fl;
@@ -802,14 +679,14 @@ __global__ __launch_bounds__(256) void ntxent_wide_ds(const float* __restrict__ 
                                                       int rank, float scale2, int vec, const float* __restrict__ row_stats,
                                                       float gscale, float* __restrict__ ds, int ldds, float* __restrict__ epart,
                                                       int rows_pad) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int two_n = 2 * n, two_N = 2 * N;
   const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
   f32x4 acc[W][W];
-  wide_tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, D, m0, n0, acc);
+  gram_tile::tile<W, false, false>(lds, zk, D, two_N, vec, zq, D, two_n, vec, 0, D, m0, n0, acc);
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     const int q = n0 + 16 * W * wn + 16 * w + fl;
@@ -850,13 +727,13 @@ template <int W, bool A_KR, bool B_KR>
 __global__ __launch_bounds__(256) void ntxent_wide_gemm(const float* __restrict__ A, int lda, int avec, const float* __restrict__ B,
                                                         int ldb, int bvec, int M, int Nc, int K, float alpha, float* __restrict__ C,
                                                         int ldc) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * wop_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int m0 = blockIdx.y * E, n0 = blockIdx.x * E;
   f32x4 acc[W][W];
-  wide_tile<W, A_KR, B_KR>(lds, A, lda, M, avec, B, ldb, Nc, bvec, K, m0, n0, acc);
+  gram_tile::tile<W, A_KR, B_KR>(lds, A, lda, M, avec, B, ldb, Nc, bvec, 0, K, m0, n0, acc);
 #pragma unroll
   for (int i = 0; i < W; ++i)
 #pragma unroll

@@ -23,129 +23,15 @@
 // Cancellations avoided as in csrc/dino.hip: the non-maximum mass stays apart (log1p in the double finalize), the entropy is formed from
 // two non-negative terms, Ps - Pt is formed per element.
 //
-// MFMA mapping as in csrc/ntxent.hip: a = streamed-row fragment, b = fixed-row fragment, D[streamed = (lane >> 4) * 4 + reg][fixed = lane & 15].
-#include "common.h"
-#include <math.h>
+// MFMA mapping, tile stager (plain and PAIRED rows), S fragment, rounded logit and the three online row statistics: csrc/sweep_tile.h.
+#include "sweep_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr double kLog2ed = 1.4426950408889634;
-constexpr double kLn2d = 0.6931471805599453;
-constexpr int kTile = 64;      // rows per LDS tile / fixed rows per workgroup
+using namespace sweep;
+
 constexpr int kPart = 8;       // floats per (split, row) forward partial: {code max, non-maximum mass, sum exp2(t - m)(t - m), -, student max, non-maximum mass, -, -}
 constexpr int kMaxK = 1 << 20;
-
-// 64 x D tile, global -> LDS, 16-byte slots XOR-swizzled by the row; rows past the end read as zeros.  PAIRED: tile row i holds
-// source row p(row0 + i), p(r) = (r + n) mod 2n
-template <int D, bool PAIRED>
-__device__ __forceinline__ void load_tile(float* lds, const float* __restrict__ src, int row0, int nrows_total, int tid) {
-  constexpr int C = D / 4;
-  const int n = nrows_total >> 1;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int row = row0 + r;
-    if (row < nrows_total) {
-      const int srow = PAIRED ? (row < n ? row + n : row - n) : row;
-      v = *(const float4*)(src + (size_t)srow * D + c * 4);
-    }
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
-
-// S fragment: acc[r] = <tile row sub * 16 + 4 g + r, this lane's fixed row>
-template <int D>
-__device__ __forceinline__ f32x4 s_frag(const float* lds, int sub, int fl, int g, const float4* ff) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int trow = sub * 16 + fl;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.x, ff[s].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.y, ff[s].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.z, ff[s].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.w, ff[s].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// this lane's fragments of fixed row `row` (zeros past the end)
-template <int D>
-__device__ __forceinline__ void load_frag(float4* ff, const float* __restrict__ x, int row, bool valid, int g) {
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s)
-    ff[s] = valid ? *(const float4*)(x + (size_t)row * D + 16 * s + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// the rounded base-2 logit with its offset: two separate roundings, the same two in every sweep that recomputes it
-__device__ __forceinline__ float logit2(float dot, float scale2, float off2) {
-  float t = dot * scale2;
-  asm volatile("" : "+v"(t));
-  t += off2;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-
-// online (max, sum) in the base-2 domain (csrc/moco.hip)
-__device__ __forceinline__ void ml_push(float& m, float& l, float x) {
-  const float mn = fmaxf(m, x);
-  l = l * exp2f(m - mn) + exp2f(x - mn);
-  m = mn;
-}
-__device__ __forceinline__ void ml_merge(float& m, float& l, float m2, float l2) {
-  const float mn = fmaxf(m, m2);
-  const float a = (m == -INFINITY) ? 0.f : l * exp2f(m - mn);
-  const float b = (m2 == -INFINITY) ? 0.f : l2 * exp2f(m2 - mn);
-  m = mn; l = a + b;
-}
-
-// Row statistics in the base-2 domain (csrc/dino.hip): m = the maximum, r = sum over every element BUT one instance of the maximum of
-// exp2(t - m), a = sum over all of exp2(t - m) (t - m) (every term <= 0).  The softmax sum is 1 + r.
-__device__ __forceinline__ void mra_push(float& m, float& r, float& a, float t) {
-  if (m == -INFINITY) { m = t; return; }     // r = a = 0 already
-  if (t > m) {
-    const float dm = m - t, e = exp2f(dm), l = r + 1.f;
-    a = e * (a + l * dm);
-    r = l * e;
-    m = t;
-  } else {
-    const float x = t - m, p = exp2f(x);
-    a += p * x;
-    r += p;
-  }
-}
-__device__ __forceinline__ void mra_merge(float& m, float& r, float& a, float m2, float r2, float a2) {
-  if (m2 == -INFINITY) return;
-  if (m == -INFINITY) { m = m2; r = r2; a = a2; return; }
-  if (m2 > m) {
-    const float tm = m, tr = r, ta = a;
-    m = m2; r = r2; a = a2; m2 = tm; r2 = tr; a2 = ta;
-  }
-  const float dm = m2 - m, e = exp2f(dm), l2 = r2 + 1.f;   // the other side's maximum is one more non-maximum element here
-  r += l2 * e;
-  a += e * (a2 + l2 * dm);
-}
-
-// the same without a (the student side needs its log-sum-exp only)
-__device__ __forceinline__ void mr_push(float& m, float& r, float t) {
-  if (m == -INFINITY) { m = t; return; }
-  if (t > m) {
-    r = (r + 1.f) * exp2f(m - t);
-    m = t;
-  } else {
-    r += exp2f(t - m);
-  }
-}
-__device__ __forceinline__ void mr_merge(float& m, float& r, float m2, float r2) {
-  if (m2 == -INFINITY) return;
-  if (m == -INFINITY) { m = m2; r = r2; return; }
-  if (m2 > m) {
-    const float tm = m, tr = r;
-    m = m2; r = r2; m2 = tm; r2 = tr;
-  }
-  r += (r2 + 1.f) * exp2f(m2 - m);
-}
 
 // ======================================================= Sinkhorn-Knopp ==============================================================
 // ---- column sweep: a workgroup owns 64 prototypes and streams 64-row tiles of z_all with their beta; cpart[split][view][prototype] =
@@ -169,7 +55,7 @@ __global__ __launch_bounds__(256) void swav_col_sweep(const float* __restrict__ 
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int rt = tile_begin; rt < tile_end; ++rt) {
     __syncthreads();
-    load_tile<D, false>(lds, z, rt * kTile, rows_all, tid);
+    load_tile<D>(lds, z, rt * kTile, rows_all, tid);
     if (tid < kTile) ldb[tid] = (beta2 != nullptr && rt * kTile + tid < rows_all) ? beta2[rt * kTile + tid] : 0.f;
     __syncthreads();
 #pragma unroll
@@ -242,7 +128,7 @@ __global__ __launch_bounds__(256) void swav_row_sweep(const float* __restrict__ 
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     if (tid < 2 * kTile) {
       const int col = kt * kTile + (tid & 63);
       lda[tid] = col < K ? alpha2[(size_t)(tid >> 6) * k_pad + col] : 0.f;
@@ -304,7 +190,7 @@ __global__ __launch_bounds__(256) void swav_stats_sweep(const float* __restrict_
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     if (tid < 2 * kTile) {
       const int col = kt * kTile + (tid & 63);
       lda[tid] = col < K ? alpha[(size_t)(tid >> 6) * K + col] * kLog2e : 0.f;
@@ -400,7 +286,7 @@ __global__ __launch_bounds__(256) void swav_prob_sweep(const float* __restrict__
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     if (CODE && tid < 2 * kTile) {
       const int col = kt * kTile + (tid & 63);
       lda[tid] = col < K ? alpha[(size_t)(tid >> 6) * K + col] * kLog2e : 0.f;
@@ -543,8 +429,8 @@ __global__ __launch_bounds__(256) void swav_bwd_w_sweep(const float* __restrict_
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int rt = tile_begin; rt < tile_end; ++rt) {
     __syncthreads();
-    load_tile<D, false>(lds, q, rt * kTile, two_n, tid);
-    load_tile<D, true>(ldk, q, rt * kTile, two_n, tid);
+    load_tile<D>(lds, q, rt * kTile, two_n, tid);
+    load_tile<D, RowMap::kPaired>(ldk, q, rt * kTile, two_n, tid);
     if (tid < kTile) {
       const int row = rt * kTile + tid;
       const bool ok = row < two_n;
@@ -621,19 +507,7 @@ size_t off_cpart(const Plan& p) { return off_alpha2(p) + 2 * (size_t)p.k_pad; }
 size_t off_rpart(const Plan& p) { return off_cpart(p) + (size_t)p.rs * 2 * p.k_pad * 2; }
 size_t sink_words(const Plan& p) { return off_rpart(p) + (size_t)p.fks * p.rows_pad * 2; }
 
-bool dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
 bool shape_ok(int rows, int K) { return rows >= 2 && rows % 2 == 0 && rows <= (1 << 22) && K >= 2 && K <= kMaxK; }
-bool pos_finite(float x) { return x > 0.f && x <= 3.0e38f; }          // (NaN fails the comparison)
-bool al16(const void* a) { return a && ((uintptr_t)a & 15) == 0; }
-bool al4(const void* a) { return a && ((uintptr_t)a & 3) == 0; }
-bool al8(const void* a) { return a && ((uintptr_t)a & 7) == 0; }
-
-// more than 64 KB of dynamic LDS has to be asked for (csrc/knn.hip)
-template <typename F>
-bool raise_lds(F kernel, size_t lds) {
-  if (lds <= 65536 || simclr_dry_run()) return true;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-}
 
 template <int D>
 int sinkhorn_launch(const float* z, const float* w, int rows_all, int K, float scale2, int iters, float* alpha, float* wsp,

@@ -14,90 +14,15 @@
 // order, no atomics: two calls are bitwise equal.  The code logit of the key-side sweep is the one csrc/swav.hip's statistics sweep
 // rounded (the same dot product order, the same two roundings), so the lse_t of simclr_swav_fwd's row_stats normalises it.
 //
-// MFMA mapping as in csrc/ntxent.hip: a = streamed-row fragment, b = fixed-row fragment, D[streamed = (lane >> 4) * 4 + reg][fixed = lane & 15].
-#include "common.h"
-#include <math.h>
+// MFMA mapping, tile stager (plain and WRAPPED rows), S fragment, rounded logit and the (m, r) row statistics: csrc/sweep_tile.h.
+#include "sweep_tile.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr double kLog2ed = 1.4426950408889634;
-constexpr double kLn2d = 0.6931471805599453;
-constexpr int kTile = 64;      // rows per LDS tile / fixed rows per workgroup
+using namespace sweep;
+
 constexpr int kMaxK = 1 << 20;
 constexpr int kMaxRows = 1 << 22;
-
-// 64 x D tile, global -> LDS, 16-byte slots XOR-swizzled by the row; rows past the end read as zeros.  WRAP: src has nrows_total / 2
-// rows and tile row i holds source row (row0 + i) mod (nrows_total / 2) (m of the image of a global row)
-template <int D, bool WRAP>
-__device__ __forceinline__ void load_tile(float* lds, const float* __restrict__ src, int row0, int nrows_total, int tid) {
-  constexpr int C = D / 4;
-  const int n = nrows_total >> 1;
-  for (int idx = tid; idx < kTile * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int row = row0 + r;
-    if (row < nrows_total) {
-      const int srow = WRAP ? (row < n ? row : row - n) : row;
-      v = *(const float4*)(src + (size_t)srow * D + c * 4);
-    }
-    *(float4*)(lds + r * D + ((c ^ (r & 15)) * 4)) = v;
-  }
-}
-
-// S fragment: acc[r] = <tile row sub * 16 + 4 g + r, this lane's fixed row>
-template <int D>
-__device__ __forceinline__ f32x4 s_frag(const float* lds, int sub, int fl, int g, const float4* ff) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int trow = sub * 16 + fl;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const float4 tf = *(const float4*)(lds + trow * D + (((4 * s + g) ^ (trow & 15)) * 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.x, ff[s].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.y, ff[s].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.z, ff[s].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(tf.w, ff[s].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// this lane's fragments of fixed row `row` (zeros past the end)
-template <int D>
-__device__ __forceinline__ void load_frag(float4* ff, const float* __restrict__ x, int row, bool valid, int g) {
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s)
-    ff[s] = valid ? *(const float4*)(x + (size_t)row * D + 16 * s + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// the rounded base-2 logit with its offset: two separate roundings, the same two as in csrc/swav.hip
-__device__ __forceinline__ float logit2(float dot, float scale2, float off2) {
-  float t = dot * scale2;
-  asm volatile("" : "+v"(t));
-  t += off2;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-
-// Row statistics in the base-2 domain (csrc/swav.hip): m = the maximum, r = sum over every element BUT one instance of the maximum
-// of exp2(t - m).  The softmax sum is 1 + r.
-__device__ __forceinline__ void mr_push(float& m, float& r, float t) {
-  if (m == -INFINITY) { m = t; return; }
-  if (t > m) {
-    r = (r + 1.f) * exp2f(m - t);
-    m = t;
-  } else {
-    r += exp2f(t - m);
-  }
-}
-__device__ __forceinline__ void mr_merge(float& m, float& r, float m2, float r2) {
-  if (m2 == -INFINITY) return;
-  if (m == -INFINITY) { m = m2; r = r2; return; }
-  if (m2 > m) {
-    const float tm = m, tr = r;
-    m = m2; r = r2; m2 = tm; r2 = tr;
-  }
-  r += (r2 + 1.f) * exp2f(m2 - m);
-}
 
 // ---- statistics sweep: part[split][row] = the online (max, non-maximum mass) of s2_rj over the split's prototypes ------------------
 template <int D>
@@ -116,7 +41,7 @@ __global__ __launch_bounds__(256) void swavl_stats_sweep(const float* __restrict
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
@@ -212,7 +137,7 @@ __global__ __launch_bounds__(256) void swavl_prob_sweep(const float* __restrict_
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int kt = tile_begin; kt < tile_end; ++kt) {
     __syncthreads();
-    load_tile<D, false>(lds, w, kt * kTile, K, tid);
+    load_tile<D>(lds, w, kt * kTile, K, tid);
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
@@ -308,8 +233,8 @@ __global__ __launch_bounds__(256) void swavl_bwd_w_sweep(const float* __restrict
   const int tile_end = min(ntiles, tile_begin + tiles_per_split);
   for (int rt = tile_begin; rt < tile_end; ++rt) {
     __syncthreads();
-    load_tile<D, false>(lds, src, rt * kTile, rows, tid);
-    if (CODE) load_tile<D, true>(ldm, mult, rt * kTile, rows, tid);
+    load_tile<D>(lds, src, rt * kTile, rows, tid);
+    if (CODE) load_tile<D, RowMap::kWrapped>(ldm, mult, rt * kTile, rows, tid);
     if (tid < kTile) {
       const int row = rt * kTile + tid;
       lst[tid] = row < rows ? row_stats[CODE ? 2 * row + 1 : row] : 0.f;
@@ -404,20 +329,8 @@ size_t off_spart(const Plan& p, int D) { return off_m(p, D) + (size_t)p.b_pad * 
 size_t off_cpart(const Plan& p, int D) { return off_spart(p, D) + (size_t)p.rs * p.k_pad * D; }
 size_t total_words(const Plan& p, int D) { return off_cpart(p, D) + (size_t)p.gs * p.k_pad * D; }
 
-bool dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
 bool shape_ok(int b, int L, int K) {
   return b >= 1 && L >= 1 && L <= 8 && (long long)b * L <= kMaxRows && 2LL * b <= kMaxRows && K >= 2 && K <= kMaxK;
-}
-bool pos_finite(float x) { return x > 0.f && x <= 3.0e38f; }          // (NaN fails the comparison)
-bool al16(const void* a) { return a && ((uintptr_t)a & 15) == 0; }
-bool al4(const void* a) { return a && ((uintptr_t)a & 3) == 0; }
-bool al8(const void* a) { return a && ((uintptr_t)a & 7) == 0; }
-
-// more than 64 KB of dynamic LDS has to be asked for (csrc/knn.hip)
-template <typename F>
-bool raise_lds(F kernel, size_t lds) {
-  if (lds <= 65536 || simclr_dry_run()) return true;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
 }  // namespace

@@ -24,14 +24,14 @@
 // squares in double: the rounding of the centring is common to both.  The sums and the subtraction run in double in a fixed order and
 // cov is reported as computed, never clamped.
 //
-// Matrix products run on the exact fp32-input MFMA (v_mfma_f32_16x16x4_f32) in the LDS-tiled form of csrc/barlow.hip: a workgroup
+// Matrix products run on the exact fp32-input MFMA (v_mfma_f32_16x16x4_f32) as the staged-k Gram tile of csrc/gram_tile.h: a workgroup
 // of 4 waves (2 x 2) owns an E x E output tile, E = 32 W, operands are staged global -> registers -> LDS one k-chunk of 32 ahead, and
 // loads past the logical extents read zeros.  Unlike Barlow's Gram launch a workgroup carries ONE view (grid z), so one accumulator
 // set, and where the grid of both views' tiles has fewer than 256 workgroups the k range (D) is split into S parts at multiples of
 // the 32-wide stage: every part writes its partial tile, and a merge launch adds them in the order ((p0 + p1) + p2) + ... in fp32.
 // No atomics anywhere: a second call is bitwise the first, and everything computed from the gathered block alone is identical on
 // every replica.
-#include "common.h"
+#include "gram_tile.h"
 
 #include <math.h>
 
@@ -39,145 +39,14 @@
 
 namespace {
 
-constexpr int kVrKc = 32;   // k per LDS stage
-
-template <int E> constexpr int vr_op_floats() { return E * (kVrKc + 4); }   // LDS floats per staged operand (RK pitch kVrKc+4, KR pitch E+4)
-
-// the float4s of one E x kVrKc operand chunk this thread moves: RK -> (row r, k..k+3) of X[r * ld + k], KR -> (k, rows r..r+3) of
-// X[k * ld + r]; zeros out of range
-template <int E, bool KR>
-__device__ __forceinline__ void vr_fetch(float4* pf, const float* __restrict__ X, int ld, int rlim, int klim, int r0, int k0, bool vec,
-                                         int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kVrKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    const int r = KR ? (idx % (E / 4)) * 4 : idx / (kVrKc / 4);
-    const int k = KR ? idx / (E / 4) : (idx % (kVrKc / 4)) * 4;
-    const int gr = r0 + r, gk = k0 + k;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (KR) {
-      if (gk < klim) {
-        const float* p = X + (size_t)gk * ld + gr;
-        if (vec && gr + 3 < rlim) v = *(const float4*)p;
-        else {
-          if (gr < rlim) v.x = p[0];
-          if (gr + 1 < rlim) v.y = p[1];
-          if (gr + 2 < rlim) v.z = p[2];
-          if (gr + 3 < rlim) v.w = p[3];
-        }
-      }
-    } else {
-      if (gr < rlim) {
-        const float* p = X + (size_t)gr * ld + gk;
-        if (vec && gk + 3 < klim) v = *(const float4*)p;
-        else {
-          if (gk < klim) v.x = p[0];
-          if (gk + 1 < klim) v.y = p[1];
-          if (gk + 2 < klim) v.z = p[2];
-          if (gk + 3 < klim) v.w = p[3];
-        }
-      }
-    }
-    pf[j] = v;
-  }
-}
-template <int E, bool KR>
-__device__ __forceinline__ void vr_store(float* s, const float4* pf, int tid) {
-#pragma unroll
-  for (int j = 0; j < E * kVrKc / 1024; ++j) {
-    const int idx = tid + j * 256;
-    if (KR) *(float4*)(s + (idx / (E / 4)) * (E + 4) + (idx % (E / 4)) * 4) = pf[j];
-    else *(float4*)(s + (idx / (kVrKc / 4)) * (kVrKc + 4) + (idx % (kVrKc / 4)) * 4) = pf[j];
-  }
-}
-// MFMA operand of tile row rr for the 16-k group kq: component j = X(rr, 16 kq + 4 g + j) -- k-slot g of MFMA step j (both operands
-// use this k order).  The pitches (kVrKc+4, E+4 = 4 mod 32 dwords) keep both reads free of bank conflicts.
-template <int E, bool KR>
-__device__ __forceinline__ float4 vr_frag(const float* s, int rr, int kq, int g) {
-  if (KR) {
-    const float* p = s + (16 * kq + 4 * g) * (E + 4) + rr;
-    return make_float4(p[0], p[E + 4], p[2 * (E + 4)], p[3 * (E + 4)]);
-  }
-  return *(const float4*)(s + rr * (kVrKc + 4) + 16 * kq + 4 * g);
-}
-
-// acc[i][w][r] = sum_{kbeg <= k < kend} A(m, k) B(c, k) for m = m0 + 16 W wm + 16 i + 4 g + r, c = n0 + 16 W wn + 16 w + fl
-// (wm = wave & 1, wn = wave >> 1): rows on the MFMA's A side, columns on the lane.  kbeg is a multiple of the stage; k runs in a
-// fixed order.
-template <int W, bool A_KR, bool B_KR>
-__device__ __forceinline__ void vr_tile(float* lds, const float* __restrict__ A, int lda, int mlim, bool avec,
-                                        const float* __restrict__ B, int ldb, int nlim, bool bvec, int kbeg, int kend, int m0, int n0,
-                                        f32x4 (&acc)[W][W]) {
-  constexpr int E = 32 * W;
-  float* sa = lds;
-  float* sb = lds + vr_op_floats<E>();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
-#pragma unroll
-  for (int i = 0; i < W; ++i)
-#pragma unroll
-    for (int w = 0; w < W; ++w) acc[i][w] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float4 pa[E * kVrKc / 1024], pb[E * kVrKc / 1024];
-  const int nst = (kend - kbeg + kVrKc - 1) / kVrKc;
-  if (nst > 0) {
-    vr_fetch<E, A_KR>(pa, A, lda, mlim, kend, m0, kbeg, avec, tid);
-    vr_fetch<E, B_KR>(pb, B, ldb, nlim, kend, n0, kbeg, bvec, tid);
-  }
-  for (int st = 0; st < nst; ++st) {
-    __syncthreads();
-    vr_store<E, A_KR>(sa, pa, tid);
-    vr_store<E, B_KR>(sb, pb, tid);
-    __syncthreads();
-    if (st + 1 < nst) {
-      vr_fetch<E, A_KR>(pa, A, lda, mlim, kend, m0, kbeg + (st + 1) * kVrKc, avec, tid);
-      vr_fetch<E, B_KR>(pb, B, ldb, nlim, kend, n0, kbeg + (st + 1) * kVrKc, bvec, tid);
-    }
-#pragma unroll
-    for (int kq = 0; kq < kVrKc / 16; ++kq) {
-      float4 a[W], b[W];
-#pragma unroll
-      for (int i = 0; i < W; ++i) a[i] = vr_frag<E, A_KR>(sa, 16 * W * wm + 16 * i + fl, kq, g);
-#pragma unroll
-      for (int w = 0; w < W; ++w) b[w] = vr_frag<E, B_KR>(sb, 16 * W * wn + 16 * w + fl, kq, g);
-#pragma unroll
-      for (int i = 0; i < W; ++i)
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b[w].x, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b[w].y, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b[w].z, acc[i][w], 0, 0, 0);
-          acc[i][w] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b[w].w, acc[i][w], 0, 0, 0);
-        }
-    }
-  }
-}
-
-// ---- column reductions: a workgroup owns 32 columns; thread (q = tid & 7, rg = tid >> 3) walks rows rg, rg + 32, ... of the column
-// quad 4q .. 4q+3 with 16-byte loads and sums in double; the 32 row groups of a column are then added in the order 0 .. 31.
-constexpr int kVrCols = 32;
-// v[4] of every thread -> res[32] (column totals); sh holds 32 x 32 doubles.  Ends with a barrier: res is readable by all threads.
-__device__ __forceinline__ void vr_col_reduce(const double (&v)[4], double* sh, double* res) {
-  const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  __syncthreads();     // sh / res may still be read from an earlier reduction
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sh[rg * kVrCols + 4 * q + k] = v[k];
-  __syncthreads();
-  if (tid < kVrCols) {
-    double s = 0.0;
-    for (int r = 0; r < 32; ++r) s += sh[r * kVrCols + tid];
-    res[tid] = s;
-  }
-  __syncthreads();
-}
-
 // Centre: blockIdx.y = view, blockIdx.x = 32-column group.  Pass 1 the mean; pass 2 writes xc = fl32(h - mu) and sums the squares of
 // the ROUNDED value it stored, so var is the variance of what the Gram launch reads.  stats[v][0][j] = var, stats[v][1][j] = std.
 __global__ __launch_bounds__(256) void vr_center(const float* __restrict__ h_all, int N, int D, double eps, float* __restrict__ xc_all,
                                                  double* __restrict__ stats) {
-  __shared__ double sh[32 * kVrCols];
-  __shared__ double res[kVrCols];
+  __shared__ double sh[32 * gram_tile::kCols];
+  __shared__ double res[gram_tile::kCols];
   const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  const int j0 = blockIdx.x * kVrCols + 4 * q;
+  const int j0 = blockIdx.x * gram_tile::kCols + 4 * q;
   const float* h = h_all + (size_t)blockIdx.y * N * D + j0;
   float* xc = xc_all + (size_t)blockIdx.y * N * D + j0;
   double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -185,7 +54,7 @@ __global__ __launch_bounds__(256) void vr_center(const float* __restrict__ h_all
     const float4 x = *(const float4*)(h + (size_t)a * D);
     v[0] += (double)x.x; v[1] += (double)x.y; v[2] += (double)x.z; v[3] += (double)x.w;
   }
-  vr_col_reduce(v, sh, res);
+  gram_tile::col_reduce(v, sh, res);
   double mu[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) { mu[k] = res[4 * q + k] / (double)N; v[k] = 0.0; }
@@ -197,10 +66,10 @@ __global__ __launch_bounds__(256) void vr_center(const float* __restrict__ h_all
     v[0] += (double)c.x * (double)c.x; v[1] += (double)c.y * (double)c.y;
     v[2] += (double)c.z * (double)c.z; v[3] += (double)c.w * (double)c.w;
   }
-  vr_col_reduce(v, sh, res);
-  if (tid < kVrCols) {
+  gram_tile::col_reduce(v, sh, res);
+  if (tid < gram_tile::kCols) {
     const double var = res[tid] / (double)(N - 1);
-    const int j = blockIdx.x * kVrCols + tid;
+    const int j = blockIdx.x * gram_tile::kCols + tid;
     stats[((size_t)blockIdx.y * 2 + 0) * D + j] = var;
     stats[((size_t)blockIdx.y * 2 + 1) * D + j] = sqrt(var + eps);
   }
@@ -208,10 +77,10 @@ __global__ __launch_bounds__(256) void vr_center(const float* __restrict__ h_all
 
 // invpart[blockIdx.x] = sum over the local rows and this workgroup's 32 columns of (h1 - h2)^2, in double.
 __global__ __launch_bounds__(256) void vr_inv(const float* __restrict__ h_all, int n, int N, int D, int rank, double* __restrict__ invpart) {
-  __shared__ double sh[32 * kVrCols];
-  __shared__ double res[kVrCols];
+  __shared__ double sh[32 * gram_tile::kCols];
+  __shared__ double res[gram_tile::kCols];
   const int tid = threadIdx.x, q = tid & 7, rg = tid >> 3;
-  const int j0 = blockIdx.x * kVrCols + 4 * q;
+  const int j0 = blockIdx.x * gram_tile::kCols + 4 * q;
   const float* h1 = h_all + (size_t)rank * n * D + j0;
   const float* h2 = h_all + ((size_t)N + (size_t)rank * n) * D + j0;
   double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -221,10 +90,10 @@ __global__ __launch_bounds__(256) void vr_inv(const float* __restrict__ h_all, i
                  d3 = (double)x.w - (double)y.w;
     v[0] += d0 * d0; v[1] += d1 * d1; v[2] += d2 * d2; v[3] += d3 * d3;
   }
-  vr_col_reduce(v, sh, res);
+  gram_tile::col_reduce(v, sh, res);
   if (tid == 0) {
     double s = 0.0;
-    for (int k = 0; k < kVrCols; ++k) s += res[k];
+    for (int k = 0; k < gram_tile::kCols; ++k) s += res[k];
     invpart[blockIdx.x] = s;
   }
 }
@@ -237,7 +106,7 @@ __global__ __launch_bounds__(256) void vr_inv(const float* __restrict__ h_all, i
 template <int W, bool SPLIT>
 __global__ __launch_bounds__(256) void vr_gram(const float* __restrict__ xc_all, int n, int N, int D, int rank, int S, int kchunk,
                                                float* __restrict__ dst, int ldg, int rows_pad, double* __restrict__ sums) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * vr_op_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   __shared__ double wsum[4];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -248,7 +117,7 @@ __global__ __launch_bounds__(256) void vr_gram(const float* __restrict__ xc_all,
   const int kbeg = p * kchunk, kend = min(D, kbeg + kchunk);
   const float* x = xc_all + (size_t)v * N * D;
   f32x4 acc[W][W];
-  vr_tile<W, false, false>(lds, x, D, N, true, x + (size_t)rank * n * D, D, n, true, kbeg, kend, m0, n0, acc);
+  gram_tile::tile<W, false, false>(lds, x, D, N, true, x + (size_t)rank * n * D, D, n, true, kbeg, kend, m0, n0, acc);
   float* out = dst + ((size_t)p * 2 + v) * rows_pad * ldg;
   double s = 0.0;
 #pragma unroll
@@ -340,14 +209,15 @@ __global__ __launch_bounds__(256) void vr_bwd_gemm(const float* __restrict__ h_a
                                                    const double* __restrict__ stats, const float* __restrict__ gram, int ldg, int rows_pad,
                                                    int n, int N, int D, int rank, float c_gram, float c_var, float c_std, float c_inv,
                                                    float gamma, float* __restrict__ dh_local) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * vr_op_floats<32 * W>()];
+  __shared__ __attribute__((aligned(16))) float lds[2 * gram_tile::op_floats<32 * W>()];
   constexpr int E = 32 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, fl = lane & 15, wm = wave & 1, wn = wave >> 1;
   const int v = blockIdx.z;
   const int m0 = blockIdx.x * E, n0 = blockIdx.y * E;
   f32x4 acc[W][W];
-  vr_tile<W, true, false>(lds, xc_all + (size_t)v * N * D, D, D, true, gram + (size_t)v * rows_pad * ldg, ldg, n, true, 0, N, m0, n0, acc);
+  gram_tile::tile<W, true, false>(lds, xc_all + (size_t)v * N * D, D, D, true, gram + (size_t)v * rows_pad * ldg, ldg, n, true, 0, N, m0, n0,
+                                  acc);
   const size_t own = ((size_t)v * N + (size_t)rank * n) * D, other = ((size_t)(1 - v) * N + (size_t)rank * n) * D;
   float* out = dh_local + (size_t)v * n * D;
 #pragma unroll
@@ -394,15 +264,15 @@ VrPlan vr_plan(int n, int N, int D) {
   p.rows_pad = ceil_div(n, p.E) * p.E;
   p.ldg = ceil_div(N, p.E) * p.E;
   p.ntiles = (p.rows_pad / p.E) * (p.ldg / p.E);
-  const int wgs = 2 * p.ntiles, stages = D / kVrKc;
+  const int wgs = 2 * p.ntiles, stages = D / gram_tile::kKc;
   int S = 1;
   if (wgs < kVrFillWgs) S = std::max(1, std::min(std::min(ceil_div(kVrTargetWgs, wgs), stages / kVrMinStages), kVrMaxSplits));
   const int chunk_stages = ceil_div(stages, S);
   p.S = ceil_div(stages, chunk_stages);          // no empty part; the last one may be shorter
-  p.kchunk = chunk_stages * kVrKc;
+  p.kchunk = chunk_stages * gram_tile::kKc;
   // S = 1: one sum per tile; S > 1: one per merge workgroup (1024 float4s of a view's block)
   p.nsums = p.S == 1 ? p.ntiles : (int)((size_t)p.rows_pad * p.ldg / 4096);
-  p.off_sums = (size_t)(D / kVrCols) * sizeof(double);
+  p.off_sums = (size_t)(D / gram_tile::kCols) * sizeof(double);
   p.off_gram = (p.off_sums + (size_t)2 * p.nsums * sizeof(double) + 255) / 256 * 256;
   p.off_parts = p.off_gram + (size_t)2 * p.rows_pad * p.ldg * sizeof(float);
   p.bytes = p.off_parts + (p.S > 1 ? (size_t)p.S * 2 * p.rows_pad * p.ldg * sizeof(float) : 0);
@@ -430,7 +300,7 @@ int simclr_vicreg_center(const float* h_all, int N, int D, float eps, float* xc_
   SIMCLR_CHECK_ARG(eps >= 0.f, "vicreg_center: eps must be >= 0");
   SIMCLR_CHECK_ARG(h_all && xc_all && stats, "vicreg_center: null argument");
   SIMCLR_CHECK_ARG(vr_vec_ok(h_all) && vr_vec_ok(xc_all) && vr_vec_ok(stats), "vicreg_center: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(vr_center, dim3(D / kVrCols, 2), dim3(256), 0, stream, h_all, N, D, (double)eps, xc_all, stats);
+  hipLaunchKernelGGL(vr_center, dim3(D / gram_tile::kCols, 2), dim3(256), 0, stream, h_all, N, D, (double)eps, xc_all, stats);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }
@@ -451,7 +321,7 @@ int simclr_vicreg_fwd(const float* h_all, const float* xc_all, const double* sta
   double* sums = (double*)((char*)workspace + p.off_sums);
   float* gram = (float*)((char*)workspace + p.off_gram);
   float* parts = (float*)((char*)workspace + p.off_parts);
-  hipLaunchKernelGGL(vr_inv, dim3(D / kVrCols), dim3(256), 0, stream, h_all, n, N, D, rank, invpart);
+  hipLaunchKernelGGL(vr_inv, dim3(D / gram_tile::kCols), dim3(256), 0, stream, h_all, n, N, D, rank, invpart);
   SIMCLR_CHECK_LAUNCH();
   if (p.S == 1) {
     dim3 grid(p.ldg / p.E, p.rows_pad / p.E, 2);
@@ -472,7 +342,7 @@ int simclr_vicreg_fwd(const float* h_all, const float* xc_all, const double* sta
   }
   // R / (N-1)^2 with R = N / n; inv over the local rows
   const double frob_scale = (double)(N / n) / ((double)(N - 1) * (double)(N - 1));
-  hipLaunchKernelGGL(vr_finish, dim3(1), dim3(256), 0, stream, stats, D, sums, p.nsums, invpart, D / kVrCols, frob_scale,
+  hipLaunchKernelGGL(vr_finish, dim3(1), dim3(256), 0, stream, stats, D, sums, p.nsums, invpart, D / gram_tile::kCols, frob_scale,
                      1.0 / ((double)n * (double)D), (double)gamma, (double)sim_coeff, (double)std_coeff, (double)cov_coeff, out);
   SIMCLR_CHECK_LAUNCH();
   return 0;
