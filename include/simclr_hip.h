@@ -158,6 +158,31 @@ int simclr_supcon_fwd(const float* z_local, const float* z_all, const int* label
 int simclr_supcon_bwd(const float* z_local, const float* z_all, const int* labels_all, int n, int N, int D, int rank, float temperature,
                       const float* row_stats, float grad_scale, float* dz_local, float* dz_all, void* workspace, simclr_stream_t stream);
 
+/* ---- hard-negative and debiased NT-Xent (Robinson et al. 2021, Contrastive Learning with Hard Negative Samples: beta; Chuang et al.
+ * 2020, Debiased Contrastive Learning: tau_plus), csrc/hcl.hip ----
+ * The formulas are this project's definition of the two corrections, not a parity claim with either paper's code.  Layout as
+ * simclr_ntxent_fwd.  Local row i (view v = i / n, sample s = i % n) has the own column self(i) = v*N + rank*n + s and the positive
+ * column pos(i) = (1 - v)*N + rank*n + s; Neg(i) = the other M = 2N - 2 columns.  With a = 1 / T and s_ik = z_i.z_k:
+ *   p_i = exp(a s_i,pos),  A_i = sum_{k in Neg(i)} exp((1 + beta) a s_ik),  B_i = sum_{k in Neg(i)} exp(beta a s_ik)
+ *   G_raw_i = (M A_i / B_i - tau_plus M p_i) / (1 - tau_plus),  G_i = max(G_raw_i, M exp(-a))  (the floor)
+ *   l_i = log(p_i + G_i) - a s_i,pos
+ * At beta = 0 and tau_plus = 0 this is simclr_ntxent_fwd's loss.  D in {64, 128, 256}, any n >= 1 with N = R*n >= 2; T > 0 and finite,
+ * beta >= 0 and finite, tau_plus in [0, 1); z_local, z_all, row_stats, dz_local, dz_all and the workspace 16-byte aligned.  Anything else
+ * returns 1 and launches nothing.  Exact fp32-input MFMA, the [2n, 2N] matrix never written, the row finalize in double, no atomics:
+ * bitwise run-to-run deterministic.  The workspace holds one fwd/bwd pair. */
+size_t simclr_hcl_workspace_bytes(int n, int N, int D);        /* 0 for a shape the kernels refuse */
+/* out[0] = loss = (1 / n) sum_{i < 2n} l_i (the sum of the two per-view means), out[1] = the share of the 2n local rows on the floor.
+ * row_stats [2n, 4] = {log2 A_i, log2 B_i, the row's negative coefficient a w_i (0 on the floor), its positive coefficient}, kept for
+ * the backward, which reads the forward's decision about the floor and never re-decides. */
+int simclr_hcl_fwd(const float* z_local, const float* z_all, int n, int N, int D, int rank, float temperature, float beta, float tau_plus,
+                   float* out, float* row_stats, void* workspace, simclr_stream_t stream);
+/* The gradient through the logits, times grad_scale / n: above the floor dS_ik = a w_i ((1 + beta) P1_ik - beta P0_ik) for k in Neg(i),
+ * w_i = (M A_i / B_i) / ((1 - tau_plus)(p_i + G_i)), P1 / P0 the softmaxes over Neg(i) at scales (1 + beta) a / beta a, and
+ * dS_i,pos = a (p_i (1 - tau_plus M / (1 - tau_plus)) / (p_i + G_i) - 1); on the floor dS_ik = 0 and dS_i,pos = a (p_i / (p_i + G_i) - 1);
+ * dS_{i, self(i)} = 0.  dz_local [2n, D] = dS z_all, dz_all [2N, D] = dS^T z_local (to be reduce-scattered like simclr_ntxent_bwd's). */
+int simclr_hcl_bwd(const float* z_local, const float* z_all, int n, int N, int D, int rank, float temperature, float beta, float tau_plus,
+                   const float* row_stats, float grad_scale, float* dz_local, float* dz_all, void* workspace, simclr_stream_t stream);
+
 /* ---- Barlow Twins loss (Zbontar et al. 2021, Barlow Twins: Self-Supervised Learning via Redundancy Reduction), csrc/barlow.hip ----
  * The Gram form: with zhat the per-view, per-dimension standardisation of the gathered block over the GLOBAL batch,
  * C = zhat1^T zhat2 / N ([D, D], never formed), c_i = C_ii, G1 = zhat1 zhat1^T, G2 = zhat2 zhat2^T,

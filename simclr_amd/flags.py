@@ -120,6 +120,14 @@ _DEFS = [
     ('gcl_lambda', 1.0, float, 'MI355X build: weight of the distribution-matching term (lambda_weight).'),
     ('gcl_loss_scaling', 1.0, float, 'MI355X build: factor on the whole generalized loss (loss_scaling).'),
     ('gcl_seed', 0, int, 'MI355X build: seed of the SWD projection basis and prior samples; the draws of a step depend on (gcl_seed, step) only.'),
+    # the two corrections of NT-Xent itself (add_hard_negative_contrastive_loss), read under --contrastive_loss=ntxent only
+    ('hard_negative_beta', 0.0, float, 'MI355X build: hard-negative re-weighting of NT-Xent (Robinson et al. 2021): every negative weighs '
+                                       'exp(beta * s / temperature), differentiated through.  >= 0 and finite; 0 = NT-Xent.  A nonzero value '
+                                       'needs --contrastive_loss=ntxent, --hidden_norm=true, a loss width of 64, 128 or 256 and '
+                                       '--train_batch_size >= 2.  Ignored by --train_mode=finetune and --mode=eval.'),
+    ('debiased_tau_plus', 0.0, float, 'MI355X build: debiasing correction of NT-Xent (Chuang et al. 2020): the class prior of a false negative, '
+                                      'whose expected mass is taken out of the negative term (floored at M exp(-1 / temperature)).  In [0, 1); '
+                                      '0 = NT-Xent.  Same requirements as --hard_negative_beta.'),
     # Barlow Twins (Zbontar et al. 2021) in place of NT-Xent for pretraining
     ('bt_lambda', 0.0051, float, 'MI355X build: weight of the off-diagonal (redundancy-reduction) term of the Barlow Twins loss (lambda_weight).'),
     ('bt_loss_scaling', 1.0, float, 'MI355X build: factor on the whole Barlow Twins loss (loss_scaling).'),

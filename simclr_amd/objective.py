@@ -14,6 +14,9 @@ distribution-matching term: decoupled NT-Xent, or sliced Wasserstein against a n
 `add_supcon_loss` is the supervised contrastive loss of Khosla et al. 2020 (NT-Xent with every same-class row of the global batch as a
 positive) on the kernels of csrc/supcon.hip.
 
+`add_hard_negative_contrastive_loss` is NT-Xent with the hard-negative re-weighting of Robinson et al. 2021 (beta) and the debiasing
+correction of Chuang et al. 2020 (tau_plus) on the kernels of csrc/hcl.hip; at beta = 0 and tau_plus = 0 it is NT-Xent.
+
 `add_barlow_twins_loss` is the Barlow Twins loss of Zbontar et al. 2021 (redundancy reduction on the cross-correlation of the two views'
 batch-standardised hiddens; no negatives) in its Gram form on the kernels of csrc/barlow.hip.
 
@@ -418,6 +421,90 @@ def add_supcon_loss(hidden, labels, hidden_norm=True, temperature=1.0, strategy=
     loss.acc, loss.positives = out[1:2], out[2:3]
     loss.normalized = z
     return loss
+
+
+class _NtxentScoredLogits(LazyLogits):
+    """The LazyLogits of a loss whose own kernels score nothing: contrast_acc / contrast_entropy come from one NT-Xent forward and one
+    zero-gradient NT-Xent backward sweep over the same (z_local, z_all, T), launched when the first of the two is read."""
+
+    def __init__(self, z_local, z_all, temperature, rank):
+        super().__init__(z_local, z_all, temperature, None, None)
+        self._rank = rank
+
+    def _score(self):
+        if self._out is None:
+            out, row_stats, ws = ops.ntxent_fwd(self._z_local, self._z_all, self._rank, self._t)
+            ops.ntxent_bwd(self._z_local, self._z_all, self._rank, self._t, row_stats, 0.0, out, ws)
+            self._out = out
+        return self._out
+
+    @property
+    def contrast_acc(self):
+        return self._kept[0] if self._kept is not None else self._score()[1]
+
+    @property
+    def contrast_entropy(self):
+        return self._kept[1] if self._kept is not None else self._score()[2]
+
+
+def add_hard_negative_contrastive_loss(hidden, temperature=1.0, beta=0.0, tau_plus=0.0, strategy=None, overlap=None):
+    """NT-Xent with hard-negative re-weighting (Robinson et al. 2021: beta) and the debiasing correction (Chuang et al. 2020: tau_plus)
+    on the kernels of csrc/hcl.hip.  The formulas are this project's definition of the two corrections, not a parity claim.
+
+    With Neg(i) = the M = 2N - 2 columns of the gathered block that are neither row i's own nor its other view, a = 1 / temperature
+    and s = the dot products of the l2-normalised rows,
+      p_i = exp(a s_i,pos),  A_i = sum_{Neg(i)} exp((1 + beta) a s_ik),  B_i = sum_{Neg(i)} exp(beta a s_ik),
+      G_i = max((M A_i / B_i - tau_plus M p_i) / (1 - tau_plus), M exp(-a)),   l_i = log(p_i + G_i) - a s_i,pos,
+      loss = (1 / n) sum_{i < 2n} l_i,
+    the sum of the two per-view means, as add_contrastive_loss forms NT-Xent; at beta = 0 and tau_plus = 0 the loss and its gradient
+    are add_contrastive_loss's.  The weights exp(beta a s) are differentiated through (no stop-gradient).  The hidden block is always
+    l2-normalised: the floor M exp(-a) assumes s >= -1.
+
+    Args:
+      hidden: float32 device tensor [2n, D] = [view-a rows; view-b rows], D in {64, 128, 256}; the global batch holds N >= 2 images.
+      temperature: > 0.  beta: >= 0, the concentration on hard negatives.  tau_plus: in [0, 1), the class prior of a false negative.
+      strategy, overlap: as add_contrastive_loss (the hidden block is gathered asynchronously; overlap() runs meanwhile).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> gradient wrt hidden), the device scalar .floor_share (the
+      share of the local rows whose G sits on the floor: those rows pull on their positive only) and .normalized; the logits handle
+      (contrast_acc / contrast_entropy of the same logits matrix, scored by the NT-Xent kernels when read); the labels handle.
+    """
+    assert hidden.dtype == torch.float32 and hidden.dim() == 2
+    hidden = hidden.contiguous()
+    n = hidden.shape[0] // 2
+    if hidden.shape[1] not in ops.HCL_DIMS:
+        raise ValueError('the hard-negative / debiased NT-Xent supports hidden widths %s (got %d)'
+                         % ('/'.join(map(str, ops.HCL_DIMS)), hidden.shape[1]))
+    if not temperature > 0 or not ops.hcl_beta_ok(beta) or not ops.hcl_tau_plus_ok(tau_plus):
+        raise ValueError('add_hard_negative_contrastive_loss: need temperature > 0, beta >= 0 and finite, tau_plus in [0, 1) '
+                         '(got %r, %r, %r)' % (temperature, beta, tau_plus))
+    z, inv = ops.l2norm_fwd(hidden)
+    R, rank = num_replicas(strategy), replica_id(strategy)
+    pending = gather_hidden(z, strategy, async_op=True)
+    if overlap is not None:
+        overlap()
+    z_all = pending()
+    out, row_stats, ws = ops.hcl_fwd(z, z_all, rank, temperature, beta, tau_plus)
+    state = {}
+
+    def backward_start(grad_scale=1.0):
+        dz_local, dz_all = ops.hcl_bwd(z, z_all, rank, temperature, beta, tau_plus, row_stats, grad_scale, ws)
+        state['dz_local'] = dz_local
+        state['slot'] = scatter_hidden_grad(dz_all, strategy, async_op=True)   # transpose of the concat, as NT-Xent's
+
+    def backward_finish():
+        dz_local, dz_slot = state.pop('dz_local'), state.pop('slot')()
+        ops.axpy_f32(1.0, dz_slot, dz_local)
+        return ops.l2norm_bwd(z, inv, dz_local)
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.floor_share = out[1:2]
+    loss.normalized = z
+    return loss, _NtxentScoredLogits(z, z_all, temperature, rank), LazyLabels(n, n * R, rank, z.device)
 
 
 def add_barlow_twins_loss(hidden, lambda_weight=0.0051, loss_scaling=1.0, eps=1e-5, strategy=None, overlap=None):

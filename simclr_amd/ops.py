@@ -392,6 +392,65 @@ def supcon_bwd(z_local, z_all, labels_all, rank, temperature, row_stats, grad_sc
     return dz_local, dz_all
 
 
+# ---------------------------------------------------------------- hard-negative and debiased NT-Xent (csrc/hcl.hip)
+HCL_DIMS = (64, 128, 256)           # hidden widths the hard-negative / debiased NT-Xent kernels are instantiated for
+
+
+def hcl_beta_ok(beta):
+    return 0.0 <= beta < float('inf')          # (NaN fails the comparison)
+
+
+def hcl_tau_plus_ok(tau_plus):
+    return 0.0 <= tau_plus < 1.0
+
+
+def _hcl_check(z_local, z_all, beta, tau_plus):
+    n, D = z_local.shape[0] // 2, z_local.shape[1]
+    N = z_all.shape[0] // 2
+    assert z_local.dtype == torch.float32 and z_all.dtype == torch.float32 and z_all.shape[1] == D
+    if D not in HCL_DIMS:
+        raise ValueError('the hard-negative / debiased NT-Xent supports hidden widths %s (got %d)' % ('/'.join(map(str, HCL_DIMS)), D))
+    if n < 1 or z_local.shape[0] != 2 * n or N < 2 or N < n or N % n != 0 or z_all.shape[0] != 2 * N:
+        raise ValueError('hcl: need z_local [2n, D] with n >= 1 and z_all [2N, D] with N = R*n >= 2 (got %d and %d rows)'
+                         % (z_local.shape[0], z_all.shape[0]))
+    if not hcl_beta_ok(beta):
+        raise ValueError('hcl: beta must be >= 0 and finite (got %r)' % (beta,))
+    if not hcl_tau_plus_ok(tau_plus):
+        raise ValueError('hcl: tau_plus must lie in [0, 1) (got %r)' % (tau_plus,))
+    return n, N, D
+
+
+def hcl_workspace(n, N, D, device):
+    nbytes = lib().hcl_workspace_bytes(n, N, D)
+    assert nbytes > 0, 'hcl_workspace: bad shape n=%d N=%d D=%d' % (n, N, D)
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+
+
+def hcl_fwd(z_local, z_all, rank, temperature, beta, tau_plus, ws=None):
+    """Hard-negative (beta) and debiased (tau_plus) NT-Xent forward.  Returns out = [loss, share of the local rows on the floor]
+    (device), row_stats [2n, 4] = {log2 A, log2 B, negative coefficient, positive coefficient}, the workspace."""
+    n, N, D = _hcl_check(z_local, z_all, beta, tau_plus)
+    if ws is None:
+        ws = hcl_workspace(n, N, D, z_local.device)
+    out = step_scalars(4, z_local.device)
+    row_stats = torch.empty(2 * n, 4, device=z_local.device, dtype=torch.float32)
+    _launch('hcl_fwd', 8.0 * n * N * D, 4.0 * (2 * n + 2 * N) * D,
+            lambda: lib().hcl_fwd(_p(z_local), _p(z_all), n, N, D, int(rank), float(temperature), float(beta), float(tau_plus), _p(out),
+                                  _p(row_stats), _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def hcl_bwd(z_local, z_all, rank, temperature, beta, tau_plus, row_stats, grad_scale, ws):
+    n, N, D = _hcl_check(z_local, z_all, beta, tau_plus)
+    assert tuple(row_stats.shape) == (2 * n, 4) and row_stats.dtype == torch.float32
+    dz_local = torch.empty_like(z_local)
+    dz_all = torch.empty_like(z_all)
+    _launch('hcl_bwd', 24.0 * n * N * D, 2.0 * (2 * n + 2 * N) * D * 4,
+            lambda: lib().hcl_bwd(_p(z_local), _p(z_all), n, N, D, int(rank), float(temperature), float(beta), float(tau_plus),
+                                  _p(row_stats), float(grad_scale), _p(dz_local), _p(dz_all), _p(ws), _s()))
+    return dz_local, dz_all
+
+
 # ---------------------------------------------------------------- Barlow Twins loss (csrc/barlow.hip)
 BT_DIM_STEP, BT_MIN_DIM, BT_MAX_DIM = 64, 64, 8192       # hidden widths the Barlow Twins kernels take: multiples of 64 in [64, 8192]
 BT_EPS = 1e-5

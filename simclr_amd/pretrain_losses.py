@@ -95,6 +95,39 @@ def _check_barlow():
     _need_loss_width('barlow', ops.bt_dim_ok, ops.BT_DIM_STEP, ops.BT_MIN_DIM, ops.BT_MAX_DIM, 'Barlow Twins kernels')
 
 
+def ntxent_corrections_on():
+    """A nonzero --hard_negative_beta or --debiased_tau_plus (NaN counts: the check refuses it) in an NT-Xent pretraining run outside
+    --mode=eval: the step trains add_hard_negative_contrastive_loss.  Fine-tuning and evaluation ignore the two flags."""
+    return (model_lib.pretrain_loss() == 'ntxent' and FLAGS.mode != 'eval'
+            and not (FLAGS.hard_negative_beta == 0 and FLAGS.debiased_tau_plus == 0))
+
+
+def check_ntxent_corrections():
+    """The start-up check of --hard_negative_beta / --debiased_tau_plus, run for every pretraining loss: the two flags correct NT-Xent
+    and nothing else."""
+    beta, tau_plus = FLAGS.hard_negative_beta, FLAGS.debiased_tau_plus
+    if beta == 0 and tau_plus == 0:
+        return
+    _need_range(('hard_negative_beta',), ops.hcl_beta_ok, 'be >= 0 and finite')
+    _need_range(('debiased_tau_plus',), ops.hcl_tau_plus_ok, 'lie in [0, 1)')
+    if model_lib.pretrain_loss() != 'ntxent':
+        raise ValueError('--hard_negative_beta and --debiased_tau_plus correct NT-Xent: a nonzero value needs --contrastive_loss=ntxent '
+                         '(got %r with hard_negative_beta=%r, debiased_tau_plus=%r)' % (FLAGS.contrastive_loss, beta, tau_plus))
+    if not FLAGS.hidden_norm:
+        raise ValueError('--hard_negative_beta / --debiased_tau_plus need --hidden_norm=true: the floor M exp(-1 / temperature) of the '
+                         'negative term assumes dot products >= -1')
+    width = model_lib.projection_width()
+    if width not in ops.HCL_DIMS:
+        raise ValueError('--hard_negative_beta / --debiased_tau_plus need a loss width of %s (got %d from proj_head_mode=%r, '
+                         'proj_out_dim=%d): the hard-negative / debiased NT-Xent kernels are instantiated for those widths only'
+                         % ('/'.join(map(str, ops.HCL_DIMS)), width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+    if FLAGS.train_batch_size < 2:
+        raise ValueError('--hard_negative_beta / --debiased_tau_plus need --train_batch_size >= 2 (got %r): a row needs a negative'
+                         % (FLAGS.train_batch_size,))
+    if not FLAGS.temperature > 0:
+        raise ValueError('--hard_negative_beta / --debiased_tau_plus need --temperature > 0 (got %r)' % (FLAGS.temperature,))
+
+
 def _check_generalized():
     if FLAGS.gcl_dist not in obj_lib.GCL_DISTS:
         raise ValueError('Unknown prior {}'.format(FLAGS.gcl_dist))
@@ -110,6 +143,11 @@ def _check_generalized():
 # supervised part, run while collective A is in flight); target_outputs and keys (losses with a target); frozen (losses with
 # prototypes); logits_con (None; NT-Xent sets it).  Each function returns the loss handle.
 def _ntxent(c):
+    if ntxent_corrections_on():           # --hard_negative_beta / --debiased_tau_plus: the same logits, another loss over them
+        con_loss, c.logits_con, _ = obj_lib.add_hard_negative_contrastive_loss(
+            c.outputs, temperature=FLAGS.temperature, beta=FLAGS.hard_negative_beta, tau_plus=FLAGS.debiased_tau_plus,
+            strategy=c.strategy, overlap=c.overlap)
+        return con_loss
     con_loss, c.logits_con, _ = obj_lib.add_contrastive_loss(                           # tf2/run.py:582-586
         c.outputs, hidden_norm=FLAGS.hidden_norm, temperature=FLAGS.temperature, strategy=c.strategy, overlap=c.overlap)
     return con_loss
@@ -230,6 +268,12 @@ LOSSES = {
 }
 
 
+# the ntxent row while --hard_negative_beta / --debiased_tau_plus is nonzero: one more metric, everything else the row's own
+_NTXENT_CORRECTED = LOSSES['ntxent']._replace(metrics=LOSSES['ntxent'].metrics + (('train/contrast_floor_share', 'floor_share'),))
+
+
 def active():
     """The row of the active pretraining loss, or None outside a pretraining run."""
+    if ntxent_corrections_on():
+        return _NTXENT_CORRECTED
     return LOSSES.get(model_lib.pretrain_loss())

@@ -115,7 +115,8 @@ def local_crop_plan():
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover: the multi-crop flags,
-    the loss name, then the check of that loss's row of pretrain_losses.LOSSES (a pretraining run outside --mode=eval only).
+    the loss name, then --hard_negative_beta / --debiased_tau_plus and the check of that loss's row of pretrain_losses.LOSSES (a
+    pretraining run outside --mode=eval only).
     Returns True for the generalized loss in such a run, False otherwise (model.pretrain_loss() tells the others)."""
     check_swav_local_flags()
     check_dino_local_flags()
@@ -125,6 +126,7 @@ def check_contrastive_loss_flags():
     spec = loss_lib.active()
     if spec is None or FLAGS.mode == 'eval':
         return False
+    loss_lib.check_ntxent_corrections()
     if spec.check is not None:
         spec.check()
     return spec is loss_lib.LOSSES['generalized']

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -337,6 +337,41 @@ def main():
                     row['supcon_over_gcl_lse_fwd'], row['supcon_over_gcl_lse_bwd']), flush=True)
             res.append(row)
             del zl, za, ws, gws, sws
+    if 'hcl' in what:
+        # hard-negative / debiased NT-Xent (csrc/hcl.hip) beside the supervised contrastive sweeps and NT-Xent at the same shapes in the
+        # same run: the median of --iters launches with [min, max].  beta = 0.5, tau_plus = 0.1 (both online pairs, both exp2 per element)
+        # and beta = 0 (the second pair skipped).  Matrix FLOPs as supcon's: 8nND forward, 24nND backward.
+        def spread(fn):
+            ts = sorted(timeit(fn, 1, warm=0) for _ in range(args.iters))
+            return dict(median=ts[len(ts) // 2], min=ts[0], max=ts[-1])
+        for (n, N) in [(512, 512), (512, 4096)]:
+            D = 128
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            labels = torch.randint(0, 100, (N,), device=dev, dtype=torch.int32)
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            sws = ops.supcon_workspace(n, N, D, dev)
+            _, srs, _ = ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)
+            hws = ops.hcl_workspace(n, N, D, dev)
+            _, hrs, _ = ops.hcl_fwd(zl, za, 0, 0.1, 0.5, 0.1, ws=hws)
+            _, hrs0, _ = ops.hcl_fwd(zl, za, 0, 0.1, 0.0, 0.1, ws=hws)
+            for fn in (lambda: ops.hcl_fwd(zl, za, 0, 0.1, 0.5, 0.1, ws=hws), lambda: ops.hcl_bwd(zl, za, 0, 0.1, 0.5, 0.1, hrs, 1.0, hws)):
+                timeit(fn, 2)                                 # warm-up of every launch before the first timed one
+            row = dict(layer='hcl n%d N%d D%d' % (n, N, D), fwd_flops=8.0 * n * N * D, bwd_flops=24.0 * n * N * D, iters=args.iters,
+                       hcl_fwd_us=spread(lambda: ops.hcl_fwd(zl, za, 0, 0.1, 0.5, 0.1, ws=hws)),
+                       hcl_bwd_us=spread(lambda: ops.hcl_bwd(zl, za, 0, 0.1, 0.5, 0.1, hrs, 1.0, hws)),
+                       hcl_beta0_fwd_us=spread(lambda: ops.hcl_fwd(zl, za, 0, 0.1, 0.0, 0.1, ws=hws)),
+                       hcl_beta0_bwd_us=spread(lambda: ops.hcl_bwd(zl, za, 0, 0.1, 0.0, 0.1, hrs0, 1.0, hws)),
+                       supcon_fwd_us=spread(lambda: ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)),
+                       supcon_bwd_us=spread(lambda: ops.supcon_bwd(zl, za, labels, 0, 0.1, srs, 1.0, sws)),
+                       ntxent_fwd_us=spread(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws)),
+                       ntxent_bwd_us=spread(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws)))
+            print('hcl n=%d N=%d D=%d: ' % (n, N, D) + ' | '.join(
+                '%s %.0f [%.0f, %.0f] us' % (k[:-3], v['median'], v['min'], v['max']) for k, v in row.items() if k.endswith('_us')), flush=True)
+            res.append(row)
+            del zl, za, ws, sws, hws
     if 'barlow' in what:
         # Barlow Twins loss (csrc/barlow.hip) beside NT-Xent at the same (n, N, D) in the same run: the register-resident sweeps at
         # D = 128, the wide kernels above 256 -- the same exact fp32-input MFMA.  Matrix FLOPs: the two Gram blocks 2 x 2nND = 4nND forward,
