@@ -183,6 +183,26 @@ int simclr_hcl_fwd(const float* z_local, const float* z_all, int n, int N, int D
 int simclr_hcl_bwd(const float* z_local, const float* z_all, int n, int N, int D, int rank, float temperature, float beta, float tau_plus,
                    const float* row_stats, float grad_scale, float* dz_local, float* dz_all, void* workspace, simclr_stream_t stream);
 
+/* ---- NNCLR: nearest-neighbour positives for NT-Xent (after Dwibedi et al. 2021, With a Little Help from My Friends), csrc/nnclr.hip ----
+ * This project's definition, written from memory of the paper, not a parity claim.  nn_local [2n, D] = the neighbour row of every
+ * local row (view-a rows, then view-b rows; constants), z_local [2n, D] = the local rows themselves (read for nn_sim only), z_all
+ * [2N, D] laid out as simclr_ntxent_fwd's.  Local row r (view v = r / n, sample s = r % n) contrasts its neighbour against the N
+ * columns of the OTHER view, C(r) = [(1 - v)*N, (1 - v)*N + N), with the positive p(r) = (1 - v)*N + rank*n + s.  With a = 1 / T:
+ *   l_r = logsumexp_{c in C(r)}(a nn_r.z_all[c]) - a nn_r.z_all[p(r)]
+ * D in {64, 128, 256}, any n >= 1 with N = R*n >= 2; T > 0 and finite; every matrix, row_stats and the workspace 16-byte aligned.
+ * Anything else returns 1 and launches nothing.  Exact fp32-input MFMA, the [2n, N] matrix never written, the row finalize in double,
+ * no atomics: bitwise run-to-run deterministic.  The workspace holds one fwd/bwd pair. */
+size_t simclr_nnclr_workspace_bytes(int n, int N, int D);      /* 0 for a shape the kernels refuse */
+/* out[0] = the replica's loss share = (1 / n) sum_{r < 2n} l_r (the sum of the two per-view means), out[1] = the share of the 2n local
+ * rows whose positive column is the lowest-index maximum of C(r), out[2] = the mean of z_r.nn_r.  row_stats [2n, 4] = {log2-sum-exp2 of
+ * the row's base-2 logits as a float, what the float left of it, 1 - P_r,p(r), z_r.nn_r}; the backward reads the first three. */
+int simclr_nnclr_fwd(const float* nn_local, const float* z_local, const float* z_all, int n, int N, int D, int rank, float temperature,
+                     float* out, float* row_stats, void* workspace, simclr_stream_t stream);
+/* The column gradient, the only one there is: dz_all [2N, D] = (grad_scale a / n) sum_{r : c in C(r)} (P_rc - [c = p(r)]) nn_r, P_r the
+ * softmax over C(r) (to be reduce-scattered like simclr_ntxent_bwd's dz_all).  No row-side term: the neighbour rows are constants. */
+int simclr_nnclr_bwd(const float* nn_local, const float* z_all, int n, int N, int D, int rank, float temperature, const float* row_stats,
+                     float grad_scale, float* dz_all, void* workspace, simclr_stream_t stream);
+
 /* ---- Barlow Twins loss (Zbontar et al. 2021, Barlow Twins: Self-Supervised Learning via Redundancy Reduction), csrc/barlow.hip ----
  * The Gram form: with zhat the per-view, per-dimension standardisation of the gathered block over the GLOBAL batch,
  * C = zhat1^T zhat2 / N ([D, D], never formed), c_i = C_ii, G1 = zhat1 zhat1^T, G2 = zhat2 zhat2^T,

@@ -128,6 +128,13 @@ _DEFS = [
     ('debiased_tau_plus', 0.0, float, 'MI355X build: debiasing correction of NT-Xent (Chuang et al. 2020): the class prior of a false negative, '
                                       'whose expected mass is taken out of the negative term (floored at M exp(-1 / temperature)).  In [0, 1); '
                                       '0 = NT-Xent.  Same requirements as --hard_negative_beta.'),
+    # NNCLR: nearest-neighbour positives for NT-Xent (add_nn_contrastive_loss), read under --contrastive_loss=ntxent only
+    ('nn_queue_size', 0, int, 'MI355X build: rows K of the support queue of NNCLR (after Dwibedi et al. 2021): the anchor of every row is '
+                              'its nearest neighbour among the last K view-a embeddings of the global batch.  0 = NT-Xent.  A nonzero value '
+                              'must be a multiple of --train_batch_size, at least that, and needs --contrastive_loss=ntxent, '
+                              '--hidden_norm=true, a loss width of 64, 128 or 256, --train_batch_size >= 2 and both --hard_negative_beta and '
+                              '--debiased_tau_plus at 0.  Ignored by --train_mode=finetune and --mode=eval.'),
+    ('nn_queue_seed', 0, int, 'MI355X build: seed of the random unit rows the support queue of NNCLR starts from.'),
     # Barlow Twins (Zbontar et al. 2021) in place of NT-Xent for pretraining
     ('bt_lambda', 0.0051, float, 'MI355X build: weight of the off-diagonal (redundancy-reduction) term of the Barlow Twins loss (lambda_weight).'),
     ('bt_loss_scaling', 1.0, float, 'MI355X build: factor on the whole Barlow Twins loss (loss_scaling).'),

@@ -690,6 +690,33 @@ class MocoQueue:
         return ptr
 
 
+class SupportQueue(MocoQueue):
+    """The support set of NNCLR (--nn_queue_size): MocoQueue's ring under the variable name `nnclr/queue` -- a device fp32 [K, D]
+    tensor of unit rows, seeded random directions at the start, not trainable (no optimizer slot, no weight decay, no gradient).
+    enqueue(z_all[:N], step) overwrites the rows [ptr, ptr + N), ptr = moco_queue_ptr(step, N, K), with the view-a rows of the step's
+    GLOBAL batch: every replica writes the same rows, so the queues stay bitwise equal without a collective."""
+
+    NAME = 'nnclr/queue'
+
+    def checkpointable(self, model):
+        """The object run.main hands the checkpoint: the model's variables, then `nnclr/queue`."""
+        return _WithSupport(model, self)
+
+
+class _WithSupport:
+    """What an NNCLR checkpoint holds: every variable of the model under its own name (the optimizer's slots hang on these very
+    objects), then `nnclr/queue`.  Evaluation, --knn_eval and fine-tuning read such a file as a plain pretraining checkpoint: the one
+    name they do not know is left unused."""
+
+    def __init__(self, model, support):
+        self.model, self.support = model, support
+        self.supervised_head = model.supervised_head
+
+    @property
+    def variables(self):
+        return self.model.variables + self.support.variables
+
+
 class DinoCenter:
     """The centre of the DINO teacher (Caron et al. 2021, eq. 4): a device fp32 [K] vector, zeros at the start, exposed as ONE
     non-trainable Variable `dino/center` (checkpointed with the target network; no optimizer slot, no weight decay, no gradient) and

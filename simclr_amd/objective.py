@@ -17,6 +17,9 @@ positive) on the kernels of csrc/supcon.hip.
 `add_hard_negative_contrastive_loss` is NT-Xent with the hard-negative re-weighting of Robinson et al. 2021 (beta) and the debiasing
 correction of Chuang et al. 2020 (tau_plus) on the kernels of csrc/hcl.hip; at beta = 0 and tau_plus = 0 it is NT-Xent.
 
+`add_nn_contrastive_loss` is NNCLR (after Dwibedi et al. 2021): NT-Xent whose anchors are the rows' nearest neighbours in a support
+queue (ops.knn_topk for the search, the kernels of csrc/nnclr.hip for the loss); only the columns carry gradient.
+
 `add_barlow_twins_loss` is the Barlow Twins loss of Zbontar et al. 2021 (redundancy reduction on the cross-correlation of the two views'
 batch-standardised hiddens; no negatives) in its Gram form on the kernels of csrc/barlow.hip.
 
@@ -505,6 +508,66 @@ def add_hard_negative_contrastive_loss(hidden, temperature=1.0, beta=0.0, tau_pl
     loss.floor_share = out[1:2]
     loss.normalized = z
     return loss, _NtxentScoredLogits(z, z_all, temperature, rank), LazyLabels(n, n * R, rank, z.device)
+
+
+def add_nn_contrastive_loss(hidden, support, temperature=1.0, strategy=None, overlap=None):
+    """NNCLR (after Dwibedi et al. 2021): NT-Xent whose anchor is the row's nearest neighbour in a support queue, on the kernels of
+    csrc/nnclr.hip.  This project's definition, written from memory of the paper, not a parity claim.
+
+    With z = l2norm(hidden), z_all the gathered block, S = support and a = 1 / temperature, local row r (view v, global image g):
+      j(r) = argmax_k z_r . S_k  (exact fp32, ties to the lowest k, no gradient),   nn_r = S_j(r)  (a constant),
+      C(r) = the N columns of the OTHER view,   p(r) = (1 - v) N + g,
+      l_r  = logsumexp_{c in C(r)}(a nn_r . z_all[c]) - a nn_r . z_all[p(r)],   loss = (1 / n) sum_{r < 2n} l_r,
+    the sum of the two per-view means, as add_contrastive_loss forms NT-Xent (a replica's value is its share; the mean over replicas is
+    the loss).  Only the columns carry gradient: the rows of the logits matrix are queue rows.
+
+    Args:
+      hidden: float32 device tensor [2n, D] = [view-a rows; view-b rows], D in {64, 128, 256}; the global batch holds N >= 2 images.
+      support: float32 device tensor [K, D] of unit rows (model.SupportQueue.value); read, never written.
+      temperature: > 0.  strategy, overlap: as add_supcon_loss (the hidden block is gathered asynchronously; the search and overlap()
+        run meanwhile).
+    Returns:
+      A loss scalar with .backward / .backward_start / .backward_finish (-> gradient wrt hidden), the device scalars .acc (share of rows
+      whose positive column is the lowest-index maximum of C(r)) and .nn_sim (mean z_r . nn_r), .nn_index (int32 [2n]), .neighbours
+      ([2n, D]), .normalized (z) and .gathered (z_all, whose first N rows the caller enqueues after the optimizer step).
+    """
+    assert hidden.dtype == torch.float32 and hidden.dim() == 2
+    hidden = hidden.contiguous()
+    D = hidden.shape[1]
+    if D not in ops.NNCLR_DIMS:
+        raise ValueError('the NNCLR kernels support hidden widths %s (got %d)' % ('/'.join(map(str, ops.NNCLR_DIMS)), D))
+    if support.dim() != 2 or support.shape[1] != D or support.dtype != torch.float32 or support.shape[0] < 1:
+        raise ValueError('add_nn_contrastive_loss: need a float32 support queue [K, %d] (got %s %s)' % (D, tuple(support.shape), support.dtype))
+    if not 0.0 < float(temperature) < float('inf'):
+        raise ValueError('add_nn_contrastive_loss: need temperature > 0 and finite (got %r)' % (temperature,))
+    z, inv = ops.l2norm_fwd(hidden)
+    rank = replica_id(strategy)
+    pending = gather_hidden(z, strategy, async_op=True)
+    # the search needs the local rows only: it runs while the gather is in flight
+    _, top_idx = ops.knn_topk(z, support.contiguous(), 1)
+    nn_index = top_idx.reshape(-1)
+    neighbours = support.index_select(0, nn_index.long())
+    if overlap is not None:
+        overlap()
+    z_all = pending()
+    out, row_stats, ws = ops.nnclr_fwd(neighbours, z, z_all, rank, temperature)
+    state = {}
+
+    def backward_start(grad_scale=1.0):
+        dz_all = ops.nnclr_bwd(neighbours, z_all, rank, temperature, row_stats, grad_scale, ws)
+        state['slot'] = scatter_hidden_grad(dz_all, strategy, async_op=True)   # transpose of the concat, as NT-Xent's
+
+    def backward_finish():
+        return ops.l2norm_bwd(z, inv, state.pop('slot')())                       # no row-side term: the neighbours are constants
+
+    def backward(grad_scale=1.0):
+        backward_start(grad_scale)
+        return backward_finish()
+
+    loss = _Loss(out[0:1], backward, backward_start, backward_finish)
+    loss.acc, loss.nn_sim = out[1:2], out[2:3]
+    loss.nn_index, loss.neighbours, loss.normalized, loss.gathered = nn_index, neighbours, z, z_all
+    return loss
 
 
 def add_barlow_twins_loss(hidden, lambda_weight=0.0051, loss_scaling=1.0, eps=1e-5, strategy=None, overlap=None):

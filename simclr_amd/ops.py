@@ -451,6 +451,76 @@ def hcl_bwd(z_local, z_all, rank, temperature, beta, tau_plus, row_stats, grad_s
     return dz_local, dz_all
 
 
+# ---------------------------------------------------------------- NNCLR: nearest-neighbour positives for NT-Xent (csrc/nnclr.hip)
+NNCLR_DIMS = (64, 128, 256)         # hidden widths the NNCLR kernels are instantiated for
+
+
+def _nnclr_check(nn_local, z_all, temperature):
+    if (nn_local.dim() != 2 or z_all.dim() != 2 or nn_local.dtype != torch.float32 or z_all.dtype != torch.float32
+            or z_all.shape[1] != nn_local.shape[1]):
+        raise ValueError('nnclr: need float32 neighbour rows [2n, D] and z_all [2N, D] of one width (got %s %s and %s %s)'
+                         % (tuple(nn_local.shape), nn_local.dtype, tuple(z_all.shape), z_all.dtype))
+    n, D = nn_local.shape[0] // 2, nn_local.shape[1]
+    N = z_all.shape[0] // 2
+    if D not in NNCLR_DIMS:
+        raise ValueError('the NNCLR kernels support hidden widths %s (got %d)' % ('/'.join(map(str, NNCLR_DIMS)), D))
+    if n < 1 or nn_local.shape[0] != 2 * n or N < 2 or N < n or N % n != 0 or z_all.shape[0] != 2 * N:
+        raise ValueError('nnclr: need neighbour rows [2n, D] with n >= 1 and z_all [2N, D] with N = R*n >= 2 (got %d and %d rows)'
+                         % (nn_local.shape[0], z_all.shape[0]))
+    if not 0.0 < float(temperature) < float('inf'):
+        raise ValueError('nnclr: temperature must be > 0 and finite (got %r)' % (temperature,))
+    if not nn_local.is_contiguous() or not z_all.is_contiguous():
+        raise ValueError('nnclr: the neighbour rows and z_all must be contiguous')
+    return n, N, D
+
+
+def nnclr_workspace(n, N, D, device):
+    nbytes = lib().nnclr_workspace_bytes(n, N, D)
+    if nbytes <= 0:
+        raise ValueError('nnclr_workspace: bad shape n=%d N=%d D=%d' % (n, N, D))
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+
+
+def nnclr_fwd(nn_local, z_local, z_all, rank, temperature, ws=None):
+    """NNCLR forward: the neighbour rows nn_local [2n, D] against the other view's N columns of z_all [2N, D]; z_local [2n, D] is read
+    for nn_sim only.  Returns out = [loss share, acc, nn_sim, -] (device), row_stats [2n, 4] = {log2-sum-exp2 as a float, what the float left
+    of it, 1 - P_r,p(r), z_r . nn_r}, the workspace."""
+    n, N, D = _nnclr_check(nn_local, z_all, temperature)
+    if tuple(z_local.shape) != (2 * n, D) or z_local.dtype != torch.float32 or not z_local.is_contiguous():
+        raise ValueError('nnclr_fwd: z_local must be the contiguous float32 %s block the neighbours were searched for (got %s %s)'
+                         % ((2 * n, D), tuple(z_local.shape), z_local.dtype))
+    if not 0 <= int(rank) < N // n:
+        raise ValueError('nnclr_fwd: rank %d outside the %d replicas' % (rank, N // n))
+    if ws is None:
+        ws = nnclr_workspace(n, N, D, nn_local.device)
+    if ws.numel() * ws.element_size() < lib().nnclr_workspace_bytes(n, N, D):
+        raise ValueError('nnclr_fwd: the workspace is smaller than nnclr_workspace(%d, %d, %d)' % (n, N, D))
+    out = step_scalars(4, nn_local.device)
+    row_stats = torch.empty(2 * n, 4, device=nn_local.device, dtype=torch.float32)
+    _launch('nnclr_fwd', 4.0 * n * N * D, 4.0 * (4 * n + 2 * N) * D,
+            lambda: lib().nnclr_fwd(_p(nn_local), _p(z_local), _p(z_all), n, N, D, int(rank), float(temperature), _p(out),
+                                    _p(row_stats), _p(ws), _s()))
+    return out, row_stats, ws
+
+
+def nnclr_bwd(nn_local, z_all, rank, temperature, row_stats, grad_scale, ws):
+    """NNCLR backward, the key-side sweep: dz_all [2N, D] (the per-replica partial, to be reduce-scattered).  There is no row-side
+    gradient: the neighbour rows are constants."""
+    n, N, D = _nnclr_check(nn_local, z_all, temperature)
+    if tuple(row_stats.shape) != (2 * n, 4) or row_stats.dtype != torch.float32 or not row_stats.is_contiguous():
+        raise ValueError('nnclr_bwd: row_stats must be the contiguous float32 %s block of nnclr_fwd (got %s %s)'
+                         % ((2 * n, 4), tuple(row_stats.shape), row_stats.dtype))
+    if not 0 <= int(rank) < N // n:
+        raise ValueError('nnclr_bwd: rank %d outside the %d replicas' % (rank, N // n))
+    if ws is None or ws.numel() * ws.element_size() < lib().nnclr_workspace_bytes(n, N, D):
+        raise ValueError('nnclr_bwd: the workspace is smaller than nnclr_workspace(%d, %d, %d)' % (n, N, D))
+    dz_all = torch.empty_like(z_all)
+    _launch('nnclr_bwd', 8.0 * n * N * D, 4.0 * (2 * n + 4 * N) * D,
+            lambda: lib().nnclr_bwd(_p(nn_local), _p(z_all), n, N, D, int(rank), float(temperature), _p(row_stats), float(grad_scale),
+                                    _p(dz_all), _p(ws), _s()))
+    return dz_all
+
+
 # ---------------------------------------------------------------- Barlow Twins loss (csrc/barlow.hip)
 BT_DIM_STEP, BT_MIN_DIM, BT_MAX_DIM = 64, 64, 8192       # hidden widths the Barlow Twins kernels take: multiples of 64 in [64, 8192]
 BT_EPS = 1e-5

@@ -128,6 +128,40 @@ def check_ntxent_corrections():
         raise ValueError('--hard_negative_beta / --debiased_tau_plus need --temperature > 0 (got %r)' % (FLAGS.temperature,))
 
 
+def nn_positives_on():
+    """A nonzero --nn_queue_size in an NT-Xent pretraining run outside --mode=eval: the step trains add_nn_contrastive_loss against a
+    model.SupportQueue.  Fine-tuning and evaluation ignore the flag."""
+    return model_lib.pretrain_loss() == 'ntxent' and FLAGS.mode != 'eval' and FLAGS.nn_queue_size != 0
+
+
+def check_nn_positives():
+    """The start-up check of --nn_queue_size, run for every pretraining loss: the flag replaces NT-Xent's anchors and nothing else."""
+    K = FLAGS.nn_queue_size
+    if K == 0:
+        return
+    if model_lib.pretrain_loss() != 'ntxent':
+        raise ValueError('--nn_queue_size draws the positives of NT-Xent from a support queue: a nonzero value needs '
+                         '--contrastive_loss=ntxent (got %r with nn_queue_size=%r)' % (FLAGS.contrastive_loss, K))
+    if not (FLAGS.hard_negative_beta == 0 and FLAGS.debiased_tau_plus == 0):
+        raise ValueError('--nn_queue_size does not combine with --hard_negative_beta / --debiased_tau_plus (got %r with %r / %r): '
+                         'the corrected NT-Xent contrasts a block against itself' % (K, FLAGS.hard_negative_beta, FLAGS.debiased_tau_plus))
+    if FLAGS.train_batch_size < 2:
+        raise ValueError('--nn_queue_size needs --train_batch_size >= 2 (got %r): a row needs a negative' % (FLAGS.train_batch_size,))
+    rows = FLAGS.train_batch_size                   # the global N view-a rows a step enqueues
+    if K < rows or K % rows != 0 or K > ops.MOCO_MAX_QUEUE:
+        raise ValueError('--nn_queue_size must be a multiple of train_batch_size = %d, at least that and at most %d (got %r): '
+                         'the ring never wraps inside a step' % (rows, ops.MOCO_MAX_QUEUE, K))
+    if not FLAGS.hidden_norm:
+        raise ValueError('--nn_queue_size needs --hidden_norm=true: the nearest neighbour is the largest dot product of unit rows')
+    width = model_lib.projection_width()
+    if width not in ops.NNCLR_DIMS:
+        raise ValueError('--nn_queue_size needs a loss width of %s (got %d from proj_head_mode=%r, proj_out_dim=%d): the NNCLR kernels '
+                         'are instantiated for those widths only'
+                         % ('/'.join(map(str, ops.NNCLR_DIMS)), width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+    if not FLAGS.temperature > 0:
+        raise ValueError('--nn_queue_size needs --temperature > 0 (got %r)' % (FLAGS.temperature,))
+
+
 def _check_generalized():
     if FLAGS.gcl_dist not in obj_lib.GCL_DISTS:
         raise ValueError('Unknown prior {}'.format(FLAGS.gcl_dist))
@@ -141,8 +175,12 @@ def _check_generalized():
 # c: the namespace run.single_step fills for one step -- model, target, strategy, steps_per_epoch; step (optimizer.iterations before
 # its increment: a restored run continues every schedule derived from it); outputs (the online projection), labels, overlap (the
 # supervised part, run while collective A is in flight); target_outputs and keys (losses with a target); frozen (losses with
-# prototypes); logits_con (None; NT-Xent sets it).  Each function returns the loss handle.
+# prototypes); support (the model.SupportQueue of --nn_queue_size, or None);
+# logits_con (None; NT-Xent sets it).  Each function returns the loss handle.
 def _ntxent(c):
+    if nn_positives_on():                 # --nn_queue_size: the anchors are the rows' nearest neighbours in c.support
+        return obj_lib.add_nn_contrastive_loss(c.outputs, c.support.value, temperature=FLAGS.temperature, strategy=c.strategy,
+                                               overlap=c.overlap)
     if ntxent_corrections_on():           # --hard_negative_beta / --debiased_tau_plus: the same logits, another loss over them
         con_loss, c.logits_con, _ = obj_lib.add_hard_negative_contrastive_loss(
             c.outputs, temperature=FLAGS.temperature, beta=FLAGS.hard_negative_beta, tau_plus=FLAGS.debiased_tau_plus,
@@ -272,8 +310,15 @@ LOSSES = {
 _NTXENT_CORRECTED = LOSSES['ntxent']._replace(metrics=LOSSES['ntxent'].metrics + (('train/contrast_floor_share', 'floor_share'),))
 
 
+# the ntxent row while --nn_queue_size is nonzero: the loss scores its own logits (no LazyLogits), and reports how close the neighbours are
+_NTXENT_NN = LOSSES['ntxent']._replace(
+    metrics=LOSSES['ntxent'].metrics + (('train/contrast_acc', 'acc'), ('train/nn_similarity', 'nn_sim')), logits_metrics=())
+
+
 def active():
     """The row of the active pretraining loss, or None outside a pretraining run."""
+    if nn_positives_on():
+        return _NTXENT_NN
     if ntxent_corrections_on():
         return _NTXENT_CORRECTED
     return LOSSES.get(model_lib.pretrain_loss())

@@ -115,8 +115,8 @@ def local_crop_plan():
 
 def check_contrastive_loss_flags():
     """Raise before any device work when the pretraining loss flags name something the kernels do not cover: the multi-crop flags,
-    the loss name, then --hard_negative_beta / --debiased_tau_plus and the check of that loss's row of pretrain_losses.LOSSES (a
-    pretraining run outside --mode=eval only).
+    the loss name, then --hard_negative_beta / --debiased_tau_plus, --nn_queue_size and the check of that loss's row of
+    pretrain_losses.LOSSES (a pretraining run outside --mode=eval only).
     Returns True for the generalized loss in such a run, False otherwise (model.pretrain_loss() tells the others)."""
     check_swav_local_flags()
     check_dino_local_flags()
@@ -127,6 +127,7 @@ def check_contrastive_loss_flags():
     if spec is None or FLAGS.mode == 'eval':
         return False
     loss_lib.check_ntxent_corrections()
+    loss_lib.check_nn_positives()
     if spec.check is not None:
         spec.check()
     return spec is loss_lib.LOSSES['generalized']
@@ -260,7 +261,7 @@ def all_reduce_stats_async(tensor, strategy):
     return wait
 
 
-def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None, steps_per_epoch=None):
+def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None, target=None, steps_per_epoch=None, support=None):
     """Returns single_step(features, labels) -- tf2/run.py:557-622.
     A pretraining step trains the row of pretrain_losses.LOSSES that model.pretrain_loss() names: the row's `call` makes the loss, its
     (metric name, attribute) pairs are logged and re-pointed by one loop each; the phases that differ between losses (below) are
@@ -276,6 +277,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     both prototype tables, add_dino_loss, backward (loss kernels, the normalisations, the heads, the encoder), gradient synchronisation,
     optimizer (without the prototypes while they are frozen), target.update(step), THEN wait for the mean and move the centre.
     --contrastive_loss=swav needs no target (passing one is refused) and steps_per_epoch >= 1, which the freeze of the prototypes counts.
+    support: model.SupportQueue, required while --nn_queue_size is nonzero in an NT-Xent pretraining run and refused otherwise.  The
+    step is then: online forward, normalise and gather, the exact top-1 search of the local rows in the queue AS IT STANDS,
+    add_nn_contrastive_loss, backward, optimizer, then support.enqueue of the global batch's view-a rows.
     The step is the NT-Xent step with add_swav_loss in place of the loss: online forward, normalise the rows and the prototypes, gather
     the normalised block, the Sinkhorn on it, the loss on the local rows, backward, gradient synchronisation, optimizer (without the
     prototypes while they are frozen).
@@ -313,6 +317,14 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     elif target is not None:
         raise ValueError('a target network belongs to the BYOL pretraining step (got contrastive_loss=%r, train_mode=%r)'
                          % (FLAGS.contrastive_loss, FLAGS.train_mode))
+    nn_positives = loss_lib.nn_positives_on()
+    if nn_positives and (support is None or getattr(support, 'enqueue', None) is None):
+        raise ValueError('--nn_queue_size=%d needs a support queue: make_single_step(..., support=model.SupportQueue(K, D, seed))'
+                         % FLAGS.nn_queue_size)
+    if not nn_positives and support is not None:
+        raise ValueError('a support queue belongs to the NT-Xent pretraining step under a nonzero --nn_queue_size (got '
+                         'contrastive_loss=%r, train_mode=%r, nn_queue_size=%r)'
+                         % (FLAGS.contrastive_loss, FLAGS.train_mode, FLAGS.nn_queue_size))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
     local_crops = local_crop_plan()[0]
 
@@ -336,7 +348,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             # training arithmetic again, for the rest of the step
             teacher_logits = teacher(features)
         c = types.SimpleNamespace(model=model, target=target, strategy=strategy, steps_per_epoch=steps_per_epoch, step=step,
-                                  labels=labels, target_outputs=None, keys=None, frozen=False, logits_con=None)
+                                  labels=labels, target_outputs=None, keys=None, frozen=False, logits_con=None, support=support)
         if target is not None:
             # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
             if FLAGS.use_blur:
@@ -457,6 +469,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             # The enqueue comes AFTER the backward: the backward recomputes the logits from the queue, and a queue that already held
             # this step's keys would silently differentiate another loss (every query would find its own positive among the negatives).
             target.queue.enqueue(moco_gather(), step)
+        if nn_positives:
+            # The enqueue comes AFTER the backward, which recomputes the logits from the neighbour rows it gathered (a copy: the queue
+            # itself is not re-read), and after the search of this step: a row never finds itself.  Every replica writes the same N rows.
+            support.enqueue(con_loss.gathered[:con_loss.gathered.shape[0] // 2], step)
         if name == 'dino':
             # The centre moves AFTER the backward, which recomputes the teacher softmax from it (moved earlier, the step would
             # differentiate another loss in silence), and it reads the target prototypes the FORWARD used, not the ones update() left.
@@ -754,8 +770,11 @@ def main(argv):
     # and the freeze of its prototypes counts epochs
     spec = loss_lib.active()
     target = spec.make_target(model, train_steps, epoch_steps) if spec is not None and spec.make_target is not None else None
+    # --nn_queue_size: the support queue of NNCLR, seeded (the same on every replica) and checkpointed after the model's variables
+    support = (model_lib.SupportQueue(FLAGS.nn_queue_size, model_lib.projection_width(), FLAGS.nn_queue_seed)
+               if loss_lib.nn_positives_on() else None)
     step_fn = make_single_step(model, optimizer, strategy, teacher=teacher, target=target,
-                               steps_per_epoch=max(epoch_steps, 1) if swav_loss_on() else None)
+                               steps_per_epoch=max(epoch_steps, 1) if swav_loss_on() else None, support=support)
     per_replica = FLAGS.train_batch_size // R                                   # tf2/data.py:45
     data = None
     if builder is None:
@@ -773,8 +792,8 @@ def main(argv):
         model(torch.zeros(2, FLAGS.image_size, FLAGS.image_size, 3, device=RT.device), training=False)
         if swav_loss_on() and model.prototype_head.kernel is None:
             model.prototype_head.build(model_lib.projection_width())    # last: every other initial value is that of an ntxent run
-        manager, status = try_restore_from_checkpoint(target.checkpointable() if target is not None else model, optimizer,
-                                                      FLAGS.model_dir, FLAGS.checkpoint,
+        saved = target.checkpointable() if target is not None else support.checkpointable(model) if support is not None else model
+        manager, status = try_restore_from_checkpoint(saved, optimizer, FLAGS.model_dir, FLAGS.checkpoint,
                                                       FLAGS.keep_checkpoint_max, FLAGS.zero_init_logits_layer)
         if target is not None and status is not None:
             # --checkpoint, or a file without these entries: the copy of the online model is made after the restore; likewise the
@@ -786,6 +805,9 @@ def main(argv):
                     (target.center, lambda: target.center.NAME in missing, lambda: target.center.reset())):
                 if part is not None and (not manager.latest_checkpoint or absent()):
                     reset()
+        if support is not None and status is not None and (not manager.latest_checkpoint
+                                                           or support.NAME in status.missing_in_checkpoint):
+            support.reset()          # --checkpoint (a weights-only restore may have filled it), or a file without the queue: the seeded rows
         if status is not None and manager.latest_checkpoint:
             step = int(optimizer.iterations)
             logging.info('restored %s; continuing from step %d', manager.latest_checkpoint, step)

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -372,6 +372,46 @@ def main():
                 '%s %.0f [%.0f, %.0f] us' % (k[:-3], v['median'], v['min'], v['max']) for k, v in row.items() if k.endswith('_us')), flush=True)
             res.append(row)
             del zl, za, ws, sws, hws
+    if 'nnclr' in what:
+        # NNCLR (csrc/nnclr.hip) beside NT-Xent and the supervised contrastive sweeps at the same (n, N, D) in the same run, and the new
+        # cost of the step, the exact top-1 search of the 2n local rows in a K = 65536 queue (ops.knn_topk): the median of --iters
+        # launches with [min, max].  Matrix FLOPs: 4nND forward (N candidate columns a row, not 2N), 8nND backward (the key side only).
+        def spread(fn):
+            ts = sorted(timeit(fn, 1, warm=0) for _ in range(args.iters))
+            return dict(median=ts[len(ts) // 2], min=ts[0], max=ts[-1])
+        K = 65536
+        for (n, N) in [(512, 512), (512, 4096)]:
+            D = 128
+            zl = torch.nn.functional.normalize(torch.randn(2 * n, D, device=dev), dim=1)
+            za = torch.nn.functional.normalize(torch.randn(2 * N, D, device=dev), dim=1)
+            za[:n] = zl[:n]; za[N:N + n] = zl[n:]
+            queue = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            labels = torch.randint(0, 100, (N,), device=dev, dtype=torch.int32)
+            ws = ops.ntxent_workspace(n, N, D, dev)
+            out, rs, _ = ops.ntxent_fwd(zl, za, 0, 0.1, ws)
+            sws = ops.supcon_workspace(n, N, D, dev)
+            _, srs, _ = ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)
+            _, idx = ops.knn_topk(zl, queue, 1)
+            nn = queue.index_select(0, idx.reshape(-1).long())
+            nws = ops.nnclr_workspace(n, N, D, dev)
+            _, nrs, _ = ops.nnclr_fwd(nn, zl, za, 0, 0.1, ws=nws)
+            for fn in (lambda: ops.nnclr_fwd(nn, zl, za, 0, 0.1, ws=nws), lambda: ops.nnclr_bwd(nn, za, 0, 0.1, nrs, 1.0, nws),
+                       lambda: ops.knn_topk(zl, queue, 1)):
+                timeit(fn, 2)                                 # warm-up of every launch before the first timed one
+            row = dict(layer='nnclr n%d N%d D%d K%d' % (n, N, D, K), fwd_flops=4.0 * n * N * D, bwd_flops=8.0 * n * N * D,
+                       search_flops=4.0 * n * K * D, iters=args.iters,
+                       nnclr_fwd_us=spread(lambda: ops.nnclr_fwd(nn, zl, za, 0, 0.1, ws=nws)),
+                       nnclr_bwd_us=spread(lambda: ops.nnclr_bwd(nn, za, 0, 0.1, nrs, 1.0, nws)),
+                       nnclr_search_us=spread(lambda: ops.knn_topk(zl, queue, 1)),
+                       nnclr_gather_us=spread(lambda: queue.index_select(0, idx.reshape(-1).long())),
+                       supcon_fwd_us=spread(lambda: ops.supcon_fwd(zl, za, labels, 0, 0.1, ws=sws)),
+                       supcon_bwd_us=spread(lambda: ops.supcon_bwd(zl, za, labels, 0, 0.1, srs, 1.0, sws)),
+                       ntxent_fwd_us=spread(lambda: ops.ntxent_fwd(zl, za, 0, 0.1, ws)),
+                       ntxent_bwd_us=spread(lambda: ops.ntxent_bwd(zl, za, 0, 0.1, rs, 1.0, out, ws)))
+            print('nnclr n=%d N=%d D=%d K=%d: ' % (n, N, D, K) + ' | '.join(
+                '%s %.0f [%.0f, %.0f] us' % (k[:-3], v['median'], v['min'], v['max']) for k, v in row.items() if k.endswith('_us')), flush=True)
+            res.append(row)
+            del zl, za, ws, sws, nws, queue
     if 'barlow' in what:
         # Barlow Twins loss (csrc/barlow.hip) beside NT-Xent at the same (n, N, D) in the same run: the register-resident sweeps at
         # D = 128, the wide kernels above 256 -- the same exact fp32-input MFMA.  Matrix FLOPs: the two Gram blocks 2 x 2nND = 4nND forward,
