@@ -589,10 +589,11 @@ __global__ __launch_bounds__(256) void conv_igemm(const ConvP p) {
 template <typename T, int MODE, int BM, int BN, int NW, int STAGES, bool STATS, bool BNEPI, bool EXT = false,
           bool WIN = false, bool FAPPLY = false, int SPL = 0, bool TAIL = false, bool PSB = false, int FAS = 0, int EPS = 0, bool PSX = false>
 __global__ __launch_bounds__(NW * 64, (NW == 8 || STAGES == 3) ? 1 : (BN == 64 && (sizeof(T) == 2 || SPL == 13 || (SPL == 3 && PSB))) ? SIMCLR_BN64_WPE : 2) void conv_igemm_persistent(const ConvP p) {
-  // EPS (bf16 BNEPI only): the mask mode and the accumulate flag of the fused BatchNorm-backward-reduce epilogue as compile-time
+  // EPS (BNEPI only): the mask mode and the accumulate flag of the fused BatchNorm-backward-reduce epilogue as compile-time
   // constants -- EPS - 1 = 2 * (mode == 4) + accumulate for the modes a ResNet step uses (2: mask recomputed from the BatchNorm
   // input, 4: mask bits, sum(dm) only).  0: read from the kernel arguments.
-  static_assert(EPS == 0 || (BNEPI && sizeof(T) == 2 && EPS <= 4), "EPS specialises the bf16 BNEPI epilogue");
+  // fp32 storage: three-term data gradients with both operands pre-split (f32_eps_exists), register-direct epilogue below.
+  static_assert(EPS == 0 || (BNEPI && EPS <= 4 && (sizeof(T) == 2 || (MODE == MODE_DGRAD && SPL == 3 && PSB && PSX && !EXT))), "EPS specialises the BNEPI epilogue");
   const int bnm = EPS ? (((EPS - 1) >> 1) ? 4 : 2) : p.bn_mode;
   const bool accu = EPS ? ((EPS - 1) & 1) != 0 : p.accumulate != 0;
   // FAS (FAPPLY only): the run-time options of the fused BatchNorm-apply epilogue as compile-time constants for the two shapes every
@@ -1337,6 +1338,85 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || STAGES == 3) ? 1 : (BN == 64 &
     }
     __builtin_amdgcn_sched_barrier(0);      // the next batch's 32 load registers are not live before this batch has been stored
     }   // mb
+    } else if constexpr (EPS != 0 && sizeof(T) == 4) {
+    // ---- fp32 fused BatchNorm-backward-reduce epilogue with the mask mode / accumulate flag compiled in (EPS; N a multiple of 64, so a
+    // wave's 64 columns are valid or not together).  The generic loop below pays two or three dependent memory round trips per 16 x 16
+    // fragment (prior value -> wait -> BatchNorm input / mask byte -> wait -> store, and the next fragment's wait covers that store too).
+    // Here every global operand of a fragment ROW (NI fragments) is requested back to back, the row is computed in place over its
+    // accumulators, the NEXT row's operands are requested into the registers the computation freed, and only then is the row stored:
+    // one round trip per row, and the stores travel with the next row's loads.  Same arithmetic in the same order as the generic loop
+    // (mi outer, ni inner): same bits.  One row per batch is what the registers allow with no scratch at the parent's occupancy.
+    // Mask bits (mode 4): the NI fragments x 4 lane groups of a row use 16 consecutive, 16-byte aligned mask bytes -> one 16-byte load
+    // per row (byte ni * 4 + g is this lane's), the same address across the row's lanes.
+    // (no __restrict__ on the BatchNorm input / mask: the order of loads and stores below is the source order, nothing else is assumed)
+    static_assert(!EXT && !WIN, "the K-extended reduce and the halo window keep the generic epilogue");
+    constexpr int EBM = ((EPS - 1) >> 1) ? 4 : 2;
+    constexpr bool EAC = ((EPS - 1) & 1) != 0;
+    const float* bx = (const float*)p.bn_x;
+    const unsigned char* bmk = (const unsigned char*)p.bn_mask;
+    const int nl0 = wn * 64 + g * 4;                       // this lane's first column in the tile; fragment ni adds 16 * ni
+    const bool cok = n0 + wn * 64 < p.N;
+    long long offs[MI];                                   // element offset of (row, first column), -1: nothing to do
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const long long o = row_off(m0 + wm * (MI * 16) + mi * 16 + fl);
+      offs[mi] = (o >= 0 && cok) ? o + n0 + nl0 : -1;
+    }
+    float4 pr[NI], xr[NI];
+    u32x4 mr;
+    auto load_row = [&](int mi) __attribute__((always_inline)) {
+      const bool ok = offs[mi] >= 0;
+      const long long a = ok ? offs[mi] : 0;              // masked lanes read (and ignore) the first elements of the tensor
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        if (EAC) pr[ni] = *(const float4*)(Y + a + ni * 16);
+        if (EBM == 2) xr[ni] = *(const float4*)(bx + a + ni * 16);
+      }
+      if (EBM == 4) mr = *(const u32x4*)(bmk + ((a - (ok ? g * 4 : 0)) >> 2));
+    };
+    load_row(0);
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        if (offs[mi] >= 0) {
+          const int nl = nl0 + ni * 16;
+          float v[4] = {acc[ni][mi][0], acc[ni][mi][1], acc[ni][mi][2], acc[ni][mi][3]};
+          if (EAC) { v[0] += pr[ni].x; v[1] += pr[ni].y; v[2] += pr[ni].z; v[3] += pr[ni].w; }
+          float xf[4] = {0.f, 0.f, 0.f, 0.f}, mk[4];
+          if (EBM == 4) {
+            const unsigned mbits = mr[ni] >> (8 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mk[r] = ((mbits >> r) & 1u) ? 1.f : 0.f;
+          } else {
+            xf[0] = xr[ni].x; xf[1] = xr[ni].y; xf[2] = xr[ni].z; xf[3] = xr[ni].w;
+            const float4 sc = *(const float4*)(bnp + nl), sh = *(const float4*)(bnp + BN + nl);
+            mk[0] = fmaf(xf[0], sc.x, sh.x); mk[1] = fmaf(xf[1], sc.y, sh.y);
+            mk[2] = fmaf(xf[2], sc.z, sh.z); mk[3] = fmaf(xf[3], sc.w, sh.w);
+          }
+          const float4 mu = *(const float4*)(bnp + 2 * BN + nl), rs = *(const float4*)(bnp + 3 * BN + nl);
+          const float mua[4] = {mu.x, mu.y, mu.z, mu.w}, rsa[4] = {rs.x, rs.y, rs.z, rs.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            // The moment as the generic loop's code object has it: (v * (x - mean)) * rstd, then the sum -- three roundings, no fma.
+            // Contraction is left to the compiler there; it is pinned here, and the bitwise tests compare the two.
+#pragma clang fp contract(off)
+            v[r] = mk[r] > 0.f ? v[r] : 0.f;
+            st_s[ni][r] += v[r];
+            st_q[ni][r] += v[r] * (xf[r] - mua[r]) * rsa[r];
+            acc[ni][mi][r] = v[r];
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);                // one fragment's LDS constants live at a time
+      }
+      if (mi + 1 < MI) load_row(mi + 1);                  // before this row's stores
+      __builtin_amdgcn_sched_barrier(0);
+      if (offs[mi] >= 0) {
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+          *(float4*)(Y + offs[mi] + ni * 16) = make_float4(acc[ni][mi][0], acc[ni][mi][1], acc[ni][mi][2], acc[ni][mi][3]);
+      }
+    }
     } else {
     // ---- fp32 parity mode: registers -> NHWC (4 consecutive channels per lane), no LDS, no barrier
     float4 pvt[NI];                                   // pivoted statistics: this lane's 4 x NI pivots, once per tile
@@ -3452,6 +3532,20 @@ static bool igemm_use_256(const ConvP& p, bool fwd) {
   return !p.fapply;
 }
 
+// SIMCLR_F32_EPI_BATCH (default 1, read per launch): 0 keeps the per-fragment fp32 reduce epilogue everywhere -- the other side of the A/B
+// and of the bit-identity tests of the batched epilogue (tests/test_gpu_conv_f32_epilogue.py).
+static bool f32_epi_batch() {
+  const char* e = getenv("SIMCLR_F32_EPI_BATCH");
+  return !e || atoi(e) != 0;
+}
+
+// The batched fp32 reduce epilogues that exist (EPS - 1 = 2 * (mode == 4) + accumulate), all on a pre-split dy and the gathered / flat
+// operand path -- the classes whose launches measured faster than the per-fragment loop (profiles/f32_epilogue_step_time.json): mask
+// bits + accumulate (conv1 of a block) and mask mode 2 store, on the tiles of either width.  Not instantiated: the halo window (3x3:
+// within the noise of the measurement at either width), the K-extended reduce, mode 2 + accumulate and the mask-bit store (no launch of
+// a training step, not measured).
+static constexpr bool f32_eps_exists(bool win, int eps) { return !win && (eps == 1 || eps == 4); }
+
 // Eight-phase 256 x 256 tile (csrc/igemm_wide.h).  SIMCLR_IGEMM_WIDE: 0 = off, 2 = on wherever the kernel is applicable (tests),
 // anything else = on for the layers the rule below picks.  Applicable: bf16, Cout a multiple of 256, whole 64-channel k-tiles, no
 // K-extension / fused BatchNorm-apply epilogue (those stay on conv_igemm_persistent).
@@ -3805,14 +3899,21 @@ static IgemmPlan plan_igemm(const ConvP& p0, bool can_split, bool can_presplit) 
     else if (p.bn_mode == 4) eps = p.accumulate ? 4 : 3;
   }
   k.win = bf16 ? win3 : win3 && k.psb && (fwd ? !p.bn_mode : p.x_ps && (p.bn_mode != 0) == st);
+  // fp32 storage: the same constants for the register-direct epilogue of the three-term data gradients on a pre-split dy -- its batched
+  // form, a fragment row's operands requested before the previous row is stored -- where f32_eps_exists has an instantiation.  Mask modes
+  // 1 and 3, the sparse accumulate (2), the K-extended launches and Cout not a multiple of 64 keep the generic per-fragment loop;
+  // SIMCLR_F32_EPI_BATCH=0 (read per launch) keeps it everywhere.
+  if (!bf16 && !fwd && k.psb && k.spl == 3 && k.psx && !k.ext && (p.bn_mode == 2 || p.bn_mode == 4) && p.accumulate < 2 && (p.N & 63) == 0 &&
+      ((uintptr_t)p.bn_mask & 15) == 0 && f32_eps_exists(k.win, 1 + (p.bn_mode == 4 ? 2 : 0) + p.accumulate) && f32_epi_batch())
+    eps = 1 + (p.bn_mode == 4 ? 2 : 0) + p.accumulate;
   if (k.win) {
     const int rows = ((128 + 2 * (p.IW + 1)) + 31) / 32 * 32;
     p.win_j = rows / 32;
     p.win_bytes = (!bf16 || rows * 128 > 128 * BN * 2) ? rows * 128 : 128 * BN * 2;     // (bf16: doubles as the C staging tile)
     k.lds = (size_t)p.win_bytes + 2 * BN * 128 + 5 * BN * sizeof(float) + 128 * sizeof(long long) + 128;
-    k.eps = eps == 1 ? 1 : 0;
+    k.eps = (!bf16 || eps == 1) ? eps : 0;
   } else {
-    k.eps = eps == 1 || (!k.ext && eps >= 3) ? eps : 0;
+    k.eps = !bf16 || eps == 1 || (!k.ext && eps >= 3) ? eps : 0;
     if (k.psx && k.ext) k.family = IgemmPlan::UNSUPPORTED;       // no K-extended kernel reads a pre-split dy
   }
   return k;
@@ -3841,7 +3942,9 @@ static constexpr bool tile128_exists(bool bf16, bool fwd, int bn, bool st, bool 
   if (fas || !epilogue_exists(st, be, ex) || (win && ex)) return false;
   if (bf16)      // split tail on the 128 x 128 tile; mask mode / accumulate of the reduce compiled in (EPS)
     return spl == 0 && !psb && !psx && (eps ? st && be && !tail && (eps == 1 || (!ex && !win && (eps == 3 || eps == 4))) : !tail || bn == 128);
-  if (tail || eps) return false;
+  if (tail) return false;
+  // fp32 reduce epilogue with its options compiled in: three-term data gradient on a pre-split dy
+  if (eps) return !fwd && st && be && psb && spl == 3 && !ex && psx && f32_eps_exists(win, eps);
   // fp32: the halo window = three-term launches with pre-split weights (and a pre-split dy in the data gradient)
   if (win) return psb && (fwd ? spl == 13 && !be && !psx : spl == 3 && psx);
   if (psx) return !fwd && !ex && psb && spl == 3;
@@ -3873,12 +3976,23 @@ static bool launch_plan(const IgemmPlan& k, hipStream_t s) {
         }, Bools{}, k.stats, Bools{}, k.bnepi, Bools{}, k.ext, Bools{}, k.fapply, Bools{}, k.tail);
       return false;
     case IgemmPlan::TILE128: {
-      // per storage only the arguments that vary: bf16 TAIL / FAS / EPS, fp32 SPL / PSB / PSX
+      // per storage only the arguments that vary: bf16 TAIL / FAS / EPS, fp32 SPL / PSB / PSX / EPS
       using Spl = std::conditional_t<bf16, among<int, 0>, among<int, 0, 3, 6, 13>>;
       using FpBools = std::conditional_t<bf16, among<bool, false>, Bools>;
       using HBools = std::conditional_t<bf16, Bools, among<bool, false>>;
       using Fas = std::conditional_t<bf16, among<int, 0, 1, 2>, among<int, 0>>;
       using Eps = std::conditional_t<bf16, among<int, 0, 1, 3, 4>, among<int, 0>>;
+      // fp32 epilogues with their options compiled in: few instantiations, dispatched on the arguments that vary among them only (every
+      // list multiplies the combinations the general dispatch below has to be compiled for)
+      if constexpr (!bf16 && !fwd) {
+        if (k.eps)
+          return k.stats && k.bnepi && !k.ext && !k.win && !k.fapply && k.spl == 3 && !k.tail && k.psb && !k.fas && k.psx &&
+                 with_consts([&](auto BN, auto EPS) {
+                   static_assert(f32_eps_exists(false, EPS), "the list below = the epilogues f32_eps_exists names");
+                   run_persistent<T, MODE, 128, BN, 4, 2, true, true, false, false, false, 3, false, true, 0, EPS, true>(g, b, k.lds, s, k.p);
+                   return true;
+                 }, among<int, 64, 128>{}, k.bn, among<int, 1, 4>{}, k.eps);
+      }
       return with_consts([&](auto BN, auto ST, auto BE, auto EX, auto WIN, auto FA, auto SPL, auto TAIL, auto PSB, auto FAS, auto EPS, auto PSX) {
         if constexpr (!tile128_exists(bf16, fwd, BN, ST, BE, EX, WIN, FA, SPL, TAIL, PSB, FAS, EPS, PSX)) return false;
         else { run_persistent<T, MODE, 128, BN, 4, 2, ST, BE, EX, WIN, FA, SPL, TAIL, PSB, FAS, EPS, PSX>(g, b, k.lds, s, k.p); return true; }

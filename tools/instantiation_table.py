@@ -93,6 +93,15 @@ def rows(views):
                         L.conv2d_dgrad_bn(FAKE, FAKE, FAKE, 1, None, FAKE, None, None, None, None, 4, FAKE, nsl_in, V, H, H, Cin, OH, OH,
                                           Cout, k, k, 1, pad, dtype, None)
                         kinds.append(('dgrad + accumulate + BN-backward sums (mode 4)', last()))
+                    if dtype == 0 and terms == (13, 3) and Cout % 32 == 0:
+                        # the parity mode's step: dy arrives pre-split from the BatchNorm backward (fp32 epilogue constants, halo window)
+                        L.conv2d_dgrad_bn(FAKE, FAKE, FAKE, 0, FAKE, None, FAKE, FAKE, FAKE, FAKE, 2, FAKE, nsl_in, V, H, H, Cin, OH, OH, Cout,
+                                          k, k, 1, pad, dtype | PS_IN, None)
+                        kinds.append(('dgrad + BN-backward reduce (mode 2), pre-split dy', last()))
+                        if 'reduce' in name:
+                            L.conv2d_dgrad_bn(FAKE, FAKE, FAKE, 1, None, FAKE, None, None, None, None, 4, FAKE, nsl_in, V, H, H, Cin, OH, OH,
+                                              Cout, k, k, 1, pad, dtype | PS_IN, None)
+                            kinds.append(('dgrad + accumulate + BN-backward sums (mode 4), pre-split dy', last()))
                 for kind, inst in kinds:
                     out.append((mode, name, cnt, kind, inst))
     finally:

@@ -100,6 +100,52 @@ def main():
             del x, dy, y, dx
         print('per-step totals (ms): fwd %.2f (no stats %.2f)  dgrad %.2f  wgrad %.2f' % (
             tot['fwd'] / 1e3, tot['fwd_nostats'] / 1e3, tot['dgrad'] / 1e3, tot['wgrad'] / 1e3), flush=True)
+    if 'epi' in what:
+        # A/B of the fp32 reduce epilogue (--dtype f32 --f32_matmul f16x3_3): SIMCLR_F32_EPI_BATCH = 0 (per-fragment loop) / 1 (operands of
+        # a fragment row requested before the previous row is stored), read per launch, so both sides run in this process on the
+        # same buffers.  Rows: dgrad + BatchNorm-backward reduce with mask mode 2 (store) and mode 4 + accumulate (conv1 of a block adds
+        # to the shortcut gradient); bytes = every tensor pass of the launch once.
+        assert dt == torch.float32, '--what epi times the fp32 epilogues'
+        print('%-22s %-14s | us 0 / 1 | TB/s 0 / 1' % ('layer', 'launch'))
+
+        def ab(fn):
+            ts = []
+            for sw in ('0', '1'):
+                os.environ['SIMCLR_F32_EPI_BATCH'] = sw
+                ts.append(timeit(fn, args.iters))
+            os.environ.pop('SIMCLR_F32_EPI_BATCH')
+            return ts
+        tot_e = {}
+        for (H, Cin, Cout, k, s, cnt) in R50:
+            if s != 1 or Cout % 32 or Cin % 64:
+                continue
+            pad = (k - 1) // 2
+            M = V * H * H
+            w = torch.randn(k, k, Cin, Cout, device=dev) * (k * k * Cin) ** -0.5
+            w_d = ops.prep_weights(w, 1, dt)
+            dy = torch.randn(V, H, H, Cout, device=dev)
+            one, zero = torch.ones(Cout, device=dev), torch.zeros(Cout, device=dev)
+            dy, _ = ops.bn_bwd_apply(dy, dy, None, one, zero, zero, one, zero, zero, 0, ps_out=True)
+            x = torch.randn(V, H, H, Cin, device=dev)
+            dx = torch.randn(V, H, H, Cin, device=dev)
+            rows = []
+            bn2 = dict(x=x, mask=None, scale=torch.rand(Cin, device=dev) - 0.4, shift=torch.randn(Cin, device=dev) * 0.3,
+                       mean=torch.randn(Cin, device=dev) * 0.2, rstd=torch.rand(Cin, device=dev) + 0.5, mode=2)
+            rows.append(('dgrad_bn m2', 4.0 * M * (Cout + 2 * Cin), lambda: ops.conv2d_dgrad_bn(dy, w_d, k, k, pad, H, H, bn2, out=dx)))
+            if k == 1 and Cin > Cout:
+                bn4 = dict(mask=(torch.rand(M, Cin // 4, device=dev) * 16).to(torch.uint8), mode=4)
+                rows.append(('dgrad_bn m4+acc', 4.0 * M * (Cout + 2 * Cin) + M * Cin / 4,
+                             lambda: ops.conv2d_dgrad_bn(dy, w_d, k, k, pad, H, H, bn4, out=dx, accumulate=True)))
+            name = '%dx%d %d->%d k%d x%d' % (H, H, Cin, Cout, k, cnt)
+            for kind, nbytes, fn in rows:
+                t0, t1 = ab(fn)
+                print('%-22s %-14s | %6.0f %6.0f | %5.2f %5.2f' % (name, kind, t0, t1, nbytes / t0 / 1e6, nbytes / t1 / 1e6), flush=True)
+                res.append(dict(layer=name, launch=kind, count=cnt, bytes=nbytes, us_switch0=t0, us_switch1=t1))
+                e = tot_e.setdefault(kind, [0.0, 0.0])
+                e[0] += cnt * t0; e[1] += cnt * t1
+            del x, dx, dy, rows
+        for kind, (t0, t1) in tot_e.items():
+            print('weighted total %-14s: %.2f -> %.2f ms (every layer class x its count; a step launches each kind on a subset)' % (kind, t0 / 1e3, t1 / 1e3))
     if 'tile' in what:
         # A/B of the forward / dgrad tile: default (128-wide) vs SIMCLR_IGEMM_TILE=256 on every layer whose width allows it
         print('%-26s | fwd+stats 128 / 256 | fwd 128 / 256 | dgrad 128 / 256 | dgrad_bn 128 / 256  (us)' % 'layer')
