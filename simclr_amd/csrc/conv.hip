@@ -97,6 +97,9 @@ struct ConvP {
   unsigned x_bytes;  // conv_igemm_wide: size of the gathered tensor in bytes (range check of its buffer descriptor)
   // conv_igemm_wide: (images, class rows, class columns) that 8, 128 and 136 consecutive GEMM rows advance an output pixel
   int rs_dq[3], rs_drow[3], rs_dcol[3];
+  // conv_igemm_nwalk (csrc/igemm_nwalk.h): a workgroup owns an M-tile and nw_gw consecutive output columns (a group of N-tiles);
+  // N = nw_groups * nw_gw
+  int nw_groups, nw_gw;
 };
 
 // Diagnostic build (build.sh diag -> libsimclr_hip_diag.so): parts of a kernel can be switched off at run time
@@ -1583,6 +1586,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || STAGES == 3) ? 1 : (BN == 64 &
 }
 
 #include "igemm_wide.h"
+#include "igemm_nwalk.h"
 
 // ------------------------------------------------------------------------------------
 // wgrad: dW[K, N] (fp32 split-slabs) = sum over pixels A(m, k) * dY(m, n).
@@ -3426,6 +3430,17 @@ static void run_persistent(dim3 grid, dim3 block, size_t lds, hipStream_t stream
                        grid, block, lds, stream, p);
 }
 
+// N-inner walk: the record names the walk and the N-group (columns per workgroup, groups) after the usual fields
+template <int KPT, int FAS>
+static void run_nwalk(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const ConvP& p) {
+  char name[64];
+  snprintf(name, sizeof(name), "conv_igemm_nwalk<%d, %d>", KPT, FAS);
+  record_inst<float, MODE_FWD>(name, grid.x, block.x, lds, p);
+  const size_t len = strlen(g_last_inst);
+  snprintf(g_last_inst + len, sizeof(g_last_inst) - len, " walk=n_inner n_group=%d n_groups=%d", p.nw_gw, p.nw_groups);
+  if (!dry_run()) hipLaunchKernelGGL((conv_igemm_nwalk<KPT, FAS>), grid, block, lds, stream, p);
+}
+
 // The weight-gradient, Gram and pre-split stem launches write the same kind of record (role = wgrad | gram | stem_wgrad_ps): the
 // kernel with its template arguments (trailing arguments that equal their defaults left out), the split-K geometry of its
 // parameter struct, and -- appended by run_slab_reduce -- the grid of the slab reduction that follows it.
@@ -3764,7 +3779,8 @@ struct IgemmPlan {
     WIDE,           // eight-phase 256 x 256 tile (conv_igemm_wide)
     TILE256,        // 256 x 256 persistent tile, 8 waves
     TILE128,        // 128 x BN persistent tile, 4 waves: gather, halo window (win) or fused BatchNorm apply (fapply)
-    FALLBACK,       // non-persistent conv_igemm (no taps, or more than 64 N-tiles)
+    NWALK,          // N-inner walk (conv_igemm_nwalk): activation panel resident across the N-tiles of a group, see plan_nwalk
+    FALLBACK,     // non-persistent conv_igemm (no taps, or more than 64 N-tiles)
   } family = EMPTY;
   ConvP p;
   int bn = 0, spl = 0, fas = 0, eps = 0;                           // conv_igemm(_persistent) template arguments
@@ -3775,6 +3791,44 @@ struct IgemmPlan {
   size_t tile_floats = 0;          // split tail (p.rem_parts >= 2): fp32 partial-tile size of the scratch
   bool presplit = false;           // psb with weights the launch pre-splits itself (fp16 pieces when spl == 13)
 };
+
+// SIMCLR_IGEMM_NWALK (default 1, read per launch like SIMCLR_F32_EPI_BATCH): 0 keeps conv_igemm_persistent's M-inner walk everywhere --
+// the other side of the A/B (tools/microbench.py --what nwalk) and of the bit-identity tests (tests/test_gpu_conv_nwalk.py).
+static bool igemm_nwalk_on() {
+  const char* e = getenv("SIMCLR_IGEMM_NWALK");
+  return !e || atoi(e) != 0;
+}
+
+// N-inner walk (csrc/igemm_nwalk.h) for a planned TILE128 launch, where its one instantiation class applies: fp32 storage, forward with
+// three fp16-piece terms on pre-split weights and the fused bottleneck-tail epilogue (residual + ReLU + ReLU bit mask: FAS 1, with the
+// residual's own BatchNorm: FAS 2), flat 1x1 stride 1, IC = 64 | 128, 128 < Cout <= 512 a multiple of 64 (two or more N-tiles of the
+// M-inner walk).  Everything else -- statistics forward, K-extension, halo window, split tail, bf16, IC >= 256 -- keeps the M-inner walk.
+// Work split: 64-row M-tiles; a workgroup's N-group is ALL of Cout when that leaves about two rounds of workgroups busy, otherwise N is
+// halved (whole 64-column N-tiles) until it does.  Grid as igemm_persistent_grid: a multiple of 8 * groups, at most one workgroup per
+// M-tile and group, as many as stay resident (three per CU while the group's LDS allows: 16 | 32 KB panel + 16 KB ring + constants).
+static void plan_nwalk(IgemmPlan& k) {
+  ConvP& p = k.p;
+  const bool flat = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.cs == 1 && p.IH == p.OH && p.IW == p.OW;
+  if (!igemm_nwalk_on() || !flat || !k.fapply || !k.psb || k.spl != 13 || k.psx || p.x2 || (p.IC != 64 && p.IC != 128) || p.K != p.IC ||
+      p.pixpitch < p.IC || (p.pixpitch & 3) || (p.N & 63) || p.N <= 128 || p.N > 512 || !p.bn_x || !p.bn_mode || !p.bn_mask ||
+      ((uintptr_t)p.bn_mask & 15) || p.rem_parts >= 2)
+    return;
+  const int m_tiles = ceil_div(p.M, 64);
+  int groups = 1;
+  while (m_tiles * groups < 2 * 3 * 256 && (p.N / groups) % 128 == 0) groups *= 2;
+  const int gw = p.N / groups;
+  const size_t lds = (size_t)(p.IC / 32) * 64 * 128 + 2 * 64 * 128 + (p.bn_mean ? 4 : 2) * gw * sizeof(float);
+  const int per_cu = 3 * lds <= 160 * 1024 ? 3 : 2;
+  const int unit = 8 * groups;
+  int pg = max(unit, (per_cu * 256 / unit) * unit);
+  const int need = ceil_div(m_tiles, 8) * unit;
+  if (pg > need) pg = need;
+  k.family = IgemmPlan::NWALK;
+  k.bn = 64; k.fas = p.bn_mean ? 2 : 1;
+  k.grid = pg; k.block = 256; k.lds = lds;
+  p.m_tiles = m_tiles; p.n_tiles = p.N / 64;
+  p.nw_groups = groups; p.nw_gw = gw;
+}
 
 template <typename T, int MODE>
 static IgemmPlan plan_igemm(const ConvP& p0, bool can_split, bool can_presplit) {
@@ -3889,6 +3943,7 @@ static IgemmPlan plan_igemm(const ConvP& p0, bool can_split, bool can_presplit) 
     k.stats = k.bnepi = k.ext = false;
     // the two option sets every fused bottleneck tail uses get instantiations with the options compiled in (FAS, bf16)
     if (bf16 && p.bn_x && p.bn_mode && p.bn_mask && (p.N & 31) == 0) k.fas = p.bn_mean ? 2 : 1;
+    if (!bf16 && fwd) plan_nwalk(k);     // short-K bottleneck tails in fp32 storage: the N-inner walk where it applies
     return k;
   }
   // fused BatchNorm-backward-reduce epilogue with its mask mode / accumulate flag compiled in (EPS instantiations, bf16, no split tail):
@@ -3999,6 +4054,11 @@ static bool launch_plan(const IgemmPlan& k, hipStream_t s) {
       }, among<int, 64, 128>{}, k.bn, Bools{}, k.stats, Bools{}, k.bnepi, Bools{}, k.ext, Bools{}, k.win, Bools{}, k.fapply, Spl{}, k.spl,
          HBools{}, k.tail, FpBools{}, k.psb, Fas{}, k.fas, Eps{}, k.eps, FpBools{}, k.psx);
     }
+    case IgemmPlan::NWALK:
+      if constexpr (!bf16 && fwd)
+        return with_consts([&](auto KPT, auto FAS) { run_nwalk<KPT, FAS>(g, b, k.lds, s, k.p); return true; },
+                           among<int, 2, 4>{}, k.p.IC / 32, among<int, 1, 2>{}, k.fas);
+      return false;
     default:
       return false;
   }

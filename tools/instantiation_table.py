@@ -80,6 +80,12 @@ def rows(views):
                 if dtype == 1 and 'expand' in name:      # fused bottleneck tail: conv3 + bn3 + shortcut + ReLU + mask bits (bf16)
                     L.conv2d_fwd_bn_apply(FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, None, None, 1, FAKE, V, H, H, Cin, OH, OH, Cout, k, k, s, pad, dtype, None)
                     kinds.append(('fwd + fused BatchNorm apply / residual / ReLU', last()))
+                if dtype == 0 and terms == (13, 3) and 'expand' in name:
+                    # the parity mode's fused bottleneck tail: the short-K layers take the N-inner walk (conv_igemm_nwalk, SIMCLR_IGEMM_NWALK);
+                    # the first block of a stage applies the projection shortcut's own BatchNorm to the residual
+                    for rbn, what in ((None, ''), (FAKE, ', BatchNorm shortcut')):
+                        L.conv2d_fwd_bn_apply(FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, rbn, rbn, 1, FAKE, V, H, H, Cin, OH, OH, Cout, k, k, s, pad, dtype, None)
+                        kinds.append(('fwd + fused BatchNorm apply / residual / ReLU' + what, last()))
                 if H > 1 or True:
                     L.conv2d_dgrad(FAKE, FAKE, FAKE, 0, V, H, H, Cin, OH, OH, Cout, k, k, s, pad, dtype, None)
                     kinds.append(('dgrad', last()))

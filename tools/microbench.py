@@ -146,6 +146,70 @@ def main():
             del x, dx, dy, rows
         for kind, (t0, t1) in tot_e.items():
             print('weighted total %-14s: %.2f -> %.2f ms (every layer class x its count; a step launches each kind on a subset)' % (kind, t0 / 1e3, t1 / 1e3))
+    if 'nwalk' in what:
+        # A/B of the walk of the persistent implicit GEMM on the short-K 1x1 layers with a wide output (--dtype f32 --f32_matmul f16x3_3):
+        # SIMCLR_IGEMM_NWALK = 0 (a workgroup owns an N-tile and walks M-tiles) / 1 (a workgroup owns an M-tile and walks its N-tiles,
+        # csrc/igemm_nwalk.h), read per launch, so both sides run in this process on the same buffers.  Rows: the 13 launches of a step
+        # in the forms the step uses -- the fused bottleneck tail (conv3 + bn3 + shortcut + ReLU + mask bits; FAS 2 = the shortcut has
+        # its own BatchNorm: first block of a stage) and conv1's data gradient with the fused BatchNorm-backward reduce on a pre-split dy
+        # (mask mode 2 store, mask bits + accumulate) -- each with its narrow-output twin (same M, K and N swapped: same algorithmic
+        # bytes and FLOPs).  bytes = every tensor pass of the launch once.  A class without an N-inner instantiation runs the same
+        # kernel in both columns: their difference is the noise of the row.
+        assert dt == torch.float32, '--what nwalk times the fp32 launches'
+        print('%-34s %-16s | us 0 / 1 | TB/s 0 / 1 | kernel with the switch on' % ('layer', 'launch'))
+        from simclr_amd._lib import lib as _lib
+
+        def ab_nw(fn):
+            ts, rec = [], ''
+            for sw in ('0', '1'):
+                os.environ['SIMCLR_IGEMM_NWALK'] = sw
+                ts.append(timeit(fn, args.iters))
+                rec = _lib().conv2d_last_instantiation().decode()
+            os.environ.pop('SIMCLR_IGEMM_NWALK')
+            return ts[0], ts[1], rec.split(')')[0].lstrip('(')
+        tot_n = {}
+        # (H, channels of the narrow side, of the wide side, fused tails with a plain / BatchNorm shortcut, conv1 data gradients per step)
+        for (H, Cn, Cw, n_fas1, n_fas2, n_dg) in [(56, 64, 256, 2, 1, 2), (56, 128, 256, 0, 0, 1), (28, 128, 512, 3, 1, 3)]:
+            M = V * H * H
+            for twin in (False, True):
+                K, N = (Cw, Cn) if twin else (Cn, Cw)
+                x = torch.randn(V, H, H, K, device=dev)
+                w = torch.randn(1, 1, K, N, device=dev) * K ** -0.5
+                w_t = ops.prep_weights(w, 0, dt)
+                resid = torch.randn(V, H, H, N, device=dev)
+                scale, shift = torch.rand(N, device=dev) + 0.5, torch.randn(N, device=dev) * 0.2
+                rs, rb = torch.rand(N, device=dev) + 0.5, torch.randn(N, device=dev) * 0.3
+                rows = []
+                nb_tail = 4.0 * M * (K + 2 * N) + M * N / 4
+                if n_fas1 or n_fas2:
+                    rows.append(('tail FAS1', n_fas1, nb_tail,
+                                 lambda: ops.conv2d_fwd_bn_apply(x, w_t, 1, 1, 1, 0, H, H, scale, shift, res=resid, relu=True, want_bits=True)))
+                    rows.append(('tail FAS2', n_fas2, nb_tail,
+                                 lambda: ops.conv2d_fwd_bn_apply(x, w_t, 1, 1, 1, 0, H, H, scale, shift, res=resid, relu=True, want_bits=True,
+                                                                 rscale=rs, rshift=rb)))
+                # data gradient of a K <- N convolution's twin: dy has K channels, dx (and the producer BatchNorm's input) N
+                w_d = ops.prep_weights(torch.randn(1, 1, N, K, device=dev) * N ** -0.5, 1, dt)
+                one, zero = torch.ones(K, device=dev), torch.zeros(K, device=dev)
+                dy, _ = ops.bn_bwd_apply(x, x, None, one, zero, zero, one, zero, zero, 0, ps_out=True)
+                bn2 = dict(x=resid, mask=None, scale=torch.rand(N, device=dev) - 0.4, shift=torch.randn(N, device=dev) * 0.3,
+                           mean=torch.randn(N, device=dev) * 0.2, rstd=torch.rand(N, device=dev) + 0.5, mode=2)
+                bn4 = dict(mask=(torch.rand(M, N // 4, device=dev) * 16).to(torch.uint8), mode=4)
+                dx = torch.randn(V, H, H, N, device=dev)
+                rows.append(('dgrad_bn m2', 0, 4.0 * M * (K + 2 * N), lambda: ops.conv2d_dgrad_bn(dy, w_d, 1, 1, 0, H, H, bn2, out=dx)))
+                rows.append(('dgrad_bn m4+acc', n_dg, 4.0 * M * (K + 2 * N) + M * N / 4,
+                             lambda: ops.conv2d_dgrad_bn(dy, w_d, 1, 1, 0, H, H, bn4, out=dx, accumulate=True)))
+                name = '%dx%d %d->%d%s' % (H, H, K, N, ' (narrow twin)' if twin else '')
+                for kind, cnt, nbytes, fn in rows:
+                    t0, t1, kern = ab_nw(fn)
+                    print('%-34s %-16s | %6.0f %6.0f | %5.2f %5.2f | %s' % (name, kind, t0, t1, nbytes / t0 / 1e6, nbytes / t1 / 1e6, kern), flush=True)
+                    res.append(dict(layer=name, launch=kind, twin=twin, count=0 if twin else cnt, bytes=nbytes, us_switch0=t0, us_switch1=t1,
+                                    kernel_switch1=kern))
+                    if not twin:
+                        e = tot_n.setdefault(kind, [0.0, 0.0])
+                        e[0] += cnt * t0; e[1] += cnt * t1
+                del x, resid, dy, dx, rows, bn2, bn4
+        for kind, (t0, t1) in tot_n.items():
+            print('per step %-16s: %.2f -> %.2f ms (each target launch x its count in a ResNet-50 step)' % (kind, t0 / 1e3, t1 / 1e3))
     if 'tile' in what:
         # A/B of the forward / dgrad tile: default (128-wide) vs SIMCLR_IGEMM_TILE=256 on every layer whose width allows it
         print('%-26s | fwd+stats 128 / 256 | fwd 128 / 256 | dgrad 128 / 256 | dgrad_bn 128 / 256  (us)' % 'layer')

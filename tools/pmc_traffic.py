@@ -10,6 +10,10 @@ then
 Counters are in KB.  FETCH_SIZE under-reports wide (16 B/lane) coalesced reads by exactly 2x on gfx950 (guide, HBM
 section); every streaming load in this library is 16 B/lane, so fetch_corrected = 2 x raw.  WRITE_SIZE is taken as is.
 The run has 2 steps (1 warm-up + 1 timed): per-step values are the totals halved.
+
+Per launch class of `tools/microbench.py --what nwalk` (the same two passes over `python tools/microbench.py --dtype f32 --f32_matmul f16x3_3
+--what nwalk --iters N --out MB.json` instead of bench.py):
+  python tools/pmc_traffic.py --nwalk FETCH.csv WRITE.csv MB.json N OUT.json
 """
 import csv
 import gzip
@@ -54,7 +58,46 @@ def ntxent_rows(fpath, wpath, tpath):
     return rows
 
 
+def nwalk_rows(fpath, wpath, mbpath, iters, warm=2):
+    """HBM traffic per row of `tools/microbench.py --what nwalk --iters N` from two PMC passes of it (counters in runs of their own).
+    The conv_igemm* dispatches of that run come in the order of its rows: (warm + iters) launches with SIMCLR_IGEMM_NWALK=0, then as
+    many with 1.  Per row and switch: mean FETCH_SIZE x 2 / WRITE_SIZE per launch beside the operand bytes microbench.py counted."""
+    def seq(path, counter):
+        op = gzip.open if path.endswith('.gz') else open
+        out = []
+        with op(path, 'rt') as f:
+            for r in csv.DictReader(f):
+                if r['Counter_Name'] == counter and 'conv_igemm' in r['Kernel_Name']:
+                    out.append((int(r['Dispatch_Id']), r['Kernel_Name'], float(r['Counter_Value']) * 1024.0))
+        return sorted(out)
+    fetch, write = seq(fpath, 'FETCH_SIZE'), seq(wpath, 'WRITE_SIZE')
+    rows = [r for r in json.load(open(mbpath)) if 'us_switch0' in r]
+    n = warm + iters
+    assert len(fetch) == len(write) == 2 * n * len(rows), (len(fetch), len(write), len(rows), n)
+    out = []
+    for i, r in enumerate(rows):
+        d = dict(layer=r['layer'], launch=r['launch'], operand_bytes=r['bytes'])
+        for sw in (0, 1):
+            fs, ws = fetch[(2 * i + sw) * n:(2 * i + sw + 1) * n], write[(2 * i + sw) * n:(2 * i + sw + 1) * n]
+            assert len({k for _, k, _ in fs}) == 1, fs
+            d['switch%d' % sw] = dict(kernel=fs[0][1].replace('void (anonymous namespace)::', '')[:110],
+                                      fetch_corrected_bytes=2 * sum(v for _, _, v in fs) / n, write_bytes=sum(v for _, _, v in ws) / n)
+        out.append(d)
+    return out
+
+
 def main():
+    if sys.argv[1] == '--nwalk':
+        fpath, wpath, mbpath, iters, out = sys.argv[2:7]
+        rows = nwalk_rows(fpath, wpath, mbpath, int(iters))
+        json.dump(dict(note='rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of tools/microbench.py --what nwalk at 1024 views; '
+                            'FETCH x2 for 16 B/lane loads, WRITE as is; mean per launch; operand_bytes = every tensor pass once', rows=rows),
+                  open(out, 'w'), indent=1)
+        for r in rows:
+            print('%-34s %-16s operands %6.2f GB | switch 0 fetch %6.2f write %6.2f | switch 1 fetch %6.2f write %6.2f GB' % (
+                r['layer'], r['launch'], r['operand_bytes'] / 1e9, r['switch0']['fetch_corrected_bytes'] / 1e9, r['switch0']['write_bytes'] / 1e9,
+                r['switch1']['fetch_corrected_bytes'] / 1e9, r['switch1']['write_bytes'] / 1e9))
+        return
     if sys.argv[1] == '--ntxent':
         fpath, wpath, tpath, out = sys.argv[2:6]
         res = json.load(open(out))
