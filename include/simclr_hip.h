@@ -388,8 +388,9 @@ int simclr_bn_bwd_reduce_slots(long long rows, int C, int dtype);
  * for BatchNorm (resnet.py:50-78) -- of the fp32 accumulators (128-wide tiles, eight-phase 256-wide tile); the 256 x 256
  * instantiation of the persistent kernel (SIMCLR_IGEMM_TILE=256 / K-extended dgrad classes) takes them over the bf16-ROUNDED
  * outputs, the tensor the reference's moments see: the two differ by the output rounding (<= 2^-9 relative per element,
- * ~1e-5 sigma on the mean at 10^5 rows).  Cin % 64 == 0 (bf16) / 32 (f32); Cout % 4 == 0.
- * y == NULL (bf16, stats required): statistics-only pass -- the convolution is computed, nothing is stored. */
+ * ~1e-5 sigma on the mean at 10^5 rows).  Cin % 64 == 0 (bf16) / 32 (f32); Cout % 4 == 0 (bf16 with Cout % 8 != 0 runs the
+ * non-persistent kernel, like Cout > 8192: the persistent kernels store bf16 rows in 16-byte chunks of 8 channels).
+ * y == NULL (bf16, stats required, Cout % 8 == 0, Cout <= 8192): statistics-only pass -- the convolution is computed, nothing is stored. */
 int simclr_conv2d_fwd(const void* x, const void* w_t, void* y, float* stats, int nslot, int V, int IH,
                       int IW, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int pad,
                       int dtype, simclr_stream_t stream);
@@ -422,7 +423,7 @@ int simclr_conv2d_dgrad(const void* dy, const void* w_d, void* dx, int accumulat
  * dm = dx*mask.  stats float[nslot][2][Cin] zeroed by the caller.  mask_mode 1: bn_mask>0 (tensor after the
  * ReLU, e.g. the block output of resnet.py:487); 2: bn_x*scale+shift>0; 3: bn_mask = the bit tensor written by
  * simclr_bn_apply(relu_bits) (16x less traffic than mode 1); 4: as 3 but ONLY sum(dm) is produced and bn_x / bn_mean /
- * bn_rstd are not read (may be NULL) -- sum(dm*x^) then comes from simclr_bn_fold_s2.  stride 1 only. */
+ * bn_rstd are not read (may be NULL) -- sum(dm*x^) then comes from simclr_bn_fold_s2.  stride 1 only; Cin % 8 == 0 (bf16) / 4 (f32). */
 int simclr_conv2d_dgrad_bn(const void* dy, const void* w_d, void* dx, int accumulate, const void* bn_x,
                            const void* bn_mask, const float* bn_scale, const float* bn_shift,
                            const float* bn_mean, const float* bn_rstd, int mask_mode, float* stats, int nslot,

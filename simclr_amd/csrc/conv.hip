@@ -3849,8 +3849,13 @@ static IgemmPlan plan_igemm(const ConvP& p0, bool can_split, bool can_presplit) 
   k.bnepi = p.bn_mode != 0;
   k.ext = p.x2 != nullptr;
   k.stats = k.bnepi || (st && !k.ext);
-  if (p.ntaps <= 0 || p.n_tiles > 64) {
+  // bf16 storage, N not a multiple of 8: the row pass of the persistent kernels moves 16-byte chunks of 8 channels, so the last chunk of
+  // a row would spill 4 elements into the next row (and past the end of the tensor); conv_igemm stores 8-byte granules of 4 channels
+  const bool odd_n = bf16 && (p.N & 7) != 0;
+  if (p.ntaps <= 0 || p.n_tiles > 64 || odd_n) {
     if (p.x_ps || (p.w_ps && p.ntaps > 0) || p.accumulate == 2) { k.family = IgemmPlan::UNSUPPORTED; return k; }
+    // (the fused epilogues live in the persistent kernels only; their entry points ask for N % 8 == 0 in bf16)
+    if ((odd_n && (p.bn_mode || p.fapply || p.x2)) || !p.y) { k.family = IgemmPlan::UNSUPPORTED; return k; }
     k.family = IgemmPlan::FALLBACK;
     k.bn = BN; k.stats = st; k.bnepi = k.ext = false;
     k.grid = ceil_div(p.m_tiles, 8) * 8 * p.n_tiles; k.block = 256;
@@ -4474,6 +4479,7 @@ int simclr_conv2d_fwd(const void* x, const void* w_t, void* y, float* stats, int
   SIMCLR_CHECK_ARG(!stats || nslot > 0, "conv2d_fwd: nslot must be > 0 with stats");
   SIMCLR_CHECK_ARG(KH * KW <= 9, "conv2d_fwd: at most 9 taps (got %dx%d)", KH, KW);
   SIMCLR_CHECK_ARG(y || (stats && dtype == SIMCLR_DT_BF16), "conv2d_fwd: y == NULL (statistics-only pass) needs stats and bf16");
+  SIMCLR_CHECK_ARG(y || (Cout % 8 == 0 && Cout <= 64 * 128), "conv2d_fwd: the statistics-only pass lives in the persistent kernel: Cout=%d must be a multiple of 8, at most 8192", Cout);
   ConvP p;
   if (int rc = conv_params(c, x, w_t, y, V, IH, IW, Cin, OH, OW, Cout, KH, KW, stride, pad, &p)) return rc;
   p.stats = stats; p.nslot = nslot;
@@ -4596,7 +4602,7 @@ int simclr_conv2d_dgrad_bn(const void* dy, const void* w_d, void* dx, int accumu
   const int epc = dtype == SIMCLR_DT_BF16 ? 8 : 4;
   SIMCLR_CHECK_ARG(dtype == SIMCLR_DT_BF16 || dtype == SIMCLR_DT_F32, "conv2d_dgrad_bn: bad dtype %d", dtype);
   SIMCLR_CHECK_ARG(Cout % (8 * epc) == 0, "conv2d_dgrad_bn: Cout=%d must be a multiple of %d", Cout, 8 * epc);
-  SIMCLR_CHECK_ARG(Cin % 4 == 0, "conv2d_dgrad_bn: Cin=%d must be a multiple of 4", Cin);
+  SIMCLR_CHECK_ARG(Cin % epc == 0, "conv2d_dgrad_bn: Cin=%d must be a multiple of %d (one 16-byte chunk)", Cin, epc);
   SIMCLR_CHECK_ARG((long long)V * IH * IW < (1ll << 31), "conv2d_dgrad_bn: M overflows int32");
   SIMCLR_CHECK_ARG(KH * KW <= 9 && stride == 1, "conv2d_dgrad_bn: stride-1 convolutions with <= 9 taps only");
   SIMCLR_CHECK_ARG(accumulate >= 0 && accumulate <= 2 && (accumulate != 2 || dtype == SIMCLR_DT_F32),

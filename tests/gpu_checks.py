@@ -5,6 +5,7 @@ oracle (`oracle/`, float64) for the loss / LARS and plain torch-CPU float64 ops
 for conv / BN / pooling.  Used by tests/test_gpu_kernels.py (pytest -m gpu) and
 tools/run_gpu_checks.py (prints everything; first-contact diagnostics).
 """
+import contextlib
 import itertools
 import os
 
@@ -3257,4 +3258,152 @@ def check_blur_cases(H, W, height):
                                         selectors=torch.from_numpy(case['sel']))
         torch.cuda.synchronize()
         res += ar.blur_compare(y.cpu().numpy(), case, tol)
+    return res
+
+
+# ------------------------------------------------------------------ implicit-GEMM convolutions on exact integer lattices
+# (tests/test_gpu_conv_lattice.py).  Rows, operands and references come from tests/conv_reference.py: every product and partial sum of the
+# kernels is exactly representable in each matrix arithmetic, `reference` asserts that on the CPU before anything touches the device, and
+# every output -- tensors, per-slot statistics after simclr_bn_reduce_slots, pivot, ReLU bits -- is compared with tolerance 0.
+@contextlib.contextmanager
+def _switches(env):
+    """The SIMCLR_* switches of one launch (read per launch by plan_igemm / plan_wgrad), restored afterwards."""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _conv_lattice_weights(c, L):
+    """Compute copy of the row's weights: forward [Cout][KH KW Cin], data gradient [Cin][KH KW Cout] (include/simclr_hip.h), laid out on the
+    CPU; pre-split rows take the (hi, lo) copy ops.WeightPairBatch makes (SIMCLR_FMT_PS_W), whose plain copy must be that layout."""
+    fwd = c.op in ('fwd', 'fwd_pivoted', 'fwd_bn_apply')
+    w = L['w']
+    plain = (w.permute(3, 0, 1, 2).reshape(c.Cout, -1) if fwd else w.permute(2, 0, 1, 3).reshape(c.Cin, -1)).contiguous()
+    if not c.psw:
+        return _dev(plain, c.dtype), None
+    pair = ops.WeightPairBatch([(_dev(w, torch.float32), 0, 0)], torch.float32).run()[0]
+    wt = pair[0] if fwd else pair[1]
+    torch.cuda.synchronize()
+    assert wt._psw is not None and wt._psw[1] == (c.tf if fwd else c.tb), 'no pre-split copy for this arithmetic'
+    assert torch.equal(wt.double().cpu(), plain), 'prep_weights_pair_multi layout'
+    return wt._psw[0], wt
+
+
+def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
+    """One row of tests/conv_reference.CASES through the C ABI.  Every output lives in a guarded buffer that starts from a sentinel (or from
+    `prev` when accumulating); after each launch the recorded instantiation must name the family and template arguments the row claims.
+    Rows with statistics run once per slot count: simclr_conv2d_stats_slots + 5 (own-slot stores, the five spare slots stay zero), then
+    1 and 3 (the float-atomics branch: same totals)."""
+    from tests import conv_reference as cr
+    L, want = cr.reference(c)
+    f32 = torch.float32
+    T = c.dtype
+    dgrad = c.op in ('dgrad', 'dgrad_bn')
+    rows = c.V * (c.H * c.W if dgrad else c.OH * c.OW)
+    ch = c.Cin if dgrad else c.Cout
+    res = []
+    keep = []                                                     # device tensors the pointers refer to
+    ptr = lambda t: ops._pp(t) if t is not None else None
+
+    def dev(name, dtype):
+        t = _dev(L[name], dtype)
+        keep.append(t)
+        return ptr(t)
+
+    ops.set_f32_matmul(c.arith if T == f32 else 'exact')
+    try:
+        with _switches(c.env):
+            P = {}
+            wdev, wkeep = _conv_lattice_weights(c, L)
+            keep += [wdev, wkeep]
+            P['w'] = ptr(wdev)
+            if c.op != 'dgrad' and c.op != 'dgrad_bn':
+                P['x'] = dev('x', T)
+            if c.op in ('dgrad', 'dgrad_bn', 'wgrad'):
+                if c.psx:
+                    t = ps_encode(L['dy'].float()).to(DEV)
+                    keep.append(t)
+                    P['dy'] = ptr(t)
+                else:
+                    P['dy'] = dev('dy', T)
+            if c.op == 'dgrad_bn':
+                for n in ('scale', 'shift', 'mean', 'rstd'):
+                    P[n] = dev(n, f32)
+                P['bnx'] = dev('bnx', T)
+                if c.mode == 1:
+                    P['msk'] = dev('msk', T)
+                elif c.mode in (3, 4):
+                    t = want['mask_bits'].to(DEV).contiguous()
+                    keep.append(t)
+                    P['msk'] = ptr(t)
+            if c.op == 'fwd_bn_apply':
+                for n in ('scale', 'shift', 'rscale', 'rshift'):
+                    P[n] = dev(n, f32)
+                P['res'] = dev('res', T)
+            stat_runs = [None]
+            if c.stats:
+                own = lib().conv2d_stats_slots(rows, ch)
+                stat_runs = [own + 5 if s == 'spare' else s for s in slot_counts]
+            for nslot in stat_runs:
+                tag = 'conv_lattice %s%s' % (c.id, '' if nslot is None else ' nslot=%d' % nslot)
+                guards = []
+
+                def out(name, shape, dtype, start):
+                    fill = start if torch.is_tensor(start) else torch.full(shape, start, dtype=torch.float64)
+                    v, chk = _guarded(shape, dtype, fill=fill.to(dtype).to(DEV))
+                    guards.append(chk)
+                    P[name] = ptr(v)
+                    return v
+
+                got = {}
+                if c.op == 'wgrad':
+                    got['out'] = out('dw', (c.k * c.k * c.Cin, c.Cout), f32, L['prev'] if c.acc else 99.0)
+                    nbytes = lib().conv2d_wgrad_workspace_bytes(c.V, c.OH, c.OW, c.Cin, c.Cout, c.k, c.k, DT_BF16 if T == torch.bfloat16 else DT_F32)
+                    out('ws', ((nbytes + 3) // 4,), f32, 99.0)
+                elif dgrad:
+                    got['out'] = out('dx', (c.V, c.H, c.W, c.Cin), T, L['prev'] if c.acc else 99.0)
+                elif c.store:
+                    got['out'] = out('y', (c.V, c.OH, c.OW, c.Cout), T, 99.0)
+                if c.op == 'fwd_bn_apply' and c.bits:
+                    got['bits'] = out('bits', (rows, c.Cout // c.epc), torch.uint8, 0xA5)
+                if c.op == 'fwd_pivoted':
+                    got['pivot'] = out('pivot', (c.Cout,), f32, 99.0)
+                if nslot is not None:
+                    part = out('stats', (nslot, 2, ch), f32, 0.0)
+                cr.launch(lib(), c, P, nslot=nslot or 0, stream=ops._s())
+                rec = lib().conv2d_last_instantiation().decode()
+                parts = lib().conv2d_last_split_parts()
+                cr.check_record(c, rec)
+                if c.tail:
+                    assert parts >= 2, rec
+                if nslot is not None:
+                    sums = torch.empty(2, ch, device=DEV, dtype=torch.float64)
+                    if c.op == 'fwd_pivoted':
+                        lib().bn_reduce_slots_pivoted(ptr(part), nslot, ch, P['pivot'], float(rows), ptr(sums), ops._s())
+                    else:
+                        lib().bn_reduce_slots(ptr(part), nslot, ch, ptr(sums), ops._s())
+                torch.cuda.synchronize()
+                for n in ('out', 'bits', 'pivot'):
+                    if n in got:
+                        res.append(_bitwise('%s %s' % (tag, n), got[n], want[n]))
+                if nslot is not None:
+                    res.append(_bitwise(tag + ' sum', sums[0], want['s1']))
+                    if 's2' in want:
+                        res.append(_bitwise(tag + (' sum x^' if dgrad else ' sum of squares'), sums[1], want['s2']))
+                    if c.op == 'fwd_pivoted':
+                        res += [_bitwise(tag + ' slot totals about the pivot', part.double().sum(0), torch.stack([want['p1'], want['p2']]))]
+                    if nslot > 3:
+                        res.append(_bitwise(tag + ' spare slots stay zero', part[nslot - 5:], torch.zeros(5, 2, ch)))
+                res.append(_guards(tag, *guards))
+            if c.tail:
+                res.append(_entry('conv_lattice %s split-tail partners timed out' % c.id, ops.check_split_tail_health(), 0.0))
+    finally:
+        ops.set_f32_matmul('exact')
     return res

@@ -114,6 +114,11 @@ def main():
             run(gc.check_avgpool2, 2, H, 192, s, dt, W=W)
     for nslot, C in [(1, 8), (33, 40), (129, 64), (160, 40), (768, 2048)]:
         run(gc.check_bn_slot_kernels, nslot, C)
+    # implicit-GEMM convolutions on exact integer lattices, tolerance 0 (tests/test_gpu_conv_lattice.py); --quick: the small rows only
+    from tests import conv_reference as cr
+    for c in cr.CASES:
+        if '--quick' not in sys.argv or c.V * c.H * c.W * max(c.Cin, c.Cout) <= 2 ** 21:
+            run(gc.check_conv_lattice, c)
     # augmentation and blur kernels stage by stage (tests/test_gpu_augment.py)
     for views in (1, 2, 3):
         run(gc.check_augment_identity, 15, 17, views)
