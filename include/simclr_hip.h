@@ -527,6 +527,13 @@ int simclr_global_avgpool_bwd(const void* dy, const void* mask_src, void* dx, in
 /* ---- on-device augmentation: batch_random_blur, tf2/data_util.py:323-361,413-440 (tf2/model.py:255-258) ---- */
 int simclr_batch_blur(const float* images, float* tmp, float* out, const float* filt, const float* selector,
                       int b, int H, int W, int nviews, int K, simclr_stream_t stream);
+/* the same followed by solarization in the blur's last pass: solarize [nviews][b] in {0,1} (laid out like selector); after the
+ * clip an element v of a (view, image) whose coin is set becomes v >= threshold ? 1 - v : v.  Unselected images are copied,
+ * clipped and solarized; K = 1 with an all-zero selector is copy + clip + solarize.  All coins 0: bitwise simclr_batch_blur.
+ * Error code for a null pointer, a non-positive size, an even or non-positive K, a threshold outside [0, 1] or NaN. */
+int simclr_batch_blur_solarize(const float* images, float* tmp, float* out, const float* filt, const float* selector,
+                               const float* solarize, float threshold, int b, int H, int W, int nviews, int K,
+                               simclr_stream_t stream);
 
 /* ---- ResNet-D shortcut pool (tf2/resnet.py:330-338,400-408) and selective-kernel unit (:266-277) ---- */
 int simclr_avgpool2_fwd(const void* x, void* y, int V, int H, int W, int C, int stride, int dtype,

@@ -560,10 +560,14 @@ __global__ void global_avgpool_bwd(const T* __restrict__ dy, const T* __restrict
 // One thread per (image, pixel, view): 3 channels, taps along x (HORIZONTAL pass, only for selected
 // images, writes tmp) or along y (VERTICAL pass: reads tmp for selected images, the input itself for
 // unselected ones, clips and writes the result) -- unselected images are touched once.
-template <bool VERT>
+// SOL (vertical pass only; simclr_batch_blur_solarize): after the clip, an element v of an image whose coin
+// solarize[view][image] is set becomes v >= threshold ? 1 - v : v (torchvision's and BYOL's rule: an element AT the
+// threshold inverts).  Without SOL the two trailing arguments are not read.
+template <bool VERT, bool SOL = false>
 __global__ void blur1d(const float* __restrict__ in, const float* __restrict__ tmp, float* __restrict__ out,
                        const float* __restrict__ filt, const float* __restrict__ selector, int b, int H, int W,
-                       int nviews, int K) {
+                       int nviews, int K, const float* __restrict__ solarize, float threshold) {
+  static_assert(VERT || !SOL, "solarization belongs to the last (vertical) pass");
   const int C = 3 * nviews;
   const long long total = (long long)b * H * W * nviews;
   const int r = K / 2;
@@ -595,6 +599,9 @@ __global__ void blur1d(const float* __restrict__ in, const float* __restrict__ t
     }
     if (VERT) {                                  // clip_by_value(., 0, 1), tf2/data_util.py:437
       a0 = fminf(fmaxf(a0, 0.f), 1.f); a1 = fminf(fmaxf(a1, 0.f), 1.f); a2 = fminf(fmaxf(a2, 0.f), 1.f);
+      if (SOL && solarize[view * b + n] != 0.f) {
+        a0 = a0 >= threshold ? 1.f - a0 : a0; a1 = a1 >= threshold ? 1.f - a1 : a1; a2 = a2 >= threshold ? 1.f - a2 : a2;
+      }
       out[e] = a0; out[e + 1] = a1; out[e + 2] = a2;
     } else {
       out[e] = a0; out[e + 1] = a1; out[e + 2] = a2;
@@ -1207,9 +1214,31 @@ int simclr_batch_blur(const float* images, float* tmp, float* out, const float* 
   SIMCLR_CHECK_ARG(b > 0 && nviews > 0 && K > 0 && (K & 1), "batch_blur: bad shape (K must be odd)");
   const long long total = (long long)b * H * W * nviews;
   hipLaunchKernelGGL((blur1d<false>), dim3(grid_for(total)), dim3(256), 0, stream, images, (const float*)nullptr, tmp,
-                     filt, selector, b, H, W, nviews, K);
+                     filt, selector, b, H, W, nviews, K, (const float*)nullptr, 0.f);
   hipLaunchKernelGGL((blur1d<true>), dim3(grid_for(total)), dim3(256), 0, stream, images, (const float*)tmp, out,
-                     filt, selector, b, H, W, nviews, K);
+                     filt, selector, b, H, W, nviews, K, (const float*)nullptr, 0.f);
+  SIMCLR_CHECK_LAUNCH();
+  return 0;
+}
+
+/* simclr_batch_blur followed by solarization, in the blur's last pass (the order of the BYOL recipe: colour jitter, grayscale,
+ * blur, THEN solarize).  solarize [nviews][b] in {0,1}, laid out like selector: after the clip to [0,1] an element v of a
+ * (view, image) whose coin is set becomes v >= threshold ? 1 - v : v -- an element equal to the threshold inverts.  An
+ * unselected (unblurred) image is still passed through once and solarized if its coin says so; K = 1 with an all-zero selector
+ * is copy + clip + solarize.  The horizontal pass is simclr_batch_blur's own; with every coin 0 the output is bitwise that
+ * entry's.  Refused (nothing launched): a null pointer, b / H / W / nviews < 1, an even or non-positive K, a threshold outside
+ * [0, 1] or NaN. */
+int simclr_batch_blur_solarize(const float* images, float* tmp, float* out, const float* filt, const float* selector,
+                               const float* solarize, float threshold, int b, int H, int W, int nviews, int K,
+                               hipStream_t stream) {
+  SIMCLR_CHECK_ARG(images && tmp && out && filt && selector && solarize, "batch_blur_solarize: null argument");
+  SIMCLR_CHECK_ARG(b > 0 && H > 0 && W > 0 && nviews > 0 && K > 0 && (K & 1), "batch_blur_solarize: bad shape (K must be odd)");
+  SIMCLR_CHECK_ARG(threshold >= 0.f && threshold <= 1.f, "batch_blur_solarize: threshold must lie in [0, 1] (got %g)", (double)threshold);
+  const long long total = (long long)b * H * W * nviews;
+  hipLaunchKernelGGL((blur1d<false>), dim3(grid_for(total)), dim3(256), 0, stream, images, (const float*)nullptr, tmp,
+                     filt, selector, b, H, W, nviews, K, (const float*)nullptr, 0.f);
+  hipLaunchKernelGGL((blur1d<true, true>), dim3(grid_for(total)), dim3(256), 0, stream, images, (const float*)tmp, out,
+                     filt, selector, b, H, W, nviews, K, solarize, threshold);
   SIMCLR_CHECK_LAUNCH();
   return 0;
 }

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import data_util, ops
-from .flags import FLAGS, local_crop_flags
+from .flags import FLAGS, aug_plan, local_crop_flags
 
 FORMAT = 'simclr-arrays-1'
 LAYOUT = ('<data_dir>/<dataset>/info.json {"format": "%s", "num_classes": K, "splits": {"train": N, ...}}, '
@@ -189,6 +189,8 @@ class DatasetIterator:
         # get_preprocess_fn (tf2/data.py:101-115): jitter strength 0 outside pretraining, no test crop for image_size <= 32
         s = FLAGS.color_jitter_strength if color_jitter_strength is None else color_jitter_strength
         self.strength = float(s) if self.pretrain else 0.
+        # the jitter components of the augmentation recipe (flags.aug_plan): the global and the local views draw from the same ranges
+        self.jitter_components = aug_plan().jitter_components
         self.test_crop = self.size > 32
         self.views = 2 if self.pretrain else 1
         # multi-crop: L local views per image at their own size, area range and generator (pretraining with --contrastive_loss=swav or
@@ -228,7 +230,7 @@ class DatasetIterator:
             rng = np.random.default_rng([self.seed, int(step), self.r])
             hw = self.split.index[idx, 1:3]
             params = data_util.draw_train_params(self.b, hw[:, 0], hw[:, 1], self.size, self.size, self.strength,
-                                                 views=self.views, rng=rng)
+                                                 views=self.views, rng=rng, jitter_components=self.jitter_components)
         else:
             idx, w = eval_indices(self.n, step, self.B, self.r, self.R)
             hw = self.split.index[idx, 1:3]
@@ -243,7 +245,7 @@ class DatasetIterator:
         rng = np.random.default_rng([self.seed, int(step), self.r, 1])
         hw = self.split.index[idx, 1:3]
         return data_util.draw_local_params(self.b, hw[:, 0], hw[:, 1], self.local_size, self.local_crops, self.local_scale[0],
-                                           self.local_scale[1], self.strength, rng=rng)
+                                           self.local_scale[1], self.strength, rng=rng, jitter_components=self.jitter_components)
 
     def _host_buffer(self, slot, nbytes):
         buf = slot['host']

@@ -49,10 +49,39 @@ def gaussian_filter(kernel_size, sigma):
     return f if sig.dim() else f[0]
 
 
-def batch_random_blur_tensor(images, height, width, blur_probability=0.5, sigmas=None, selectors=None):
+_prob_columns = {}
+
+
+def _per_view(p, k, dev, what):
+    """A probability as the right-hand side of `rand(k, b) < .`: a scalar as it is (today's expression), a sequence of k numbers
+    as a float32 [k, 1] column on the device (made once per (device, values): the hot path copies nothing from the host)."""
+    if not isinstance(p, (list, tuple, np.ndarray)) and not torch.is_tensor(p):
+        return p
+    vals = tuple(float(v) for v in (p.tolist() if hasattr(p, 'tolist') else p))
+    if len(vals) != k:
+        raise ValueError('%s: %d probabilities for %d views' % (what, len(vals), k))
+    key = (str(dev), vals)
+    if key not in _prob_columns:
+        _prob_columns[key] = torch.tensor(vals, dtype=torch.float32).reshape(k, 1).to(dev)
+    return _prob_columns[key]
+
+
+def _any_positive(p):
+    if torch.is_tensor(p):
+        p = p.tolist()
+    return any(float(v) > 0 for v in (p if isinstance(p, (list, tuple, np.ndarray)) else (p,)))
+
+
+def batch_random_blur_tensor(images, height, width, blur_probability=0.5, sigmas=None, selectors=None,
+                             solarize_probability=0.0, solarize=None, threshold=0.5):
     """Fused form used by Model: images float32 [b,H,W,3k] -> blurred/clipped tensor of the same shape.
     sigmas [k] / selectors [k,b] may be given explicitly (tests); otherwise drawn like the reference:
-    sigma ~ U(0.1, 2.0) once per view (:405), selector = uniform(0,1) < p per image (:425-430)."""
+    sigma ~ U(0.1, 2.0) once per view (:405), selector = uniform(0,1) < p per image (:425-430).
+    blur_probability / solarize_probability: a scalar, or one number per view.  solarize [k,b] of 0/1: the solarization coins
+    (drawn as uniform(0,1) < solarize_probability when that is > 0 for some view); an image whose coin is set has every element
+    v >= threshold replaced by 1 - v AFTER the blur's clip (ops.batch_blur).  The device generator is consumed in the order sigmas,
+    blur selectors, solarization coins, and the coins are drawn only when some solarize probability is positive: at the defaults
+    it is consumed exactly as before the coins existed, and the launches are those of simclr_batch_blur."""
     b, H, W, C = images.shape
     k = C // 3
     dev = images.device
@@ -61,10 +90,63 @@ def batch_random_blur_tensor(images, height, width, blur_probability=0.5, sigmas
     else:
         sigmas = torch.as_tensor(sigmas, dtype=torch.float32).to(dev)
     if selectors is None:
-        selectors = (torch.rand(k, b, generator=_generator(dev), device=dev) < blur_probability).float()
+        selectors = (torch.rand(k, b, generator=_generator(dev), device=dev) < _per_view(blur_probability, k, dev, 'blur_probability')).float()
+    if solarize is None and _any_positive(solarize_probability):
+        solarize = (torch.rand(k, b, generator=_generator(dev), device=dev)
+                    < _per_view(solarize_probability, k, dev, 'solarize_probability')).float()
     filt = gaussian_filter(height // 10, sigmas)                                                  # :406-407
     sel = torch.as_tensor(selectors, dtype=torch.float32).to(dev).contiguous()
-    return ops.batch_blur(images.contiguous(), filt.contiguous(), sel)
+    if solarize is not None:
+        solarize = torch.as_tensor(solarize, dtype=torch.float32).to(dev).contiguous()
+    return ops.batch_blur(images.contiguous(), filt.contiguous(), sel, solarize, threshold)
+
+
+_no_blur = {}
+
+
+def apply_view_plan(images, plan, height=None, local=False, sigmas=None, selectors=None, solarize=None):
+    """The device-side stages of the resolved augmentation plan (flags.aug_plan) on a block of views [b,H,W,3k]: random blur, then
+    solarization, in one pass over the block.  `height` sizes the filter (default: the block's own).
+    Global views (view a is channels 0:3): the plan's per-view blur and solarize probabilities.  local=True (the low-resolution
+    views of multi-crop, blurred at their own size): probability 0.5 and no solarization, whatever the recipe.
+    A plan that blurs and solarizes nothing returns `images` itself and launches nothing.  Probabilities that are equal across the
+    views are passed as the scalar they are, so the `simclr` plan draws and launches exactly what a run without the recipe flags
+    does.  No blur (--use_blur=False, or both probabilities 0) with solarization on: a 1-tap filter and zero selectors, no sigma
+    and no selector is drawn -- copy, clip, solarize.
+    sigmas / selectors / solarize: explicit draws (tests), as in batch_random_blur_tensor; local views take no coins."""
+    b, H, W, C = images.shape
+    k = C // 3
+    height = H if height is None else height
+    if local:
+        if not plan.use_blur:
+            return images
+        return batch_random_blur_tensor(images, height, W, 0.5, sigmas=sigmas, selectors=selectors)
+    blur_p, sol_p = _views_of(plan.blur_probs, k, '--blur_probs'), _views_of(plan.solarize_probs, k, '--solarize_probs')
+    if not _any_positive(sol_p):
+        if not _any_positive(blur_p):
+            return images
+        return batch_random_blur_tensor(images, height, W, blur_p, sigmas=sigmas, selectors=selectors)
+    if not _any_positive(blur_p):
+        dev = images.device
+        key = (str(dev), k, b)
+        if key not in _no_blur:
+            _no_blur[key] = (torch.ones(k, 1, device=dev), torch.zeros(k, b, device=dev))
+        filt, sel = _no_blur[key]
+        if solarize is None:
+            solarize = (torch.rand(k, b, generator=_generator(dev), device=dev) < _per_view(sol_p, k, dev, '--solarize_probs')).float()
+        solarize = torch.as_tensor(solarize, dtype=torch.float32).to(dev).contiguous()
+        return ops.batch_blur(images.contiguous(), filt, sel, solarize, plan.solarize_threshold)
+    return batch_random_blur_tensor(images, height, W, blur_p, sigmas=sigmas, selectors=selectors, solarize_probability=sol_p,
+                                    solarize=solarize, threshold=plan.solarize_threshold)
+
+
+def _views_of(probs, k, flag):
+    """The plan's (view a, view b) pair for a block of k views: the scalar when both are equal (any k), the pair for k = 2."""
+    if len(set(probs)) == 1:
+        return probs[0]
+    if len(probs) != k:
+        raise ValueError('%s=%s names %d views, the block has %d' % (flag, ','.join('%g' % p for p in probs), len(probs), k))
+    return tuple(probs)
 
 
 def batch_random_blur(images_list, height, width, blur_probability=0.5):
@@ -77,6 +159,7 @@ def batch_random_blur(images_list, height, width, blur_probability=0.5):
 
 # --------------------------------------------------------------------------- crop / flip / colour jitter (input pipeline)
 CROP_PROPORTION = 0.875            # tf2/data_util.py:22
+JITTER_COMPONENTS = (0.8, 0.8, 0.8, 0.2)    # brightness, contrast, saturation, hue per unit of strength, tf2/data_util.py:70-73
 PARAM_FIELDS = ('crop_y', 'crop_x', 'crop_h', 'crop_w', 'flip', 'jitter_on', 'perm0', 'perm1', 'perm2', 'perm3',
                 'brightness', 'contrast', 'saturation', 'hue', 'gray_on', 'pad')
 _np_rng = {}
@@ -144,10 +227,13 @@ def sample_crop_boxes(rng, heights, widths, out_h, out_w, max_attempts=100, area
 
 
 def draw_train_params(b, heights, widths, height, width, color_jitter_strength=1.0, crop=True, flip=True, views=2,
-                      rng=None, area_range=(0.08, 1.0), min_object_covered=0.1):
+                      rng=None, area_range=(0.08, 1.0), min_object_covered=0.1, jitter_components=None):
     """Random draws of preprocess_for_train (tf2/data_util.py:443-475) for `views` views of each of `b` images.
     heights / widths: per-image source sizes (int or arrays).  Returns float32 [b, views, 16] laid out as PARAM_FIELDS.
-    area_range / min_object_covered: sample_crop_boxes's; draw_local_params sets them for SwAV's local views."""
+    area_range / min_object_covered: sample_crop_boxes's; draw_local_params sets them for SwAV's local views.
+    jitter_components: four non-negative numbers (brightness, contrast, saturation, hue); the range of each factor is its
+    component times color_jitter_strength.  None: the reference's (0.8, 0.8, 0.8, 0.2)."""
+    cb, cc_, cs, ch = JITTER_COMPONENTS if jitter_components is None else (float(v) for v in jitter_components)
     rng = _rng() if rng is None else rng
     m = b * views
     Hh = np.repeat(np.broadcast_to(np.asarray(heights, np.int64), (b,)), views)
@@ -161,7 +247,7 @@ def draw_train_params(b, heights, widths, height, width, color_jitter_strength=1
     if s > 0:                                                                      # :380-389
         p[:, 5] = rng.random(m) < 0.8
         p[:, 6:10] = np.argsort(rng.random((m, 4)), axis=1)                        # a uniform random order, :168
-        bb, cc, ss, hh = 0.8 * s, 0.8 * s, 0.8 * s, 0.2 * s                        # :70-73
+        bb, cc, ss, hh = cb * s, cc_ * s, cs * s, ch * s                           # :70-73 (0.8 s, 0.8 s, 0.8 s, 0.2 s)
         p[:, 10] = rng.uniform(max(1.0 - bb, 0.0), 1.0 + bb, m)                    # :37-39
         p[:, 11] = rng.uniform(1 - cc, 1 + cc, m)
         p[:, 12] = rng.uniform(1 - ss, 1 + ss, m)
@@ -170,13 +256,15 @@ def draw_train_params(b, heights, widths, height, width, color_jitter_strength=1
     return p.reshape(b, views, len(PARAM_FIELDS))
 
 
-def draw_local_params(b, heights, widths, size, views, min_scale, max_scale, color_jitter_strength=1.0, rng=None):
+def draw_local_params(b, heights, widths, size, views, min_scale, max_scale, color_jitter_strength=1.0, rng=None,
+                      jitter_components=None):
     """draw_train_params for the `views` LOCAL views of SwAV's multi-crop (Caron et al. 2020, section 4): square crops of `size`
     pixels whose area is a [min_scale, max_scale] share of the image, the same flip and colour jitter as the global views.  The
     cover is the minimum scale: left at the sampler's 0.1, a [0.05, 0.14] range would silently become [0.1, 0.14].
     Returns float32 [b, views, 16]."""
     return draw_train_params(b, heights, widths, size, size, color_jitter_strength, views=views, rng=rng,
-                             area_range=(float(min_scale), float(max_scale)), min_object_covered=float(min_scale))
+                             area_range=(float(min_scale), float(max_scale)), min_object_covered=float(min_scale),
+                             jitter_components=jitter_components)
 
 
 def _sizes(images, sizes):

@@ -6,6 +6,7 @@ spellings, defaults and `--name=value` / `--noname` command-line syntax behind a
 module-level `FLAGS` namespace.  TPU flags are accepted and ignored.
 """
 import argparse
+import collections
 import contextlib
 
 # The product default of f32_matmul is the fast tolerance-meeting mode.  SIMCLR_DEFAULT_F32_MATMUL overrides the DEFAULT only (tests/conftest.py
@@ -188,6 +189,23 @@ _DEFS = [
     ('knn_temperature', 0.07, float, 'MI355X build: temperature of the k-NN vote weights exp(similarity / temperature).'),
     ('knn_bank_examples', 0, int, 'MI355X build: examples of --train_split in the k-NN bank: 0 = the whole split, n > 0 = the first n positions of '
                                   'epoch_permutation(data_seed, 0, N).  --dataset=synthetic: a bank of random images, at most 8 eval batches.'),
+    # asymmetric view augmentation (flags.aug_plan): per-view blur and solarization of the two global views, jitter components.
+    # None = take the column from --aug_recipe.  Read in pretraining only: --train_mode=finetune and --mode=eval ignore all five.
+    ('aug_recipe', 'simclr', str, "MI355X build: augmentation recipe of the two global views, 'simclr' (default: blur 0.5 / 0.5, no "
+                                  "solarization, jitter components 0.8,0.8,0.8,0.2), 'byol' (the asymmetric recipe this project defines "
+                                  'for BYOL, Barlow Twins, VICReg and the global views of DINO: view a always blurred and never solarized, '
+                                  "view b blurred with probability 0.1 and solarized with probability 0.2, components 0.4,0.4,0.2,0.1) or "
+                                  "'mocov2' (blur 0.5 / 0.5, no solarization, components 0.4,0.4,0.4,0.1).  Independent of "
+                                  '--contrastive_loss: nothing is switched on implicitly.  Local views of multi-crop keep blur 0.5 and no '
+                                  'solarization; they take the jitter components.'),
+    ('blur_probs', None, str, "MI355X build: 'pa,pb', blur probability of global view a (channels 0:3) and b; overrides the recipe's.  "
+                              'Each in [0, 1].  --use_blur=False zeroes both and leaves solarization on.'),
+    ('solarize_probs', None, str, "MI355X build: 'pa,pb', probability that global view a / b is solarized after the blur's clip; "
+                                  "overrides the recipe's.  Each in [0, 1]."),
+    ('solarize_threshold', 0.5, float, 'MI355X build: an element v >= threshold of a solarized image becomes 1 - v (an element equal to '
+                                       'the threshold inverts).  In [0, 1].'),
+    ('color_jitter_components', None, str, "MI355X build: 'b,c,s,h', the brightness, contrast, saturation and hue ranges per unit of "
+                                           "--color_jitter_strength; overrides the recipe's.  Each >= 0, hue <= 0.5."),
 ]
 
 
@@ -203,6 +221,70 @@ def local_crop_flags(flags=None):
         return 0, int(flags.swav_local_crop_size), float(flags.swav_local_crop_min_scale), float(flags.swav_local_crop_max_scale)
     get = lambda name: getattr(flags, '%s_local_%s' % (loss, name))
     return int(get('crops')), int(get('crop_size')), float(get('crop_min_scale')), float(get('crop_max_scale'))
+
+
+# --aug_recipe -> (blur probability of view a and b, solarize probability of view a and b, jitter components b, c, s, h).  'byol' is
+# the asymmetric recipe of BYOL, Barlow Twins, VICReg and DINO's global views as this project defines it (a choice, not a parity claim)
+AUG_RECIPES = {
+    'simclr': ((0.5, 0.5), (0.0, 0.0), (0.8, 0.8, 0.8, 0.2)),
+    'byol': ((1.0, 0.1), (0.0, 0.2), (0.4, 0.4, 0.2, 0.1)),
+    'mocov2': ((0.5, 0.5), (0.0, 0.0), (0.4, 0.4, 0.4, 0.1)),
+}
+AugPlan = collections.namedtuple('AugPlan', 'recipe use_blur blur_probs solarize_probs solarize_threshold jitter_components')
+
+
+def _number_list(flag, text, n):
+    """'a,b,...' (or a sequence) -> n floats; ValueError naming the flag for another length or a non-number."""
+    parts = list(text) if isinstance(text, (list, tuple)) else [t.strip() for t in str(text).split(',')]
+    if len(parts) != n:
+        raise ValueError('--%s needs %d comma-separated numbers (got %r)' % (flag, n, text))
+    try:
+        return tuple(float(t) for t in parts)
+    except (TypeError, ValueError):
+        raise ValueError('--%s: %r is not a list of numbers' % (flag, text))
+
+
+def aug_plan(flags=None):
+    """The resolved augmentation plan of the two global views -- the ONE reader of --aug_recipe, --blur_probs, --solarize_probs,
+    --solarize_threshold and --color_jitter_components (the model, run.py and data.py call it): the recipe's row with every
+    explicitly given flag in place of its column.  --use_blur=False zeroes the blur probabilities and leaves solarization on;
+    --color_jitter_strength keeps scaling the components (data_util.draw_train_params).  Outside pretraining
+    (--train_mode=finetune, --mode=eval) the five flags are not read: the plan is the `simclr` one.
+    ValueError naming the flag -- run.main raises it before any device work -- for an unknown recipe, a list of the wrong length
+    or with a non-number, a probability or the threshold outside [0, 1] or NaN, a negative or NaN component, a hue component
+    above 0.5."""
+    flags = FLAGS if flags is None else flags
+    use_blur = bool(getattr(flags, 'use_blur', True))
+    pretrain = getattr(flags, 'train_mode', 'pretrain') == 'pretrain' and getattr(flags, 'mode', 'train') != 'eval'
+    recipe = getattr(flags, 'aug_recipe', 'simclr') if pretrain else 'simclr'
+    if recipe not in AUG_RECIPES:
+        raise ValueError("--aug_recipe must be 'simclr', 'byol' or 'mocov2' (got %r)" % (recipe,))
+    blur, sol, comp = AUG_RECIPES[recipe]
+    thr = 0.5
+    if pretrain:
+        given = lambda name: getattr(flags, name, None) not in (None, '')
+        if given('blur_probs'):
+            blur = _number_list('blur_probs', flags.blur_probs, 2)
+        if given('solarize_probs'):
+            sol = _number_list('solarize_probs', flags.solarize_probs, 2)
+        if given('color_jitter_components'):
+            comp = _number_list('color_jitter_components', flags.color_jitter_components, 4)
+        try:
+            thr = float(getattr(flags, 'solarize_threshold', 0.5))
+        except (TypeError, ValueError):
+            raise ValueError('--solarize_threshold: %r is not a number' % (flags.solarize_threshold,))
+    for name, probs in (('blur_probs', blur), ('solarize_probs', sol)):
+        if not all(0.0 <= p <= 1.0 for p in probs):                       # (NaN fails the comparison)
+            raise ValueError('--%s: a probability lies in [0, 1] (got %r)' % (name, probs))
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError('--solarize_threshold must lie in [0, 1] (got %r)' % (thr,))
+    if not all(c >= 0.0 for c in comp):
+        raise ValueError('--color_jitter_components: a component is a number >= 0 (got %r)' % (comp,))
+    if comp[3] > 0.5:
+        raise ValueError('--color_jitter_components: the hue component is at most 0.5 (got %r)' % (comp[3],))
+    if not use_blur:
+        blur = (0.0, 0.0)
+    return AugPlan(recipe, use_blur, tuple(blur), tuple(sol), thr, tuple(comp))
 
 
 def parse_dropblock_keep_probs(text):

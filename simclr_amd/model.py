@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import data_util, lars_optimizer, ops, optimizers, resnet
-from .flags import FLAGS, check_dropblock_flags
+from .flags import FLAGS, aug_plan, check_dropblock_flags
 from .lars_optimizer import Variable
 from .resnet import RT, Act, Layer, PackedInput, scope
 
@@ -412,9 +412,10 @@ class Model(Layer):
         # activations to fp16's range (a freshly initialised network's moving averages do not normalise at all): the split-fp16 forward is
         # for training-mode BatchNorm only, an inference forward runs its fp32 products as six bf16 terms instead (same accuracy class).
         ops.select_f32_matmul(inference=not training)
-        if blur and FLAGS.use_blur and training and FLAGS.train_mode == 'pretrain':
-            # batch_random_blur on the device (tf2/model.py:255-258), fused over the k views
-            inputs = data_util.batch_random_blur_tensor(inputs, FLAGS.image_size, FLAGS.image_size)
+        if blur and training and FLAGS.train_mode == 'pretrain':
+            # batch_random_blur on the device (tf2/model.py:255-258), fused over the k views, and the plan's solarization in its
+            # last pass; --use_blur=False without solarization launches nothing
+            inputs = data_util.apply_view_plan(inputs, aug_plan(), height=FLAGS.image_size)
         num_transforms = inputs.shape[3] // 3
         k, s = self.resnet_model.stem_kernel_stride
         # (training: the 7x7 stem's weight gradient reads the image as bf16 pieces in the three-term modes -- written by the packing pass)

@@ -1980,14 +1980,21 @@ def global_avgpool_bwd(dy, H, W, mask_src=None):
     return dx
 
 
-def batch_blur(images, filt, selector):
-    """images f32 [b,H,W,3k]; filt [k,K]; selector [k,b] of 0/1."""
+def batch_blur(images, filt, selector, solarize=None, threshold=0.5):
+    """images f32 [b,H,W,3k]; filt [k,K]; selector [k,b] of 0/1.
+    solarize: None (simclr_batch_blur, the launches of a run without solarization), or [k,b] of 0/1 laid out like selector
+    (simclr_batch_blur_solarize): after the clip, v >= threshold ? 1 - v : v on the images whose coin is set."""
     b, H, W, C = images.shape
     k, K = filt.shape
     assert C == 3 * k and images.dtype == torch.float32
     tmp = torch.empty_like(images)
     out = torch.empty_like(images)
-    lib().batch_blur(_p(images), _p(tmp), _p(out), _p(filt), _p(selector), b, H, W, k, K, _s())
+    if solarize is None:
+        lib().batch_blur(_p(images), _p(tmp), _p(out), _p(filt), _p(selector), b, H, W, k, K, _s())
+    else:
+        assert tuple(solarize.shape) == (k, b) and solarize.dtype == torch.float32 and solarize.is_contiguous()
+        lib().batch_blur_solarize(_p(images), _p(tmp), _p(out), _p(filt), _p(selector), _p(solarize), float(threshold),
+                                  b, H, W, k, K, _s())
     return out
 
 

@@ -23,7 +23,7 @@ from . import model as model_lib
 from . import objective as obj_lib
 from . import pretrain_losses as loss_lib
 from .comm import Strategy, collectives_on, num_replicas
-from .flags import FLAGS, check_dropblock_flags, local_crop_flags
+from .flags import FLAGS, aug_plan, check_dropblock_flags, local_crop_flags
 from .resnet import RT, join_wgrad_stream, set_dropblock_step
 
 
@@ -327,6 +327,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                          % (FLAGS.contrastive_loss, FLAGS.train_mode, FLAGS.nn_queue_size))
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
     local_crops = local_crop_plan()[0]
+    aug_plan()                                # (raises for malformed augmentation flags; the steps resolve the plan as they read it)
 
     def single_step(features, labels):
         # optimizer.iterations is a host int that apply_gradients increments: every "before the increment" read of the step is this
@@ -350,9 +351,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         c = types.SimpleNamespace(model=model, target=target, strategy=strategy, steps_per_epoch=steps_per_epoch, step=step,
                                   labels=labels, target_outputs=None, keys=None, frozen=False, logits_con=None, support=support)
         if target is not None:
-            # one draw of the random blur for both networks (Model.__call__ would draw its own inside each)
-            if FLAGS.use_blur:
-                features = data_util.batch_random_blur_tensor(features, FLAGS.image_size, FLAGS.image_size)
+            # one draw of the random blur (and of the plan's solarization) for both networks (Model.__call__ would draw its own
+            # inside each): view a stays channels 0:3 -- rows [0, b) of both projections
+            features = data_util.apply_view_plan(features, aug_plan(), height=FLAGS.image_size)
             c.target_outputs = target(features)        # released before the online forward: the two activation sets never coexist
             if name == 'mocov2':
                 # the keys of this step, and their gather for the enqueue at the END of the step: in flight during the online forward,
@@ -427,9 +428,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             # are set aside; the buffer is zeroed because pass B writes no supervised-head (and no frozen-prototype) slot
             saved_grads = model._flat_grads.clone()
             model._flat_grads.zero_()
-            if FLAGS.use_blur:
-                # Model.__call__ blurs at FLAGS.image_size: the local views are blurred here, at their own size
-                local_features = data_util.batch_random_blur_tensor(local_features, local_features.shape[1], local_features.shape[2])
+            # Model.__call__ blurs at FLAGS.image_size: the local views are blurred here, at their own size (probability 0.5 and no
+            # solarization under every recipe)
+            local_features = data_util.apply_view_plan(local_features, aug_plan(), local=True)
             local_outputs, _ = model(local_features, training=True, blur=False, supervised=False)
             global_loss = con_loss
             if name == 'dino':
@@ -688,6 +689,7 @@ def main(argv):
     logging.basicConfig(level=logging.INFO)
     distill = check_distillation_flags()
     check_contrastive_loss_flags()
+    aug_plan()                                # a malformed --aug_recipe / --blur_probs / ... raises here, before any device work
     check_dropblock_flags()
     check_knn_flags()
     builder = None
