@@ -29,7 +29,12 @@ What the kernels compute, where that differs from the obvious (documented in inc
   * bf16 storage with a channel count of the output that is no multiple of 8 runs the non-persistent kernel (plan_igemm, odd_n);
   * simclr_conv2d_dgrad_bn accumulates sum(dm) and the raw moment sum(dm * x) and converts the latter per slot,
     (sum(dm x) - mean sum(dm)) * rstd = sum(dm * x^); mask mode 4 produces sum(dm) only (the second row of the slots is not compared);
-  * simclr_conv2d_fwd_bn_apply computes act(T(conv) * scale + shift + r) from the convolution output ROUNDED to the storage type T.
+  * simclr_conv2d_fwd_bn_apply computes act(T(conv) * scale + shift + r) from the convolution output ROUNDED to the storage type T;
+  * simclr_conv2d_dgrad_ext / _bn_ext (`ext` rows) reduce over K = Cout + Cin from two operand streams, dx (+)= dm Wext[:, :Cout]^T +
+    h Wext[:, Cout:]^T + bias: the data-gradient reference on the concatenated operands, w_ext thinned by Cout + Cin, an integer bias;
+  * accumulate = 3 (`sparse` rows, 1x1 stride 2) stores the even (row, column) pixels and leaves every other element of dx as it was;
+    accumulate = 2 adds earlier data at those even pixels only and stores elsewhere, whatever the other elements hold (SENTINEL here).
+The stem chain and the Gram chain have a sibling table, tests/stem_gram_reference.py.
 """
 import math
 import re
@@ -47,6 +52,7 @@ DT_F32, DT_BF16 = 0, 1
 PS_IN, PS_W = 0x100, 0x100000            # SIMCLR_FMT_PS_IN, SIMCLR_FMT_PS_W
 F16_WSCALE = 256.0                       # 2^F16_WSCALE_LOG2: the fp16 pieces of the three-term forward hold 2^8 w
 LIMIT = float(2 ** 24)
+SENTINEL = 12345.0                       # what dx holds before a sparse store (finite: a leak shows as a wrong number, not as a masked compare)
 
 
 def terms_field(t):
@@ -157,8 +163,8 @@ def mask_of(c, L, dtype=F64):
 def dgrad_bn_ref(c, L, dtype=F64, perm=None):
     """dm = (dx [+ prev]) * mask; (sum dm, sum dm * x^), x^ = (bn_x - mean) * rstd -- and the same second sum the way the kernel forms it,
     (sum(dm * bn_x) - mean * sum(dm)) * rstd."""
-    dx = conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W, dtype)
-    if c.acc:
+    dx = dgrad_of(c, L, dtype)
+    if c.adds:
         dx = dx + L['prev'].to(dtype)
     dm = dx * mask_of(c, L, dtype).to(dtype)
     a = dm.reshape(-1, c.Cin)
@@ -184,7 +190,7 @@ def fwd_bn_apply_ref(c, L, conv, dtype=F64):
 
 # --------------------------------------------------------------------------------------------------------------------- cases
 _DEFAULTS = dict(k=1, s=1, env=None, fam=(), args=None, psx=False, psw=False, mode=0, acc=0, stats=False, store=True, relu=1, res=None,
-                 bits=True, dense=None, tail=None, multi=False, splits=None, note='')
+                 bits=True, dense=None, tail=None, multi=False, splits=None, note='', ext=False)
 OPS = ('fwd', 'fwd_pivoted', 'fwd_bn_apply', 'dgrad', 'dgrad_bn', 'wgrad')
 
 
@@ -193,7 +199,13 @@ def make_case(id, op, arith, V, H, W, Cin, Cout, **kw):
     env: the SIMCLR_* switches of the launch; fam: the family tags (tags_of) the recorded instantiation must carry; args: template
     arguments it must name; tail: True / False = split tail planned / not; multi: some workgroup owns several M-tiles; splits: 'one' |
     'many' slabs of the weight gradient; psx / psw: dy / the weights in the pre-split (hi, lo) block format; stats: fwd with statistics;
-    store=False: the statistics-only pass (y == NULL); dense: 'acc' | 'rounded' = a designated bf16 rounding row."""
+    store=False: the statistics-only pass (y == NULL); dense: 'acc' | 'rounded' = a designated bf16 rounding row.
+    ext (dgrad, dgrad_bn; 1x1 stride 1): the K-extended launch simclr_conv2d_dgrad(_bn)_ext -- L['dy'] holds [dm | h] (Cout + Cin channels),
+    L['w'] the rows of w_ext [Cin][Cout + Cin], L['bias'] the bias.
+    acc (data gradient): 0 store | 1 dx += | 3 (stride 2) the sparse store: only the pixel classes that receive a tap are written, the
+    others keep what dx held (SENTINEL in the check) | 2 the sparse accumulate: dx holds earlier data at the even (row, column) pixels only
+    -- what a 1x1 stride-2 call with accumulate = 3 from dy1 / w1 (Cout channels) left in a buffer full of SENTINEL, which is how the
+    check produces it -- and SENTINEL must not leak from the other pixels."""
     assert op in OPS and arith in ARITH, (op, arith)
     bad = set(kw) - set(_DEFAULTS)
     assert not bad, bad
@@ -208,6 +220,12 @@ def make_case(id, op, arith, V, H, W, Cin, Cout, **kw):
     c.OH, c.OW = out_hw(H, W, c.k, c.s)
     c.M = V * c.OH * c.OW                 # output rows of the forward; the data gradient's GEMM has V * H * W
     c.epc = 8 if c.dtype == BF16 else 4
+    assert c.acc in (0, 1) or op in ('dgrad', 'dgrad_bn'), id
+    assert c.acc != 3 or c.s == 2, id
+    assert c.acc != 2 or (c.k == 1 and c.s == 1 and c.dtype == F32), id
+    assert not c.ext or (op in ('dgrad', 'dgrad_bn') and c.k == 1 and c.s == 1 and not c.psx), id
+    c.adds = c.acc in (1, 2)                  # dx / dw += : the row has a `prev`
+    c.Cy = Cout + Cin if c.ext else Cout      # channels of L['dy'] and reduction length per tap of the data gradient
     if op in ('fwd_pivoted', 'dgrad_bn'):
         c.stats = True
     return c
@@ -232,11 +250,18 @@ def lattice(c):
         L['w'] = (torch.rand(k, k, Cin, Cout, generator=g, dtype=F64) < dens).double()
         return L
     L['x'] = _ints((c.V, c.H, c.W, Cin), 2, g)
-    L['dy'] = _ints((c.V, c.OH, c.OW, Cout), 2, g)
-    sign = torch.randint(0, 2, (k, k, Cin, Cout), generator=g).double() * 2 - 1
-    u = torch.rand(k, k, Cin, Cout, generator=g, dtype=F64)
-    if c.acc:
+    L['dy'] = _ints((c.V, c.OH, c.OW, c.Cy), 2, g)
+    sign = torch.randint(0, 2, (k, k, Cin, c.Cy), generator=g).double() * 2 - 1
+    u = torch.rand(k, k, Cin, c.Cy, generator=g, dtype=F64)
+    if c.acc == 2:          # what the sparse store of a stride-2 1x1 data gradient leaves at the even pixels (zero elsewhere: nothing is added there)
+        OH2, OW2 = out_hw(c.H, c.W, 1, 2)
+        L['dy1'] = _ints((c.V, OH2, OW2, Cout), 2, g)
+        L['w1'] = (torch.randint(0, 2, (1, 1, Cin, Cout), generator=g).double() * 2 - 1) * (torch.rand(1, 1, Cin, Cout, generator=g, dtype=F64) < min(1.0, 6.0 / Cout)).double()
+        L['prev'] = conv_dgrad_ref(L['dy1'], L['w1'], 1, 2, c.H, c.W)
+    elif c.adds:
         L['prev'] = _ints((k * k * Cin, Cout) if c.op == 'wgrad' else (c.V, c.H, c.W, Cin), 4, g)
+    if c.ext:
+        L['bias'] = _ints((Cin,), 4, g)
     if c.op == 'dgrad_bn':
         L.update(lattice_params(Cin, g))
         L['bnx'] = quarters((c.V, c.H, c.W, Cin), 4, g)
@@ -244,7 +269,7 @@ def lattice(c):
     if c.op == 'fwd_bn_apply':
         L.update(lattice_params(Cout, g))
         L['res'] = quarters((c.V, c.OH, c.OW, Cout), 4, g)
-    red = k * k * (Cout if c.op in ('dgrad', 'dgrad_bn') else Cin)
+    red = k * k * (c.Cy if c.op in ('dgrad', 'dgrad_bn') else Cin)
     dens = min(1.0, 12.0 / red)
     for _ in range(12):
         L['w'] = sign * (u < dens).double()
@@ -254,16 +279,30 @@ def lattice(c):
     raise AssertionError('no weight density meets the bounds of %s' % c.id)
 
 
+def dgrad_of(c, L, dtype=F64):
+    """The data gradient before `prev`: conv_dgrad_ref, and in a K-extended row dm Wext[:, :Cout]^T + h Wext[:, Cout:]^T + bias -- the
+    same reference on the concatenated operands [dm | h], plus the bias."""
+    dx = conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W, dtype)
+    return dx + L['bias'].to(dtype) if c.ext else dx
+
+
+def even_pixels(c):
+    """bool [1, H, W, 1]: the pixels with even row and even column -- the one class a 1x1 stride-2 data gradient has taps for."""
+    m = torch.zeros(1, c.H, c.W, 1, dtype=torch.bool)
+    m[:, ::2, ::2] = True
+    return m
+
+
 def _main_output(c, L, dtype=F64):
     if c.op in ('fwd', 'fwd_pivoted', 'fwd_bn_apply'):
         return conv_fwd_ref(L['x'], L['w'], c.k, c.s, dtype)
     if c.op == 'dgrad':
-        dx = conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W, dtype)
-        return dx + L['prev'].to(dtype) if c.acc else dx
+        dx = dgrad_of(c, L, dtype)
+        return dx + L['prev'].to(dtype) if c.adds else dx
     if c.op == 'dgrad_bn':
         return dgrad_bn_ref(c, L, dtype)['dm']
     dw = conv_wgrad_ref(L['x'], L['dy'], c.k, c.s, dtype).reshape(c.k * c.k * c.Cin, c.Cout)
-    return dw + L['prev'].to(dtype) if c.acc else dw
+    return dw + L['prev'].to(dtype) if c.adds else dw
 
 
 def _abs_sums(c, L, out):
@@ -283,19 +322,21 @@ def _abs_sums(c, L, out):
 def _bounds_ok(c, L):
     out = _main_output(c, L)
     if c.op == 'dgrad_bn':          # the unmasked gradient is what the accumulators hold
-        dx = conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W)
-        out = dx + L['prev'] if c.acc else dx
+        dx = dgrad_of(c, L)
+        out = dx + L['prev'] if c.adds else dx
     return float(out.abs().max()) <= 256 and float(_abs_sums(c, L, out)) < LIMIT
 
 
 def shares(c, L, out):
     """The shares `reference` puts floors under."""
     s = dict(nonzero=float((out != 0).double().mean()))
+    if c.acc == 3 and c.k == 1:       # (among the pixels that receive a tap: the others are structural zeros, not a thin lattice)
+        s['nonzero'] = float((out[:, ::2, ::2] != 0).double().mean())
     if c.op == 'dgrad_bn':
         m = mask_of(c, L)
         s['masked_off'] = float((~m).double().mean())
-        dx = conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W)
-        s['masked_off_nonzero'] = float((~m & ((dx + L['prev'] if c.acc else dx) != 0)).double().mean())
+        dx = dgrad_of(c, L)
+        s['masked_off_nonzero'] = float((~m & ((dx + L['prev'] if c.adds else dx) != 0)).double().mean())
         if c.mode == 2:
             arg = L['bnx'] * L['scale'] + L['shift']
             s['arg_zero'] = float((arg == 0).double().mean())
@@ -365,14 +406,15 @@ def reference(c, check_ps=True):
             want.pop('s2')
         want.pop('s2_raw')
     # storage: every operand survives its type (and, pre-split, the block format; the fp16 pieces of the forward hold 2^8 w)
-    ops_ = {n: L[n] for n in ('x', 'w', 'dy', 'prev', 'bnx', 'msk', 'res') if n in L and not (n == 'prev' and c.op == 'wgrad')}
+    ops_ = {n: L[n] for n in ('x', 'w', 'dy', 'prev', 'bnx', 'msk', 'res', 'dy1', 'w1') if n in L and not (n == 'prev' and c.op == 'wgrad')}
     assert_survives(ops_, c.dtype)
     assert_survives({n: v for n, v in L.items() if v.dim() == 1}, F32)
     if c.dtype == F32:
-        assert_survives(dict(w=L['w']), BF16)
+        assert_survives({n: L[n] for n in ('w', 'w1') if n in L}, BF16)
         assert_survives(dict(w256=L['w'] * F16_WSCALE, x=L['x']), torch.float16)
         if c.psx and check_ps:
             assert torch.equal(ps_roundtrip(L['dy']), L['dy']), c.id
+            assert c.acc != 2 or torch.equal(ps_roundtrip(L['dy1']), L['dy1']), c.id
     raw = _main_output(c, L)
     if c.dense:
         assert float((round_to(raw, BF16) != raw).double().mean()) >= 0.25, c.id       # the rounding is real
@@ -396,6 +438,15 @@ def reference(c, check_ps=True):
     if c.op == 'dgrad_bn' and c.mode in (3, 4):
         want['mask_bits'] = pack_bits(L['msk'] > 0, c.epc)
     _assert_shares(c, shares(c, L, raw), raw.numel())
+    if c.acc == 2:          # the earlier data: non-zero at some even pixel, nothing at the others
+        ev = even_pixels(c)
+        assert float((L['prev'] * ev != 0).double().mean()) >= 0.02 and not bool((L['prev'] * ~ev).any()), c.id
+        assert float((~ev).double().mean()) > 0 or c.H * c.W == 1, c.id
+    if c.acc == 3:          # the sparse store: the pixel classes without a tap keep the sentinel
+        sent = float(round_to(torch.tensor([SENTINEL], dtype=F64), c.dtype))
+        if c.k == 1:
+            assert not bool((want['out'] * ~even_pixels(c)).any()), c.id
+            want['out'] = torch.where(even_pixels(c), want['out'], torch.full_like(want['out'], sent))
     return L, want
 
 
@@ -416,8 +467,16 @@ def launch(lib, c, P, nslot=0, stream=None):
         rbn = c.res == 'bn'
         return lib.conv2d_fwd_bn_apply(g('x'), g('w'), g('y'), g('scale'), g('shift'), g('res') if c.res else None, g('rscale') if rbn else None,
                                        g('rshift') if rbn else None, int(c.relu), g('bits') if c.bits else None, *geo, fw, stream)
+    if c.op == 'dgrad' and c.ext:
+        return lib.conv2d_dgrad_ext(g('dy'), g('h'), g('w'), g('bias'), g('dx'), int(c.acc), c.V, c.H, c.W, c.Cin, c.Cout, bw, stream)
     if c.op == 'dgrad':
         return lib.conv2d_dgrad(g('dy'), g('w'), g('dx'), int(c.acc), *geo, bw, stream)
+    if c.op == 'dgrad_bn' and c.ext:
+        m4 = c.mode == 4
+        return lib.conv2d_dgrad_bn_ext(g('dy'), g('h'), g('w'), g('bias'), g('dx'), int(c.acc), None if m4 else g('bnx'),
+                                       None if c.mode == 2 else g('msk'), g('scale') if c.mode == 2 else None,
+                                       g('shift') if c.mode == 2 else None, None if m4 else g('mean'), None if m4 else g('rstd'), c.mode,
+                                       g('stats'), nslot, c.V, c.H, c.W, c.Cin, c.Cout, bw, stream)
     if c.op == 'dgrad_bn':
         m4 = c.mode == 4
         return lib.conv2d_dgrad_bn(g('dy'), g('w'), g('dx'), int(c.acc), None if m4 else g('bnx'), None if c.mode == 2 else g('msk'),
@@ -427,8 +486,15 @@ def launch(lib, c, P, nslot=0, stream=None):
                             c.pad, dt | terms_field(c.tb) | (PS_IN if c.psx else 0), stream)
 
 
+def launch_first(lib, c, P, stream=None):
+    """The call before a sparse-accumulate row (acc == 2): the 1x1 stride-2 data gradient of dy1 / w1 with accumulate = 3 into dx."""
+    OH2, OW2 = out_hw(c.H, c.W, 1, 2)
+    bw = DT_F32 | terms_field(c.tb) | (PS_IN if c.psx else 0)
+    return lib.conv2d_dgrad(P.get('dy1'), P.get('w1'), P.get('dx'), 3, c.V, c.H, c.W, c.Cin, OH2, OW2, c.Cout, 1, 1, 2, 0, bw, stream)
+
+
 POINTERS = ('x', 'w', 'y', 'dy', 'dx', 'dw', 'ws', 'stats', 'pivot', 'scale', 'shift', 'mean', 'rstd', 'bnx', 'msk', 'res', 'rscale',
-            'rshift', 'bits')
+            'rshift', 'bits', 'h', 'bias', 'dy1', 'w1')
 
 
 # --------------------------------------------------------------------------------------------------------------------- the record
@@ -471,6 +537,12 @@ def tags_of(c, rec):
         t.add('WIDE ' + ('flat' if a['FLAT'] == 'true' else 'gathered') + (' split tail' if f['tail_parts'] >= 2 else ''))
     elif kernel == 'conv_igemm_nwalk':
         t.add('NWALK FAS%s' % a['FAS'])
+    if kernel == 'conv_igemm_persistent' and a['EXT'] == 'true':
+        t.add('EXT TILE%s %s%s' % (a['BM'], 'f32' if f32 else 'bf16', ' reduce' if a['BNEPI'] == 'true' else ''))
+    if c.acc >= 2 and c.op in ('dgrad', 'dgrad_bn') and kernel == 'conv_igemm_persistent':
+        t.add('SPARSE acc%d %s%s' % (c.acc, 'f32' if f32 else 'bf16', ' reduce' if a['BNEPI'] == 'true' else ''))
+    if kernel in ('conv_igemm', 'conv_igemm_wide', 'conv_igemm_nwalk'):
+        pass
     elif kernel == 'conv_igemm_persistent' and a['BM'] == '256':
         t.add('TILE256' + (' split tail' if a['TAIL'] == 'true' else ''))
         if a['FAPPLY'] == 'true':
@@ -509,8 +581,8 @@ def tags_of(c, rec):
     return t
 
 
-# the families part 3 of the issue names.  TILE256_BF16 (weight gradient) has no forcing switch -- it needs M >= 150000 -- and is left out;
-# so are the stem, the K-extended launches, the Gram launch and the sparse accumulate (2, 3).
+# the families the rows must reach.  TILE256_BF16 (weight gradient) has no forcing switch -- it needs M >= 150000 -- and is left out.
+# The stem and the Gram chain have their own table (tests/stem_gram_reference.py).
 REQUIRED_FWD_DGRAD = ['FALLBACK', 'TILE128 gather BN64', 'TILE128 gather BN128', 'TILE128 window bf16', 'TILE128 window f32 fwd',
                       'TILE128 window f32 dgrad psx', 'TILE128 window f32 dgrad psx reduce', 'TILE128 split tail', 'TILE256',
                       'TILE256 split tail', 'WIDE flat', 'WIDE gathered', 'WIDE flat split tail', 'WIDE gathered split tail', 'NWALK FAS1',
@@ -519,7 +591,11 @@ REQUIRED_FWD_DGRAD = ['FALLBACK', 'TILE128 gather BN64', 'TILE128 gather BN128',
 WGRAD_FAMILIES = ['REG_STAGED', 'DMA_RING stages 2', 'DMA_RING stages 3', 'DMA_RING stages 4', 'DMA_RING', 'NINE_TAP_BF16', 'NINE_TAP_F32PS',
                   'TILE256_F32']
 REQUIRED_WGRAD = ['%s acc%d splits%s' % (fam, acc, sp) for fam in WGRAD_FAMILIES for acc in (0, 1) for sp in ('1', '>1')]
-REQUIRED = REQUIRED_FWD_DGRAD + REQUIRED_WGRAD
+# K-extended data gradient (EXT = true: 128-row tile in both storage types, the 256 x 256 tile in bf16; plain and with the fused reduce)
+# and the sparse store / accumulate of the 1x1 stride-2 shortcut (accumulate 3 in both storage types, 2 in fp32 only)
+REQUIRED_EXT = ['EXT TILE%s %s%s' % (bm, st, r) for (bm, st) in (('128', 'f32'), ('128', 'bf16'), ('256', 'bf16')) for r in ('', ' reduce')]
+REQUIRED_SPARSE = ['SPARSE acc3 f32', 'SPARSE acc3 bf16', 'SPARSE acc2 f32', 'SPARSE acc2 f32 reduce']
+REQUIRED = REQUIRED_FWD_DGRAD + REQUIRED_WGRAD + REQUIRED_EXT + REQUIRED_SPARSE
 
 
 def check_record(c, rec):
@@ -814,6 +890,51 @@ def build_cases():
     add('wgrad3_blocks8', 'wgrad', 'bf16', 3, 20, 30, 128, 128, k=3, env={'SIMCLR_WGRAD3_BLOCKS': '8'}, splits='many', fam=['NINE_TAP_BF16'])
     add('wgrad3_blocks8_f32ps', 'wgrad', 'bf16x3', 3, 30, 20, 64, 128, k=3, psx=True, env={'SIMCLR_WGRAD3_BLOCKS': '8'}, splits='many',
         fam=['NINE_TAP_F32PS'])
+    # ---- K-extended data gradient: dx (+)= dm Wext[:, :Cout]^T + h Wext[:, Cout:]^T + bias, plain and with the fused reduce.  Both channel
+    # counts are multiples of 8 chunks (32 fp32, 64 bf16); fp32 32 + 64 = 96 is no multiple of a 64-element k-tile.
+    EXT_AR = ('bf16', 'exact', 'bf16x3', 'f16x3_3')
+    ext_ch = lambda ar: [(64, 64), (64, 128), (128, 64)] if ar == 'bf16' else [(32, 32), (32, 96), (96, 32), (64, 32), (32, 64)]
+    for ar in EXT_AR:
+        e128 = 'EXT TILE128 ' + ('bf16' if ar == 'bf16' else 'f32')
+        for i, (Cin, Cout) in enumerate(ext_ch(ar)):
+            H, W = NONSQUARE[i % len(NONSQUARE)]
+            t = 'cin%d_cout%d_%s' % (Cin, Cout, ar)
+            add('ext_dgrad_' + t, 'dgrad', ar, 3, H, W, Cin, Cout, ext=True, acc=i % 2, env=NO_WIDE, fam=[e128], args=dict(EXT='true'))
+            add('ext_dgrad_bn_' + t, 'dgrad_bn', ar, 3, W, H, Cin, Cout, ext=True, mode=1 + i % 4, acc=(i + 1) % 2, env=NO_WIDE, fam=[e128 + ' reduce'])
+        Cin, Cout = ext_ch(ar)[1]
+        for i, M in enumerate((1, 127, 128, 129, 255, 256, 257)):
+            V, H, W = ROWS[M]
+            add('ext_rows%d_dgrad_%s' % (M, ar), 'dgrad', ar, V, H, W, Cin, Cout, ext=True, acc=i % 2, env=NO_WIDE, fam=[e128])
+            add('ext_rows%d_dgrad_bn_%s' % (M, ar), 'dgrad_bn', ar, V, H, W, Cout, Cin, ext=True, mode=1 + i % 4, acc=(i // 4) % 2, env=NO_WIDE,
+                fam=[e128 + ' reduce'])
+        Cin, Cout = ext_ch(ar)[0]
+        for mode in (1, 2, 3, 4):
+            for acc in (0, 1):
+                H, W = NONSQUARE[(mode + acc) % len(NONSQUARE)]
+                add('ext_dgrad_bn_m%d_acc%d_%s' % (mode, acc, ar), 'dgrad_bn', ar, 3, H, W, Cin, Cout, ext=True, mode=mode, acc=acc, env=NO_WIDE,
+                    fam=[e128 + ' reduce'])
+    # (the SIMCLR_IGEMM_TILE=256 class: bf16, 256 channels of dx)
+    for i, M in enumerate((255, 256, 257)):
+        V, H, W = ROWS[M]
+        add('ext_rows%d_tile256_dgrad' % M, 'dgrad', 'bf16', V, H, W, 256, 64, ext=True, acc=i % 2, env=T256, fam=['EXT TILE256 bf16'])
+        add('ext_rows%d_tile256_dgrad_bn' % M, 'dgrad_bn', 'bf16', V, H, W, 256, 64, ext=True, mode=2 + i, acc=(i + 1) % 2, env=T256,
+            fam=['EXT TILE256 bf16 reduce'])
+    add('ext_tile256_dgrad_bn_m1', 'dgrad_bn', 'bf16', 3, 6, 10, 256, 128, ext=True, mode=1, env=T256, fam=['EXT TILE256 bf16 reduce'])
+
+    # ---- sparse store (accumulate = 3) and sparse accumulate (2) of the 1x1 stride-2 shortcut: odd and even extents per axis, so that the
+    # last row / column is an even-index pixel in some rows and an odd one in others; dx channels 64 <- 32 and 32 <- 64
+    SPARSE_MAPS = [(3, 7, 10), (3, 10, 7), (3, 1, 9), (3, 9, 1)] + [ROWS[M] for M in (1, 127, 128, 129)]
+    for i, (V, H, W) in enumerate(SPARSE_MAPS):
+        for j, ar in enumerate(('exact', 'bf16x3', 'f16x3_3')):
+            Cin, Cout = ((64, 32), (32, 64))[(i + j) % 2]
+            t = '%dx%dx%d_%s' % (V, H, W, ar)
+            psx = ar == 'f16x3_3'
+            add('sparse_store_' + t, 'dgrad', ar, V, H, W, Cin, Cout, s=2, acc=3, psx=psx, fam=['SPARSE acc3 f32'])
+            add('sparse_acc_' + t, 'dgrad', ar, V, H, W, Cin, Cout, acc=2, psx=psx, fam=['SPARSE acc2 f32'])
+            add('sparse_acc_bn_' + t, 'dgrad_bn', ar, V, H, W, Cin, Cout, acc=2, mode=2 if (i + j) % 2 else 4, psx=psx, fam=['SPARSE acc2 f32 reduce'])
+            add('sparse_acc_bn2_' + t, 'dgrad_bn', ar, V, H, W, Cout, Cin, acc=2, mode=4 if (i + j) % 2 else 2, fam=['SPARSE acc2 f32 reduce'])
+        add('sparse_store_%dx%dx%d_bf16' % (V, H, W), 'dgrad', 'bf16', V, H, W, (64, 32)[i % 2], 64, s=2, acc=3, fam=['SPARSE acc3 bf16'])
+
     ids = [c.id for c in rows]
     assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1]
     return rows

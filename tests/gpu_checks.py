@@ -3298,7 +3298,8 @@ def _conv_lattice_weights(c, L):
 
 def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
     """One row of tests/conv_reference.CASES through the C ABI.  Every output lives in a guarded buffer that starts from a sentinel (or from
-    `prev` when accumulating); after each launch the recorded instantiation must name the family and template arguments the row claims.
+    `prev` when accumulating, from conv_reference.SENTINEL in the sparse rows: accumulate = 3 must leave it at the pixels without a tap,
+    accumulate = 2 -- run on what such a store left -- must not let it leak); after each launch the recorded instantiation must name the family and template arguments the row claims.
     Rows with statistics run once per slot count: simclr_conv2d_stats_slots + 5 (own-slot stores, the five spare slots stay zero), then
     1 and 3 (the float-atomics branch: same totals)."""
     from tests import conv_reference as cr
@@ -3326,13 +3327,24 @@ def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
             P['w'] = ptr(wdev)
             if c.op != 'dgrad' and c.op != 'dgrad_bn':
                 P['x'] = dev('x', T)
-            if c.op in ('dgrad', 'dgrad_bn', 'wgrad'):
+            if c.ext:                                             # K-extended: L['dy'] = [dm | h], two operand streams
+                for n, t in (('dy', L['dy'][..., :c.Cout]), ('h', L['dy'][..., c.Cout:])):
+                    t = _dev(t, T)
+                    keep.append(t)
+                    P[n] = ptr(t)
+                P['bias'] = dev('bias', f32)
+            elif c.op in ('dgrad', 'dgrad_bn', 'wgrad'):
                 if c.psx:
                     t = ps_encode(L['dy'].float()).to(DEV)
                     keep.append(t)
                     P['dy'] = ptr(t)
                 else:
                     P['dy'] = dev('dy', T)
+            if c.acc == 2:                                        # the operands of the sparse store that comes first
+                t = ps_encode(L['dy1'].float()).to(DEV) if c.psx else _dev(L['dy1'], T)
+                w1 = _dev(L['w1'].permute(2, 0, 1, 3).reshape(c.Cin, -1), T)
+                keep += [t, w1]
+                P['dy1'], P['w1'] = ptr(t), ptr(w1)
             if c.op == 'dgrad_bn':
                 for n in ('scale', 'shift', 'mean', 'rstd'):
                     P[n] = dev(n, f32)
@@ -3368,7 +3380,7 @@ def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
                     nbytes = lib().conv2d_wgrad_workspace_bytes(c.V, c.OH, c.OW, c.Cin, c.Cout, c.k, c.k, DT_BF16 if T == torch.bfloat16 else DT_F32)
                     out('ws', ((nbytes + 3) // 4,), f32, 99.0)
                 elif dgrad:
-                    got['out'] = out('dx', (c.V, c.H, c.W, c.Cin), T, L['prev'] if c.acc else 99.0)
+                    got['out'] = out('dx', (c.V, c.H, c.W, c.Cin), T, L['prev'] if c.acc == 1 else cr.SENTINEL if c.acc else 99.0)
                 elif c.store:
                     got['out'] = out('y', (c.V, c.OH, c.OW, c.Cout), T, 99.0)
                 if c.op == 'fwd_bn_apply' and c.bits:
@@ -3377,6 +3389,8 @@ def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
                     got['pivot'] = out('pivot', (c.Cout,), f32, 99.0)
                 if nslot is not None:
                     part = out('stats', (nslot, 2, ch), f32, 0.0)
+                if c.acc == 2:         # dx: the sentinel everywhere, then the even pixels from the sparse store (accumulate = 3)
+                    cr.launch_first(lib(), c, P, stream=ops._s())
                 cr.launch(lib(), c, P, nslot=nslot or 0, stream=ops._s())
                 rec = lib().conv2d_last_instantiation().decode()
                 parts = lib().conv2d_last_split_parts()
@@ -3407,3 +3421,192 @@ def check_conv_lattice(c, slot_counts=('spare', 1, 3)):
     finally:
         ops.set_f32_matmul('exact')
     return res
+
+
+# ------------------------------------------------------------------ stem chain and Gram chain on exact lattices (tests/stem_gram_reference.py)
+def _refused(fn, *needles):
+    """fn() must be refused by an argument check: rc != 0 (SimclrHipError) and simclr_last_error names the reason."""
+    from simclr_amd._lib import SimclrHipError
+    try:
+        fn()
+    except SimclrHipError as e:
+        msg = str(e) + ' ' + lib().last_error()
+        return all(n in msg for n in needles)
+    return False
+
+
+def check_stem_lattice(c, slot_counts=('spare', 1, 3)):
+    """One row of stem_gram_reference.STEM_CASES through the C ABI, every comparison at tolerance zero and every output in a guarded
+    buffer: simclr_pack_views (fp32: and simclr_pack_views_ps, simclr_presplit_packed), simclr_prep_weights mode 2, simclr_stem_conv_fwd with
+    statistics at simclr_stem_stats_slots + 5 / 1 / 3 slots, the weight gradient through simclr_conv2d_wgrad (pixpitch 4) +
+    simclr_unpack_stem_dw and, where supported, through simclr_stem_wgrad_ps -- each with accumulate 0 and 1.  A Cout the argument checks
+    refuse is asserted to be refused."""
+    from tests import stem_gram_reference as sg
+    from tests import conv_reference as cr
+    L, want = sg.stem_reference(c)
+    f32, T = torch.float32, c.dtype
+    geo = c.geo
+    dtc = DT_BF16 if T == torch.bfloat16 else DT_F32
+    res, guards = [], []
+    ptr = lambda t: ops._pp(t)
+    tag = 'stem_lattice ' + c.id
+
+    def out(shape, dtype, start):
+        fill = start if torch.is_tensor(start) else torch.full(tuple(shape), float(start), dtype=torch.float64)
+        v, chk = _guarded(tuple(shape), dtype, fill=fill.to(dtype).to(DEV))
+        guards.append(chk)
+        return v
+
+    ops.set_f32_matmul(c.arith if T == f32 else 'exact')
+    try:
+        with _switches(c.env):
+            img = _dev(L['img'], f32)
+            xp = out((c.V, c.HP, c.WP, 4), T, 99.0)
+            lib().pack_views(ptr(img), ptr(xp), c.b, c.H, c.W, c.views, c.HP, c.WP, geo['pad'], dtc, ops._s())
+            res.append(_bitwise(tag + ' xp', xp, want['xp']))
+            xq = None
+            if T == f32:
+                xp2, xq2, xq = (out((c.V, c.HP, c.WP, 4), f32, 99.0) for _ in range(3))
+                lib().pack_views_ps(ptr(img), ptr(xp2), ptr(xq2), c.b, c.H, c.W, c.views, c.HP, c.WP, geo['pad'], ops._s())
+                lib().presplit_packed(ptr(xp), ptr(xq), c.V * c.HP * c.WP, ops._s())
+                torch.cuda.synchronize()
+                hi, lo = sg.xq_ref(want['xp'])
+                raw = xq.view(torch.int16).view(torch.bfloat16).reshape(-1, 8).float().cpu()
+                raw2 = xq2.view(torch.int16).view(torch.bfloat16).reshape(-1, 8).float().cpu()
+                res += [_bitwise(tag + ' xp (pack_views_ps)', xp2, want['xp']),
+                        _bitwise(tag + ' xq hi', raw[:, :4], hi.reshape(-1, 4)), _bitwise(tag + ' xq lo', raw[:, 4:], lo.reshape(-1, 4)),
+                        _bitwise(tag + ' xq hi (pack_views_ps)', raw2[:, :4], hi.reshape(-1, 4)),
+                        _bitwise(tag + ' xq lo (pack_views_ps)', raw2[:, 4:], lo.reshape(-1, 4))]
+            w32 = _dev(L['w'], f32)
+            w_s = out((c.Cout, c.KP), T, 99.0)
+            lib().prep_weights(ptr(w32), ptr(w_s), c.k, c.k, 3, c.Cout, 2, geo['KHP'], geo['KWP'], 0, 0, dtc, ops._s())
+            res.append(_bitwise(tag + ' w_s', w_s, want['ws']))
+            fw = dtc | cr.terms_field(c.tf)
+            fwd_args = lambda y, st, n: (ptr(xp), ptr(w_s), ptr(y), ptr(st), n, c.V, c.HP, c.WP, c.OH, c.OW, c.Cout, geo['KHP'], geo['KWP'],
+                                         c.s, fw, ops._s())
+            if not c.fwd_ok:
+                y, st = out((c.M, c.Cout), T, 99.0), out((1, 2, c.Cout), f32, 0.0)
+                ok = _refused(lambda: lib().stem_conv_fwd(*fwd_args(y, st, 1)), 'stem_conv_fwd', 'Cout=%d' % c.Cout)
+                res.append(_entry(tag + ' forward refused by the argument check', 0.0 if ok else 1.0, 0.0))
+                res.append(_bitwise(tag + ' refused forward wrote nothing', y, torch.full((c.M, c.Cout), 99.0).to(T)))
+            else:
+                own = lib().stem_stats_slots(c.M)
+                assert own == sg.stem_inst(c)[1][0]
+                for nslot in [own + 5 if s == 'spare' else s for s in slot_counts]:
+                    t2 = '%s nslot=%d' % (tag, nslot)
+                    y, st = out((c.V, c.OH, c.OW, c.Cout), T, 99.0), out((nslot, 2, c.Cout), f32, 0.0)
+                    lib().stem_conv_fwd(*fwd_args(y, st, nslot))
+                    sums = torch.empty(2, c.Cout, device=DEV, dtype=torch.float64)
+                    lib().bn_reduce_slots(ptr(st), nslot, c.Cout, ptr(sums), ops._s())
+                    torch.cuda.synchronize()
+                    res += [_bitwise(t2 + ' y', y, want['y']), _bitwise(t2 + ' sum', sums[0], want['s1']),
+                            _bitwise(t2 + ' sum of squares', sums[1], want['s2'])]
+                    if nslot > 3:
+                        res.append(_bitwise(t2 + ' spare slots stay zero', st[nslot - 5:], torch.zeros(5, 2, c.Cout)))
+            # ---- weight gradient
+            dy = _dev(L['dy'], T)
+            bw = dtc | cr.terms_field(c.tb)
+            nbytes = lib().conv2d_wgrad_workspace_bytes(c.V, c.OH, c.OW, 32, c.Cout, geo['KHP'], 1, dtc)
+            ws = out(((nbytes + 3) // 4,), f32, 99.0)
+            wg_args = lambda kn, acc: (ptr(xp), ptr(dy), ptr(kn), acc, ptr(ws), c.V, c.HP, c.WP, 32, 4, c.OH, c.OW, c.Cout, geo['KHP'], 1, c.s, 0,
+                                       bw, ops._s())
+            unpack = lambda kn, dst, acc: lib().unpack_stem_dw(ptr(kn), ptr(dst), c.k, c.k, 3, c.Cout, geo['KWP'], acc, ops._s())
+            if not c.wgrad_ok:
+                kn = out((c.KP, c.Cout), f32, 99.0)
+                ok = _refused(lambda: lib().conv2d_wgrad(*wg_args(kn, 0)), 'conv2d_wgrad', 'Cout=%d' % c.Cout)
+                res.append(_entry(tag + ' weight gradient refused by the argument check', 0.0 if ok else 1.0, 0.0))
+                res.append(_bitwise(tag + ' refused weight gradient wrote nothing', kn, torch.full((c.KP, c.Cout), 99.0)))
+            else:
+                kn0, kn1 = out((c.KP, c.Cout), f32, 99.0), out((c.KP, c.Cout), f32, L['prev_kn'])
+                d0, d1, d2 = out((c.k, c.k, 3, c.Cout), f32, 99.0), out((c.k, c.k, 3, c.Cout), f32, L['prev']), out((c.k, c.k, 3, c.Cout), f32, 99.0)
+                lib().conv2d_wgrad(*wg_args(kn0, 0))
+                rec = lib().conv2d_last_instantiation().decode()
+                lib().conv2d_wgrad(*wg_args(kn1, 1))
+                unpack(kn0, d0, 0)
+                unpack(kn0, d1, 1)
+                unpack(kn1, d2, 0)
+                torch.cuda.synchronize()
+                sg.check_stem_records(c, rec, None)
+                res += [_bitwise(tag + ' dw', d0, want['dw']), _bitwise(tag + ' dw, unpack accumulates', d1, want['dw_acc']),
+                        _bitwise(tag + ' dw, wgrad accumulates', d2, want['dw_kn_acc'])]
+            if c.ps_ok:
+                assert lib().stem_wgrad_ps_supported(geo['KHP'], geo['KWP'], c.s, c.Cout) == 1
+                dyp = ps_encode(L['dy'].float()).to(DEV)
+                nb = lib().stem_wgrad_ps_workspace_bytes(c.V, c.OH, c.OW, geo['KHP'])
+                wsp = out(((nb + 3) // 4,), f32, 99.0)
+                kn0, kn1 = out((c.KP, c.Cout), f32, 99.0), out((c.KP, c.Cout), f32, L['prev_kn'])
+                d0, d1 = out((c.k, c.k, 3, c.Cout), f32, 99.0), out((c.k, c.k, 3, c.Cout), f32, L['prev'])
+                ps_args = lambda kn, acc: (ptr(xq), ptr(dyp), ptr(kn), acc, ptr(wsp), c.V, c.HP, c.WP, c.OH, c.OW, c.Cout, geo['KHP'], geo['KWP'],
+                                           c.s, ops._s())
+                lib().stem_wgrad_ps(*ps_args(kn0, 0))
+                rec = lib().conv2d_last_instantiation().decode()
+                lib().stem_wgrad_ps(*ps_args(kn1, 1))
+                unpack(kn0, d0, 0)
+                unpack(kn1, d1, 1)
+                torch.cuda.synchronize()
+                sg.check_stem_records(c, None, rec)
+                res += [_bitwise(tag + ' dw (pre-split)', d0, want['dw']),
+                        _bitwise(tag + ' dw (pre-split), both accumulate', d1, want['dw_both'])]
+            elif c.dtype == f32 and c.Cout != 64:
+                ok = _refused(lambda: lib().stem_wgrad_ps(None, None, None, 0, None, c.V, c.HP, c.WP, c.OH, c.OW, c.Cout, geo['KHP'], geo['KWP'],
+                                                          c.s, ops._s()), 'stem_wgrad_ps', 'Cout=%d' % c.Cout)
+                res.append(_entry(tag + ' pre-split weight gradient refused by the argument check', 0.0 if ok else 1.0, 0.0))
+            torch.cuda.synchronize()
+            res.append(_guards(tag, *guards))
+    finally:
+        ops.set_f32_matmul('exact')
+    return res
+
+
+def check_gram_lattice(c):
+    """One row of stem_gram_reference.GRAM_CASES: simclr_conv2d_gram (workspace of exactly simclr_conv2d_gram_workspace_bytes) ->
+    simclr_small_gemm_nt_f32 -> simclr_bn_sums_from_gram (the cs32 and the cs64 entry), each output guarded and compared bitwise."""
+    from tests import stem_gram_reference as sg
+    from tests import conv_reference as cr
+    br = sg.gram_br(lib(), c.K, c.dtype)
+    M = sg.gram_rows(c, br)
+    L, want = sg.gram_reference(c, M)
+    f32, T, K, N = torch.float32, c.dtype, c.K, c.N
+    dtc = DT_BF16 if T == torch.bfloat16 else DT_F32
+    guards = []
+    tag = 'gram_lattice %s M=%d' % (c.id, M)
+
+    def out(shape, dtype):
+        v, chk = _guarded(tuple(shape), dtype, fill=torch.full(tuple(shape), 99.0, dtype=dtype, device=DEV))
+        guards.append(chk)
+        return v
+
+    h = _dev(L['h'], T)
+    o = out((K * K + K,), f32)
+    nbytes = lib().conv2d_gram_workspace_bytes(M, K, dtc)
+    assert nbytes % 4 == 0
+    ws = out((nbytes // 4,), f32)
+    lib().conv2d_gram(ops._p(h), ops._p(o), ops._p(ws), M, K, dtc | (cr.terms_field(c.tf) if T == f32 else 0), ops._s())
+    rec = lib().conv2d_last_instantiation().decode()
+    sg.check_gram_record(c, rec, br, M)
+    wt = _dev(L['w'].t(), f32)                                       # [N][K]: the B operand of A B^T
+    wkn = _dev(L['w'], f32)
+    G = o[:K * K].view(K, K).contiguous()
+    gw = out((K, N), f32)
+    lib().small_gemm_nt_f32(ops._p(G), ops._p(wt), ops._p(gw), K, N, K, ops._s())
+    s32, s64 = out((2, N), torch.float64), out((2, N), torch.float64)
+    cs32 = o[K * K:].contiguous()
+    cs64 = cs32.double()
+    lib().bn_sums_from_gram(ops._p(gw), ops._p(wkn), None, ops._p(cs32), K, N, ops._p(s32), ops._s())
+    lib().bn_sums_from_gram(ops._p(gw), ops._p(wkn), ops._p(cs64), None, K, N, ops._p(s64), ops._s())
+    torch.cuda.synchronize()
+    return [_bitwise(tag + ' gram matrix', o[:K * K].view(K, K), want['G']), _bitwise(tag + ' column sums', o[K * K:], want['cs']),
+            _bitwise(tag + ' (h^T h) W', gw, want['GW']), _bitwise(tag + ' sums (cs32)', s32, want['sums']),
+            _bitwise(tag + ' sums (cs64)', s64, want['sums']), _guards(tag, *guards)]
+
+
+def check_small_gemm_lattice(c):
+    """simclr_small_gemm_nt_f32 on integers, both tile branches, bitwise."""
+    from tests import stem_gram_reference as sg
+    L, want = sg.gemm_reference(c)
+    a, b = _dev(L['a'], torch.float32), _dev(L['b'], torch.float32)
+    v, chk = _guarded((c.M, c.N), torch.float32, fill=torch.full((c.M, c.N), 99.0, device=DEV))
+    lib().small_gemm_nt_f32(ops._p(a), ops._p(b), ops._p(v), c.M, c.N, c.K, ops._s())
+    torch.cuda.synchronize()
+    tag = 'small_gemm_lattice ' + c.id
+    return [_bitwise(tag, v, want['c']), _guards(tag, chk)]

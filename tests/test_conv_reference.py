@@ -159,8 +159,8 @@ def _mutants(c, L, want):
             o = R.round_to(R.fwd_bn_apply_ref(m, Lm, o), c.dtype)
         out.append(('IH / IW swapped', (not same_shape) or not torch.equal(o.reshape(-1), want['out'].reshape(-1))))
     if c.op == 'dgrad_bn':
-        dx = R.conv_dgrad_ref(L['dy'], L['w'], c.k, c.s, c.H, c.W)
-        if c.acc:
+        dx = R.dgrad_of(c, L)
+        if c.adds:
             dx = dx + L['prev']
         idx = tuple(dx.nonzero()[0].tolist())
         mask = R.mask_of(c, L).clone()

@@ -25,8 +25,19 @@ the eight-phase tile; every weight-gradient family with accumulate 0 / 1 and one
 outputs exceed 8 significant bits (128-wide tile: statistics of the exact accumulators; SIMCLR_IGEMM_TILE=256: of the bf16-rounded
 outputs; y = the exact value rounded once in both) plus the same on the eight-phase tile.
 
-Left out: the TILE256_BF16 weight gradient (no forcing switch: it needs M >= 150000), the stem, the K-extended launches, the Gram launch
-and the sparse accumulate (2, 3).  The non-persistent fallback kernel adds its statistics with float atomics into slot (M-tile % nslot)
+`ext` rows: the K-extended data gradient simclr_conv2d_dgrad_ext (accumulate 0 / 1) and simclr_conv2d_dgrad_bn_ext (the four mask modes,
+store and accumulate, statistics at the three slot counts) -- dm and h on the lattice, w_ext in {-1, 0, 1} thinned by Cout + Cin, an
+integer bias; Cin = / < / > Cout, fp32 32 + 64 channels (no multiple of a 64-element k-tile), rows 1, 127 / 128 / 129, 255 / 256 / 257, the
+128-row tile in both storage types and the SIMCLR_IGEMM_TILE=256 class in bf16; arithmetics bf16, exact, bf16x3, f16x3_3.
+`sparse` rows: the 1x1 stride-2 data gradient with accumulate = 3 into a dx full of a finite sentinel (12345: even (row, column) pixels =
+the reference, every other element still the sentinel; fp32 and bf16), then a stride-1 data gradient (plain, and with the fused reduce
+in mask modes 2 and 4) with accumulate = 2 into what that call left: second + first at the even pixels, second alone elsewhere -- a
+leaked sentinel is a wrong number, not a masked compare; maps 7x10, 10x7, 1x9, 9x1 and rows 1, 127 / 128 / 129, channels 32 <-> 64.
+The stem chain and the Gram chain have their own module, tests/test_gpu_stem_gram_lattice.py.
+
+Left out: the TILE256_BF16 weight gradient (no forcing switch: it needs M >= 150000); the persistent-loop tail of the stem forward (more
+than 2048 M-tiles need 306 456 rows: tests/test_gpu_kernels.py covers it with Gaussian inputs); the K-extended launch on a pre-split dm
+(plan_igemm has no such kernel and refuses it).  The non-persistent fallback kernel adds its statistics with float atomics into slot (M-tile % nslot)
 whatever the slot count, so "spare slots stay zero" holds for it only because its rows here have a single M-tile."""
 import pytest
 

@@ -119,6 +119,11 @@ def main():
     for c in cr.CASES:
         if '--quick' not in sys.argv or c.V * c.H * c.W * max(c.Cin, c.Cout) <= 2 ** 21:
             run(gc.check_conv_lattice, c)
+    # the stem chain and the Gram chain on the same lattices (tests/test_gpu_stem_gram_lattice.py)
+    from tests import stem_gram_reference as sg
+    for check, cases in ((gc.check_stem_lattice, sg.STEM_CASES), (gc.check_gram_lattice, sg.GRAM_CASES), (gc.check_small_gemm_lattice, sg.GEMM_CASES)):
+        for c in cases:
+            run(check, c)
     # augmentation and blur kernels stage by stage (tests/test_gpu_augment.py)
     for views in (1, 2, 3):
         run(gc.check_augment_identity, 15, 17, views)
