@@ -278,6 +278,23 @@ int simclr_vicreg_bwd(const float* h_all, const float* xc_all, const double* sta
                       float std_coeff, float cov_coeff, float gamma, float grad_scale, void* workspace, float* dh_local,
                       simclr_stream_t stream);
 
+/* ---- label-free representation diagnostics, csrc/repr.hip ----
+ * z_all [2N, D] fp32 = the l2-normalised projections of the gathered global batch, view a in rows [0, N), view b in rows [N, 2N).
+ * Per view v: xc = z_v - colmean(z_v), G = xc xc^T ([N, N], never written), r_a = G_aa.  out4 = {align, uniform, std, rank}:
+ *   align   = (1 / N) sum_i |z_a,i - z_b,i|^2                                                    in [0, 4]
+ *   uniform = (1/2) sum_v log((1 / (N (N-1))) sum_{a != b} exp(-t max(r_a + r_b - 2 G_ab, 0)))   in [-4t, 0]; 0 = one point
+ *   std     = (1/2) sum_v sqrt(D) (1 / D) sum_k sqrt(sum_a xc_ak^2 / (N-1))                      about 1 healthy, 0 collapsed
+ *   rank    = (1/2) sum_v (sum_a G_aa)^2 / sum_ab G_ab^2 (the participation ratio of the covariance spectrum, in [1, min(D, N-1)]);
+ *             a view with sum_a G_aa / (N-1) <= 1e-12 counts 0.
+ * D a multiple of 64 in [64, 8192], 2 <= N <= 65536, 0 < t <= 16.  fp32 storage, exact fp32-input MFMA, every sum in double in a fixed
+ * order, no atomics: bitwise run-to-run deterministic and identical on every replica that holds the same block.  Reads z_all only;
+ * writes the workspace (16-byte aligned, simclr_repr_workspace_bytes) and out4. */
+size_t simclr_repr_workspace_bytes(int N, int D);   /* 0 for a shape the kernels refuse */
+/* Edge of the tile of G a workgroup of the pairs launch owns: 128 where both views' tiles give >= 256 workgroups (N >= 1409), else 64.
+ * 0 for a refused shape. */
+int simclr_repr_tile_edge(int N, int D);
+int simclr_repr_stats(const float* z_all, int N, int D, float t, void* ws, float* out4, simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

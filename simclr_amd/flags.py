@@ -206,6 +206,14 @@ _DEFS = [
                                        'the threshold inverts).  In [0, 1].'),
     ('color_jitter_components', None, str, "MI355X build: 'b,c,s,h', the brightness, contrast, saturation and hue ranges per unit of "
                                            "--color_jitter_strength; overrides the recipe's.  Each >= 0, hue <= 0.5."),
+    # label-free representation diagnostics (metrics.representation_stats, csrc/repr.hip): the same four numbers under every loss
+    ('repr_metrics_steps', 0, int, 'MI355X build: every K-th pretraining step (those with (step + 1) % K == 0) measures alignment, '
+                                   'uniformity, the per-feature standard deviation and the participation ratio of the l2-normalised online '
+                                   'projection over the global batch and logs train/repr_align, train/repr_uniform, train/repr_std and '
+                                   'train/repr_rank.  0 = off (default).  K > 0 needs a loss width that is a multiple of 64 in [64, 8192] and '
+                                   '2 <= --train_batch_size <= 65536.  Read-only: the weights are bitwise those of K = 0.  Ignored by '
+                                   '--train_mode=finetune and --mode=eval.'),
+    ('repr_uniform_t', 2.0, float, 'MI355X build: scale t of the uniformity log mean exp(-t |z_a - z_b|^2).  In (0, 16].'),
 ]
 
 

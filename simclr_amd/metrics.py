@@ -134,6 +134,53 @@ def update_finetune_metrics_train(supervised_loss_metric, supervised_acc_metric,
     supervised_acc_metric.update_state(acc)
 
 
+REPR_METRICS = (('train/repr_align', 'align'), ('train/repr_uniform', 'uniform'), ('train/repr_std', 'std'), ('train/repr_rank', 'rank'))
+
+
+class ReprStats:
+    """What representation_stats returns: `values` fp32 [4] = {align, uniform, std, rank} on the device, the four as one-element
+    views of it, `normalized` [2n, D] (the l2-normalised local block) and `gathered` [2N, D] (the block the kernels read)."""
+
+    def __init__(self, values, normalized, gathered):
+        self.values, self.normalized, self.gathered = values, normalized, gathered
+        self.align, self.uniform, self.std, self.rank = (values[i:i + 1] for i in range(4))
+
+
+def representation_stats(hidden, strategy=None, t=2.0):
+    """Label-free diagnostics of an embedding batch (csrc/repr.hip), comparable across every pretraining loss.
+    hidden [2n, D]: this replica's projections, view a in rows [0, n), view b in rows [n, 2n); always l2-normalised here.  The
+    normalised block is gathered over the replicas (view-major, comm.gather_hidden) and every replica runs the kernels on the whole
+    [2N, D] block: no collective beyond the gather, and the four values are bitwise the same everywhere.
+      align   = mean_i |z_a,i - z_b,i|^2                                       [0, 4], 0 = the views agree
+      uniform = mean over the views of log mean_{a != b} exp(-t |z_a - z_b|^2)   [-4t, 0], 0 = one point
+      std     = sqrt(D) x the mean per-feature standard deviation              about 1 healthy, 0 collapsed
+      rank    = the participation ratio of the covariance spectrum             [1, min(D, N-1)], 0 for a collapsed view
+    Takes no gradient, keeps no state and writes nothing it was given."""
+    return start_representation_stats(hidden, strategy, t)()
+
+
+def start_representation_stats(hidden, strategy=None, t=2.0):
+    """representation_stats in two halves: checks, normalises and starts the gather now; the zero-argument function it returns waits
+    for the gather, runs the kernels and returns the handle (the training step puts the loss between the two)."""
+    from . import ops
+    from .comm import gather_hidden
+    if not torch.is_tensor(hidden) or hidden.dim() != 2 or hidden.shape[0] < 2 or hidden.shape[0] % 2 or hidden.dtype != torch.float32:
+        raise ValueError('representation_stats: hidden holds both views, float32 [2n, D] with n >= 1 (got %s %s)'
+                         % (tuple(getattr(hidden, 'shape', ())), getattr(hidden, 'dtype', type(hidden))))
+    if not ops.repr_dim_ok(hidden.shape[1]):
+        raise ValueError('representation_stats supports widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (ops.REPR_DIM_STEP, ops.REPR_MIN_DIM, ops.REPR_MAX_DIM, hidden.shape[1]))
+    if not ops.repr_t_ok(t):
+        raise ValueError('representation_stats: t must lie in (0, %g] (got %r)' % (ops.REPR_MAX_T, t))
+    z, _ = ops.l2norm_fwd(hidden.detach().contiguous())
+    wait = gather_hidden(z, strategy, async_op=True)
+
+    def finish():
+        z_all = wait()
+        return ReprStats(ops.repr_stats(z_all, t), z, z_all)
+    return finish
+
+
 class JsonlSummaryWriter:
     """Stand-in for tf.summary.create_file_writer(model_dir) (tf2/run.py:356, :526): every scalar becomes one JSON
     line {"step": s, "tag": name, "value": v} in <model_dir>/summaries.jsonl (TensorBoard-importable, grep-able).

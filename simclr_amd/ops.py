@@ -714,6 +714,64 @@ def vicreg_bwd(h_all, xc_all, stats, n, rank, sim_coeff, std_coeff, cov_coeff, g
     return dh
 
 
+# ---------------------------------------------------------------- representation diagnostics (csrc/repr.hip)
+REPR_DIM_STEP, REPR_MIN_DIM, REPR_MAX_DIM = 64, 64, 8192   # widths the diagnostics take: multiples of 64 in [64, 8192]
+REPR_MIN_ROWS, REPR_MAX_ROWS = 2, 65536                    # rows per view (the global batch)
+REPR_MAX_T = 16.0
+
+
+def repr_dim_ok(D):
+    return REPR_MIN_DIM <= D <= REPR_MAX_DIM and D % REPR_DIM_STEP == 0
+
+
+def repr_t_ok(t):
+    """The scale t of the uniformity: 0 < t <= 16 (NaN fails the comparison)."""
+    return 0.0 < float(t) <= REPR_MAX_T
+
+
+def _repr_check_shape(N, D):
+    if not repr_dim_ok(D):
+        raise ValueError('repr_stats supports widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (REPR_DIM_STEP, REPR_MIN_DIM, REPR_MAX_DIM, D))
+    if not REPR_MIN_ROWS <= N <= REPR_MAX_ROWS:
+        raise ValueError('repr_stats needs %d <= N <= %d rows per view (got %d)' % (REPR_MIN_ROWS, REPR_MAX_ROWS, N))
+
+
+def repr_workspace(N, D, device):
+    N, D = int(N), int(D)
+    _repr_check_shape(N, D)
+    nbytes = lib().repr_workspace_bytes(N, D)
+    assert nbytes > 0
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def repr_tile_edge(N, D):
+    """Edge (64 or 128) of the Gram tile a workgroup of repr_stats' pairs launch owns at this shape (0 for a refused shape)."""
+    return int(lib().repr_tile_edge(int(N), int(D)))
+
+
+def repr_stats(z_all, t=2.0, ws=None):
+    """z_all [2N, D] fp32 = [view-a rows; view-b rows] of the l2-normalised global batch -> fp32 [4] = {align, uniform, std, rank}
+    (include/simclr_hip.h).  Reads z_all only; `ws` (repr_workspace) is scratch, a fresh one by default."""
+    if not torch.is_tensor(z_all) or z_all.dtype != torch.float32 or z_all.dim() != 2 or z_all.shape[0] % 2:
+        raise ValueError('repr_stats: need a float32 [2N, D] block (got %s %s)'
+                         % (tuple(getattr(z_all, 'shape', ())), getattr(z_all, 'dtype', type(z_all))))
+    N, D = z_all.shape[0] // 2, z_all.shape[1]
+    _repr_check_shape(N, D)
+    z_all = z_all.contiguous()
+    if not repr_t_ok(t):
+        raise ValueError('repr_stats: t must lie in (0, %g] (got %r)' % (REPR_MAX_T, t))
+    if ws is None:
+        ws = repr_workspace(N, D, z_all.device)
+    elif ws.numel() * ws.element_size() < lib().repr_workspace_bytes(N, D) or ws.data_ptr() % 16:
+        raise ValueError('repr_stats: the workspace holds %d bytes at %#x; N = %d, D = %d needs %d bytes, 16-byte aligned'
+                         % (ws.numel() * ws.element_size(), ws.data_ptr(), N, D, lib().repr_workspace_bytes(N, D)))
+    out = torch.empty(4, device=z_all.device, dtype=torch.float32)
+    _launch('repr_stats', 4.0 * N * N * D, 4.0 * 2 * N * D,
+            lambda: lib().repr_stats(_p(z_all), N, D, float(t), _p(ws), _p(out), _s()), impl_bytes=4.0 * 8 * N * D)
+    return out
+
+
 # ---------------------------------------------------------------- BYOL (csrc/byol.hip)
 BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
 

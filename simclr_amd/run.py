@@ -133,12 +133,44 @@ def check_contrastive_loss_flags():
     return spec is loss_lib.LOSSES['generalized']
 
 
+def repr_metrics_steps():
+    """K of --repr_metrics_steps in a pretraining run (0: off); train_mode=finetune and --mode=eval ignore the flag.  The one reader of
+    the flag: check_repr_flags and build_metrics call it."""
+    if FLAGS.train_mode != 'pretrain' or FLAGS.mode == 'eval':
+        return None
+    return FLAGS.repr_metrics_steps
+
+
+def check_repr_flags():
+    """--repr_metrics_steps / --repr_uniform_t (metrics.representation_stats), checked before any device work.  Returns K."""
+    K = repr_metrics_steps()
+    if K is None:
+        return 0
+    if K < 0:
+        raise ValueError('--repr_metrics_steps must be >= 0 (got %r): 0 is off, K measures every K-th step' % (K,))
+    if not ops.repr_t_ok(FLAGS.repr_uniform_t):
+        raise ValueError('--repr_uniform_t must lie in (0, %g] (got %r)' % (ops.REPR_MAX_T, FLAGS.repr_uniform_t))
+    if K > 0:
+        width = model_lib.projection_width()
+        if not ops.repr_dim_ok(width):
+            raise ValueError('--repr_metrics_steps=%d needs a loss width that is a multiple of %d in [%d, %d] (got %d from '
+                             'proj_head_mode=%r, proj_out_dim=%d): the diagnostics kernels take those widths only'
+                             % (K, ops.REPR_DIM_STEP, ops.REPR_MIN_DIM, ops.REPR_MAX_DIM, width, FLAGS.proj_head_mode, FLAGS.proj_out_dim))
+        if not ops.REPR_MIN_ROWS <= FLAGS.train_batch_size <= ops.REPR_MAX_ROWS:
+            raise ValueError('--repr_metrics_steps=%d needs %d <= --train_batch_size <= %d (got %r): the pairwise terms run over the '
+                             'global batch' % (K, ops.REPR_MIN_ROWS, ops.REPR_MAX_ROWS, FLAGS.train_batch_size))
+    return int(K)
+
+
 def build_metrics():
-    """The metric set of tf2/run.py:534-549; the pretraining names are those of the loss's row of pretrain_losses.LOSSES."""
+    """The metric set of tf2/run.py:534-549; the pretraining names are those of the loss's row of pretrain_losses.LOSSES, and with
+    --repr_metrics_steps > 0 the four of metrics.REPR_METRICS."""
     names = ['train/weight_decay', 'train/total_loss']
     spec = loss_lib.active()
     if spec is not None:
         names += [n for n, _ in spec.metrics + spec.logits_metrics]
+        if (repr_metrics_steps() or 0) > 0:
+            names += [n for n, _ in metrics.REPR_METRICS]
     if FLAGS.train_mode == 'finetune' and getattr(FLAGS, 'teacher_checkpoint', None):
         names += ['train/distill_loss', 'train/distill_agreement']       # distillation: the teacher replaces the labels
     elif FLAGS.train_mode == 'finetune' or FLAGS.lineareval_while_pretraining:
@@ -289,6 +321,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     blurs the local views at their own size, forwards them in training mode (BatchNorm on statistics of its own), add_swav_local_loss
     against pass A's codes, backward without the supervised head; the saved buffer is added back, the gradients are all-reduced ONCE
     (after the add: the sum is linear, one reduction is cheaper than two), then one optimizer step.
+    --repr_metrics_steps=K > 0: a step with (step + 1) % K == 0 is measured.  Right after the online forward the projection is
+    normalised into a tensor of its own and its gather starts; after the loss call metrics.representation_stats' kernels run on the
+    gathered block.  Read-only: nothing the step reads is written, and the weights are bitwise those of K = 0.  The four values go
+    through the metric bank on measured steps only, and the handle is returned under `repr_stats` (None on other steps).
     --dino_local_crops=L > 0: the same two passes under --contrastive_loss=dino, pass B's loss being add_dino_local_loss against pass
     A's teacher rows.  The teacher sees the global views only: the target forward, the keys, their mean and the centre are pass A's.
     target.update(step), the wait for the mean and the centre update stay after the optimizer step, that is after pass B, whose
@@ -328,6 +364,7 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
     dropblock = any(p is not None for p in (check_dropblock_flags()[0] or []))
     local_crops = local_crop_plan()[0]
     aug_plan()                                # (raises for malformed augmentation flags; the steps resolve the plan as they read it)
+    repr_every = check_repr_flags() if spec is not None else 0
 
     def single_step(features, labels):
         # optimizer.iterations is a host int that apply_gradients increments: every "before the increment" read of the step is this
@@ -372,6 +409,11 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         R = num_replicas(strategy)
         con_loss = sup_loss = None
         sup_box = {}
+        # the label-free diagnostics of a measured step: the online projection (before the predictor under byol, the online side under
+        # mocov2 / dino, pass A's global views under multi-crop); the gather is in flight during the loss
+        repr_finish = repr_handle = None
+        if repr_every and (step + 1) % repr_every == 0 and projection_head_outputs is not None:
+            repr_finish = metrics.start_representation_stats(projection_head_outputs, strategy, FLAGS.repr_uniform_t)
 
         def supervised_part():
             if teacher_logits is not None:
@@ -388,6 +430,8 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
             con_loss = spec.call(c)
         else:
             supervised_part()
+        if repr_finish is not None:
+            repr_handle = repr_finish()
         sup_loss = sup_box.get('loss')
         weight_decay = model_lib.add_weight_decay(model, adjust_per_optimizer=True)         # :609-610
 
@@ -510,6 +554,9 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
         if sup_loss is not None:
             vals[sup_names[0]] = sup_loss.value.reshape(-1)[:1]
             vals[sup_names[1]] = sup_loss.acc.reshape(-1)[:1]
+        if repr_handle is not None:
+            for nm, attr in metrics.REPR_METRICS:
+                vals[nm] = getattr(repr_handle, attr)
         names = [nm for nm in order if nm in vals]
         # one launch: bank[index(name)] += value(name); the metrics absent this step keep their sums
         srcs = [vals.get(nm, state['zero']) for nm in order]
@@ -535,7 +582,10 @@ def make_single_step(model, optimizer, strategy, all_metrics=None, teacher=None,
                 sup_loss.acc = at[sup_names[1]]
         if torch.is_tensor(weight_decay) and 'train/weight_decay' in at:
             weight_decay = at['train/weight_decay']
-        return dict(con_loss=con_loss, sup_loss=sup_loss, weight_decay=weight_decay, total_loss=total, logits_con=c.logits_con)
+        out = dict(con_loss=con_loss, sup_loss=sup_loss, weight_decay=weight_decay, total_loss=total, logits_con=c.logits_con)
+        if repr_every:
+            out['repr_stats'] = repr_handle
+        return out
 
     single_step.metrics = m
     return single_step
@@ -692,6 +742,7 @@ def main(argv):
     aug_plan()                                # a malformed --aug_recipe / --blur_probs / ... raises here, before any device work
     check_dropblock_flags()
     check_knn_flags()
+    check_repr_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
         # before any device work: a missing / unset --data_dir raises here, naming the expected layout and the converter
@@ -827,12 +878,14 @@ def main(argv):
             dt = time.time() - t0
             t0 = time.time()
             if rank0:
-                vals = {k: v.result() for k, v in step_fn.metrics.items()}
+                # a window without a measured step has no representation diagnostics: the keys are left out, never written as 0.0
+                logged = {k: v for k, v in step_fn.metrics.items() if v._count or k not in dict(metrics.REPR_METRICS)}
+                vals = {k: v.result() for k, v in logged.items()}
                 vals.update(step=step, images_per_sec=FLAGS.train_batch_size * log_every / dt,
                             learning_rate=learning_rate(step))
                 print(json.dumps(vals), flush=True)
                 if summary_writer is not None:                                              # :645-652
-                    metrics.log_and_write_metrics_to_summary(list(step_fn.metrics.values()), step, summary_writer)
+                    metrics.log_and_write_metrics_to_summary(list(logged.values()), step, summary_writer)
                     summary_writer.scalar('learning_rate', learning_rate(step), step)
                     summary_writer.flush()
             for v in step_fn.metrics.values():

@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn,repr]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -608,6 +608,44 @@ def main():
                      row['bt_fwd_spread_us'], row['bt_bwd_us'], row['bt_bwd_tfs'], row['bt_apply_us'], row['vicreg_over_bt_fwd']), flush=True)
             res.append(row)
             del h, bws, zhat, rstd, g, cs, vws, xc, st
+    if 'repr' in what:
+        # Representation diagnostics (csrc/repr.hip): the four launches of ops.repr_stats at the global batch N, beside simclr_vicreg_fwd at
+        # n = N in the same run -- both form two [N, N] Gram matrices over D (4 N^2 D matrix FLOPs); VICReg's stores its blocks and may
+        # split k, this one reduces each tile through g^2 and exp2 in its epilogue and writes two doubles per workgroup.
+        # Median of --iters launches with [min, max].
+        def med(fn):
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.iters):
+                a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
+                a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) * 1e3)
+            ts.sort()
+            return ts[len(ts) // 2], [ts[0], ts[-1]]
+        for (N, D) in [(4096, 128), (4096, 2048), (512, 8192)]:
+            h = torch.randn(2 * N, D, device=dev)
+            z, _ = ops.l2norm_fwd(h)
+            rws = ops.repr_workspace(N, D, dev)
+            vws = ops.vicreg_workspace(N, N, D, dev)
+            xc, st = ops.vicreg_center(z)
+            row = dict(layer='repr N%d D%d' % (N, D), flops=4.0 * N * N * D, iters=args.iters, repr_workspace_bytes=rws.numel() * 8,
+                       vicreg_k_splits=ops.vicreg_k_splits(N, N, D))
+            for name, fn in (('repr_stats', lambda: ops.repr_stats(z, 2.0, rws)), ('vicreg_center', lambda: ops.vicreg_center(z)),
+                             ('vicreg_fwd', lambda: ops.vicreg_fwd(z, xc, st, N, 0, ws=vws)), ('l2norm_fwd', lambda: ops.l2norm_fwd(h))):
+                row[name + '_us'], row[name + '_min_max_us'] = med(fn)
+            row['repr_tfs'] = row['flops'] / row['repr_stats_us'] / 1e6
+            row['vicreg_fwd_tfs'] = row['flops'] / row['vicreg_fwd_us'] / 1e6
+            row['repr_over_vicreg_center_plus_fwd'] = row['repr_stats_us'] / (row['vicreg_center_us'] + row['vicreg_fwd_us'])
+            print('repr N=%d D=%d: repr_stats %.0f us [%.0f, %.0f] (%.1f TF/s) | vicreg centre %.0f us + fwd %.0f us [%.0f, %.0f] (%.1f TF/s, '
+                  'S=%d) | l2norm %.0f us | repr / (vicreg centre + fwd) %.2f'
+                  % (N, D, row['repr_stats_us'], *row['repr_stats_min_max_us'], row['repr_tfs'], row['vicreg_center_us'], row['vicreg_fwd_us'],
+                     *row['vicreg_fwd_min_max_us'], row['vicreg_fwd_tfs'], row['vicreg_k_splits'], row['l2norm_fwd_us'],
+                     row['repr_over_vicreg_center_plus_fwd']), flush=True)
+            res.append(row)
+            del h, z, rws, vws, xc, st
     if 'byol' in what:
         # BYOL (csrc/byol.hip).  The moving average of the target network over ResNet-50's variable list (the list of the 'lars' entry
         # below) in GB/s of 12 bytes per element (target read + write, online read), beside simclr_lars_multi_tensor on the same list in
