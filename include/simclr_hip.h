@@ -295,6 +295,30 @@ size_t simclr_repr_workspace_bytes(int N, int D);   /* 0 for a shape the kernels
 int simclr_repr_tile_edge(int N, int D);
 int simclr_repr_stats(const float* z_all, int N, int D, float t, void* ws, float* out4, simclr_stream_t stream);
 
+/* ---- cached-feature linear probe: l2-regularised multinomial logistic regression, csrc/logreg.hip ----
+ * x [n, D] fp32 = a slab of standardised features, w [C, D], b [C], labels [n] int32 in [0, C) (the CALLER guarantees the range: a label
+ * outside matches no class and is never used as an index), weights [n] fp32 (0 = a padding row), inv_S = 1 / the weight total of the
+ * whole bank.  s_nc = x_n . w_c + b_c on the exact fp32-input MFMA, k in a fixed order.
+ * simclr_logreg_fwd: lse [n] double = logsumexp_c s_nc; out3 = {sum_n w_n (lse_n - s_n,y_n), sum of w_n over the rows whose label is the
+ *   lowest-index maximum, sum_n w_n} as three doubles (NOT scaled by inv_S).  mode 0: nothing else is written.  mode 1: store [n, pitch]
+ *   fp32 (pitch = simclr_logreg_store_pitch(C) = C rounded up to 4; columns >= C are never written; the column sum of the backward reads them with their
+ *   16-byte quad and ignores them) receives
+ *   G_nc = (w_n inv_S) (softmax_c(s_n) - [c = y_n]).  mode 2: store receives the raw logits s_nc.
+ * simclr_logreg_bwd: dw [C, D] (+)= G^T X, db [C] (+)= colsum(G) of a slab (accumulate != 0 adds to what dw / db hold).  The slab's rows
+ *   are cut into simclr_logreg_row_splits parts (a multiple of 32 rows each, the last one ragged) where the C x D grid alone would leave
+ *   CUs idle; the parts are added as ((p0 + p1) + p2) + ... in fp32.
+ * D a multiple of 64 in [64, 8192], 2 <= C <= 4096, 1 <= n <= 65536, every pointer 16-byte aligned.  No atomics, every reduction in a
+ * fixed order: repeat calls are bitwise equal.  Both calls share one workspace of simclr_logreg_workspace_bytes. */
+size_t simclr_logreg_workspace_bytes(int n, int D, int C);   /* 0 for a shape the kernels refuse */
+int simclr_logreg_row_splits(int n, int D, int C);           /* row parts of the backward product; 0 for a refused shape */
+int simclr_logreg_tile_edge(int n, int D, int C);            /* edge (64 or 128) of the forward's logit tile; 0 for a refused shape */
+int simclr_logreg_bwd_tile_edge(int n, int D, int C);        /* edge (64 or 128) of the backward's dW tile; 0 for a refused shape */
+int simclr_logreg_store_pitch(int C);                        /* floats per row of store; 0 for a refused C */
+int simclr_logreg_fwd(const float* x, const float* w, const float* b, const int* labels, const float* weights, int n, int D, int C,
+                      double inv_S, int mode, float* store, double* lse, double* out3, void* workspace, simclr_stream_t stream);
+int simclr_logreg_bwd(const float* g, const float* x, int n, int D, int C, float* dw, float* db, int accumulate, void* workspace,
+                      simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

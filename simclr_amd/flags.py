@@ -189,6 +189,17 @@ _DEFS = [
     ('knn_temperature', 0.07, float, 'MI355X build: temperature of the k-NN vote weights exp(similarity / temperature).'),
     ('knn_bank_examples', 0, int, 'MI355X build: examples of --train_split in the k-NN bank: 0 = the whole split, n > 0 = the first n positions of '
                                   'epoch_permutation(data_seed, 0, N).  --dataset=synthetic: a bank of random images, at most 8 eval batches.'),
+    # cached-feature linear probe (simclr_amd/logreg.py): l2-regularised softmax regression on frozen features, fitted with L-BFGS
+    ('logreg_eval', False, bool, 'MI355X build: --mode=eval / train_then_eval also encode --train_split once under evaluation preprocessing, fit an '
+                                 'l2-regularised multinomial logistic regression on the standardised features with L-BFGS, score '
+                                 '--eval_split with it and write logreg_result.json; runs with or without a linear head.'),
+    ('logreg_l2', '1e-4', str, 'MI355X build: l2 coefficient of the probe (weights and bias), one value > 0 or a comma list: the values are '
+                               'fitted in the order given, each warm-started from the one before, all are reported, none is selected.'),
+    ('logreg_max_iterations', 200, int, 'MI355X build: L-BFGS iteration cap of the probe (1..10000).'),
+    ('logreg_tolerance', 1e-5, float, 'MI355X build: the probe stops when |g|_inf <= logreg_tolerance * max(1, |f|); in (0, 1).'),
+    ('logreg_history', 10, int, 'MI355X build: (s, y) pairs the L-BFGS recursion of the probe keeps (1..64).'),
+    ('logreg_bank_examples', 0, int, 'MI355X build: examples of --train_split the probe is fitted on: 0 = the whole split, n > 0 = the first n '
+                                     'positions of epoch_permutation(data_seed, 0, N) (the rule of --knn_bank_examples).'),
     # asymmetric view augmentation (flags.aug_plan): per-view blur and solarization of the two global views, jitter components.
     # None = take the column from --aug_recipe.  Read in pretraining only: --train_mode=finetune and --mode=eval ignore all five.
     ('aug_recipe', 'simclr', str, "MI355X build: augmentation recipe of the two global views, 'simclr' (default: blur 0.5 / 0.5, no "

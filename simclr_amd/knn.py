@@ -39,10 +39,11 @@ def knn_predict(queries, bank, bank_labels, num_classes, k=200, temperature=0.07
     return ops.knn_vote(top_val, top_label, num_classes, temperature)
 
 
-def extract_features(model, data, steps=None):
+def extract_features(model, data, steps=None, normalize=True):
     """One pass of an eval-style iterator of (features [b, H, W, 3], {'labels': one-hot, 'mask': weights}) through model.features.
     `steps`: batches to read (None: until the iterator ends).  Returns (L2-normalised features [n, C] fp32, labels [n] int64,
-    weights [n] fp32); a padded last batch keeps its rows, with weight 0 (absent 'mask' = every sample counts)."""
+    weights [n] fp32); a padded last batch keeps its rows, with weight 0 (absent 'mask' = every sample counts).  normalize=False
+    returns the pooled features as they are (simclr_amd/logreg.py standardises them instead)."""
     feats, labels, weights = [], [], []
     i = 0
     while steps is None or i < steps:
@@ -51,7 +52,7 @@ def extract_features(model, data, steps=None):
         except StopIteration:
             break
         h = model.features(x)
-        z, _ = ops.l2norm_fwd(h)
+        z = ops.l2norm_fwd(h)[0] if normalize else h
         feats.append(z)
         labels.append(lab['labels'].argmax(1))
         w = lab.get('mask')

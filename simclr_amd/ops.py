@@ -772,6 +772,127 @@ def repr_stats(z_all, t=2.0, ws=None):
     return out
 
 
+# ---------------------------------------------------------------- cached-feature linear probe (csrc/logreg.hip)
+LOGREG_DIM_STEP, LOGREG_MIN_DIM, LOGREG_MAX_DIM = 64, 64, 8192   # feature widths: multiples of 64 in [64, 8192]
+LOGREG_MIN_CLASSES, LOGREG_MAX_CLASSES = 2, 4096
+LOGREG_MAX_ROWS = 65536                                          # rows per call (a slab of the bank)
+
+
+def logreg_dim_ok(D):
+    return LOGREG_MIN_DIM <= D <= LOGREG_MAX_DIM and D % LOGREG_DIM_STEP == 0
+
+
+def _logreg_check_shape(n, D, C):
+    if not logreg_dim_ok(D):
+        raise ValueError('logreg supports feature widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (LOGREG_DIM_STEP, LOGREG_MIN_DIM, LOGREG_MAX_DIM, D))
+    if not LOGREG_MIN_CLASSES <= C <= LOGREG_MAX_CLASSES:
+        raise ValueError('logreg needs %d <= C <= %d classes (got %d)' % (LOGREG_MIN_CLASSES, LOGREG_MAX_CLASSES, C))
+    if not 1 <= n <= LOGREG_MAX_ROWS:
+        raise ValueError('logreg takes 1 <= n <= %d rows per call (got %d)' % (LOGREG_MAX_ROWS, n))
+
+
+def logreg_store_pitch(C):
+    """Floats per row of the [n, pitch] logit / G buffer: C rounded up to 4."""
+    return (int(C) + 3) // 4 * 4
+
+
+def logreg_workspace(n, D, C, device):
+    n, D, C = int(n), int(D), int(C)
+    _logreg_check_shape(n, D, C)
+    nbytes = lib().logreg_workspace_bytes(n, D, C)
+    assert nbytes > 0
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def logreg_row_splits(n, D, C):
+    """Row parts of logreg_bwd's product at this shape (0 for a refused shape)."""
+    return int(lib().logreg_row_splits(int(n), int(D), int(C)))
+
+
+def logreg_tile_edge(n, D, C, backward=False):
+    """Edge (64 or 128) of the tile a workgroup of the forward (or backward) product owns at this shape (0 for a refused shape)."""
+    return int((lib().logreg_bwd_tile_edge if backward else lib().logreg_tile_edge)(int(n), int(D), int(C)))
+
+
+def _logreg_f32(name, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError('logreg: %s must be a float32 tensor of shape %s (got %s %s)'
+                         % (name, tuple(shape), tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError('logreg: %s must be contiguous and 16-byte aligned' % name)
+
+
+def _logreg_ws(ws, n, D, C, device):
+    if ws is None:
+        return logreg_workspace(n, D, C, device)
+    need = lib().logreg_workspace_bytes(n, D, C)
+    if not torch.is_tensor(ws) or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+        raise ValueError('logreg: the workspace must hold %d bytes, 16-byte aligned, for n = %d, D = %d, C = %d' % (need, n, D, C))
+    return ws
+
+
+def logreg_fwd(x, w, b, labels, weights, inv_S, mode=0, store=None, lse=None, ws=None, check_labels=True):
+    """x [n, D], w [C, D], b [C] fp32, labels [n] int32 in [0, C), weights [n] fp32.  Returns (out, lse, store): out = fp64 [3] =
+    {sum_n w_n (lse_n - s_n,y_n), weighted top-1 hits, sum_n w_n}, lse fp64 [n], store [n, pitch] fp32 = None (mode 0), G (mode 1) or the
+    raw logits (mode 2); columns >= C of store are never written (include/simclr_hip.h).  check_labels=False skips the range check of
+    the labels (one device synchronisation) for a caller that has made it already."""
+    if not torch.is_tensor(x) or x.dim() != 2 or not torch.is_tensor(w) or w.dim() != 2:
+        raise ValueError('logreg_fwd: need x [n, D] and w [C, D]')
+    (n, D), C = x.shape, w.shape[0]
+    _logreg_check_shape(n, D, C)
+    _logreg_f32('x', x, (n, D)); _logreg_f32('w', w, (C, D)); _logreg_f32('b', b, (C,)); _logreg_f32('weights', weights, (n,))
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous() \
+            or labels.data_ptr() % 16:
+        raise ValueError('logreg_fwd: labels must be a contiguous, 16-byte aligned int32 tensor of shape (%d,)' % n)
+    if mode not in (0, 1, 2):
+        raise ValueError('logreg_fwd: mode must be 0 (value), 1 (value and G) or 2 (logits) (got %r)' % (mode,))
+    inv_S = float(inv_S)
+    if not 0.0 < inv_S < float('inf'):
+        raise ValueError('logreg_fwd: inv_S must be a finite number > 0 (got %r)' % (inv_S,))
+    if check_labels and (int(labels.min()) < 0 or int(labels.max()) >= C):
+        raise ValueError('logreg_fwd: labels must lie in [0, %d) (got %d .. %d)' % (C, int(labels.min()), int(labels.max())))
+    pitch = logreg_store_pitch(C)
+    if mode == 0:
+        store = None
+    elif store is None:
+        store = torch.empty(n, pitch, device=x.device, dtype=torch.float32)
+    else:
+        if not torch.is_tensor(store) or store.dtype != torch.float32 or store.numel() < n * pitch or not store.is_contiguous() \
+                or store.data_ptr() % 16:
+            raise ValueError('logreg_fwd: store must be a contiguous, 16-byte aligned float32 tensor of at least %d x %d elements' % (n, pitch))
+        store = store.view(-1)[:n * pitch].view(n, pitch)
+    if lse is None:
+        lse = torch.empty(n, device=x.device, dtype=torch.float64)
+    elif not torch.is_tensor(lse) or lse.dtype != torch.float64 or tuple(lse.shape) != (n,) or not lse.is_contiguous() or lse.data_ptr() % 16:
+        raise ValueError('logreg_fwd: lse must be a contiguous, 16-byte aligned float64 tensor of shape (%d,)' % n)
+    ws = _logreg_ws(ws, n, D, C, x.device)
+    out = torch.empty(3, device=x.device, dtype=torch.float64)
+    _launch('logreg_fwd', 2.0 * n * D * C, 4.0 * (n * D + C * D + (n * C if mode else 0)),
+            lambda: lib().logreg_fwd(_p(x), _p(w), _p(b), _p(labels), _p(weights), n, D, C, inv_S, int(mode), _p(store), _p(lse), _p(out),
+                                     _p(ws), _s()))
+    return out, lse, store
+
+
+def logreg_bwd(g, x, C, dw=None, db=None, accumulate=False, ws=None):
+    """g [n, pitch] fp32 = the G of logreg_fwd mode 1, x [n, D] -> dw [C, D] (+)= G^T X, db [C] (+)= colsum(G) (accumulate=True adds to
+    the dw / db given)."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError('logreg_bwd: need x [n, D]')
+    (n, D), C = x.shape, int(C)
+    _logreg_check_shape(n, D, C)
+    _logreg_f32('x', x, (n, D)); _logreg_f32('g', g, (n, logreg_store_pitch(C)))
+    if accumulate and (dw is None or db is None):
+        raise ValueError('logreg_bwd: accumulate=True needs dw and db')
+    dw = torch.empty(C, D, device=x.device, dtype=torch.float32) if dw is None else dw
+    db = torch.empty(C, device=x.device, dtype=torch.float32) if db is None else db
+    _logreg_f32('dw', dw, (C, D)); _logreg_f32('db', db, (C,))
+    ws = _logreg_ws(ws, n, D, C, x.device)
+    _launch('logreg_bwd', 2.0 * n * D * C, 4.0 * (n * D + C * D + n * C),
+            lambda: lib().logreg_bwd(_p(g), _p(x), n, D, C, _p(dw), _p(db), 1 if accumulate else 0, _p(ws), _s()))
+    return dw, db
+
+
 # ---------------------------------------------------------------- BYOL (csrc/byol.hip)
 BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
 

@@ -276,6 +276,34 @@ def check_knn_flags(num_train_examples=None):
     return bank
 
 
+def check_logreg_flags(num_train_examples=None):
+    """--logreg_eval (simclr_amd/logreg.py), checked before any device work.  Returns the number of bank examples (None with the flag
+    off, in --mode=train, or for the whole split when its size is not known yet)."""
+    if not FLAGS.logreg_eval or FLAGS.mode == 'train':
+        return None
+    from . import logreg as logreg_lib
+    for l2 in logreg_lib.parse_l2_list(FLAGS.logreg_l2):
+        logreg_lib.check_fit_arguments(l2, FLAGS.logreg_max_iterations, FLAGS.logreg_tolerance, FLAGS.logreg_history)
+    if FLAGS.logreg_bank_examples < 0:
+        raise ValueError('--logreg_bank_examples must be >= 0 (got %d)' % FLAGS.logreg_bank_examples)
+    width = (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
+    if not ops.logreg_dim_ok(width):
+        raise ValueError('--logreg_eval needs an encoder width that is a multiple of %d in [%d, %d] (resnet_depth=%d, width_multiplier=%d '
+                         'give %d)' % (ops.LOGREG_DIM_STEP, ops.LOGREG_MIN_DIM, ops.LOGREG_MAX_DIM, FLAGS.resnet_depth,
+                                       FLAGS.width_multiplier, width))
+    if num_train_examples is None:
+        return FLAGS.logreg_bank_examples or None
+    if FLAGS.logreg_bank_examples > num_train_examples:
+        raise ValueError('--logreg_bank_examples=%d exceeds the %d examples of --train_split=%s'
+                         % (FLAGS.logreg_bank_examples, num_train_examples, FLAGS.train_split))
+    return FLAGS.logreg_bank_examples or int(num_train_examples)
+
+
+def check_logreg_classes(num_classes):
+    if FLAGS.logreg_eval and FLAGS.mode != 'train' and not ops.LOGREG_MIN_CLASSES <= num_classes <= ops.LOGREG_MAX_CLASSES:
+        raise ValueError('--logreg_eval takes %d..%d classes (the dataset has %d)' % (ops.LOGREG_MIN_CLASSES, ops.LOGREG_MAX_CLASSES, num_classes))
+
+
 def all_reduce_stats_async(tensor, strategy):
     """SUM of a small statistics tensor over the replicas on the route the SyncBN sums and the Barlow Twins column sums use, started
     now; returns a zero-argument function that waits for it and returns the tensor.  One replica: nothing to do."""
@@ -742,6 +770,7 @@ def main(argv):
     aug_plan()                                # a malformed --aug_recipe / --blur_probs / ... raises here, before any device work
     check_dropblock_flags()
     check_knn_flags()
+    check_logreg_flags()
     check_repr_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
@@ -752,8 +781,14 @@ def main(argv):
         if FLAGS.knn_eval and FLAGS.mode != 'train':
             builder.split(FLAGS.train_split)
             check_knn_flags(builder.info.splits[FLAGS.train_split].num_examples)
-    elif FLAGS.knn_eval:
-        check_knn_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        if FLAGS.logreg_eval and FLAGS.mode != 'train':
+            builder.split(FLAGS.train_split)
+            check_logreg_flags(builder.info.splits[FLAGS.train_split].num_examples)
+            check_logreg_classes(builder.info.features['label'].num_classes)
+    else:
+        if FLAGS.knn_eval:
+            check_knn_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        check_logreg_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
     strategy = init_distributed()
     R = num_replicas(strategy)
     rank0 = strategy is None or strategy.rank == 0
@@ -777,26 +812,40 @@ def main(argv):
             return data_lib.build_distributed_dataset(builder, FLAGS.eval_batch_size, False, strategy)
         return synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device, seed=100 + rep)
 
+    def bank_iterator(n_bank, subset, knn_lib):
+        """This replica's shard of the bank under evaluation preprocessing: n_bank examples of --train_split (`subset`: the first
+        positions of the epoch-0 permutation), or, with --dataset=synthetic, whole batches of random images."""
+        if builder is not None:
+            split = builder.split(FLAGS.train_split, cache=FLAGS.cache_dataset)
+            if subset:
+                sel = knn_lib.knn_bank_indices(FLAGS.data_seed, split.index.shape[0], n_bank)
+                split = data_lib.Split(split.index[sel], split.images)
+            # evaluation preprocessing of the TRAINING split; the last batch is padded with weight 0 and trimmed from the bank
+            return data_lib.DatasetIterator(split, num_classes, FLAGS.eval_batch_size, False, replica=rep, num_replicas=R, device=RT.device)
+        import itertools
+        steps = int(math.ceil(n_bank / FLAGS.eval_batch_size))
+        return itertools.islice(synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device,
+                                                       seed=7000 + rep, pool=steps), steps)
+
     def knn_evaluation(ckpt, result):
         """--knn_eval: the weighted k-NN evaluation after perform_evaluation (which may have skipped); the union of both results."""
         from . import knn as knn_lib
         # --dataset=synthetic: at most SYNTHETIC_KNN_BANK_BATCHES batches, each drawn once -- a longer bank would only repeat them
         n_bank = check_knn_flags(num_train_examples if builder is not None else SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
-        if builder is not None:
-            split = builder.split(FLAGS.train_split, cache=FLAGS.cache_dataset)
-            if FLAGS.knn_bank_examples:
-                sel = knn_lib.knn_bank_indices(FLAGS.data_seed, split.index.shape[0], n_bank)
-                split = data_lib.Split(split.index[sel], split.images)
-            # evaluation preprocessing of the TRAINING split; the last batch is padded with weight 0 and trimmed from the bank
-            bank_data = data_lib.DatasetIterator(split, num_classes, FLAGS.eval_batch_size, False, replica=rep, num_replicas=R,
-                                                 device=RT.device)
-        else:
-            import itertools
-            steps = int(math.ceil(n_bank / FLAGS.eval_batch_size))
-            bank_data = itertools.islice(synthetic_eval_batches(FLAGS.eval_batch_size // R, FLAGS.image_size, num_classes, RT.device,
-                                                                seed=7000 + rep, pool=steps), steps)
+        bank_data = bank_iterator(n_bank, FLAGS.knn_bank_examples, knn_lib)
         knn_result = knn_lib.perform_knn_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
         return dict(result or {}, **knn_result)
+
+    def logreg_evaluation(ckpt, result):
+        """--logreg_eval: the cached-feature linear probe, after perform_evaluation (which may have skipped) and the k-NN vote; the
+        union of the results.  --dataset=synthetic: the bank of the k-NN path."""
+        from . import knn as knn_lib
+        from . import logreg as logreg_lib
+        n_bank = check_logreg_flags(num_train_examples if builder is not None else SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        check_logreg_classes(num_classes)
+        bank_data = bank_iterator(n_bank, FLAGS.logreg_bank_examples, knn_lib)
+        logreg_result = logreg_lib.perform_logreg_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
+        return dict(result or {}, **logreg_result)
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
@@ -813,6 +862,8 @@ def main(argv):
         result = perform_evaluation(model, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
         if FLAGS.knn_eval:
             result = knn_evaluation(ckpt, result)
+        if FLAGS.logreg_eval:
+            result = logreg_evaluation(ckpt, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
@@ -907,6 +958,8 @@ def main(argv):
         result = perform_evaluation(model, eval_data(), eval_steps, manager.latest_checkpoint, strategy, FLAGS.model_dir)
         if FLAGS.knn_eval:
             result = knn_evaluation(manager.latest_checkpoint, result)
+        if FLAGS.logreg_eval:
+            result = logreg_evaluation(manager.latest_checkpoint, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
