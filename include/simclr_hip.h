@@ -319,6 +319,31 @@ int simclr_logreg_fwd(const float* x, const float* w, const float* b, const int*
 int simclr_logreg_bwd(const float* g, const float* x, int n, int D, int C, float* dw, float* db, int accumulate, void* workspace,
                       simclr_stream_t stream);
 
+/* ---- spherical k-means on frozen features: assignment, segmented sums and the centroid finish, csrc/kmeans.hip ----
+ * x [n, D] fp32 = a slab of unit rows, c [K, D] fp32 = unit centroids, weights [n] fp32 (0 = a padding row).  A score x_n . c_k runs on
+ * the exact fp32-input MFMA, k in a fixed order that depends on neither the tile's position nor n nor K: it is a function of the two rows.
+ * simclr_kmeans_assign: assign [n] int32 = argmax_k x_n . c_k (ties to the lowest k, a NaN score below every number; a row whose scores
+ *   are all NaN gets 0 and best = NaN), best [n] fp32 = that score, out3 = {sum_n w_n (1 - best_n), sum_n w_n, the number of rows with
+ *   w_n > 0 whose assignment differs from the value assign held ON ENTRY} as three doubles; only rows with w_n > 0 enter them.  assign is
+ *   read before it is written: the first call passes it filled with -1.  The [n, K] scores are never written.
+ * simclr_kmeans_update: sums [K, D] double (+)= sum_j w_r x_r over r = order[j], offsets[k] <= j < offsets[k+1], in ascending j;
+ *   wsum [K] double (+)= the same sum of w_r (accumulate != 0 adds to what they hold).  order [n] int32 = the slab's rows sorted by
+ *   assignment (stable), offsets [K + 1] int32 = the segment starts.  No index read from memory is dereferenced unchecked: an order
+ *   entry outside [0, n) is skipped, an offsets entry is clamped to [0, n].
+ * simclr_kmeans_finish: c_new_k = fp32(sums_k / |sums_k|), normalised in double; a cluster with wsum_k <= 0 or |sums_k|^2 <= 1e-24 (or
+ *   not finite) keeps c_prev_k.  out2 = {number of kept clusters, max_k (1 - c_new_k . c_prev_k)} as two doubles.  c_new may not alias
+ *   c_prev.  Its workspace is the head (2 K doubles) of any workspace of simclr_kmeans_workspace_bytes(n, D, K).
+ * D a multiple of 64 in [64, 8192], 2 <= K <= 16384, 1 <= n <= 65536, every pointer 16-byte aligned.  No atomics, every reduction in a
+ * fixed order: repeat calls are bitwise equal. */
+size_t simclr_kmeans_workspace_bytes(int n, int D, int K);   /* 0 for a shape the kernels refuse */
+int simclr_kmeans_tile_edge(int n, int D, int K);            /* edge (64 or 128) of the assignment's score tile; 0 for a refused shape */
+int simclr_kmeans_assign(const float* x, const float* c, const float* weights, int n, int D, int K, int* assign, float* best, double* out3,
+                         void* workspace, simclr_stream_t stream);
+int simclr_kmeans_update(const float* x, const float* weights, const int* order, const int* offsets, int n, int D, int K, double* sums,
+                         double* wsum, int accumulate, simclr_stream_t stream);
+int simclr_kmeans_finish(const double* sums, const double* wsum, const float* c_prev, int K, int D, float* c_new, double* out2,
+                         void* workspace, simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

@@ -200,6 +200,18 @@ _DEFS = [
     ('logreg_history', 10, int, 'MI355X build: (s, y) pairs the L-BFGS recursion of the probe keeps (1..64).'),
     ('logreg_bank_examples', 0, int, 'MI355X build: examples of --train_split the probe is fitted on: 0 = the whole split, n > 0 = the first n '
                                      'positions of epoch_permutation(data_seed, 0, N) (the rule of --knn_bank_examples).'),
+    # k-means clustering evaluation (simclr_amd/kmeans.py): spherical k-means on frozen features, scored against the labels
+    ('kmeans_eval', False, bool, 'MI355X build: --mode=eval / train_then_eval also cluster the l2-normalised encoder features of --train_split '
+                                 '(evaluation preprocessing) with spherical k-means, score --eval_split by NMI, ARI and cluster accuracy '
+                                 'and write kmeans_result.json; runs with or without a linear head.'),
+    ('kmeans_k', 0, int, 'MI355X build: clusters of the k-means evaluation (2..16384); 0 = the class count of the dataset.'),
+    ('kmeans_restarts', 1, int, 'MI355X build: k-means restarts (1..16); the one with the lowest objective on the bank is scored.'),
+    ('kmeans_max_iterations', 50, int, 'MI355X build: Lloyd iteration cap of a restart (1..1000).'),
+    ('kmeans_tolerance', 1e-6, float, 'MI355X build: a restart stops when J_prev - J <= kmeans_tolerance * J_prev (or no assignment '
+                                      'changed); in [0, 1).'),
+    ('kmeans_seed', 0, int, 'MI355X build: restart r starts from rows drawn with numpy.random.default_rng([kmeans_seed, r]).'),
+    ('kmeans_bank_examples', 0, int, 'MI355X build: examples of --train_split that are clustered: 0 = the whole split, n > 0 = the first n '
+                                     'positions of epoch_permutation(data_seed, 0, N) (the rule of --knn_bank_examples).'),
     # asymmetric view augmentation (flags.aug_plan): per-view blur and solarization of the two global views, jitter components.
     # None = take the column from --aug_recipe.  Read in pretraining only: --train_mode=finetune and --mode=eval ignore all five.
     ('aug_recipe', 'simclr', str, "MI355X build: augmentation recipe of the two global views, 'simclr' (default: blur 0.5 / 0.5, no "

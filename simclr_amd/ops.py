@@ -893,6 +893,120 @@ def logreg_bwd(g, x, C, dw=None, db=None, accumulate=False, ws=None):
     return dw, db
 
 
+# ---------------------------------------------------------------- spherical k-means (csrc/kmeans.hip)
+KMEANS_DIM_STEP, KMEANS_MIN_DIM, KMEANS_MAX_DIM = 64, 64, 8192   # feature widths: multiples of 64 in [64, 8192]
+KMEANS_MIN_K, KMEANS_MAX_K = 2, 16384
+KMEANS_MAX_ROWS = 65536                                          # rows per call (a slab of the bank)
+
+
+def kmeans_dim_ok(D):
+    return KMEANS_MIN_DIM <= D <= KMEANS_MAX_DIM and D % KMEANS_DIM_STEP == 0
+
+
+def _kmeans_check_shape(n, D, K):
+    if not kmeans_dim_ok(D):
+        raise ValueError('kmeans supports feature widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (KMEANS_DIM_STEP, KMEANS_MIN_DIM, KMEANS_MAX_DIM, D))
+    if not KMEANS_MIN_K <= K <= KMEANS_MAX_K:
+        raise ValueError('kmeans needs %d <= K <= %d centroids (got %d)' % (KMEANS_MIN_K, KMEANS_MAX_K, K))
+    if not 1 <= n <= KMEANS_MAX_ROWS:
+        raise ValueError('kmeans takes 1 <= n <= %d rows per call (got %d)' % (KMEANS_MAX_ROWS, n))
+
+
+def kmeans_workspace(n, D, K, device):
+    n, D, K = int(n), int(D), int(K)
+    _kmeans_check_shape(n, D, K)
+    nbytes = lib().kmeans_workspace_bytes(n, D, K)
+    assert nbytes > 0
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def kmeans_tile_edge(n, D, K):
+    """Edge (64 or 128) of the score tile a workgroup of the assignment owns at this shape (0 for a refused shape)."""
+    return int(lib().kmeans_tile_edge(int(n), int(D), int(K)))
+
+
+def _kmeans_t(name, t, shape, dtype):
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError('kmeans: %s must be a %s tensor of shape %s (got %s %s)'
+                         % (name, str(dtype).replace('torch.', ''), tuple(shape), tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError('kmeans: %s must be contiguous and 16-byte aligned' % name)
+
+
+def _kmeans_ws(ws, n, D, K, device):
+    if ws is None:
+        return kmeans_workspace(n, D, K, device)
+    need = lib().kmeans_workspace_bytes(n, D, K)
+    if not torch.is_tensor(ws) or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+        raise ValueError('kmeans: the workspace must hold %d bytes, 16-byte aligned, for n = %d, D = %d, K = %d' % (need, n, D, K))
+    return ws
+
+
+def kmeans_assign(x, c, weights, assign=None, best=None, ws=None):
+    """x [n, D] unit rows, c [K, D] unit centroids, weights [n], all fp32.  Returns (assign, best, out): assign int32 [n] = argmax_k
+    x_n . c_k (ties to the lowest k), best fp32 [n] = that score, out = fp64 [3] = {sum w (1 - best), sum w, rows of weight > 0 whose
+    assignment differs from the value `assign` held on entry}.  Without `assign` the previous assignment is -1 everywhere."""
+    if not torch.is_tensor(x) or x.dim() != 2 or not torch.is_tensor(c) or c.dim() != 2:
+        raise ValueError('kmeans_assign: need x [n, D] and c [K, D]')
+    (n, D), K = x.shape, c.shape[0]
+    _kmeans_check_shape(n, D, K)
+    _kmeans_t('x', x, (n, D), torch.float32); _kmeans_t('c', c, (K, D), torch.float32); _kmeans_t('weights', weights, (n,), torch.float32)
+    if assign is None:
+        assign = torch.full((n,), -1, device=x.device, dtype=torch.int32)
+    _kmeans_t('assign', assign, (n,), torch.int32)
+    best = torch.empty(n, device=x.device, dtype=torch.float32) if best is None else best
+    _kmeans_t('best', best, (n,), torch.float32)
+    ws = _kmeans_ws(ws, n, D, K, x.device)
+    out = torch.empty(3, device=x.device, dtype=torch.float64)
+    _launch('kmeans_assign', 2.0 * n * D * K, 4.0 * (n * D + K * D),
+            lambda: lib().kmeans_assign(_p(x), _p(c), _p(weights), n, D, K, _p(assign), _p(best), _p(out), _p(ws), _s()))
+    return assign, best, out
+
+
+def kmeans_update(x, weights, assign, K, sums=None, wsum=None, accumulate=False):
+    """sums [K, D] fp64 (+)= the weighted rows of x [n, D] summed per cluster of assign int32 [n] (values in [0, K)), wsum [K] fp64 (+)=
+    the weights.  The rows are sorted by assignment here (torch.sort, stable) and the kernel adds every segment in that order."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError('kmeans_update: need x [n, D]')
+    (n, D), K = x.shape, int(K)
+    _kmeans_check_shape(n, D, K)
+    _kmeans_t('x', x, (n, D), torch.float32); _kmeans_t('weights', weights, (n,), torch.float32)
+    _kmeans_t('assign', assign, (n,), torch.int32)
+    if accumulate and (sums is None or wsum is None):
+        raise ValueError('kmeans_update: accumulate=True needs sums and wsum')
+    sums = torch.empty(K, D, device=x.device, dtype=torch.float64) if sums is None else sums
+    wsum = torch.empty(K, device=x.device, dtype=torch.float64) if wsum is None else wsum
+    _kmeans_t('sums', sums, (K, D), torch.float64); _kmeans_t('wsum', wsum, (K,), torch.float64)
+    key, order = torch.sort(assign, stable=True)
+    order = order.to(torch.int32)
+    # offsets[k] = the first sorted position whose assignment is >= k; a value outside [0, K) lands in no segment
+    offsets = torch.searchsorted(key, torch.arange(K + 1, device=x.device, dtype=torch.int32)).to(torch.int32)
+    _launch('kmeans_update', 2.0 * n * D, 4.0 * n * D + 8.0 * K * D,
+            lambda: lib().kmeans_update(_p(x), _p(weights), _p(order), _p(offsets), n, D, K, _p(sums), _p(wsum), 1 if accumulate else 0, _s()))
+    return sums, wsum
+
+
+def kmeans_finish(sums, wsum, c_prev, c_new=None, ws=None):
+    """c_new [K, D] fp32 = the rows of sums [K, D] fp64 normalised in double and rounded; a cluster with wsum <= 0 or |sums_k|^2 <= 1e-24
+    keeps c_prev_k.  Returns (c_new, out): out = fp64 [2] = {kept clusters, max_k (1 - c_new_k . c_prev_k)}."""
+    if not torch.is_tensor(sums) or sums.dim() != 2:
+        raise ValueError('kmeans_finish: need sums [K, D]')
+    K, D = sums.shape
+    _kmeans_check_shape(1, D, K)
+    _kmeans_t('sums', sums, (K, D), torch.float64); _kmeans_t('wsum', wsum, (K,), torch.float64)
+    _kmeans_t('c_prev', c_prev, (K, D), torch.float32)
+    c_new = torch.empty(K, D, device=sums.device, dtype=torch.float32) if c_new is None else c_new
+    _kmeans_t('c_new', c_new, (K, D), torch.float32)
+    if c_new.data_ptr() == c_prev.data_ptr():
+        raise ValueError('kmeans_finish: c_new may not alias c_prev')
+    ws = _kmeans_ws(ws, 1, D, K, sums.device)
+    out = torch.empty(2, device=sums.device, dtype=torch.float64)
+    _launch('kmeans_finish', 3.0 * K * D, 16.0 * K * D,
+            lambda: lib().kmeans_finish(_p(sums), _p(wsum), _p(c_prev), K, D, _p(c_new), _p(out), _p(ws), _s()))
+    return c_new, out
+
+
 # ---------------------------------------------------------------- BYOL (csrc/byol.hip)
 BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
 

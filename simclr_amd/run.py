@@ -304,6 +304,38 @@ def check_logreg_classes(num_classes):
         raise ValueError('--logreg_eval takes %d..%d classes (the dataset has %d)' % (ops.LOGREG_MIN_CLASSES, ops.LOGREG_MAX_CLASSES, num_classes))
 
 
+def check_kmeans_flags(num_train_examples=None, num_classes=None):
+    """--kmeans_eval (simclr_amd/kmeans.py), checked before any device work.  Returns the number of bank examples (None with the flag
+    off, in --mode=train, or for the whole split when its size is not known yet).  K = --kmeans_k, or the class count once it is
+    known."""
+    if not FLAGS.kmeans_eval or FLAGS.mode == 'train':
+        return None
+    from . import kmeans as kmeans_lib
+    K = int(FLAGS.kmeans_k) or num_classes
+    if FLAGS.kmeans_k < 0 or (K is not None and not ops.KMEANS_MIN_K <= K <= ops.KMEANS_MAX_K):
+        raise ValueError('--kmeans_k must be 0 (the class count) or %d..%d (got %d%s)'
+                         % (ops.KMEANS_MIN_K, ops.KMEANS_MAX_K, FLAGS.kmeans_k, '' if FLAGS.kmeans_k else '; the dataset has %r classes' % K))
+    kmeans_lib.check_fit_arguments(K or ops.KMEANS_MIN_K, FLAGS.kmeans_seed, FLAGS.kmeans_restarts, FLAGS.kmeans_max_iterations,
+                                   FLAGS.kmeans_tolerance)
+    if FLAGS.kmeans_bank_examples < 0:
+        raise ValueError('--kmeans_bank_examples must be >= 0 (got %d)' % FLAGS.kmeans_bank_examples)
+    width = (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
+    if not ops.kmeans_dim_ok(width):
+        raise ValueError('--kmeans_eval needs an encoder width that is a multiple of %d in [%d, %d] (resnet_depth=%d, width_multiplier=%d '
+                         'give %d)' % (ops.KMEANS_DIM_STEP, ops.KMEANS_MIN_DIM, ops.KMEANS_MAX_DIM, FLAGS.resnet_depth,
+                                       FLAGS.width_multiplier, width))
+    if num_train_examples is None:
+        bank = FLAGS.kmeans_bank_examples or None
+    else:
+        if FLAGS.kmeans_bank_examples > num_train_examples:
+            raise ValueError('--kmeans_bank_examples=%d exceeds the %d examples of --train_split=%s'
+                             % (FLAGS.kmeans_bank_examples, num_train_examples, FLAGS.train_split))
+        bank = FLAGS.kmeans_bank_examples or int(num_train_examples)
+    if bank is not None and K is not None and K > bank:
+        raise ValueError('--kmeans_k: %d clusters exceed the %d bank examples (--kmeans_bank_examples)' % (K, bank))
+    return bank
+
+
 def all_reduce_stats_async(tensor, strategy):
     """SUM of a small statistics tensor over the replicas on the route the SyncBN sums and the Barlow Twins column sums use, started
     now; returns a zero-argument function that waits for it and returns the tensor.  One replica: nothing to do."""
@@ -771,6 +803,7 @@ def main(argv):
     check_dropblock_flags()
     check_knn_flags()
     check_logreg_flags()
+    check_kmeans_flags()
     check_repr_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
@@ -785,10 +818,14 @@ def main(argv):
             builder.split(FLAGS.train_split)
             check_logreg_flags(builder.info.splits[FLAGS.train_split].num_examples)
             check_logreg_classes(builder.info.features['label'].num_classes)
+        if FLAGS.kmeans_eval and FLAGS.mode != 'train':
+            builder.split(FLAGS.train_split)
+            check_kmeans_flags(builder.info.splits[FLAGS.train_split].num_examples, builder.info.features['label'].num_classes)
     else:
         if FLAGS.knn_eval:
             check_knn_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
         check_logreg_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        check_kmeans_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size, 10 if FLAGS.image_size <= 32 else 1000)
     strategy = init_distributed()
     R = num_replicas(strategy)
     rank0 = strategy is None or strategy.rank == 0
@@ -846,6 +883,17 @@ def main(argv):
         bank_data = bank_iterator(n_bank, FLAGS.logreg_bank_examples, knn_lib)
         logreg_result = logreg_lib.perform_logreg_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
         return dict(result or {}, **logreg_result)
+
+    def kmeans_evaluation(ckpt, result):
+        """--kmeans_eval: the k-means clustering evaluation, after perform_evaluation (which may have skipped), the k-NN vote and the
+        probe; the union of the results.  --dataset=synthetic: the bank of the k-NN path."""
+        from . import kmeans as kmeans_lib
+        from . import knn as knn_lib
+        n_bank = check_kmeans_flags(num_train_examples if builder is not None else SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size,
+                                    num_classes)
+        bank_data = bank_iterator(n_bank, FLAGS.kmeans_bank_examples, knn_lib)
+        kmeans_result = kmeans_lib.perform_kmeans_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
+        return dict(result or {}, **kmeans_result)
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
@@ -864,6 +912,8 @@ def main(argv):
             result = knn_evaluation(ckpt, result)
         if FLAGS.logreg_eval:
             result = logreg_evaluation(ckpt, result)
+        if FLAGS.kmeans_eval:
+            result = kmeans_evaluation(ckpt, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
@@ -960,6 +1010,8 @@ def main(argv):
             result = knn_evaluation(manager.latest_checkpoint, result)
         if FLAGS.logreg_eval:
             result = logreg_evaluation(manager.latest_checkpoint, result)
+        if FLAGS.kmeans_eval:
+            result = kmeans_evaluation(manager.latest_checkpoint, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result

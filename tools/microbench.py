@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn,repr,logreg]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn,repr,logreg,kmeans]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -689,6 +689,72 @@ def main():
                      *row['bwd_min_max_us'], row['bwd_tfs']), flush=True)
             res.append(row)
             del x, W, b, labels, weights, ws, store, lse, dW, db
+    if 'kmeans' in what:
+        # Spherical k-means (csrc/kmeans.hip) on one slab.  The assignment in TF/s of 2 n D K beside, at the same shape in the same run,
+        # the value-only forward of the linear probe (ops.logreg_fwd mode 0: the same tile and the same matrix work; its C is capped at
+        # 4096) and the top-1 search ops.knn_topk(x, c, 1).  The update (the sort of the wrapper included, and the kernel alone) beside a
+        # plain device copy of the slab: it reads n D floats once.  Median of --iters launches with [min, max].
+        def med(fn):
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.iters):
+                a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
+                a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) * 1e3)
+            ts.sort()
+            return ts[len(ts) // 2], [ts[0], ts[-1]]
+        from simclr_amd._lib import lib as _klib
+        for (n, D, K) in [(65536, 2048, 1000), (65536, 2048, 10000), (65536, 128, 3000)]:
+            x = torch.nn.functional.normalize(torch.randn(n, D, device=dev), dim=1)
+            c = torch.nn.functional.normalize(torch.randn(K, D, device=dev), dim=1)
+            weights = torch.ones(n, device=dev)
+            ws = ops.kmeans_workspace(n, D, K, dev)
+            assign = torch.full((n,), -1, device=dev, dtype=torch.int32)
+            best = torch.empty(n, device=dev)
+            sums, wsum = torch.empty(K, D, device=dev, dtype=torch.float64), torch.empty(K, device=dev, dtype=torch.float64)
+            row = dict(layer='kmeans n%d D%d K%d' % (n, D, K), flops=2.0 * n * D * K, iters=args.iters, workspace_bytes=ws.numel() * 8,
+                       tile_edge=ops.kmeans_tile_edge(n, D, K))
+            row['assign_us'], row['assign_min_max_us'] = med(lambda: ops.kmeans_assign(x, c, weights, assign, best, ws))
+            row['assign_tfs'] = row['flops'] / row['assign_us'] / 1e6
+            C = min(K, ops.LOGREG_MAX_CLASSES)
+            lws = ops.logreg_workspace(n, D, C, dev)
+            lse = torch.empty(n, device=dev, dtype=torch.float64)
+            bias = torch.zeros(C, device=dev)
+            labels = torch.zeros(n, device=dev, dtype=torch.int32)
+            cc = c[:C].contiguous()
+            row['logreg_classes'] = C
+            row['logreg_fwd0_us'], row['logreg_fwd0_min_max_us'] = med(
+                lambda: ops.logreg_fwd(x, cc, bias, labels, weights, 1.0 / n, 0, None, lse, lws, check_labels=False))
+            row['logreg_fwd0_tfs'] = 2.0 * n * D * C / row['logreg_fwd0_us'] / 1e6
+            row['knn_top1_us'], row['knn_top1_min_max_us'] = med(lambda: ops.knn_topk(x, c, 1))
+            row['knn_top1_tfs'] = row['flops'] / row['knn_top1_us'] / 1e6
+            row['update_us'], row['update_min_max_us'] = med(lambda: ops.kmeans_update(x, weights, assign, K, sums, wsum))
+            key, order = torch.sort(assign, stable=True)
+            order = order.to(torch.int32)
+            offsets = torch.searchsorted(key, torch.arange(K + 1, device=dev, dtype=torch.int32)).to(torch.int32)
+            pp = lambda t: t.data_ptr()
+            row['update_kernel_us'], row['update_kernel_min_max_us'] = med(
+                lambda: _klib().kmeans_update(pp(x), pp(weights), pp(order), pp(offsets), n, D, K, pp(sums), pp(wsum), 0,
+                                              torch.cuda.current_stream().cuda_stream))
+            y = torch.empty_like(x)
+            row['copy_us'], row['copy_min_max_us'] = med(lambda: y.copy_(x))
+            row['update_kernel_read_gbs'] = 4.0 * n * D / row['update_kernel_us'] / 1e3
+            row['copy_read_gbs'] = 4.0 * n * D / row['copy_us'] / 1e3
+            cn = torch.empty_like(c)
+            row['finish_us'], row['finish_min_max_us'] = med(lambda: ops.kmeans_finish(sums, wsum, c, cn, ws))
+            print('kmeans n=%d D=%d K=%d (tile %d): assign %.0f us [%.0f, %.0f] (%.1f TF/s) | logreg fwd value C=%d %.0f us [%.0f, %.0f] '
+                  '(%.1f TF/s) | knn top-1 %.0f us [%.0f, %.0f] (%.1f TF/s) | update %.0f us [%.0f, %.0f], kernel alone %.0f us [%.0f, %.0f] '
+                  '(%.0f GB/s read) | copy %.0f us [%.0f, %.0f] (%.0f GB/s read) | finish %.0f us'
+                  % (n, D, K, row['tile_edge'], row['assign_us'], *row['assign_min_max_us'], row['assign_tfs'], C, row['logreg_fwd0_us'],
+                     *row['logreg_fwd0_min_max_us'], row['logreg_fwd0_tfs'], row['knn_top1_us'], *row['knn_top1_min_max_us'],
+                     row['knn_top1_tfs'], row['update_us'], *row['update_min_max_us'], row['update_kernel_us'],
+                     *row['update_kernel_min_max_us'], row['update_kernel_read_gbs'], row['copy_us'], *row['copy_min_max_us'],
+                     row['copy_read_gbs'], row['finish_us']), flush=True)
+            res.append(row)
+            del x, c, weights, ws, assign, best, sums, wsum, lws, lse, bias, labels, cc, key, order, offsets, y, cn
     if 'byol' in what:
         # BYOL (csrc/byol.hip).  The moving average of the target network over ResNet-50's variable list (the list of the 'lars' entry
         # below) in GB/s of 12 bytes per element (target read + write, online read), beside simclr_lars_multi_tensor on the same list in
