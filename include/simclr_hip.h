@@ -344,6 +344,29 @@ int simclr_kmeans_update(const float* x, const float* weights, const int* order,
 int simclr_kmeans_finish(const double* sums, const double* wsum, const float* c_prev, int K, int D, float* c_new, double* out2,
                          void* workspace, simclr_stream_t stream);
 
+/* ---- eigen-spectrum evaluation of frozen features: column sums and the centred covariance, csrc/spectrum.hip ----
+ * x [n, D] fp32 = a slab of (unnormalised) rows, weights [n] fp32.  A row is COUNTED when its weight is > 0 and not at all otherwise: the
+ * kernels select, they never multiply, and an uncounted row is not read (a NaN or inf in it changes no output bit).
+ * simclr_spectrum_colsum: sums [D + 1] double (+)= {the column sums of the counted rows, their number} (accumulate != 0 adds to what
+ *   sums holds).
+ * simclr_spectrum_cov: cov [D, D] double (+)= sum_counted (x_n - mu32)(x_n - mu32)^T, mu32 [D] fp32 = the caller's mean rounded to
+ *   fp32 (the caller applies - S delta delta^T, delta = mu - mu32, in double).  The rows are centred into an fp32 scratch in the
+ *   workspace first; the product runs on the exact fp32-input MFMA over the tile pairs (i <= j) only, the slab's rows cut into
+ *   simclr_spectrum_row_parts parts (a multiple of 32 rows each, the last one ragged, none longer than 8192 rows).  A part accumulates
+ *   in fp32; the parts, then the slab, are added in double in ascending order, and the mirror element is written from the same
+ *   register: cov[a, b] and cov[b, a] hold the same bits (with accumulate != 0, provided they did on entry).
+ * D a multiple of 64 in [64, 8192], 1 <= n <= 65536, every pointer 16-byte aligned.  No atomics, every reduction in a fixed order:
+ * repeat calls are bitwise equal. */
+int simclr_spectrum_dim_ok(int D);                           /* 1 for a width the kernels take, else 0 */
+size_t simclr_spectrum_workspace_bytes(int n, int D);        /* both entry points; 0 for a shape the kernels refuse */
+size_t simclr_spectrum_colsum_workspace_bytes(int n, int D); /* what simclr_spectrum_colsum alone needs (the head of the above); 0 if refused */
+int simclr_spectrum_tile_edge(int n, int D);                 /* edge (64 or 128) of the covariance tile; 0 for a refused shape */
+int simclr_spectrum_row_parts(int n, int D);                 /* row parts of the covariance product; 0 for a refused shape */
+int simclr_spectrum_colsum(const float* x, const float* weights, int n, int D, double* sums, int accumulate, void* workspace,
+                           simclr_stream_t stream);
+int simclr_spectrum_cov(const float* x, const float* weights, const float* mu32, int n, int D, double* cov, int accumulate,
+                        void* workspace, simclr_stream_t stream);
+
 /* ---- weighted k-NN evaluation of frozen features (Wu et al. 2018), csrc/knn.hip ---------------------------------------- */
 /* q [Q, D], bank [N, D] fp32 row-major, unpadded.  s(i, j) = sum_d q[i,d] bank[j,d] on the exact fp32-input MFMA, accumulated in a fixed
  * order over d: a function of the two rows alone (not of i, j, Q, N or the tile), so sharding the bank or the queries changes no bit.

@@ -97,7 +97,7 @@ class _Lib:
                           'simclr_dino_local_row_splits', 'simclr_dino_local_teacher_row_splits',
                           'simclr_vicreg_k_splits', 'simclr_vicreg_fwd_workgroups', 'simclr_repr_tile_edge',
                           'simclr_logreg_row_splits', 'simclr_logreg_tile_edge', 'simclr_logreg_bwd_tile_edge', 'simclr_logreg_store_pitch',
-                          'simclr_kmeans_tile_edge'}
+                          'simclr_kmeans_tile_edge', 'simclr_spectrum_dim_ok', 'simclr_spectrum_tile_edge', 'simclr_spectrum_row_parts'}
 
     def last_error(self):
         return self._dll.simclr_last_error().decode()

@@ -7,7 +7,7 @@ OUT=${SIMCLR_SO_OUT:-../libsimclr_hip.so}
 B=${SIMCLR_BUILD_DIR:-build}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result"
 # the translation units, one <name>.hip each: the compile loop and both link lines come from this list
-UNITS="runtime ntxent gcl supcon hcl nnclr barlow vicreg repr logreg kmeans byol moco dino swav swav_multicrop dino_multicrop knn dropblock lars conv bn pool augment comm"
+UNITS="runtime ntxent gcl supcon hcl nnclr barlow vicreg repr logreg kmeans spectrum byol moco dino swav swav_multicrop dino_multicrop knn dropblock lars conv bn pool augment comm"
 # an object is stale when its source or ANY header of this directory is newer
 stale() {
   [ -f $B/$1.o ] || return 0

@@ -212,6 +212,17 @@ _DEFS = [
     ('kmeans_seed', 0, int, 'MI355X build: restart r starts from rows drawn with numpy.random.default_rng([kmeans_seed, r]).'),
     ('kmeans_bank_examples', 0, int, 'MI355X build: examples of --train_split that are clustered: 0 = the whole split, n > 0 = the first n '
                                      'positions of epoch_permutation(data_seed, 0, N) (the rule of --knn_bank_examples).'),
+    # eigen-spectrum evaluation (simclr_amd/spectrum.py): the covariance spectrum of the unnormalised encoder output, label-free
+    ('spectrum_eval', False, bool, 'MI355X build: --mode=eval / train_then_eval also compute the eigenvalues of the covariance of the '
+                                   'encoder features of --train_split (evaluation preprocessing, not normalised), score them (RankMe, '
+                                   'participation ratio, numerical rank, power-law decay) and write spectrum_result.json; needs no labels.'),
+    ('spectrum_bank_examples', 0, int, 'MI355X build: examples of --train_split whose covariance is taken: 0 = the whole split, n > 0 = the '
+                                       'first n positions of epoch_permutation(data_seed, 0, N) (the rule of --knn_bank_examples).'),
+    ('spectrum_rank_threshold', 1e-6, float, 'MI355X build: the numerical rank counts the eigenvalues above spectrum_rank_threshold times '
+                                             'the largest; in (0, 1).'),
+    ('spectrum_alpha_first', 10, int, 'MI355X build: first eigenvalue index (1-based) of the power-law fit of eval/spectrum_alpha; >= 1.'),
+    ('spectrum_alpha_last', 0, int, 'MI355X build: last eigenvalue index of the power-law fit; 0 = the numerical rank, else >= '
+                                    'spectrum_alpha_first + 7.'),
     # asymmetric view augmentation (flags.aug_plan): per-view blur and solarization of the two global views, jitter components.
     # None = take the column from --aug_recipe.  Read in pretraining only: --train_mode=finetune and --mode=eval ignore all five.
     ('aug_recipe', 'simclr', str, "MI355X build: augmentation recipe of the two global views, 'simclr' (default: blur 0.5 / 0.5, no "

@@ -1007,6 +1007,98 @@ def kmeans_finish(sums, wsum, c_prev, c_new=None, ws=None):
     return c_new, out
 
 
+# ---------------------------------------------------------------- eigen-spectrum evaluation (csrc/spectrum.hip)
+SPECTRUM_DIM_STEP, SPECTRUM_MIN_DIM, SPECTRUM_MAX_DIM = 64, 64, 8192   # feature widths: multiples of 64 in [64, 8192]
+SPECTRUM_MAX_ROWS = 65536                                              # rows per call (a slab of the bank)
+
+
+def spectrum_dim_ok(D):
+    return SPECTRUM_MIN_DIM <= D <= SPECTRUM_MAX_DIM and D % SPECTRUM_DIM_STEP == 0
+
+
+def _spectrum_check_shape(n, D):
+    if not spectrum_dim_ok(D):
+        raise ValueError('spectrum supports feature widths that are multiples of %d in [%d, %d] (got %d)'
+                         % (SPECTRUM_DIM_STEP, SPECTRUM_MIN_DIM, SPECTRUM_MAX_DIM, D))
+    if not 1 <= n <= SPECTRUM_MAX_ROWS:
+        raise ValueError('spectrum takes 1 <= n <= %d rows per call (got %d)' % (SPECTRUM_MAX_ROWS, n))
+
+
+def spectrum_workspace(n, D, device, colsum_only=False):
+    """A workspace for both entry points at this shape (the centred slab and the fp32 row parts of spectrum_cov); colsum_only=True:
+    the few kilobytes spectrum_colsum alone needs."""
+    n, D = int(n), int(D)
+    _spectrum_check_shape(n, D)
+    nbytes = (lib().spectrum_colsum_workspace_bytes if colsum_only else lib().spectrum_workspace_bytes)(n, D)
+    assert nbytes > 0
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+
+
+def spectrum_tile_edge(n, D):
+    """Edge (64 or 128) of the covariance tile a workgroup owns at this shape (0 for a refused shape)."""
+    return int(lib().spectrum_tile_edge(int(n), int(D)))
+
+
+def spectrum_row_parts(n, D):
+    """Row parts of spectrum_cov's product at this shape (0 for a refused shape)."""
+    return int(lib().spectrum_row_parts(int(n), int(D)))
+
+
+def _spectrum_t(name, t, shape, dtype):
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError('spectrum: %s must be a %s tensor of shape %s (got %s %s)'
+                         % (name, str(dtype).replace('torch.', ''), tuple(shape), tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError('spectrum: %s must be contiguous and 16-byte aligned' % name)
+
+
+def _spectrum_ws(ws, n, D, device, colsum_only=False):
+    if ws is None:
+        return spectrum_workspace(n, D, device, colsum_only)
+    need = (lib().spectrum_colsum_workspace_bytes if colsum_only else lib().spectrum_workspace_bytes)(n, D)
+    if not torch.is_tensor(ws) or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+        raise ValueError('spectrum: the workspace must hold %d bytes, 16-byte aligned, for n = %d, D = %d' % (need, n, D))
+    return ws
+
+
+def spectrum_colsum(x, weights, sums=None, accumulate=False, ws=None):
+    """x [n, D] fp32, weights [n] fp32 -> sums fp64 [D + 1] (+)= {column sums of the rows of weight > 0, their number}.  The rows are
+    selected, not multiplied: a row of weight <= 0 (or NaN) is not read.  Its workspace is the head of spectrum_cov's: any workspace of
+    spectrum_workspace(n, D) serves, and without one only simclr_spectrum_colsum_workspace_bytes are allocated."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError('spectrum_colsum: need x [n, D]')
+    n, D = x.shape
+    _spectrum_check_shape(n, D)
+    _spectrum_t('x', x, (n, D), torch.float32); _spectrum_t('weights', weights, (n,), torch.float32)
+    if accumulate and sums is None:
+        raise ValueError('spectrum_colsum: accumulate=True needs sums')
+    sums = torch.empty(D + 1, device=x.device, dtype=torch.float64) if sums is None else sums
+    _spectrum_t('sums', sums, (D + 1,), torch.float64)
+    ws = _spectrum_ws(ws, n, D, x.device, colsum_only=True)
+    _launch('spectrum_colsum', 1.0 * n * D, 4.0 * n * D,
+            lambda: lib().spectrum_colsum(_p(x), _p(weights), n, D, _p(sums), 1 if accumulate else 0, _p(ws), _s()))
+    return sums
+
+
+def spectrum_cov(x, weights, mu32, cov=None, accumulate=False, ws=None):
+    """cov fp64 [D, D] (+)= sum over the rows of weight > 0 of (x_n - mu32)(x_n - mu32)^T for x [n, D] fp32 and mu32 [D] fp32.  The
+    upper tile triangle is computed and mirrored: cov[a, b] and cov[b, a] are the same bits."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError('spectrum_cov: need x [n, D]')
+    n, D = x.shape
+    _spectrum_check_shape(n, D)
+    _spectrum_t('x', x, (n, D), torch.float32); _spectrum_t('weights', weights, (n,), torch.float32)
+    _spectrum_t('mu32', mu32, (D,), torch.float32)
+    if accumulate and cov is None:
+        raise ValueError('spectrum_cov: accumulate=True needs cov')
+    cov = torch.empty(D, D, device=x.device, dtype=torch.float64) if cov is None else cov
+    _spectrum_t('cov', cov, (D, D), torch.float64)
+    ws = _spectrum_ws(ws, n, D, x.device)
+    _launch('spectrum_cov', 1.0 * n * D * (D + 1), 8.0 * n * D + 8.0 * D * D,
+            lambda: lib().spectrum_cov(_p(x), _p(weights), _p(mu32), n, D, _p(cov), 1 if accumulate else 0, _p(ws), _s()))
+    return cov
+
+
 # ---------------------------------------------------------------- BYOL (csrc/byol.hip)
 BYOL_DIM_STEP, BYOL_MIN_DIM, BYOL_MAX_DIM = 64, 64, 8192   # loss widths (and predictor hidden widths) the BYOL path takes
 

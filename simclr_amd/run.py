@@ -336,6 +336,32 @@ def check_kmeans_flags(num_train_examples=None, num_classes=None):
     return bank
 
 
+def check_spectrum_flags(num_train_examples=None):
+    """--spectrum_eval (simclr_amd/spectrum.py), checked before any device work.  Returns the number of bank examples (None with the flag
+    off, in --mode=train, or for the whole split when its size is not known yet)."""
+    if not FLAGS.spectrum_eval or FLAGS.mode == 'train':
+        return None
+    from . import spectrum as spectrum_lib
+    spectrum_lib.check_score_arguments(FLAGS.spectrum_rank_threshold, FLAGS.spectrum_alpha_first, FLAGS.spectrum_alpha_last)
+    if FLAGS.spectrum_bank_examples < 0:
+        raise ValueError('--spectrum_bank_examples must be >= 0 (got %d)' % FLAGS.spectrum_bank_examples)
+    width = (512 if FLAGS.resnet_depth in (18, 34) else 2048) * FLAGS.width_multiplier
+    if not ops.spectrum_dim_ok(width):
+        raise ValueError('--spectrum_eval needs an encoder width that is a multiple of %d in [%d, %d] (resnet_depth=%d, width_multiplier=%d '
+                         'give %d)' % (ops.SPECTRUM_DIM_STEP, ops.SPECTRUM_MIN_DIM, ops.SPECTRUM_MAX_DIM, FLAGS.resnet_depth,
+                                       FLAGS.width_multiplier, width))
+    if num_train_examples is None:
+        bank = FLAGS.spectrum_bank_examples or None
+    else:
+        if FLAGS.spectrum_bank_examples > num_train_examples:
+            raise ValueError('--spectrum_bank_examples=%d exceeds the %d examples of --train_split=%s'
+                             % (FLAGS.spectrum_bank_examples, num_train_examples, FLAGS.train_split))
+        bank = FLAGS.spectrum_bank_examples or int(num_train_examples)
+    if bank is not None and bank < 2:
+        raise ValueError('--spectrum_bank_examples: a covariance needs at least 2 bank examples (got %d)' % bank)
+    return bank
+
+
 def all_reduce_stats_async(tensor, strategy):
     """SUM of a small statistics tensor over the replicas on the route the SyncBN sums and the Barlow Twins column sums use, started
     now; returns a zero-argument function that waits for it and returns the tensor.  One replica: nothing to do."""
@@ -804,6 +830,7 @@ def main(argv):
     check_knn_flags()
     check_logreg_flags()
     check_kmeans_flags()
+    check_spectrum_flags()
     check_repr_flags()
     builder = None
     if FLAGS.dataset != 'synthetic':
@@ -821,11 +848,15 @@ def main(argv):
         if FLAGS.kmeans_eval and FLAGS.mode != 'train':
             builder.split(FLAGS.train_split)
             check_kmeans_flags(builder.info.splits[FLAGS.train_split].num_examples, builder.info.features['label'].num_classes)
+        if FLAGS.spectrum_eval and FLAGS.mode != 'train':
+            builder.split(FLAGS.train_split)
+            check_spectrum_flags(builder.info.splits[FLAGS.train_split].num_examples)
     else:
         if FLAGS.knn_eval:
             check_knn_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
         check_logreg_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
         check_kmeans_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size, 10 if FLAGS.image_size <= 32 else 1000)
+        check_spectrum_flags(SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
     strategy = init_distributed()
     R = num_replicas(strategy)
     rank0 = strategy is None or strategy.rank == 0
@@ -894,6 +925,16 @@ def main(argv):
         bank_data = bank_iterator(n_bank, FLAGS.kmeans_bank_examples, knn_lib)
         kmeans_result = kmeans_lib.perform_kmeans_evaluation(model, bank_data, eval_data(), eval_steps, ckpt, strategy, FLAGS.model_dir)
         return dict(result or {}, **kmeans_result)
+
+    def spectrum_evaluation(ckpt, result):
+        """--spectrum_eval: the eigen-spectrum evaluation, after the k-means evaluation; the union of the results.
+        --dataset=synthetic: the bank of the k-NN path."""
+        from . import knn as knn_lib
+        from . import spectrum as spectrum_lib
+        n_bank = check_spectrum_flags(num_train_examples if builder is not None else SYNTHETIC_KNN_BANK_BATCHES * FLAGS.eval_batch_size)
+        bank_data = bank_iterator(n_bank, FLAGS.spectrum_bank_examples, knn_lib)
+        spectrum_result = spectrum_lib.perform_spectrum_evaluation(model, bank_data, ckpt, strategy, FLAGS.model_dir)
+        return dict(result or {}, **spectrum_result)
     RT.reset()
     RT.strategy = strategy
     RT.device = torch.device('cuda', torch.cuda.current_device())
@@ -914,6 +955,8 @@ def main(argv):
             result = logreg_evaluation(ckpt, result)
         if FLAGS.kmeans_eval:
             result = kmeans_evaluation(ckpt, result)
+        if FLAGS.spectrum_eval:
+            result = spectrum_evaluation(ckpt, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result
@@ -1012,6 +1055,8 @@ def main(argv):
             result = logreg_evaluation(manager.latest_checkpoint, result)
         if FLAGS.kmeans_eval:
             result = kmeans_evaluation(manager.latest_checkpoint, result)
+        if FLAGS.spectrum_eval:
+            result = spectrum_evaluation(manager.latest_checkpoint, result)
         if rank0:
             print(json.dumps(result), flush=True)
         return result

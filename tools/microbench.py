@@ -1,6 +1,6 @@
 """Per-layer micro-benchmark of the hot kernels at ResNet-50 1x / 224 px / V views per GPU.
 
-python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn,repr,logreg,kmeans]
+python tools/microbench.py [--views 1024] [--dtype bf16] [--what conv,bn,ntxent,lars,gcl,supcon,hcl,nnclr,barlow,vicreg,byol,moco,dino,swav,swav_multicrop,dino_multicrop,dropblock,knn,repr,logreg,kmeans,spectrum,spectrum_eval]
 Prints one line per distinct layer shape: time (us), TFLOP/s, algorithmic GB/s; and a per-step
 total weighted by how often the shape occurs.  Timing: HIP events on the launch stream, median of
 `--iters` launches after warm-up; inputs are random (never zeros: DVFS).
@@ -755,6 +755,115 @@ def main():
                      row['copy_read_gbs'], row['finish_us']), flush=True)
             res.append(row)
             del x, c, weights, ws, assign, best, sums, wsum, lws, lse, bias, labels, cc, key, order, offsets, y, cn
+    if 'spectrum' in what:
+        # Eigen-spectrum evaluation (csrc/spectrum.hip) on one slab.  The covariance (centring launch, upper-triangle product, double
+        # finish) in TF/s of the n D (D + 1) operations of the triangle beside, at the same shape in the same run, ops.logreg_bwd at
+        # C = min(D, 4096): the full [C, D] product of the same orientation (k = the row) in fp32.  The column sums beside a plain device
+        # copy of the slab: they read n D floats once.  Median of --iters launches with [min, max].
+        def med(fn):
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.iters):
+                a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
+                a.record(); fn(); b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) * 1e3)
+            ts.sort()
+            return ts[len(ts) // 2], [ts[0], ts[-1]]
+        for (n, D) in [(65536, 2048), (65536, 8192), (65536, 128)]:
+            x = torch.relu(torch.randn(n, D, device=dev) + 0.5)
+            weights = torch.ones(n, device=dev)
+            ws = ops.spectrum_workspace(n, D, dev)
+            sums = ops.spectrum_colsum(x, weights, ws=ws)
+            mu32 = (sums[:D] / n).float()
+            cov = torch.empty(D, D, device=dev, dtype=torch.float64)
+            e, parts = ops.spectrum_tile_edge(n, D), ops.spectrum_row_parts(n, D)
+            row = dict(layer='spectrum n%d D%d' % (n, D), flops=1.0 * n * D * (D + 1), iters=args.iters, workspace_bytes=ws.numel() * 8,
+                       tile_edge=e, row_parts=parts, tile_pairs=(D // e) * (D // e + 1) // 2)
+            row['cov_us'], row['cov_min_max_us'] = med(lambda: ops.spectrum_cov(x, weights, mu32, cov, ws=ws))
+            row['cov_tfs'] = row['flops'] / row['cov_us'] / 1e6
+            row['colsum_us'], row['colsum_min_max_us'] = med(lambda: ops.spectrum_colsum(x, weights, sums, ws=ws))
+            row['colsum_read_gbs'] = 4.0 * n * D / row['colsum_us'] / 1e3
+            del ws
+            C = min(D, ops.LOGREG_MAX_CLASSES)
+            pitch = ops.logreg_store_pitch(C)
+            g = torch.randn(n, pitch, device=dev)
+            dW, db = torch.empty(C, D, device=dev), torch.empty(C, device=dev)
+            lws = ops.logreg_workspace(n, D, C, dev)
+            row['logreg_classes'] = C
+            row['logreg_bwd_us'], row['logreg_bwd_min_max_us'] = med(lambda: ops.logreg_bwd(g, x, C, dW, db, ws=lws))
+            row['logreg_bwd_tfs'] = 2.0 * n * D * C / row['logreg_bwd_us'] / 1e6
+            row['cov_over_logreg_bwd'] = row['cov_us'] / row['logreg_bwd_us']
+            del g, dW, db, lws
+            y = torch.empty_like(x)
+            row['copy_us'], row['copy_min_max_us'] = med(lambda: y.copy_(x))
+            row['copy_read_gbs'] = 4.0 * n * D / row['copy_us'] / 1e3
+            print('spectrum n=%d D=%d (tile %d, %d pairs x %d row parts): cov %.0f us [%.0f, %.0f] (%.1f TF/s of the triangle) | logreg_bwd '
+                  'C=%d %.0f us [%.0f, %.0f] (%.1f TF/s) | cov / logreg_bwd %.3f | colsum %.0f us [%.0f, %.0f] (%.0f GB/s read) | copy '
+                  '%.0f us [%.0f, %.0f] (%.0f GB/s read)'
+                  % (n, D, e, row['tile_pairs'], parts, row['cov_us'], *row['cov_min_max_us'], row['cov_tfs'], C, row['logreg_bwd_us'],
+                     *row['logreg_bwd_min_max_us'], row['logreg_bwd_tfs'], row['cov_over_logreg_bwd'], row['colsum_us'],
+                     *row['colsum_min_max_us'], row['colsum_read_gbs'], row['copy_us'], *row['copy_min_max_us'], row['copy_read_gbs']),
+                  flush=True)
+            res.append(row)
+            del x, weights, sums, mu32, cov, y
+    if 'spectrum_eval' in what:
+        # One whole evaluation on random features at the size of the ImageNet training split, single replica (no all-reduce): the two
+        # passes of spectrum.covariance over the cached slabs, the host eigvalsh at D = 2048, and eigvalsh alone at D = 8192.
+        import time
+        import numpy as np
+        from simclr_amd import spectrum
+        n, D = 1281167, 2048
+        x = torch.empty(n, D, device=dev)
+        for o in range(0, n, 65536):
+            x[o:o + 65536] = torch.relu(torch.randn(min(65536, n - o), D, device=dev) + 0.5)
+        weights = torch.ones(n, device=dev)
+        row = dict(layer='spectrum eval n%d D%d' % (n, D), slabs=len(spectrum._slabs(n)))
+
+        def passes():
+            ws = ops.spectrum_workspace(65536, D, dev)
+            sums = torch.zeros(D + 1, device=dev, dtype=torch.float64)
+            cov = torch.zeros(D, D, device=dev, dtype=torch.float64)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i, (o, e) in enumerate(spectrum._slabs(n)):
+                ops.spectrum_colsum(x[o:e], weights[o:e], sums, accumulate=i > 0, ws=ws)
+            mu32 = (sums[:D] / float(sums[D])).float()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for i, (o, e) in enumerate(spectrum._slabs(n)):
+                ops.spectrum_cov(x[o:e], weights[o:e], mu32, cov, accumulate=i > 0, ws=ws)
+            torch.cuda.synchronize()
+            return t1 - t0, time.perf_counter() - t1
+        passes()
+        runs = sorted(passes() for _ in range(3))
+        row['colsum_pass_s'], row['cov_pass_s'] = runs[1]
+        row['passes_min_max_s'] = [list(runs[0]), list(runs[-1])]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        C, S, _ = spectrum.covariance(x, weights)
+        torch.cuda.synchronize()
+        row['covariance_s'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        lam = spectrum.eigenvalues(C)
+        row['eigvalsh_s'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        s = spectrum.scores(lam)
+        row['scores_s'] = time.perf_counter() - t0
+        row['rows'], row['rankme'], row['participation_ratio'] = int(S), s['eval/spectrum_rankme'], s['eval/spectrum_participation_ratio']
+        del x, weights, C
+        A = np.random.RandomState(0).randn(8192, 8192)
+        A = A @ A.T / 8192
+        t0 = time.perf_counter()
+        np.linalg.eigvalsh(A)
+        row['eigvalsh_8192_s'] = time.perf_counter() - t0
+        print('spectrum eval n=%d D=%d (%d slabs): column-sum pass %.3f s | covariance pass %.3f s | spectrum.covariance %.3f s | eigvalsh '
+              '%.3f s | scores %.4f s | eigvalsh at D = 8192 %.1f s' % (n, D, row['slabs'], row['colsum_pass_s'], row['cov_pass_s'],
+                                                                         row['covariance_s'], row['eigvalsh_s'], row['scores_s'],
+                                                                         row['eigvalsh_8192_s']), flush=True)
+        res.append(row)
     if 'byol' in what:
         # BYOL (csrc/byol.hip).  The moving average of the target network over ResNet-50's variable list (the list of the 'lars' entry
         # below) in GB/s of 12 bytes per element (target read + write, online read), beside simclr_lars_multi_tensor on the same list in
